@@ -23,7 +23,9 @@ synthetic batch that is already resident in HBM.
     python bench.py --gpus 8                     # launches its 8 ranks itself
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8   # or under a launcher
 
-Prints ONE JSON line (rank 0).  `value` = all ranks' cells / max-rank seconds.
+Prints ONE JSON line (rank 0), a few KB: the headline and a summary of each extra below (`--details FILE`: all of it).
+`value` = all ranks' cells / max-rank seconds; `ms_per_step` = wall clock of the `--steps` timed steps / steps.
+`--dump-outputs DIR`: the matrices of the last timed step, a fixed sample of the pairs, as .npy files (dump_outputs).
 `roofline`    : algorithmic bytes per launch / mean kernel duration (HIP events on
                 the launch stream, recorded inside the timed region) vs 8 TB/s.
 `e2e`         : wall clock of the host-level call on the same batch (host buffers in ->
@@ -340,6 +342,78 @@ def plumbing_test(args, rank, world, grp):
     return 0
 
 
+# ------------------------------------------------------------------- outputs ---
+DUMP_BYTES = 64 << 20        # --dump-outputs: all files of all ranks together stay below this
+DUMP_MAX_PAIRS = 64
+DUMP_SEED = 1009
+
+
+def dump_outputs(out_dir, db, first_pair: int, rank: int, world: int) -> dict:
+    """--dump-outputs DIR: what the timed fill left in its arenas after the last step -- the match / gap_a / gap_b matrices a
+    caller of seqalign_fill_batch_device receives -- for a fixed, seeded sample of the pairs (the whole output is gigabytes).
+    match.npy, gap_a.npy, gap_b.npy: the sampled pairs' matrices one after the other, each (len_b + 1) x (len_a + 1) row-major,
+    as float64 (every int32 score exactly); pair_index.npy: their global pair indices (ascending); pair_cells.npy: their cell
+    counts.  A pair too large for the budget contributes the first cells of its matrices only.  With N > 1 ranks each writes its
+    own share of pairs, the files prefixed rank<r>_."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    budget = (DUMP_BYTES - (1 << 20)) // world // (3 * 8)          # cells per matrix this rank may write
+    n = db.host.n_pairs
+    order = np.random.default_rng([DUMP_SEED, first_pair, n]).permutation(n)
+    chosen, cells = [], 0
+    for p in order[:DUMP_MAX_PAIRS]:
+        c = int(db.cells_host[p])
+        if cells + c > budget and chosen:
+            break
+        chosen.append(int(p))
+        cells += c
+    chosen.sort()
+    mats, counts = ([], [], []), []
+    for p in chosen:
+        for acc, m in zip(mats, db.pair_matrices(p)):
+            acc.append(m[:budget])
+        counts.append(min(int(db.cells_host[p]), budget))
+    prefix = f"rank{rank}_" if world > 1 else ""
+    arrays = {"match": np.concatenate(mats[0]), "gap_a": np.concatenate(mats[1]), "gap_b": np.concatenate(mats[2]),
+              "pair_index": np.asarray(chosen, np.int64) + first_pair, "pair_cells": np.asarray(counts, np.int64)}
+    written = 0
+    for name, a in arrays.items():
+        path = out_dir / f"{prefix}{name}.npy"
+        np.save(path, a.astype(np.float64))
+        written += path.stat().st_size
+    return {"dir": str(out_dir), "pairs": len(chosen), "cells": int(sum(counts)), "bytes": written, "ranks": world}
+
+
+def result_line(out: dict, details=None) -> dict:
+    """The one line bench.py prints: the headline in full, one short summary per extra measurement.  The whole record
+    (placement search, each config's roofline, the pre-recorded profiles, sample descriptions) passed 20 KB once every
+    BASELINE config joined the line, too long for a reader that keeps only the tail of the output; --details FILE writes it."""
+    pick = lambda d, *keys: {k: d[k] for k in keys if k in d}
+    line = pick(out, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "bit_exact_vs_oracle", "dump_outputs")
+    line["config"] = {k: v for k, v in out["config"].items() if k not in ("arena_placement_search", "parallelism")}
+    line["roofline"] = {k: v for k, v in out["roofline"].items() if k not in ("traffic_source", "unplaced")}
+    if "e2e" in out:
+        e = out["e2e"]
+        line["e2e"] = pick(e, "call", "ms", "value", "first_call_ms", "cold_ms")
+        line["e2e"].update({f"{k}_ms": e[k].get("ms", e[k].get("error")) for k in ("up_to_4_hits", "cigar") if k in e})
+        if "stream" in e:
+            line["e2e"]["stream_ms_per_batch"] = e["stream"]["ms_per_batch"]
+    if "sw_reduce" in out:
+        line["sw_reduce"] = pick(out["sw_reduce"], "kernel_ms", "frac")
+    line["per_rank"] = [pick(r, "rank", "device", "kernel_ms", "arena_placement_quality", "e2e_ms") for r in out["per_rank"]]
+    if "configs" in out:
+        line["configs"] = {name: {**pick(c, "value", "ms_per_step", "steps", "kernel", "bit_exact_vs_oracle", "error"),
+                                  **({"e2e_ms": c["e2e"]["ms"]} if "e2e" in c else {})} for name, c in out["configs"].items()}
+    if "cpu_baseline" in out:
+        cb = out["cpu_baseline"]
+        line["cpu_baseline"] = {**pick(cb, "value", "unit", "kind", "cores"), "all_cores": pick(cb["all_cores"], "value", "threads"),
+                                "e2e": {"value": cb["e2e"]["value"], "all_cores": cb["e2e"]["all_cores"]["value"]}}
+    if details:
+        line["details"] = str(details)
+    return line
+
+
 # ----------------------------------------------------------------------- run ---
 def run(args) -> int:
     from seqalign_amd.dist import Group, env_world
@@ -382,7 +456,7 @@ def run(args) -> int:
 
     S.lib()                                          # raises if the HIP library is missing: no fallback
     env = dict(rank=rank, local=local, world=world, backend=backend, folded=folded, pin=pin)
-    out = measure(args, grp, env, workload, args.steps, args.warmup, args.pairs)
+    out = measure(args, grp, env, workload, args.steps, args.warmup, args.pairs, dump_dir=args.dump_outputs)
     if rank == 0:
         # Every other BASELINE config in the SAME driver-run line: configs[2] (C3), configs[3] (C4) and one GPU's
         # share of configs[4] (C5: 125 000 of the 1 M pairs), each through the same measurement as the headline -- its own context,
@@ -415,15 +489,19 @@ def run(args) -> int:
             out["cpu_baseline"] = cpu_baseline(b0, spec, is_sw, min_score=(
                 W.default_minscore(sc0.match, int(b0.len_a[0]), int(b0.len_b[0])) if is_sw else 0))
         out.pop("_batch", None)
-        print(json.dumps(out), flush=True)
+        if args.details:
+            Path(args.details).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.details).write_text(json.dumps(out, indent=1) + "\n")
+        print(json.dumps(result_line(out, args.details)), flush=True)
     grp.barrier()
     grp.close()
     return 0
 
 
-def measure(args, grp, env, workload, steps, warmup, pairs):
+def measure(args, grp, env, workload, steps, warmup, pairs, dump_dir=None):
     """One workload through the whole measurement (fill roofline with placed and unplaced arenas, the SW reduction, the host-level
-    calls): the headline's, and each entry of `configs`.  Returns the line's dict on rank 0 (None elsewhere)."""
+    calls): the headline's, and each entry of `configs`.  Returns the line's dict on rank 0 (None elsewhere).  `dump_dir`: write
+    what the last timed step left in the arenas there (dump_outputs)."""
     import torch
     import seqalign_amd as S
     rank, local, world, backend, folded, pin = (env[k] for k in ("rank", "local", "world", "backend", "folded", "pin"))
@@ -628,6 +706,8 @@ def measure(args, grp, env, workload, steps, warmup, pairs):
     kern_ms = float(np.mean([s.elapsed_time(e) for s, e in zip(starts, ends)]))
     kern_ms_max = grp.max_float(kern_ms)
 
+    dumped = dump_outputs(dump_dir, db, first_pair, rank, world) if dump_dir else None
+
     # parity spot check outside the timed region (checker = oracle): bit-exact int32
     import orclib as O
     osc = O.Scoring.from_buffer_copy(bytes(sc))
@@ -692,6 +772,8 @@ def measure(args, grp, env, workload, steps, warmup, pairs):
                          "kernel_ms": kern_ms, "kernel_ms_slowest_rank": kern_ms_max,
                          "algorithmic_bytes_per_launch": alg_bytes},
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if unplaced:
             out["roofline"]["frac_unplaced"] = alg_bytes / (unplaced["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
             out["roofline"]["unplaced"] = unplaced
@@ -773,9 +855,16 @@ def main() -> int:
                     help="output arenas: the library's spread allocator (seqalign_arenas_alloc) or one packed allocation")
     ap.add_argument("--plumbing-test", action="store_true",
                     help="CPU-only check of launcher + sharding + reductions (tests/test_multigpu_cpu.py); not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the matrices the last step computed (a fixed, seeded sample of the pairs, "
+                         "float64, under 64 MB in all) to DIR/<name>.npy")
+    ap.add_argument("--details", metavar="FILE", default=None,
+                    help="write the whole record (every field the line summarises) to FILE as JSON")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])      # no launcher around us: start the ranks ourselves
     return run(args)

@@ -2,6 +2,7 @@
 the data formats either side of the hot path."""
 import ctypes as C
 import os
+import tarfile
 from pathlib import Path
 
 import numpy as np
@@ -92,16 +93,20 @@ def test_pair_loader(tmp_path):
     assert load("pairs", p)[0] == -1
 
 
-@pytest.mark.skipif(not Path("/root/reference/scoring/BLOSUM62.txt").exists(), reason="reference data files absent")
-def test_real_ncbi_files_load_and_blosum62_equals_the_preset():
-    """Authoring container only: the reference's own scoring/ files parse, and its
+SCORING_FILES = Path(__file__).resolve().parent / "golden" / "scoring.tar.xz"
+
+
+def test_real_ncbi_files_load_and_blosum62_equals_the_preset(tmp_path):
+    """The reference's own scoring/ files (NCBI matrices, kept as data in tests/golden/scoring.tar.xz) parse, and its
     BLOSUM62.txt equals its compiled-in BLOSUM62 table."""
+    with tarfile.open(SCORING_FILES) as tar:
+        tar.extractall(tmp_path)
     preset = S.make_scoring({"preset": "BLOSUM62"})
-    rc, err, sc = load("matrix", "/root/reference/scoring/BLOSUM62.txt")
+    rc, err, sc = load("matrix", tmp_path / "BLOSUM62.txt")
     assert rc == 0, err
     assert table_of(sc) == table_of(preset)
     n = 0
-    for path in sorted(Path("/root/reference/scoring").glob("*.txt")):
+    for path in sorted(tmp_path.glob("*.txt")):
         rc, err, sc = load("matrix", path)
         assert rc == 0, (path.name, err)
         n += 1
