@@ -467,6 +467,8 @@ enum {
   SEQALIGN_K_WALK_MOVES_TILE,      /* ... one wave per walk                                                        */
   SEQALIGN_K_FILL_NW_DIRS_X4,      /* NW, direction bytes only, FOUR pairs per wave (32 lanes a couple of pairs)   */
   SEQALIGN_K_FILL_SW_BEST_X4,      /* SW best hit: direction bytes + the best cell, four pairs per wave            */
+  SEQALIGN_K_SCORE_ROWS,           /* score only (seqalign_*_score_batch), one pair per wave, rows <= 1 024 columns */
+  SEQALIGN_K_SCORE_STRIPS,         /* ... wider rows: strips of 512 columns, one wave each (items: pairs)          */
   SEQALIGN_K_COUNT
 };
 #define SEQALIGN_K_MAX 32
@@ -515,6 +517,30 @@ int seqalign_nw_batch_cigar_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
 int seqalign_sw_batch_cigar_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                   const int32_t *min_score, uint32_t max_hits, int format, seqalign_sw_hit_t *hits,
                                   uint64_t hit_cap, uint64_t *n_hits, char *cigar, uint64_t cigar_cap);
+
+/* ---- score only ------------------------------------------------------------------ */
+/* Optimal score per pair, no alignment.  NW: the global score (what seqalign_nw_batch's out_score holds).
+ * SW: the best cell in reference hit order -- score, and the 1-based matrix coordinates of that cell
+ * (end_a = i, end_b = j: the best local alignment ends with seq_a[i-1], seq_b[j-1]); score 0 and (0,0)
+ * when no cell scores above 0.  No limit on len_a * len_b.
+ * Nothing per cell is written to device memory: rows of up to 1 024 columns are swept by one wave per pair, wider rows by
+ * strips of 512 columns that hand their last column to the next strip (8 bytes per row and strip).  Batches are chunked
+ * by sequence bytes; 4 (NW) or 12 (SW) bytes per pair come back.  Same argument checks and scoring admission
+ * (SEQALIGN_E_DOMAIN) as seqalign_nw_batch / seqalign_sw_batch, without their 2^31-cell cap.  A character pair without a
+ * score (SEQALIGN_E_UNKNOWN_PAIR): the lowest failing pair's code is returned and named in seqalign_last_error. */
+int seqalign_nw_score_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                            int32_t *out_score);
+int seqalign_sw_score_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                            int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b);
+/* ... over several contexts (GPUs): contiguous ranges of nearly equal cells, results exactly the single-context call's */
+int seqalign_nw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
+                                  const scoring_t *scoring, int32_t *out_score);
+int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
+                                  const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b);
+/* Kernel time of the score-only call (seq-align_amd/tools/score_bench.py): the batch is packed and uploaded once (it must
+ * fit one chunk), then its score kernels run `repeats` times, each launch between two HIP events: ms_each[r]. */
+int seqalign_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int is_sw,
+                           int repeats, float *ms_each);
 
 /* ---- diagnostics ---------------------------------------------------------------- */
 /* The host legs of seqalign_nw_batch's direction-byte path alone, no device involved: sizes, offsets and packing of the

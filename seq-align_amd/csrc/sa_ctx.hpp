@@ -5,6 +5,7 @@
 //                     single-pair call
 //   sa_batch.hip      host-level chunking, seqalign_fill_batch, seqalign_nw_batch
 //   sa_batch_sw.hip   seqalign_sw_batch (best hit / device enumeration / host enumeration)
+//   sa_batch_score.hip seqalign_nw_score_batch / seqalign_sw_score_batch (score only)
 //   sa_multi.hip      the same calls over several contexts (GPUs) from one process
 #pragma once
 #include <hip/hip_runtime.h>
@@ -370,6 +371,7 @@ struct seqalign_ctx {
   sa_host::DevBuf t_str_off, t_out_a, t_out_b, t_meta;   // device traceback outputs
   sa_host::DevBuf e[14];                                 // device SW enumeration scratch (see sw_chunk_device_enumerate)
   sa_host::DevBuf strip_progress;                        // sa_fill_strips.hip: rows done per (pair, strip)
+  sa_host::DevBuf score_handoff;                         // sa_score.hip's strips: the last column of every strip but the last
   sa_host::HostBuf h_desc, h_arena, h_M, h_A, h_B, h_misc, h_ta, h_tb, h_tmeta;
   // the last scorings uploaded through cached_scoring (host-level entry points, legacy single-pair path): [is_sw]
   seqalign_call_info_t call_info = {};   // what the last call launched (seqalign_ctx_last_call_info)

@@ -361,6 +361,33 @@ bool sa_stream_kernel_reports_best(const SaFillParams &p, uint32_t max_len_a, ui
  * the ticket counter, sa_fill_strips.hip) */
 uint32_t sa_fill_strips_per_pair(uint32_t max_len_a);
 hipError_t sa_launch_fill_strips(const SaFillParams &p, uint32_t max_len_a, uint32_t *progress, hipStream_t stream);
+
+/* ---- score only (sa_score.hip): the row sweep of every fill, nothing stored per cell --------------------------------------
+ * Pair k of a launch: score[k] (NW: max of match / gap_a / gap_b at (len_a, len_b); SW: the best match_scores cell in hit
+ * order) and, SW only, that cell's 1-based coordinates end_a[k] = column i, end_b[k] = row j (0, 0 when no cell is above 0);
+ * f.status[k] = the first cell without a score (~0: none); *err_flag |= 1 when any pair of the launch has one.
+ * Rows of up to SA_SCORE_ROW_MAX columns: one wave per pair.  Wider: strips of 512 columns, one wave each, handing their last
+ * column over through `handoff` (no cap on len_a x len_b). */
+#define SA_SCORE_ROW_MAX 1024u
+struct SaScoreParams {
+  SaFillParams f;               /* sequences, descriptors, scoring, status; the matrix pointers are unused              */
+  int32_t *score;               /* [n]                                                                                 */
+  uint32_t *end_a, *end_b;      /* [n] (SW)                                                                            */
+  uint32_t *err_flag;           /* one word, zeroed by the caller                                                      */
+  /* strips only: */
+  uint32_t *progress;           /* [8 * ceil(n / 8) * strips_per_pair + 1] zeroed: rows done per (pair, strip), then the
+                                   ticket counter                                                                       */
+  int32_t *handoff;             /* pair k, strip s < last: rows 0 .. len_b of {max(M, A), B} of the strip's last column
+                                   at 2 * (handoff_off[k] + s * (len_b + 1))                                            */
+  const uint64_t *handoff_off;  /* [n]                                                                                 */
+  uint32_t *strip_best;         /* [4 * progress words] SW: the best cell of strips 0 .. s (score, column, row)        */
+  uint32_t strips_per_pair;
+};
+uint32_t sa_score_strips_per_pair(uint32_t max_len_a);
+/* every pair of the launch has len_a <= SA_SCORE_ROW_MAX; max_len_a picks the columns per lane */
+hipError_t sa_launch_score_rows(const SaScoreParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream);
+/* the caller zeroed progress (and err_flag) and set status to ~0 */
+hipError_t sa_launch_score_strips(const SaScoreParams &p, bool is_sw, hipStream_t stream);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */
 bool sa_wgstream_kernel_applicable(const SaFillParams &p, uint32_t max_len_a);
 hipError_t sa_launch_fill_wgstream(const SaFillParams &p, uint32_t max_len_a, hipStream_t stream);

@@ -171,3 +171,25 @@ extern "C" int seqalign_sw_batch_cigar_multi(seqalign_ctx_t *const *ctxs, int n_
   if (format != SEQALIGN_CIGAR_M && format != SEQALIGN_CIGAR_EQX) return SEQALIGN_E_ARG;
   return sw_batch_multi(ctxs, n_ctx, batch, scoring, min_score, max_hits, format, hits, hit_cap, n_hits, cigar, nullptr, cigar_cap);
 }
+
+// score only: the same contiguous ranges; every range writes its own slice of the per-pair outputs
+extern "C" int seqalign_nw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
+                                             const scoring_t *scoring, int32_t *out_score) {
+  if (bad_ctx_list(ctxs, n_ctx) || !batch || !scoring || !out_score) return SEQALIGN_E_ARG;
+  if (batch->n_pairs && (!batch->arena || !batch->off_a || !batch->off_b || !batch->len_a || !batch->len_b)) return SEQALIGN_E_ARG;
+  return for_each_shard(shard_edges(batch, n_ctx), [&](int g, uint64_t first, uint64_t count) {
+    const seqalign_batch_t s = sub_batch(batch, first, count);
+    return seqalign_nw_score_batch(ctxs[g], &s, scoring, out_score + first);
+  });
+}
+
+extern "C" int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
+                                             const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a,
+                                             uint32_t *out_end_b) {
+  if (bad_ctx_list(ctxs, n_ctx) || !batch || !scoring || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
+  if (batch->n_pairs && (!batch->arena || !batch->off_a || !batch->off_b || !batch->len_a || !batch->len_b)) return SEQALIGN_E_ARG;
+  return for_each_shard(shard_edges(batch, n_ctx), [&](int g, uint64_t first, uint64_t count) {
+    const seqalign_batch_t s = sub_batch(batch, first, count);
+    return seqalign_sw_score_batch(ctxs[g], &s, scoring, out_score + first, out_end_a + first, out_end_b + first);
+  });
+}

@@ -1,0 +1,340 @@
+// sa_score.hip -- score only: the optimal score of each pair, no matrices, no traceback, any length.
+//
+// The same row sweep as every fill (sa_rowsweep.hpp: one row per step in registers, the (max,+) scan for gap_b, the
+// GENERAL path for the reference's flags), with the stores taken out.  What is kept instead:
+//   NW  nothing per cell: after the last row a lane's X[c] IS max(match, gap_a, gap_b) of its cell on that row, and the
+//       reference's end pick (needleman_wunsch.c:54-66) is the largest of the three at (len_a, len_b) -- no_end_gap_penalty
+//       is inside RowSweep's last row and column, so the score comes out of the same cells;
+//   SW  per column the highest match_scores value and the first row that reached it (strict >: a tie keeps the lower row),
+//       reduced at the end in hit order -- score desc, column asc, row asc (smith_waterman.c:71-86).
+//
+// score_rows_kernel: rows of up to 1 024 columns, one wave per pair (CPL = 1..16 columns per lane), 4 pairs per
+// workgroup.  len_b is unlimited: seq_b's codes arrive 64 rows at a time, the left border column is arithmetic.
+//
+// score_strips_kernel: wider rows, the pipeline of sa_fill_strips.hip (tickets drawn when a workgroup starts, waits only
+// on lower tickets, agent-scope release / acquire of a rows-done word per strip) -- but what strip s hands strip s + 1 is
+// not the matrices: per row, max(M, A) and B of its last column (RowSweep::row's feedZ / feedB; the up-left boundX
+// follows from them), 8 bytes into a scratch column of len_b + 1 rows.  O(strips x len_b) bytes per pair.  Published 64
+// rows at a time: lane q keeps row j0 + q's pair of values, the 64 rows leave as one coalesced 512-byte store.  SW: each
+// strip merges its best cell into the best of the strips to its left (visible: it waited for their last rows) and hands
+// that on; the last strip writes the pair's result.  Cell indices and the error key are 64-bit (len_a x len_b may pass 2^32).
+#include "sa_rowsweep.hpp"
+
+namespace sa {
+
+constexpr int kScoreStripCPL = 8;                            // 512 columns per strip, as sa_fill_strips.hip
+constexpr uint32_t kScoreStripCols = kWave * kScoreStripCPL;
+
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+// per-column running best of match_scores (SW)
+template <int CPL>
+struct BestCells {
+  int s[CPL];
+  uint32_t r[CPL];
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) { s[c] = 0; r[c] = 0; }
+  }
+  __device__ __forceinline__ void row(const int (&mv)[CPL], uint32_t j) {
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const bool up = mv[c] > s[c];   // strict: the first (lowest) row keeps a tie
+      s[c] = up ? mv[c] : s[c];
+      r[c] = up ? j : r[c];
+    }
+  }
+  // the wave's best in hit order over my columns col0 + 1 .. (matrix column = col0 + c + 1): {score, (column << 32) | row};
+  // score 0 -> key ~0
+  __device__ __forceinline__ void reduce(uint32_t col0, int ncol, int &score, unsigned long long &key) const {
+    int b = 0;
+    unsigned long long kb = ~0ull;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)   // c ascending, strict >: the lowest column wins a tie
+      if (c < ncol && s[c] > b) { b = s[c]; kb = ((unsigned long long)(col0 + c + 1) << 32) | r[c]; }
+    score = wave_max_i32(b);
+    key = wave_min_u64(b == score && score > 0 ? kb : ~0ull);
+  }
+};
+
+template <int CPL, int SUBST, bool GENERAL, bool SW>
+__global__ void __launch_bounds__(kWave *kWavesPerBlock)
+score_rows_kernel(const SaScoreParams sp) {
+  const SaFillParams &p = sp.f;
+  extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
+  const int32_t *table = p.table;
+  if constexpr (SUBST == SA_SUBST_LDS) {
+    for (uint32_t k = threadIdx.x; k < p.K * p.K; k += blockDim.x) lds_table[k] = p.table[k];
+    __syncthreads();
+    table = lds_table;
+  }
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const uint32_t pair = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
+  if (pair >= p.n_pairs) return;   // wave-uniform, after the only barrier
+
+  const uint32_t la = p.len_a[pair], lb = p.len_b[pair];
+  const uint8_t *__restrict__ sa_ = p.arena + p.off_a[pair];
+  const uint8_t *__restrict__ sb_ = p.arena + p.off_b[pair];
+  const uint32_t W = la + 1;
+
+  const SweepConsts k(p, table);
+  const Border bd{p.floor, p.gap_open, p.ext, SW, (p.flags & SA_F_NO_START_GAP) != 0};
+
+  RowSweep<CPL, SUBST, GENERAL> sw;
+  const uint32_t col0 = lane * CPL;
+  const int ncol = max(0, min(CPL, (int)la - lane * CPL));
+  sw.start_strip(p, k, bd, sa_, la, 0, col0, lane);
+  __builtin_amdgcn_s_waitcnt(kWaitVm0);   // seq_a codes landed (see RowFeed::load)
+  BestCells<SW ? CPL : 1> best;
+  if constexpr (SW) best.init();
+
+  int code = 0;
+  for (uint32_t j = 1; j <= lb; ++j) {
+    const int q = (j - 1) & (kWave - 1);
+    if (q == 0) {   // every 64 rows: lane t fetches seq_b's code for row j + t
+      const uint32_t r = j + lane;
+      if (r <= lb) code = p.code[sb_[r - 1]];
+      __builtin_amdgcn_s_waitcnt(kWaitVm0);
+    }
+    // the border column (reference alignment.c:72-80): max(M, A) and B of cell (0, j)
+    const int feedZ = max(k.floor_, bd.edge_gap(j)), feedB = k.floor_;
+    int mv[CPL], av[CPL], bv[CPL];
+    sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(code, q), feedZ, feedB, mv, av, bv);
+    if constexpr (SW) best.row(mv, j);
+  }
+
+  const unsigned long long err = sw.reduce_err();
+  if constexpr (SW) {
+    int score;
+    unsigned long long key;
+    best.reduce(col0, ncol, score, key);
+    if (lane == 0) {
+      sp.score[pair] = score;
+      sp.end_a[pair] = score > 0 ? (uint32_t)(key >> 32) : 0u;
+      sp.end_b[pair] = score > 0 ? (uint32_t)key : 0u;
+    }
+  } else {
+    if (la == 0) {   // cell (0, len_b) of the border column
+      if (lane == 0) sp.score[pair] = lb == 0 ? 0 : max(k.floor_, bd.edge_gap(lb));
+    } else {
+#pragma unroll
+      for (int c = 0; c < CPL; ++c)
+        if (col0 + c + 1 == la) sp.score[pair] = sw.X[c];   // max(M, A, B) of (len_a, len_b)
+    }
+  }
+  if (lane == 0) {
+    p.status[pair] = err;
+    if (err != ~0ull) atomicOr(sp.err_flag, 1u);
+  }
+}
+
+template <int SUBST, bool GENERAL, bool SW>
+__global__ void __launch_bounds__(kWave)
+score_strips_kernel(const SaScoreParams sp) {
+  constexpr int CPL = kScoreStripCPL;
+  const SaFillParams &p = sp.f;
+  extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
+  const int32_t *table = p.table;
+  if constexpr (SUBST == SA_SUBST_LDS) {
+    for (uint32_t k = threadIdx.x; k < p.K * p.K; k += blockDim.x) lds_table[k] = p.table[k];
+    __syncthreads();
+    table = lds_table;
+  }
+
+  const int lane = threadIdx.x;
+  const uint32_t spp = sp.strips_per_pair;
+  // ticket = (group * strips_per_pair + strip) * 8 + pair_in_group; the counter sits behind the progress words
+  // (sa_fill_strips.hip: a strip's ticket is higher than that of the strip it waits for, and a ticket only exists once its
+  // workgroup is resident -- so a waiting wave waits only for waves that are running or done, whatever the dispatch order)
+  uint32_t ticket = 0;
+  if (lane == 0) ticket = atomicAdd(sp.progress + (uint64_t)gridDim.x, 1u);
+  ticket = __builtin_amdgcn_readfirstlane(ticket);
+  const uint32_t in_group = ticket & 7u, gs = ticket >> 3;
+  const uint32_t strip = gs % spp, pair = (gs / spp) * 8 + in_group;
+  if (pair >= p.n_pairs) return;
+
+  const uint32_t la = p.len_a[pair], lb = p.len_b[pair];
+  const uint32_t i0 = strip * kScoreStripCols;
+  if (i0 >= la && strip != 0) return;   // this pair has fewer strips
+  const uint8_t *__restrict__ sa_ = p.arena + p.off_a[pair];
+  const uint8_t *__restrict__ sb_ = p.arena + p.off_b[pair];
+  const uint32_t W = la + 1;
+  const uint64_t slot = (uint64_t)pair * spp + strip;   // my progress word / strip_best entry
+  uint32_t *done = sp.progress + (uint64_t)pair * spp;  // done[s] = rows strip s has handed over
+  const uint64_t rows = (uint64_t)lb + 1;
+  int32_t *hand_out = sp.handoff + 2 * (sp.handoff_off[pair] + (uint64_t)strip * rows);
+  const int32_t *hand_in = sp.handoff + 2 * (sp.handoff_off[pair] + (uint64_t)(strip ? strip - 1 : 0) * rows);
+
+  const SweepConsts k(p, table);
+  const Border bd{p.floor, p.gap_open, p.ext, SW, (p.flags & SA_F_NO_START_GAP) != 0};
+
+  const uint32_t cols = (i0 < la) ? min(kScoreStripCols, la - i0) : 0;
+  const bool last_strip = i0 + kScoreStripCols >= la;
+  const uint32_t col0 = i0 + lane * CPL;
+  const int ncol = max(0, min(CPL, (int)cols - lane * CPL));
+  RowSweep<CPL, SUBST, GENERAL> sw;
+  sw.start_strip(p, k, bd, sa_, la, i0, col0, lane);
+  __builtin_amdgcn_s_waitcnt(kWaitVm0);
+  BestCells<SW ? CPL : 1> best;
+  if constexpr (SW) best.init();
+
+  int code = 0, fz = 0, fb = 0;   // lane q: row j0 + q's code and, from the strip to my left, max(M, A) and B
+  int oz = 0, ob = 0;             // lane q: row j0 + q's values of my last column, for the strip to my right
+  for (uint32_t j = 1; j <= lb; ++j) {
+    const int q = (j - 1) & (kWave - 1);
+    if (q == 0) {
+      const uint32_t r = j + lane;
+      if (strip > 0) {   // rows j .. j + 63 of the strip to my left must have been handed over
+        const uint32_t need = min(j + kWave - 1, lb);
+        while (__hip_atomic_load(done + strip - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need)
+          __builtin_amdgcn_s_sleep(8);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      }
+      if (r <= lb) {
+        code = p.code[sb_[r - 1]];
+        if (strip == 0) {   // border column (reference alignment.c:72-80)
+          fz = max(k.floor_, bd.edge_gap(r));
+          fb = k.floor_;
+        } else {
+          const int2 h = *reinterpret_cast<const int2 *>(hand_in + 2ull * r);
+          fz = h.x; fb = h.y;
+        }
+      }
+      __builtin_amdgcn_s_waitcnt(kWaitVm0);   // once per 64 rows (see RowFeed::load)
+    }
+    int mv[CPL], av[CPL], bv[CPL];
+    sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(code, q), read_lane(fz, q), read_lane(fb, q), mv, av, bv);
+    if constexpr (SW) best.row(mv, j);
+    if (!last_strip) {   // a strip that is not the last is full: lane 63's last column is the strip's
+      const int z = read_lane(max(mv[CPL - 1], av[CPL - 1]), kWave - 1), b = read_lane(bv[CPL - 1], kWave - 1);
+      oz = (lane == q) ? z : oz;
+      ob = (lane == q) ? b : ob;
+      if (q == kWave - 1 || j == lb) {
+        if (lane <= q) *reinterpret_cast<int2 *>(hand_out + 2ull * (j - q + lane)) = make_int2(oz, ob);
+        if (j != lb) {   // (the last rows are published below, after the best cell)
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+          if (lane == 0) __hip_atomic_store(done + strip, j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
+  }
+
+  const unsigned long long err = sw.reduce_err();
+  if (lane == 0 && err != ~0ull) {
+    atomicMin(reinterpret_cast<unsigned long long *>(p.status + pair), err);
+    atomicOr(sp.err_flag, 1u);
+  }
+  if constexpr (SW) {
+    int score;
+    unsigned long long key;
+    best.reduce(col0, ncol, score, key);
+    if (strip > 0 && lb > 0) {   // the strips to my left: their last rows were acquired above, their best with them
+      const uint4 left = *reinterpret_cast<const uint4 *>(sp.strip_best + 4 * (slot - 1));
+      if ((int)left.x >= score && (int)left.x > 0) {   // a tie goes to the lower column: theirs
+        score = (int)left.x;
+        key = ((unsigned long long)left.y << 32) | left.z;
+      }
+    }
+    const uint32_t ea = score > 0 ? (uint32_t)(key >> 32) : 0u, eb = score > 0 ? (uint32_t)key : 0u;
+    if (lane == 0) {
+      if (last_strip) {
+        sp.score[pair] = score; sp.end_a[pair] = ea; sp.end_b[pair] = eb;
+      } else {
+        *reinterpret_cast<uint4 *>(sp.strip_best + 4 * slot) = make_uint4((uint32_t)score, ea, eb, 0u);
+      }
+    }
+  } else if (last_strip) {
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)
+      if (col0 + c + 1 == la) sp.score[pair] = sw.X[c];   // max(M, A, B) of (len_a, len_b)
+  }
+  if (!last_strip && lb > 0) {   // the last rows (and the best cell so far)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (lane == 0) __hip_atomic_store(done + strip, lb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+template <int CPL, bool SW>
+static hipError_t launch_rows_cpl(const SaScoreParams &p, hipStream_t stream) {
+  const bool general = needs_general(p.f);
+  const dim3 grid((p.f.n_pairs + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
+  const uint32_t K = p.f.K;
+  if (K <= 1) {
+    if (general) hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_SIMPLE, true, SW>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_SIMPLE, false, SW>), grid, block, 0, stream, p);
+  } else if (K <= SA_LDS_TABLE_MAX_K) {
+    const size_t lds = (size_t)K * K * sizeof(int32_t);
+    if (general) hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_LDS, true, SW>), grid, block, lds, stream, p);
+    else hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_LDS, false, SW>), grid, block, lds, stream, p);
+  } else {
+    hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_GLOBAL, true, SW>), grid, block, 0, stream, p);
+  }
+  return hipGetLastError();
+}
+
+template <bool SW>
+static hipError_t launch_rows(const SaScoreParams &p, uint32_t max_len_a, hipStream_t stream) {
+  const uint32_t need = columns_per_lane(max_len_a);
+  if (need <= 1) return launch_rows_cpl<1, SW>(p, stream);
+  if (need <= 2) return launch_rows_cpl<2, SW>(p, stream);
+  if (need <= 3) return launch_rows_cpl<3, SW>(p, stream);
+  if (need <= 4) return launch_rows_cpl<4, SW>(p, stream);
+  if (need <= 5) return launch_rows_cpl<5, SW>(p, stream);
+  if (need <= 6) return launch_rows_cpl<6, SW>(p, stream);
+  if (need <= 8) return launch_rows_cpl<8, SW>(p, stream);
+  if (need <= 12) return launch_rows_cpl<12, SW>(p, stream);
+  return launch_rows_cpl<16, SW>(p, stream);
+}
+
+template <bool SW>
+static hipError_t launch_strips(const SaScoreParams &p, const dim3 grid, hipStream_t stream) {
+  const bool general = needs_general(p.f);
+  const dim3 block(kWave);
+  const uint32_t K = p.f.K;
+  if (K <= 1) {
+    if (general) hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_SIMPLE, true, SW>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_SIMPLE, false, SW>), grid, block, 0, stream, p);
+  } else if (K <= SA_LDS_TABLE_MAX_K) {
+    const size_t lds = (size_t)K * K * sizeof(int32_t);
+    if (general) hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_LDS, true, SW>), grid, block, lds, stream, p);
+    else hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_LDS, false, SW>), grid, block, lds, stream, p);
+  } else {
+    hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_GLOBAL, true, SW>), grid, block, 0, stream, p);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace sa
+
+uint32_t sa_score_strips_per_pair(uint32_t max_len_a) {
+  return max_len_a ? (uint32_t)(((uint64_t)max_len_a + sa::kScoreStripCols - 1) / sa::kScoreStripCols) : 1;
+}
+
+hipError_t sa_launch_score_rows(const SaScoreParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream) {
+  if (p.f.n_pairs == 0) return hipSuccess;
+  if (max_len_a > SA_SCORE_ROW_MAX) return hipErrorInvalidValue;
+  sa_record_launch(SEQALIGN_K_SCORE_ROWS, p.f.n_pairs);
+  return is_sw ? sa::launch_rows<true>(p, max_len_a, stream) : sa::launch_rows<false>(p, max_len_a, stream);
+}
+
+hipError_t sa_launch_score_strips(const SaScoreParams &p, bool is_sw, hipStream_t stream) {
+  if (p.f.n_pairs == 0) return hipSuccess;
+  const uint64_t blocks = (uint64_t)((p.f.n_pairs + 7) / 8) * 8 * p.strips_per_pair;
+  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  sa_record_launch(SEQALIGN_K_SCORE_STRIPS, p.f.n_pairs);
+  const dim3 grid((unsigned)blocks);
+  return is_sw ? sa::launch_strips<true>(p, grid, stream) : sa::launch_strips<false>(p, grid, stream);
+}

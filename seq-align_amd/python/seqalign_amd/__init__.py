@@ -359,6 +359,49 @@ class Context:
                                          b=out_b[h.str_off:h.str_off + h.length].tobytes().decode()))
         return per_pair
 
+    # ---- score only (seqalign_nw_score_batch / seqalign_sw_score_batch) ------------------------------
+    def nw_score(self, batch, scoring: Scoring, peers=None) -> np.ndarray:
+        """seqalign_nw_score_batch: the global score of every pair (what nw_batch's scores are), int32[n].  No alignment, no
+        limit on len_a * len_b."""
+        _score_args(batch, scoring)
+        score = np.zeros(batch.n_pairs, np.int32)
+        d = batch_desc(batch)
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(lib().seqalign_nw_score_batch_multi(hs, nh, C.byref(d), C.byref(scoring), _ptr(score)),
+                   "seqalign_nw_score_batch_multi")
+        else:
+            _check(lib().seqalign_nw_score_batch(self._h, C.byref(d), C.byref(scoring), _ptr(score)), "seqalign_nw_score_batch")
+        return score
+
+    def sw_score(self, batch, scoring: Scoring, peers=None):
+        """seqalign_sw_score_batch: per pair the best local cell in the reference's hit order -- (score int32[n], end_a
+        uint32[n], end_b uint32[n]): the best local alignment ends with seq_a[end_a - 1], seq_b[end_b - 1]; (0, 0, 0) when
+        no cell scores above 0."""
+        _score_args(batch, scoring)
+        n = batch.n_pairs
+        score, end_a, end_b = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        d = batch_desc(batch)
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(lib().seqalign_sw_score_batch_multi(hs, nh, C.byref(d), C.byref(scoring), _ptr(score), _ptr(end_a),
+                                                       _ptr(end_b)), "seqalign_sw_score_batch_multi")
+        else:
+            _check(lib().seqalign_sw_score_batch(self._h, C.byref(d), C.byref(scoring), _ptr(score), _ptr(end_a), _ptr(end_b)),
+                   "seqalign_sw_score_batch")
+        return score, end_a, end_b
+
+    def score_time_ms(self, batch, scoring: Scoring, is_sw: int, repeats: int = 10) -> np.ndarray:
+        """seqalign_score_time_ms: the score kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
+        _score_args(batch, scoring)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "score_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_score_time_ms(self._h, C.byref(d), C.byref(scoring), C.c_int(int(is_sw)), C.c_int(repeats),
+                                            _ptr(ms)), "seqalign_score_time_ms")
+        return ms
+
     # ---- asynchronous host-level calls (seqalign_*_batch_submit / seqalign_job_wait) ---------------
     def nw_buffers(self, batch):
         """Output buffers of one seqalign_nw_batch call on `batch`: (str_off, out_a, out_b, out_len, out_score)."""
@@ -452,6 +495,25 @@ class Context:
         out = np.zeros(64, np.int32)
         _check(lib().sa_dpp_probe(self._h, C.c_int32(fill), _ptr(out)), "sa_dpp_probe")
         return out
+
+
+def _score_args(batch, scoring):
+    """What the score-only wrappers check before the library sees the batch: the descriptor arrays' types and lengths, and
+    every sequence inside the arena (the C call trusts the pointers it is given)."""
+    if not isinstance(scoring, Scoring):
+        raise SeqAlignError(E_ARG, "score: scoring must be a seqalign_amd.Scoring")
+    n = getattr(batch, "n_pairs", None)
+    if n is None:
+        raise SeqAlignError(E_ARG, "score: batch must be a workloads.Batch")
+    for name, dt in (("off_a", np.uint64), ("off_b", np.uint64), ("len_a", np.uint32), ("len_b", np.uint32)):
+        a = getattr(batch, name)
+        if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != (n,) or not a.flags.c_contiguous:
+            raise SeqAlignError(E_ARG, f"score: batch.{name} must be a contiguous {np.dtype(dt).name}[{n}]")
+    if batch.arena.dtype != np.uint8 or not batch.arena.flags.c_contiguous:
+        raise SeqAlignError(E_ARG, "score: batch.arena must be contiguous uint8")
+    size = batch.arena.nbytes
+    if n and (int((batch.off_a + batch.len_a).max()) > size or int((batch.off_b + batch.len_b).max()) > size):
+        raise SeqAlignError(E_ARG, "score: a sequence lies outside batch.arena")
 
 
 class Job:
@@ -667,6 +729,8 @@ EXPORTED_SYMBOLS = [
     "seqalign_fill_batch_multi", "seqalign_nw_batch_multi", "seqalign_sw_batch_multi", "seqalign_cigar",
     "seqalign_nw_batch_submit", "seqalign_sw_batch_submit", "seqalign_nw_batch_cigar_submit", "seqalign_job_wait", "seqalign_job_done",
     "seqalign_nw_batch_cigar", "seqalign_sw_batch_cigar", "seqalign_nw_batch_cigar_multi", "seqalign_sw_batch_cigar_multi",
+    "seqalign_nw_score_batch", "seqalign_sw_score_batch", "seqalign_nw_score_batch_multi", "seqalign_sw_score_batch_multi",
+    "seqalign_score_time_ms",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",
