@@ -22,17 +22,22 @@ synthetic batch that is already resident in HBM.
     python bench.py --gpus 1 --steps 1000 --warmup 10
     python bench.py --gpus 8                     # launches its 8 ranks itself
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8   # or under a launcher
+    python bench.py --full                       # + every extra below
 
 Prints ONE JSON line (rank 0), a few KB: the headline and a summary of each extra below (`--details FILE`: all of it).
 `value` = all ranks' cells / max-rank seconds; `ms_per_step` = wall clock of the `--steps` timed steps / steps.
+A plain run does only what the headline needs: the batch, its placed arenas and the kernel choice, the warm-up, the timed
+steps, `--dump-outputs` and the line.  `--full` adds the extras, each measured outside the timed steps: the oracle spot check
+(`bit_exact_vs_oracle`), `roofline.frac_unplaced`, `e2e`, `sw_reduce`, `config.scale_base` (N > 1), `configs` (N = 1, default
+workload) and `cpu_baseline`; the `--no-*` options leave single ones out of a `--full` run.
 `--dump-outputs DIR`: the matrices of the last timed step, a fixed sample of the pairs, as .npy files (dump_outputs).
 `roofline`    : algorithmic bytes per launch / mean kernel duration (HIP events on
                 the launch stream, recorded inside the timed region) vs 8 TB/s.
 `e2e`         : wall clock of the host-level call on the same batch (host buffers in ->
                 H2D -> fill -> device traceback -> strings out), PCIe inclusive, median of 5 calls
                 after 0.25 s of the same call (its own steady state); never `value`.
-`cpu_baseline`: the reference itself (oracle/_ref, built from /root/reference in the
-                authoring container) or, if absent, our C restatement (oracle/), timed
+`cpu_baseline`: the reference itself (oracle/_ref, built from the reference sources
+                where they are present) or, if absent, our C restatement (oracle/), timed
                 on this box's host cores by a pthread harness (oracle/cpu_bench.c) on a
                 bounded sample: 1 pinned thread, and as many threads as the container is granted
                 (min of physical cores, affinity mask, cgroup CPU quota -- all three in the line,
@@ -458,7 +463,7 @@ def run(args) -> int:
     env = dict(rank=rank, local=local, world=world, backend=backend, folded=folded, pin=pin)
     out = measure(args, grp, env, workload, args.steps, args.warmup, args.pairs, dump_dir=args.dump_outputs)
     if rank == 0:
-        # Every other BASELINE config in the SAME driver-run line: configs[2] (C3), configs[3] (C4) and one GPU's
+        # --full: every other BASELINE config in the SAME line: configs[2] (C3), configs[3] (C4) and one GPU's
         # share of configs[4] (C5: 125 000 of the 1 M pairs), each through the same measurement as the headline -- its own context,
         # its own placed arenas, the fill timed with HIP events on the launch stream, the same kernel on unplaced arenas, the
         # separate SW reduction, the host-level calls -- a few seconds each.  `value` stays C2's.
@@ -480,7 +485,7 @@ def run(args) -> int:
                     entry = {"error": f"{type(ex).__name__}: {ex}"}
                 entry["seconds_spent"] = round(time.perf_counter() - t_cfg, 2)
                 out["configs"]["C5_share" if name == "C5" else name] = entry
-        # north_star: the 1 / 2 / 4 / 8-GPU figures "next to the reference CPU path" -- rank 0 times it at every N (once, the same
+        # --full, north_star: the 1 / 2 / 4 / 8-GPU figures "next to the reference CPU path" -- rank 0 times it at every N (once, the same
         # bounded leg; the other ranks wait in the barrier below with their GPUs idle: it is outside every timed region)
         if not args.no_cpu_baseline:
             gen, kwargs, _, is_sw, spec, desc = WORKLOADS[workload]
@@ -499,9 +504,10 @@ def run(args) -> int:
 
 
 def measure(args, grp, env, workload, steps, warmup, pairs, dump_dir=None):
-    """One workload through the whole measurement (fill roofline with placed and unplaced arenas, the SW reduction, the host-level
-    calls): the headline's, and each entry of `configs`.  Returns the line's dict on rank 0 (None elsewhere).  `dump_dir`: write
-    what the last timed step left in the arenas there (dump_outputs)."""
+    """One workload through the measurement: the timed fill and its roofline, and with --full the oracle spot check, the same
+    kernel on unplaced arenas, the SW reduction, the host-level calls and (N > 1) one GPU alone: the headline's, and each entry
+    of `configs`.  Returns the line's dict on rank 0 (None elsewhere).  `dump_dir`: write what the last timed step left in the
+    arenas there (dump_outputs)."""
     import torch
     import seqalign_amd as S
     rank, local, world, backend, folded, pin = (env[k] for k in ("rank", "local", "world", "backend", "folded", "pin"))
@@ -673,10 +679,10 @@ def measure(args, grp, env, workload, steps, warmup, pairs, dump_dir=None):
     torch.cuda.synchronize()
     grp.barrier()
 
-    # N > 1: what ONE GPU does on this workload with the others idle (rank 0, a few steps) -- the base the 1 -> N efficiency
+    # --full, N > 1: what ONE GPU does on this workload with the others idle (rank 0, a few steps) -- the base the 1 -> N efficiency
     # should be read against: the N = 1 line of this file is C2 (10 k pairs), the N > 1 lines are C5's 125 k-pair shares
     scale_base = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             torch.cuda.synchronize()
             n_alone, t_a = 0, time.perf_counter()
@@ -708,15 +714,17 @@ def measure(args, grp, env, workload, steps, warmup, pairs, dump_dir=None):
 
     dumped = dump_outputs(dump_dir, db, first_pair, rank, world) if dump_dir else None
 
-    # parity spot check outside the timed region (checker = oracle): bit-exact int32
-    import orclib as O
-    osc = O.Scoring.from_buffer_copy(bytes(sc))
-    bit_exact = True
-    for p in range(0, batch.n_pairs, max(1, batch.n_pairs // 16)):
-        rc, M, A, B = O.oracle_fill(osc, batch.seq_a(p), batch.seq_b(p), is_sw)
-        gM, gA, gB = db.pair_matrices(p)
-        bit_exact &= rc == 0 and np.array_equal(M, gM) and np.array_equal(A, gA) and np.array_equal(B, gB)
-    bit_exact = grp.sum_int(0 if bit_exact else 1) == 0
+    # --full: parity spot check outside the timed region (checker = oracle): bit-exact int32
+    bit_exact = None
+    if args.full:
+        import orclib as O
+        osc = O.Scoring.from_buffer_copy(bytes(sc))
+        bit_exact = True
+        for p in range(0, batch.n_pairs, max(1, batch.n_pairs // 16)):
+            rc, M, A, B = O.oracle_fill(osc, batch.seq_a(p), batch.seq_b(p), is_sw)
+            gM, gA, gB = db.pair_matrices(p)
+            bit_exact &= rc == 0 and np.array_equal(M, gM) and np.array_equal(A, gA) and np.array_equal(B, gB)
+        bit_exact = grp.sum_int(0 if bit_exact else 1) == 0
 
     # What the SAME kernel does on arenas nobody placed: three plain arenas (option arena_scan_gib = 0: no walk), a few steps --
     # so that the line states what the placement contributes instead of implying it (roofline.frac_unplaced).  Measured LAST:
@@ -766,12 +774,13 @@ def measure(args, grp, env, workload, steps, warmup, pairs, dump_dir=None):
                        "arena_placement_search": db.placement_info,
                        "cells_per_step_per_gpu": batch.cells(), "ranks_share_devices": folded,
                        **({"scale_base": scale_base} if scale_base else {})},
-            "bit_exact_vs_oracle": bool(bit_exact),
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                          "kernel_ms": kern_ms, "kernel_ms_slowest_rank": kern_ms_max,
                          "algorithmic_bytes_per_launch": alg_bytes},
         }
+        if bit_exact is not None:
+            out["bit_exact_vs_oracle"] = bool(bit_exact)
         if dumped:
             out["dump_outputs"] = dumped
         if unplaced:
@@ -802,7 +811,7 @@ def measure(args, grp, env, workload, steps, warmup, pairs, dump_dir=None):
             out["config"]["arena_placement_note"] = (f"placement quality below 0.97 on at least one rank (worst {worst_q}): the arenas "
                                                      "disturb each other and the walk found nothing better; see per_rank / "
                                                      "arena_placement_search")
-        if is_sw:
+        if is_sw and args.full:
             # the SW local-maxima reduction as a separate kernel (4 B/cell read)
             thr = W.default_minscore(sc.match, int(batch.len_a[0]), int(batch.len_b[0]))
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(12)]
@@ -827,11 +836,14 @@ def measure(args, grp, env, workload, steps, warmup, pairs, dump_dir=None):
     return out if rank == 0 else None
 
 
-def main() -> int:
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)   # C2: ~0.42 s of kernels; the whole default run stays under a minute
+    ap.add_argument("--steps", type=int, default=1000)   # C2: ~0.42 s of kernels; a --full run stays under a minute
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="measure every extra beside the headline (oracle spot check, unplaced arenas, e2e, sw_reduce, scale_base, "
+                         "configs, cpu_baseline); a plain run does only the timed steps and what they need")
     ap.add_argument("--workload", default=None, choices=list(WORKLOADS),
                     help="default: C2 at --gpus 1, C5 (125k pairs per GPU of the 1M-pair batch) at --gpus N > 1")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
@@ -840,14 +852,14 @@ def main() -> int:
     ap.add_argument("--all-kernels", action="store_true",
                     help="--kernel auto also times wavefront / rowscan / strips (correctness paths that have never won a configuration)")
     ap.add_argument("--pairs", type=int, default=0, help="pairs per GPU (default: the config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without `cpu_baseline`")
     ap.add_argument("--no-configs", action="store_true",
-                    help="N = 1, default workload: skip the `configs` block (C3, C4, C5's share measured beside the C2 headline)")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-stream", action="store_true", help="skip e2e.stream (the host-level call as a stream of submitted batches)")
+                    help="--full, N = 1, default workload: skip the `configs` block (C3, C4, C5's share measured beside the C2 headline)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without `e2e`")
+    ap.add_argument("--no-stream", action="store_true", help="--full: skip e2e.stream (the host-level call as a stream of submitted batches)")
     ap.add_argument("--stream-batches", type=int, default=32)
     ap.add_argument("--no-unplaced", action="store_true",
-                    help="skip the few steps of the same kernel on unplaced arenas (roofline.frac_unplaced)")
+                    help="--full: skip the few steps of the same kernel on unplaced arenas (roofline.frac_unplaced)")
     ap.add_argument("--e2e-after", type=float, default=2.0,
                     help="seconds after the arena placement before `e2e` is measured (the driver's transient after the placement walk)")
     ap.add_argument("--no-pin", action="store_true", help="N > 1: do not pin the rank to its GPU's NUMA node")
@@ -860,11 +872,18 @@ def main() -> int:
                          "float64, under 64 MB in all) to DIR/<name>.npy")
     ap.add_argument("--details", metavar="FILE", default=None,
                     help="write the whole record (every field the line summarises) to FILE as JSON")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1:
         raise SystemExit("--steps must be >= 1")
+    if not args.full:     # a plain run: none of the extras (the spot check, sw_reduce and scale_base test args.full itself)
+        args.no_cpu_baseline = args.no_configs = args.no_e2e = args.no_unplaced = True
+    return args
+
+
+def main() -> int:
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])      # no launcher around us: start the ranks ourselves
     return run(args)

@@ -54,3 +54,23 @@ def test_dump_outputs_is_a_fixed_exact_bounded_sample(tmp_path):
     idx = np.load(tmp_path / "c" / "rank1_pair_index.npy")
     m = np.load(tmp_path / "c" / "rank1_match.npy")
     assert len(idx) == 1 and np.array_equal(m, big.mats[int(idx[0]) - 6][0][:len(m)])
+
+
+def test_plain_run_leaves_every_extra_to_full():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "1"])
+    assert not plain.full
+    assert plain.no_cpu_baseline and plain.no_configs and plain.no_e2e and plain.no_unplaced
+    full = bench.parse_args(["--full"])
+    assert full.full and not (full.no_cpu_baseline or full.no_configs or full.no_e2e or full.no_unplaced)
+    some = bench.parse_args(["--full", "--no-e2e"])
+    assert some.no_e2e and not (some.no_cpu_baseline or some.no_configs or some.no_unplaced)
+
+
+def test_result_line_of_a_plain_record():
+    text = (ROOT / "profiles" / "r06" / "r06h_bench_default.json").read_text()
+    full = json.loads([l for l in text.splitlines() if l.startswith("{")][-1])
+    plain = {k: v for k, v in full.items() if k not in ("bit_exact_vs_oracle", "e2e", "sw_reduce", "configs", "cpu_baseline")}
+    line = bench.result_line(plain)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] == full[k], k
+    assert not {"bit_exact_vs_oracle", "e2e", "sw_reduce", "configs", "cpu_baseline"} & set(line)

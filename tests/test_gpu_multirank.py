@@ -18,7 +18,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
-ARGS = ["--gpus", "2", "--pairs", "4000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+# --full: the oracle spot check and scale_base asserted below are extras that a plain bench run leaves out
+ARGS = ["--gpus", "2", "--pairs", "4000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
 
 
 def _clean_env(**extra):
