@@ -469,6 +469,7 @@ enum {
   SEQALIGN_K_FILL_SW_BEST_X4,      /* SW best hit: direction bytes + the best cell, four pairs per wave            */
   SEQALIGN_K_SCORE_ROWS,           /* score only (seqalign_*_score_batch), one pair per wave, rows <= 1 024 columns */
   SEQALIGN_K_SCORE_STRIPS,         /* ... wider rows: strips of 512 columns, one wave each (items: pairs)          */
+  SEQALIGN_K_SCORE_CROSS,          /* score only over two sets (seqalign_*_score_cross), one wave per (query, target) */
   SEQALIGN_K_COUNT
 };
 #define SEQALIGN_K_MAX 32
@@ -537,6 +538,35 @@ int seqalign_nw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
                                   const scoring_t *scoring, int32_t *out_score);
 int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
                                   const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b);
+/* ---- score matrices: every query against every target, score only ---------------- */
+/* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
+typedef struct {
+  uint64_t n_seqs;
+  const char *arena;
+  uint64_t arena_bytes;
+  const uint64_t *off;   /* [n_seqs] */
+  const uint32_t *len;   /* [n_seqs] */
+} seqalign_seqset_t;
+/* The result of seqalign_*_score_batch on the batch of n_queries * n_targets pairs whose pair p = q * n_targets + t has
+ * seq_a = query q and seq_b = target t -- without that batch: the outputs are dense, row-major [n_queries][n_targets]
+ * (64-bit indexing), end_a indexes the query and end_b the target.  Each distinct sequence goes to the device once per tile
+ * (tiles: query ranges x target ranges within the context's chunk budget); queries of up to 1 024 columns run one wave per
+ * (query, target), longer ones the strips of seqalign_*_score_batch.  Argument checks and scoring admission
+ * (SEQALIGN_E_DOMAIN) are the score-batch calls'; no cell cap.  n_queries * n_targets overflowing uint64_t:
+ * SEQALIGN_E_ARG, before any array is read.  No queries or no targets: SEQALIGN_OK, nothing written.  A character pair
+ * without a score: SEQALIGN_E_UNKNOWN_PAIR, and seqalign_last_error names the failing pair with the lowest
+ * q * n_targets + t as "query Q, target T: ...".  On an error the outputs are unspecified. */
+int seqalign_nw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                            const scoring_t *scoring, int32_t *out_score);
+int seqalign_sw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                            const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b);
+/* ... over several contexts (GPUs): contiguous query ranges of nearly equal cells, each context writes its own rows;
+ * results exactly the single-context call's */
+int seqalign_nw_score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                  const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score);
+int seqalign_sw_score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                  const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score,
+                                  uint32_t *out_end_a, uint32_t *out_end_b);
 /* Kernel time of the score-only call (seq-align_amd/tools/score_bench.py): the batch is packed and uploaded once (it must
  * fit one chunk), then its score kernels run `repeats` times, each launch between two HIP events: ms_each[r]. */
 int seqalign_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int is_sw,

@@ -15,19 +15,10 @@ using namespace sa_host;
 
 namespace {
 
-constexpr int kRowClasses = 9;
-constexpr uint32_t kClassCpl[kRowClasses] = {1, 2, 3, 4, 5, 6, 8, 12, 16};   // sa_score.hip's instantiations
-constexpr int kStripClass = kRowClasses;                                      // rows over SA_SCORE_ROW_MAX columns
+constexpr int kRowClasses = SA_SCORE_ROW_CLASSES;   // sa_score.hip's instantiations (sa_score_row_class)
+constexpr int kStripClass = kRowClasses;           // rows over SA_SCORE_ROW_MAX columns
 constexpr uint64_t kPairBytes = 64;   // descriptors (32), results (12), status (8), slack
 constexpr uint64_t kChunkMaxPairs = (uint64_t)1 << 24;
-
-int row_class(uint32_t la) {
-  if (la > SA_SCORE_ROW_MAX) return kStripClass;
-  const uint32_t need = (la + 63) / 64;
-  int c = 0;
-  while (kClassCpl[c] < need) ++c;
-  return c;
-}
 
 // hand-off columns of one pair: strips 0 .. last - 1, len_b + 1 rows each, in int2 units
 uint64_t handoff_rows(uint32_t la, uint32_t lb) {
@@ -55,7 +46,9 @@ std::vector<ScoreChunk> plan_score_chunks(const seqalign_batch_t *b, size_t budg
   return out;
 }
 
-SaFillParams score_fill_params(const seqalign_dev_scoring *s) {
+}  // namespace
+
+SaFillParams sa_host::score_fill_params(const seqalign_dev_scoring *s) {
   SaFillParams p;
   memset(&p, 0, sizeof(p));
   p.code = s->d_code; p.table = s->d_table; p.K = s->flat.n_classes;
@@ -64,6 +57,8 @@ SaFillParams score_fill_params(const seqalign_dev_scoring *s) {
   p.table_abs_max = s->table_abs_max;
   return p;
 }
+
+namespace {
 
 // One chunk laid out and uploaded; launch() enqueues its kernels on ctx->stream (repeatable: it re-zeroes what they count on)
 struct ScoreChunkRun {
@@ -88,7 +83,7 @@ struct ScoreChunkRun {
     uint64_t hand_total = 0;
     for (uint64_t k = 0; k < n; ++k) {
       const uint32_t la = b->len_a[c.first + k];
-      const int x = row_class(la);
+      const int x = sa_score_row_class(la);
       cls[k] = (uint8_t)x; cnt[x]++;
       cls_max_a[x] = std::max(cls_max_a[x], la);
     }
@@ -178,7 +173,7 @@ struct ScoreChunkRun {
   }
 
   // results home, in pair order; the lowest failing pair of the chunk named
-  int finish(uint64_t first, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
+  int finish(uint64_t first, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, uint64_t *fail_pair = nullptr) {
     int rc;
     const size_t words = 4 + (is_sw ? 3 : 1) * n;
     if ((rc = ctx->h_misc.reserve(std::max<size_t>(4 * words, 8 * n)))) return rc;
@@ -191,6 +186,7 @@ struct ScoreChunkRun {
       uint64_t worst = ~0ull;
       for (uint64_t s = 0; s < n; ++s)
         if (status[s] != ~0ull) worst = std::min<uint64_t>(worst, order[s]);
+      if (fail_pair) *fail_pair = first + worst;
       set_last_error("pair " + std::to_string(first + worst) + ": a character pair without a score");
       return SEQALIGN_E_UNKNOWN_PAIR;
     }
@@ -213,8 +209,10 @@ int check_score_batch(const seqalign_batch_t *b) {   // check_batch without the 
   return SEQALIGN_OK;
 }
 
-int score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw,
-                     int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
+}  // namespace
+
+int sa_host::score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw,
+                              int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, uint64_t *fail_pair) {
   int rc = check_score_batch(batch);
   if (rc) return rc;
   if (batch->n_pairs == 0) return SEQALIGN_OK;
@@ -225,12 +223,12 @@ int score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const s
   for (const ScoreChunk &c : plan_score_chunks(batch, ctx->chunk_budget)) {
     ScoreChunkRun run;
     run.ctx = ctx; run.sc = sc; run.is_sw = is_sw;
-    if ((rc = run.prepare(batch, c)) || (rc = run.launch()) || (rc = run.finish(c.first, out_score, out_end_a, out_end_b))) return rc;
+    if ((rc = run.prepare(batch, c)) || (rc = run.launch()) ||
+        (rc = run.finish(c.first, out_score, out_end_a, out_end_b, fail_pair)))
+      return rc;
   }
   return SEQALIGN_OK;
 }
-
-}  // namespace
 
 extern "C" int seqalign_nw_score_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                        int32_t *out_score) {

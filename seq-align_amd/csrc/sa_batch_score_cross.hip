@@ -1,0 +1,299 @@
+// sa_batch_score_cross.hip -- score matrices: seqalign_nw_score_cross / seqalign_sw_score_cross, every query of one set
+// against every target of another, score only.  The result is seqalign_*_score_batch's on the batch whose pair
+// q * n_targets + t is (query q, target t), but that batch is never built: its descriptors and its packed sequences grow
+// with Q x T, the sets themselves with Q + T.
+//
+// Queries of up to SA_SCORE_ROW_MAX columns: tiles of (query range x target range) within ctx->chunk_budget -- the tile's
+// sequences, their descriptors and 4 (NW) / 12 (SW) bytes of results per pair.  Usually every target fits one range and a
+// tile is a query range; the targets then go up once per call.  Per tile: each sequence uploaded once, one
+// score_cross_kernel launch per row class of its queries (sa_score.hip: wave -> (query, target), longest targets first),
+// the result rows home and copied row by row into the caller's matrix.  A failing pair leaves its tile-local index
+// q * n_t + t in one 64-bit atomicMin; a tile's order is the matrix's row-major order restricted to the tile, so the lowest
+// tile-local index is the tile's lowest failing pair, and the call's is the lowest over the tiles of the first query range
+// that has one.
+//
+// Longer queries: seqalign_*_score_batch's strips, on explicit pair lists (a few long queries x a slice of the targets),
+// results scattered into the matrix.  Such a pair is over 1 024 x len_b cells: building its descriptor costs nothing next to it.
+#include "sa_ctx.hpp"
+
+using namespace sa_host;
+
+namespace {
+
+constexpr uint64_t kSeqBytes = 16;                        // per sequence besides its bytes: offset 8, length 4, list entry 4
+constexpr uint64_t kTileMaxPairs = (uint64_t)1 << 24;     // one launch's waves (as kChunkMaxPairs of the score batches)
+constexpr uint64_t kLongSlicePairs = (uint64_t)1 << 16;   // pairs of one score-batch slice of the long queries
+
+struct Range {
+  uint64_t first = 0, count = 0, bytes = 0;   // into a list of sequences; bytes: their characters
+};
+
+// Cut `idx` (sequences of `s`) into ranges whose cost sum(len + kSeqBytes) + count * per_seq stays within `budget` and whose
+// count stays within max_count; at least one sequence per range.
+std::vector<Range> cut_ranges(const seqalign_seqset_t *s, const std::vector<uint64_t> &idx, uint64_t budget, uint64_t per_seq,
+                              uint64_t max_count) {
+  std::vector<Range> out;
+  Range r;
+  uint64_t used = 0;
+  for (uint64_t k = 0; k < idx.size(); ++k) {
+    const uint64_t len = s->len[idx[k]], need = len + kSeqBytes + per_seq;
+    if (r.count && (used + need > budget || r.count == max_count)) { out.push_back(r); r = Range(); r.first = k; used = 0; }
+    used += need;
+    r.count++; r.bytes += len;
+  }
+  if (r.count) out.push_back(r);
+  return out;
+}
+
+// the lowest failing pair of the call so far (row-major key q * n_targets + t)
+struct FailPair {
+  uint64_t key = ~0ull, q = 0, t = 0;
+  void offer(uint64_t q_, uint64_t t_, uint64_t n_t) {
+    const uint64_t k = q_ * n_t + t_;
+    if (k < key) { key = k; q = q_; t = t_; }
+  }
+  bool any() const { return key != ~0ull; }
+};
+
+struct CrossCall {
+  seqalign_ctx *ctx;
+  const seqalign_seqset_t *Q, *T;
+  const scoring_t *scoring;
+  bool is_sw;
+  int32_t *out_score;
+  uint32_t *out_end_a, *out_end_b;
+  uint64_t nT;
+  FailPair fail;
+
+  uint64_t result_bytes() const { return is_sw ? 12 : 4; }
+
+  // queries <= SA_SCORE_ROW_MAX: the cross kernel, tile by tile
+  int run_short(const std::vector<uint64_t> &qs) {
+    int rc;
+    seqalign_dev_scoring *sc = nullptr;
+    if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
+    const uint64_t budget = std::max<uint64_t>(ctx->chunk_budget, 4096), rp = result_bytes();
+
+    std::vector<uint64_t> ts(nT);
+    for (uint64_t t = 0; t < nT; ++t) ts[t] = t;
+    // targets: at most half the budget in bytes, a quarter in one row of results
+    const std::vector<Range> t_ranges = cut_ranges(T, ts, budget / 2, 0, std::max<uint64_t>(1, std::min(kTileMaxPairs, budget / 4 / rp)));
+    uint64_t tb_max = 0, nt_max = 0;
+    for (const Range &r : t_ranges) { tb_max = std::max(tb_max, r.bytes); nt_max = std::max(nt_max, r.count); }
+    const uint64_t t_room = tb_max + nt_max * kSeqBytes;
+    const std::vector<Range> q_ranges = cut_ranges(Q, qs, budget > t_room ? budget - t_room : 0, nt_max * rp,
+                                                   std::max<uint64_t>(1, kTileMaxPairs / nt_max));
+    uint64_t qb_max = 0, nq_max = 0;
+    for (const Range &r : q_ranges) { qb_max = std::max(qb_max, r.bytes); nq_max = std::max(nq_max, r.count); }
+
+    // every buffer at its largest before anything goes up (a DevBuf that grows loses its contents): sequences, targets
+    // first; descriptors off_t, off_q (u64), len_t, t_order, len_q, q_list (u32); results: err_flag, -, err_pair (u64), then
+    // score, end_a, end_b
+    const uint64_t q_at = (tb_max + 15) & ~(uint64_t)15;
+    const uint64_t desc_bytes = 16 * (nt_max + nq_max);
+    const uint64_t res_bytes = 16 + rp * nq_max * nt_max;
+    if ((rc = ctx->arena.reserve(q_at + qb_max + 16)) || (rc = ctx->off_a.reserve(desc_bytes)) ||
+        (rc = ctx->best_score.reserve(res_bytes)) || (rc = ctx->h_arena.reserve(q_at + qb_max + 16)) ||
+        (rc = ctx->h_desc.reserve(desc_bytes)) || (rc = ctx->h_misc.reserve(res_bytes)))
+      return rc;
+    uint8_t *h_seq = ctx->h_arena.as<uint8_t>();
+    uint64_t *h_off_t = ctx->h_desc.as<uint64_t>(), *h_off_q = h_off_t + nt_max;
+    uint32_t *h_len_t = reinterpret_cast<uint32_t *>(h_off_q + nq_max), *h_tord = h_len_t + nt_max;
+    uint32_t *h_len_q = h_tord + nt_max, *h_qlist = h_len_q + nq_max;
+    uint64_t *d_off_t = ctx->off_a.as<uint64_t>(), *d_off_q = d_off_t + nt_max;
+    uint32_t *d_len_t = reinterpret_cast<uint32_t *>(d_off_q + nq_max), *d_tord = d_len_t + nt_max;
+    uint32_t *d_len_q = d_tord + nt_max, *d_qlist = d_len_q + nq_max;
+    uint32_t *d_res = ctx->best_score.as<uint32_t>();
+    uint8_t *d_seq = ctx->arena.as<uint8_t>();
+    hipStream_t st = ctx->stream;
+    const SaFillParams f0 = score_fill_params(sc);
+
+    // sequences idx[first .. first + n) packed from `s` at h_seq + at: offsets (from the device arena's start) and lengths
+    auto pack = [&](const seqalign_seqset_t *s, const uint64_t *idx, uint64_t n, uint64_t at, uint64_t *h_off, uint32_t *h_len) {
+      uint64_t pos = at;
+      for (uint64_t k = 0; k < n; ++k) { h_off[k] = pos; h_len[k] = s->len[idx[k]]; pos += h_len[k]; }
+      constexpr uint64_t kTask = 256;
+      parallel_for((n + kTask - 1) / kTask, [&](uint64_t blk) {
+        for (uint64_t k = blk * kTask, e = std::min(n, (blk + 1) * kTask); k < e; ++k)
+          memcpy(h_seq + h_off[k], s->arena + s->off[idx[k]], h_len[k]);
+      });
+      return pos - at;
+    };
+
+    for (const Range &qr : q_ranges) {
+      for (const Range &tr : t_ranges) {
+        const uint64_t nq = qr.count, nt = tr.count;
+        if (t_ranges.size() > 1 || &qr == &q_ranges[0]) {   // the targets of this range (once per call when there is one range)
+          const uint64_t bytes = pack(T, ts.data() + tr.first, nt, 0, h_off_t, h_len_t);
+          for (uint64_t k = 0; k < nt; ++k) h_tord[k] = (uint32_t)k;
+          std::stable_sort(h_tord, h_tord + nt, [&](uint32_t x, uint32_t y) { return h_len_t[x] > h_len_t[y]; });
+          if (bytes) HIP_TRY(hipMemcpyAsync(d_seq, h_seq, bytes, hipMemcpyHostToDevice, st));
+          HIP_TRY(hipMemcpyAsync(d_off_t, h_off_t, 8 * nt, hipMemcpyHostToDevice, st));
+          HIP_TRY(hipMemcpyAsync(d_len_t, h_len_t, 4 * nt, hipMemcpyHostToDevice, st));
+          HIP_TRY(hipMemcpyAsync(d_tord, h_tord, 4 * nt, hipMemcpyHostToDevice, st));
+        }
+        const uint64_t bytes = pack(Q, qs.data() + qr.first, nq, q_at, h_off_q, h_len_q);
+        // the queries by row class: q_list holds class 0's, then class 1's, ...
+        uint64_t cls_first[SA_SCORE_ROW_CLASSES + 1] = {};
+        uint32_t cls_max_a[SA_SCORE_ROW_CLASSES] = {};
+        for (uint64_t k = 0; k < nq; ++k) {
+          const int x = sa_score_row_class(h_len_q[k]);
+          cls_first[x + 1]++;
+          cls_max_a[x] = std::max(cls_max_a[x], h_len_q[k]);
+        }
+        for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) cls_first[x + 1] += cls_first[x];
+        { uint64_t at[SA_SCORE_ROW_CLASSES];
+          for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) at[x] = cls_first[x];
+          for (uint64_t k = 0; k < nq; ++k) h_qlist[at[sa_score_row_class(h_len_q[k])]++] = (uint32_t)k; }
+        if (bytes) HIP_TRY(hipMemcpyAsync(d_seq + q_at, h_seq + q_at, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_off_q, h_off_q, 8 * nq, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_len_q, h_len_q, 4 * nq, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_qlist, h_qlist, 4 * nq, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_res, 0, 8, st));
+        HIP_TRY(hipMemsetAsync(d_res + 2, 0xff, 8, st));
+
+        const uint64_t n = nq * nt;
+        for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) {
+          const uint64_t m = cls_first[x + 1] - cls_first[x];
+          if (!m) continue;
+          SaScoreCrossParams p;
+          memset(&p, 0, sizeof(p));
+          p.f = f0;
+          p.f.arena = d_seq;
+          p.f.off_a = d_off_q; p.f.len_a = d_len_q; p.f.off_b = d_off_t; p.f.len_b = d_len_t;
+          p.q_list = d_qlist + cls_first[x]; p.t_order = d_tord;
+          p.nq = (uint32_t)m; p.n_t = (uint32_t)nt; p.n_waves = (uint32_t)(m * nt);
+          p.score = reinterpret_cast<int32_t *>(d_res + 4);
+          p.end_a = d_res + 4 + n; p.end_b = d_res + 4 + 2 * n;
+          p.err_flag = d_res;
+          p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
+          const hipError_t e = sa_launch_score_cross(p, cls_max_a[x], is_sw, st);
+          if (e != hipSuccess) return fail_hip(e, "score cross kernel launch");
+        }
+
+        // results home; rows into the matrix
+        uint32_t *h = ctx->h_misc.as<uint32_t>();
+        HIP_TRY(hipMemcpyAsync(h, d_res, 16 + rp * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(stream_wait_spinning(st));
+        if (h[0]) {
+          uint64_t key;
+          memcpy(&key, h + 2, 8);
+          fail.offer(qs[qr.first + key / nt], tr.first + key % nt, nT);
+          continue;
+        }
+        const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
+        const uint32_t *ha = h + 4 + n, *hb = h + 4 + 2 * n;
+        constexpr uint64_t kRows = 64;
+        parallel_for((nq + kRows - 1) / kRows, [&](uint64_t blk) {
+          for (uint64_t k = blk * kRows, e = std::min(nq, (blk + 1) * kRows); k < e; ++k) {
+            const uint64_t row = qs[qr.first + k] * nT + tr.first;
+            memcpy(out_score + row, hs + k * nt, 4 * nt);
+            if (is_sw) {
+              memcpy(out_end_a + row, ha + k * nt, 4 * nt);
+              memcpy(out_end_b + row, hb + k * nt, 4 * nt);
+            }
+          }
+        });
+      }
+      if (fail.any()) break;   // the later query ranges hold only higher pairs
+    }
+    return SEQALIGN_OK;
+  }
+
+  // queries > SA_SCORE_ROW_MAX: score-batch slices of (a few long queries x a slice of the targets), through the strips
+  int run_long(const std::vector<uint64_t> &qs) {
+    int rc;
+    // one arena of their own for the batches: the long queries, then the targets
+    std::vector<uint64_t> at_q(qs.size()), at_t(nT);
+    uint64_t pos = 0;
+    for (uint64_t k = 0; k < qs.size(); ++k) { at_q[k] = pos; pos += Q->len[qs[k]]; }
+    for (uint64_t t = 0; t < nT; ++t) { at_t[t] = pos; pos += T->len[t]; }
+    std::vector<char> arena(pos + 1);
+    for (uint64_t k = 0; k < qs.size(); ++k) memcpy(arena.data() + at_q[k], Q->arena + Q->off[qs[k]], Q->len[qs[k]]);
+    for (uint64_t t = 0; t < nT; ++t) memcpy(arena.data() + at_t[t], T->arena + T->off[t], T->len[t]);
+
+    const uint64_t t_slice = std::min(nT, kLongSlicePairs), q_rows = std::max<uint64_t>(1, kLongSlicePairs / nT);
+    std::vector<uint64_t> off_a, off_b;
+    std::vector<uint32_t> len_a, len_b, ea, eb;
+    std::vector<int32_t> sc;
+    for (uint64_t g0 = 0; g0 < qs.size(); g0 += q_rows) {
+      const uint64_t g1 = std::min<uint64_t>(qs.size(), g0 + q_rows);
+      if (fail.any() && qs[g0] > fail.q) break;   // only higher pairs from here on
+      for (uint64_t t0 = 0; t0 < nT; t0 += t_slice) {
+        const uint64_t t1 = std::min(nT, t0 + t_slice), nt = t1 - t0, n = (g1 - g0) * nt;
+        off_a.resize(n); off_b.resize(n); len_a.resize(n); len_b.resize(n); sc.resize(n); ea.resize(n); eb.resize(n);
+        for (uint64_t k = 0; k < n; ++k) {
+          const uint64_t g = g0 + k / nt, t = t0 + k % nt;
+          off_a[k] = at_q[g]; len_a[k] = Q->len[qs[g]];
+          off_b[k] = at_t[t]; len_b[k] = T->len[t];
+        }
+        seqalign_batch_t b;
+        b.n_pairs = n; b.arena = arena.data(); b.arena_bytes = arena.size();
+        b.off_a = off_a.data(); b.len_a = len_a.data(); b.off_b = off_b.data(); b.len_b = len_b.data();
+        uint64_t bad = ~0ull;
+        rc = score_batch_impl(ctx, &b, scoring, is_sw, sc.data(), ea.data(), eb.data(), &bad);
+        if (rc == SEQALIGN_E_UNKNOWN_PAIR && bad != ~0ull) {
+          fail.offer(qs[g0 + bad / nt], t0 + bad % nt, nT);
+          continue;
+        }
+        if (rc) return rc;
+        for (uint64_t k = 0; k < n; ++k) {
+          const uint64_t at = qs[g0 + k / nt] * nT + t0 + k % nt;
+          out_score[at] = sc[k];
+          if (is_sw) { out_end_a[at] = ea[k]; out_end_b[at] = eb[k]; }
+        }
+      }
+      if (fail.any()) break;
+    }
+    return SEQALIGN_OK;
+  }
+};
+
+int check_set(const seqalign_seqset_t *s) {
+  return !s || (s->n_seqs && (!s->arena || !s->off || !s->len)) ? SEQALIGN_E_ARG : SEQALIGN_OK;
+}
+
+}  // namespace
+
+int sa_host::score_cross_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets) {
+  if (check_set(queries) || check_set(targets)) return SEQALIGN_E_ARG;
+  if (targets->n_seqs && queries->n_seqs > ~0ull / targets->n_seqs) {
+    set_last_error("score cross: n_queries x n_targets overflows 64 bits");
+    return SEQALIGN_E_ARG;
+  }
+  return SEQALIGN_OK;
+}
+
+int sa_host::score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                              const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a,
+                              uint32_t *out_end_b, uint64_t q_base) {
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  StreamSyncOnExit sync(ctx->stream);
+  CrossCall call{ctx, queries, targets, scoring, is_sw, out_score, out_end_a, out_end_b, targets->n_seqs, FailPair()};
+  std::vector<uint64_t> short_q, long_q;
+  for (uint64_t q = 0; q < queries->n_seqs; ++q) (queries->len[q] > SA_SCORE_ROW_MAX ? long_q : short_q).push_back(q);
+  if (!short_q.empty() && (rc = call.run_short(short_q))) return rc;
+  if (!long_q.empty() && (rc = call.run_long(long_q))) return rc;
+  if (call.fail.any()) {
+    set_last_error("query " + std::to_string(q_base + call.fail.q) + ", target " + std::to_string(call.fail.t) +
+                   ": a character pair without a score");
+    return SEQALIGN_E_UNKNOWN_PAIR;
+  }
+  return SEQALIGN_OK;
+}
+
+extern "C" int seqalign_nw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                       const scoring_t *scoring, int32_t *out_score) {
+  if (!ctx || !scoring || !out_score) return SEQALIGN_E_ARG;
+  return score_cross_call(ctx, queries, targets, scoring, false, out_score, nullptr, nullptr, 0);
+}
+
+extern "C" int seqalign_sw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                       const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
+  if (!ctx || !scoring || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
+  return score_cross_call(ctx, queries, targets, scoring, true, out_score, out_end_a, out_end_b, 0);
+}

@@ -6,6 +6,7 @@
 //   sa_batch.hip      host-level chunking, seqalign_fill_batch, seqalign_nw_batch
 //   sa_batch_sw.hip   seqalign_sw_batch (best hit / device enumeration / host enumeration)
 //   sa_batch_score.hip seqalign_nw_score_batch / seqalign_sw_score_batch (score only)
+//   sa_batch_score_cross.hip seqalign_nw_score_cross / seqalign_sw_score_cross (score only, every query x every target)
 //   sa_multi.hip      the same calls over several contexts (GPUs) from one process
 #pragma once
 #include <hip/hip_runtime.h>
@@ -399,7 +400,19 @@ struct CallScope {
   CallScope &operator=(const CallScope &) = delete;
 };
 
-void async_shutdown(seqalign_ctx *ctx);   // sa_async.hip: drain the submitted jobs, join the lanes (seqalign_ctx_destroy)
+void async_shutdown(seqalign_ctx *ctx);
+
+// sa_batch_score.hip, shared with the cross calls (sa_batch_score_cross.hip): the score kernels' SaFillParams of an uploaded
+// scoring, and seqalign_*_score_batch without its entry checks -- fail_pair (optional): the failing pair it names
+SaFillParams score_fill_params(const seqalign_dev_scoring *s);
+int score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw,
+                     int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, uint64_t *fail_pair = nullptr);
+// sa_batch_score_cross.hip: the sets' checks (E_ARG; n_queries x n_targets must fit 64 bits), and one context's cross call
+// (its own CallScope) -- q_base: what the error message adds to a query index (the *_multi calls' ranges)
+int score_cross_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets);
+int score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                     const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b,
+                     uint64_t q_base);   // sa_async.hip: drain the submitted jobs, join the lanes (seqalign_ctx_destroy)
 
 struct CigarScope {   // RAII: the call's output format, put back on every way out
   seqalign_ctx *ctx;

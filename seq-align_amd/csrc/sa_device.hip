@@ -77,7 +77,8 @@ extern "C" const char *seqalign_kernel_kind_name(int kind) {
       "fill_wavefront", "fill_rowscan", "fill_stream", "fill_strips", "fill_wgstream", "fill_nw_dirs", "fill_nw_dirs_x2",
       "fill_sw_dirs", "fill_sw_dirs_x2", "fill_sw_best_x2", "sw_reduce", "sw_box", "sweep_regs", "sweep_lds", "sweep_strips",
       "sweep_dirs", "sweep_dirs_x2", "walk_lane", "walk_wave", "walk_dirs_lane", "walk_dirs_tile", "walk_moves_lane",
-      "walk_moves_tile", "fill_nw_dirs_x4", "fill_sw_best_x4", "score_rows", "score_strips"};
+      "walk_moves_tile", "fill_nw_dirs_x4", "fill_sw_best_x4", "score_rows", "score_strips",
+      "score_cross"};
   return kind >= 0 && kind < SEQALIGN_K_COUNT ? names[kind] : nullptr;
 }
 

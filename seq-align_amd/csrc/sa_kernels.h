@@ -388,6 +388,32 @@ uint32_t sa_score_strips_per_pair(uint32_t max_len_a);
 hipError_t sa_launch_score_rows(const SaScoreParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream);
 /* the caller zeroed progress (and err_flag) and set status to ~0 */
 hipError_t sa_launch_score_strips(const SaScoreParams &p, bool is_sw, hipStream_t stream);
+/* The one-wave kernels' row classes: columns per lane 1 .. 16 in these steps, one launch per class; a row of len_a columns
+ * takes the narrowest class that holds it (SA_SCORE_ROW_CLASSES: wider than SA_SCORE_ROW_MAX, the strips kernel). */
+#define SA_SCORE_ROW_CLASSES 9
+static inline int sa_score_row_class(uint32_t len_a) {
+  static const uint32_t cpl[SA_SCORE_ROW_CLASSES] = {1, 2, 3, 4, 5, 6, 8, 12, 16};
+  if (len_a > SA_SCORE_ROW_MAX) return SA_SCORE_ROW_CLASSES;
+  const uint32_t need = (len_a + 63) / 64;
+  int c = 0;
+  while (cpl[c] < need) ++c;
+  return c;
+}
+/* score only over two sets (seqalign_*_score_cross): one launch per row class of the queries, one wave per (query, target).
+ * f.off_a / f.len_a: the tile's queries, f.off_b / f.len_b: its targets, both into f.arena; f.n_pairs, f.status unused. */
+struct SaScoreCrossParams {
+  SaFillParams f;
+  const uint32_t *q_list;       /* [nq] the class's queries (indices into f.off_a / f.len_a)                           */
+  const uint32_t *t_order;      /* [n_t] every target of the tile, longest first (indices into f.off_b / f.len_b)       */
+  uint32_t nq, n_t;
+  uint32_t n_waves;             /* nq * n_t                                                                            */
+  int32_t *score;               /* [q * n_t + t] for every query q of the tile                                         */
+  uint32_t *end_a, *end_b;      /* (SW)                                                                                */
+  uint32_t *err_flag;           /* |= 1 when a pair has a cell without a score                                         */
+  unsigned long long *err_pair; /* min of q * n_t + t over those pairs; the caller set it to ~0                        */
+};
+/* every query of the class has len_a <= max_len_a <= SA_SCORE_ROW_MAX */
+hipError_t sa_launch_score_cross(const SaScoreCrossParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */
 bool sa_wgstream_kernel_applicable(const SaFillParams &p, uint32_t max_len_a);
 hipError_t sa_launch_fill_wgstream(const SaFillParams &p, uint32_t max_len_a, hipStream_t stream);

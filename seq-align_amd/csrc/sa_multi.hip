@@ -19,10 +19,8 @@ seqalign_batch_t sub_batch(const seqalign_batch_t *b, uint64_t first, uint64_t c
 // (balance ragged batches by W*H; contiguous, so results stay in pair order): edge k is the
 // pair boundary nearest to k/n_ctx of the cell total, ties to the later boundary -- the rule of
 // workloads.shard_edges_cells on the Python side.
-std::vector<uint64_t> shard_edges(const seqalign_batch_t *b, int n_ctx) {
-  const uint64_t n = b->n_pairs;
-  std::vector<uint64_t> cum(n + 1, 0);
-  for (uint64_t p = 0; p < n; ++p) cum[p + 1] = cum[p] + (uint64_t)(b->len_a[p] + 1ull) * (b->len_b[p] + 1ull);
+std::vector<uint64_t> shard_edges_cum(const std::vector<uint64_t> &cum, int n_ctx) {   // cum[k]: cells of items 0 .. k - 1
+  const uint64_t n = cum.size() - 1;
   const uint64_t total = cum[n];
   std::vector<uint64_t> edges((size_t)n_ctx + 1, 0);
   for (int k = 1; k < n_ctx; ++k) {
@@ -34,6 +32,13 @@ std::vector<uint64_t> shard_edges(const seqalign_batch_t *b, int n_ctx) {
   }
   edges[n_ctx] = n;
   return edges;
+}
+
+std::vector<uint64_t> shard_edges(const seqalign_batch_t *b, int n_ctx) {
+  const uint64_t n = b->n_pairs;
+  std::vector<uint64_t> cum(n + 1, 0);
+  for (uint64_t p = 0; p < n; ++p) cum[p + 1] = cum[p] + (uint64_t)(b->len_a[p] + 1ull) * (b->len_b[p] + 1ull);
+  return shard_edges_cum(cum, n_ctx);
 }
 
 // run fn(g, first, count) for the n_ctx contiguous ranges, one host thread each; first error wins
@@ -192,4 +197,37 @@ extern "C" int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_
     const seqalign_batch_t s = sub_batch(batch, first, count);
     return seqalign_sw_score_batch(ctxs[g], &s, scoring, out_score + first, out_end_a + first, out_end_b + first);
   });
+}
+
+// score matrices: contiguous query ranges of nearly equal cells -- a query's cells are (len + 1) x the targets' sum of
+// (len + 1), a factor common to all, so the ranges are cut by len + 1 -- each context writes its own rows
+namespace {
+int score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                      const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  const uint64_t nq = queries->n_seqs, nt = targets->n_seqs;
+  if (!nq || !nt) return SEQALIGN_OK;
+  std::vector<uint64_t> cum(nq + 1, 0);
+  for (uint64_t q = 0; q < nq; ++q) cum[q + 1] = cum[q] + queries->len[q] + 1ull;
+  return for_each_shard(shard_edges_cum(cum, n_ctx), [&](int g, uint64_t first, uint64_t count) {
+    seqalign_seqset_t s = *queries;
+    s.n_seqs = count; s.off = queries->off + first; s.len = queries->len + first;
+    return score_cross_call(ctxs[g], &s, targets, scoring, is_sw, out_score + first * nt,
+                            is_sw ? out_end_a + first * nt : nullptr, is_sw ? out_end_b + first * nt : nullptr, first);
+  });
+}
+}  // namespace
+
+extern "C" int seqalign_nw_score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                             const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score) {
+  if (bad_ctx_list(ctxs, n_ctx) || !scoring || !out_score) return SEQALIGN_E_ARG;
+  return score_cross_multi(ctxs, n_ctx, queries, targets, scoring, false, out_score, nullptr, nullptr);
+}
+
+extern "C" int seqalign_sw_score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                             const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score,
+                                             uint32_t *out_end_a, uint32_t *out_end_b) {
+  if (bad_ctx_list(ctxs, n_ctx) || !scoring || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
+  return score_cross_multi(ctxs, n_ctx, queries, targets, scoring, true, out_score, out_end_a, out_end_b);
 }

@@ -10,6 +10,8 @@
 //
 // score_rows_kernel: rows of up to 1 024 columns, one wave per pair (CPL = 1..16 columns per lane), 4 pairs per
 // workgroup.  len_b is unlimited: seq_b's codes arrive 64 rows at a time, the left border column is arithmetic.
+// Its CROSS form (seqalign_*_score_cross, kind "score_cross") takes a query and a target of two sets instead of a pair of
+// a list: same sweep, same end picks, only which sequences a wave reads and where its result goes differ.
 //
 // score_strips_kernel: wider rows, the pipeline of sa_fill_strips.hip (tickets drawn when a workgroup starts, waits only
 // on lower tickets, agent-scope release / acquire of a rows-done word per strip) -- but what strip s hands strip s + 1 is
@@ -18,6 +20,8 @@
 // rows at a time: lane q keeps row j0 + q's pair of values, the 64 rows leave as one coalesced 512-byte store.  SW: each
 // strip merges its best cell into the best of the strips to its left (visible: it waited for their last rows) and hands
 // that on; the last strip writes the pair's result.  Cell indices and the error key are 64-bit (len_a x len_b may pass 2^32).
+#include <type_traits>
+
 #include "sa_rowsweep.hpp"
 
 namespace sa {
@@ -69,9 +73,13 @@ struct BestCells {
   }
 };
 
-template <int CPL, int SUBST, bool GENERAL, bool SW>
+// CROSS: wave w of a launch for one row class takes target t_order[w / nq] and query q_list[w % nq].  t_order runs longest
+// first; within a class a row costs the same whatever len_a is, so a wave's cost follows its target's length and the long
+// ones start first.  That order is for speed only: which wave runs when decides no result.  The result goes to
+// [q * n_t + t] of the tile; a failing pair leaves only its index, in one 64-bit atomicMin.
+template <int CPL, int SUBST, bool GENERAL, bool SW, bool CROSS = false>
 __global__ void __launch_bounds__(kWave *kWavesPerBlock)
-score_rows_kernel(const SaScoreParams sp) {
+score_rows_kernel(const std::conditional_t<CROSS, SaScoreCrossParams, SaScoreParams> sp) {
   const SaFillParams &p = sp.f;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
   const int32_t *table = p.table;
@@ -83,11 +91,21 @@ score_rows_kernel(const SaScoreParams sp) {
 
   const int lane = threadIdx.x & (kWave - 1);
   const uint32_t pair = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
-  if (pair >= p.n_pairs) return;   // wave-uniform, after the only barrier
+  uint32_t qa = pair, tb = pair;   // descriptors of seq_a and seq_b
+  uint64_t at = pair;              // where the result goes
+  if constexpr (CROSS) {
+    if (pair >= sp.n_waves) return;   // wave-uniform, after the only barrier
+    const uint32_t ti = pair / sp.nq;
+    qa = sp.q_list[pair - ti * sp.nq];
+    tb = sp.t_order[ti];
+    at = (uint64_t)qa * sp.n_t + tb;
+  } else {
+    if (pair >= p.n_pairs) return;   // wave-uniform, after the only barrier
+  }
 
-  const uint32_t la = p.len_a[pair], lb = p.len_b[pair];
-  const uint8_t *__restrict__ sa_ = p.arena + p.off_a[pair];
-  const uint8_t *__restrict__ sb_ = p.arena + p.off_b[pair];
+  const uint32_t la = p.len_a[qa], lb = p.len_b[tb];
+  const uint8_t *__restrict__ sa_ = p.arena + p.off_a[qa];
+  const uint8_t *__restrict__ sb_ = p.arena + p.off_b[tb];
   const uint32_t W = la + 1;
 
   const SweepConsts k(p, table);
@@ -122,22 +140,29 @@ score_rows_kernel(const SaScoreParams sp) {
     unsigned long long key;
     best.reduce(col0, ncol, score, key);
     if (lane == 0) {
-      sp.score[pair] = score;
-      sp.end_a[pair] = score > 0 ? (uint32_t)(key >> 32) : 0u;
-      sp.end_b[pair] = score > 0 ? (uint32_t)key : 0u;
+      sp.score[at] = score;
+      sp.end_a[at] = score > 0 ? (uint32_t)(key >> 32) : 0u;
+      sp.end_b[at] = score > 0 ? (uint32_t)key : 0u;
     }
   } else {
     if (la == 0) {   // cell (0, len_b) of the border column
-      if (lane == 0) sp.score[pair] = lb == 0 ? 0 : max(k.floor_, bd.edge_gap(lb));
+      if (lane == 0) sp.score[at] = lb == 0 ? 0 : max(k.floor_, bd.edge_gap(lb));
     } else {
 #pragma unroll
       for (int c = 0; c < CPL; ++c)
-        if (col0 + c + 1 == la) sp.score[pair] = sw.X[c];   // max(M, A, B) of (len_a, len_b)
+        if (col0 + c + 1 == la) sp.score[at] = sw.X[c];   // max(M, A, B) of (len_a, len_b)
     }
   }
-  if (lane == 0) {
-    p.status[pair] = err;
-    if (err != ~0ull) atomicOr(sp.err_flag, 1u);
+  if constexpr (CROSS) {
+    if (lane == 0 && err != ~0ull) {
+      atomicMin(sp.err_pair, (unsigned long long)at);
+      atomicOr(sp.err_flag, 1u);
+    }
+  } else {
+    if (lane == 0) {
+      p.status[pair] = err;
+      if (err != ~0ull) atomicOr(sp.err_flag, 1u);
+    }
   }
 }
 
@@ -267,36 +292,40 @@ score_strips_kernel(const SaScoreParams sp) {
   }
 }
 
-template <int CPL, bool SW>
-static hipError_t launch_rows_cpl(const SaScoreParams &p, hipStream_t stream) {
+inline uint32_t one_wave_waves(const SaScoreParams &p) { return p.f.n_pairs; }
+inline uint32_t one_wave_waves(const SaScoreCrossParams &p) { return p.n_waves; }
+
+template <int CPL, bool SW, bool CROSS, class P>
+static hipError_t launch_rows_cpl(const P &p, hipStream_t stream) {
   const bool general = needs_general(p.f);
-  const dim3 grid((p.f.n_pairs + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
+  const dim3 grid((one_wave_waves(p) + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
   const uint32_t K = p.f.K;
   if (K <= 1) {
-    if (general) hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_SIMPLE, true, SW>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_SIMPLE, false, SW>), grid, block, 0, stream, p);
+    if (general) hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_SIMPLE, true, SW, CROSS>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_SIMPLE, false, SW, CROSS>), grid, block, 0, stream, p);
   } else if (K <= SA_LDS_TABLE_MAX_K) {
     const size_t lds = (size_t)K * K * sizeof(int32_t);
-    if (general) hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_LDS, true, SW>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_LDS, false, SW>), grid, block, lds, stream, p);
+    if (general) hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_LDS, true, SW, CROSS>), grid, block, lds, stream, p);
+    else hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_LDS, false, SW, CROSS>), grid, block, lds, stream, p);
   } else {
-    hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_GLOBAL, true, SW>), grid, block, 0, stream, p);
+    hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_GLOBAL, true, SW, CROSS>), grid, block, 0, stream, p);
   }
   return hipGetLastError();
 }
 
-template <bool SW>
-static hipError_t launch_rows(const SaScoreParams &p, uint32_t max_len_a, hipStream_t stream) {
+// the columns per lane of the widest row (sa_score_row_class's steps)
+template <bool SW, bool CROSS = false, class P>
+static hipError_t launch_rows(const P &p, uint32_t max_len_a, hipStream_t stream) {
   const uint32_t need = columns_per_lane(max_len_a);
-  if (need <= 1) return launch_rows_cpl<1, SW>(p, stream);
-  if (need <= 2) return launch_rows_cpl<2, SW>(p, stream);
-  if (need <= 3) return launch_rows_cpl<3, SW>(p, stream);
-  if (need <= 4) return launch_rows_cpl<4, SW>(p, stream);
-  if (need <= 5) return launch_rows_cpl<5, SW>(p, stream);
-  if (need <= 6) return launch_rows_cpl<6, SW>(p, stream);
-  if (need <= 8) return launch_rows_cpl<8, SW>(p, stream);
-  if (need <= 12) return launch_rows_cpl<12, SW>(p, stream);
-  return launch_rows_cpl<16, SW>(p, stream);
+  if (need <= 1) return launch_rows_cpl<1, SW, CROSS>(p, stream);
+  if (need <= 2) return launch_rows_cpl<2, SW, CROSS>(p, stream);
+  if (need <= 3) return launch_rows_cpl<3, SW, CROSS>(p, stream);
+  if (need <= 4) return launch_rows_cpl<4, SW, CROSS>(p, stream);
+  if (need <= 5) return launch_rows_cpl<5, SW, CROSS>(p, stream);
+  if (need <= 6) return launch_rows_cpl<6, SW, CROSS>(p, stream);
+  if (need <= 8) return launch_rows_cpl<8, SW, CROSS>(p, stream);
+  if (need <= 12) return launch_rows_cpl<12, SW, CROSS>(p, stream);
+  return launch_rows_cpl<16, SW, CROSS>(p, stream);
 }
 
 template <bool SW>
@@ -328,6 +357,13 @@ hipError_t sa_launch_score_rows(const SaScoreParams &p, uint32_t max_len_a, bool
   if (max_len_a > SA_SCORE_ROW_MAX) return hipErrorInvalidValue;
   sa_record_launch(SEQALIGN_K_SCORE_ROWS, p.f.n_pairs);
   return is_sw ? sa::launch_rows<true>(p, max_len_a, stream) : sa::launch_rows<false>(p, max_len_a, stream);
+}
+
+hipError_t sa_launch_score_cross(const SaScoreCrossParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream) {
+  if (p.n_waves == 0) return hipSuccess;
+  if (max_len_a > SA_SCORE_ROW_MAX || p.nq == 0) return hipErrorInvalidValue;
+  sa_record_launch(SEQALIGN_K_SCORE_CROSS, p.n_waves);
+  return is_sw ? sa::launch_rows<true, true>(p, max_len_a, stream) : sa::launch_rows<false, true>(p, max_len_a, stream);
 }
 
 hipError_t sa_launch_score_strips(const SaScoreParams &p, bool is_sw, hipStream_t stream) {

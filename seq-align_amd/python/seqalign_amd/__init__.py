@@ -68,6 +68,12 @@ class SwReduceDesc(C.Structure):
                 ("cand_score", C.c_void_p)]
 
 
+class SeqSetDesc(C.Structure):
+    """seqalign_seqset_t"""
+    _fields_ = [("n_seqs", C.c_uint64), ("arena", C.c_void_p), ("arena_bytes", C.c_uint64), ("off", C.c_void_p),
+                ("len", C.c_void_p)]
+
+
 class SwHit(C.Structure):
     """seqalign_sw_hit_t"""
     _fields_ = [("pair", C.c_uint64), ("score", C.c_int32), ("pos_a", C.c_uint32), ("pos_b", C.c_uint32),
@@ -391,6 +397,38 @@ class Context:
                    "seqalign_sw_score_batch")
         return score, end_a, end_b
 
+    # ---- score matrices (seqalign_nw_score_cross / seqalign_sw_score_cross) ------------------------------
+    def nw_score_cross(self, queries, targets, scoring: Scoring, peers=None) -> np.ndarray:
+        """seqalign_nw_score_cross: the global score of every query against every target, int32[n_queries, n_targets] --
+        what nw_score returns on workloads.cross_batch(queries, targets), without building that batch."""
+        _cross_args(queries, targets, scoring)
+        score = np.zeros((queries.n_seqs, targets.n_seqs), np.int32)
+        dq, dt = seqset_desc(queries), seqset_desc(targets)
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(lib().seqalign_nw_score_cross_multi(hs, nh, C.byref(dq), C.byref(dt), C.byref(scoring), _ptr(score)),
+                   "seqalign_nw_score_cross_multi")
+        else:
+            _check(lib().seqalign_nw_score_cross(self._h, C.byref(dq), C.byref(dt), C.byref(scoring), _ptr(score)),
+                   "seqalign_nw_score_cross")
+        return score
+
+    def sw_score_cross(self, queries, targets, scoring: Scoring, peers=None):
+        """seqalign_sw_score_cross: (score int32, end_a uint32, end_b uint32), each [n_queries, n_targets] -- sw_score on
+        workloads.cross_batch(queries, targets); end_a indexes the query, end_b the target."""
+        _cross_args(queries, targets, scoring)
+        shape = (queries.n_seqs, targets.n_seqs)
+        score, end_a, end_b = np.zeros(shape, np.int32), np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        dq, dt = seqset_desc(queries), seqset_desc(targets)
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(lib().seqalign_sw_score_cross_multi(hs, nh, C.byref(dq), C.byref(dt), C.byref(scoring), _ptr(score),
+                                                       _ptr(end_a), _ptr(end_b)), "seqalign_sw_score_cross_multi")
+        else:
+            _check(lib().seqalign_sw_score_cross(self._h, C.byref(dq), C.byref(dt), C.byref(scoring), _ptr(score),
+                                                 _ptr(end_a), _ptr(end_b)), "seqalign_sw_score_cross")
+        return score, end_a, end_b
+
     def score_time_ms(self, batch, scoring: Scoring, is_sw: int, repeats: int = 10) -> np.ndarray:
         """seqalign_score_time_ms: the score kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
         _score_args(batch, scoring)
@@ -514,6 +552,29 @@ def _score_args(batch, scoring):
     size = batch.arena.nbytes
     if n and (int((batch.off_a + batch.len_a).max()) > size or int((batch.off_b + batch.len_b).max()) > size):
         raise SeqAlignError(E_ARG, "score: a sequence lies outside batch.arena")
+
+
+def _cross_args(queries, targets, scoring):
+    """What the score-matrix wrappers check before the library sees the sets: types and lengths of off / len, and every
+    sequence inside its arena (the C call trusts the pointers it is given)."""
+    if not isinstance(scoring, Scoring):
+        raise SeqAlignError(E_ARG, "score cross: scoring must be a seqalign_amd.Scoring")
+    for what, s in (("queries", queries), ("targets", targets)):
+        n = getattr(s, "n_seqs", None)
+        if n is None:
+            raise SeqAlignError(E_ARG, f"score cross: {what} must be a workloads.SeqSet")
+        for name, dt in (("off", np.uint64), ("len", np.uint32)):
+            a = getattr(s, name)
+            if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != (n,) or not a.flags.c_contiguous:
+                raise SeqAlignError(E_ARG, f"score cross: {what}.{name} must be a contiguous {np.dtype(dt).name}[{n}]")
+        if not isinstance(s.arena, np.ndarray) or s.arena.dtype != np.uint8 or not s.arena.flags.c_contiguous:
+            raise SeqAlignError(E_ARG, f"score cross: {what}.arena must be contiguous uint8")
+        if n and int((s.off + s.len).max()) > s.arena.nbytes:
+            raise SeqAlignError(E_ARG, f"score cross: a sequence of {what} lies outside its arena")
+
+
+def seqset_desc(s: "workloads.SeqSet") -> SeqSetDesc:
+    return SeqSetDesc(s.n_seqs, s.arena.ctypes.data, s.arena.nbytes, s.off.ctypes.data, s.len.ctypes.data)
 
 
 class Job:
@@ -731,6 +792,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_batch_cigar", "seqalign_sw_batch_cigar", "seqalign_nw_batch_cigar_multi", "seqalign_sw_batch_cigar_multi",
     "seqalign_nw_score_batch", "seqalign_sw_score_batch", "seqalign_nw_score_batch_multi", "seqalign_sw_score_batch_multi",
     "seqalign_score_time_ms",
+    "seqalign_nw_score_cross", "seqalign_sw_score_cross", "seqalign_nw_score_cross_multi", "seqalign_sw_score_cross_multi",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",

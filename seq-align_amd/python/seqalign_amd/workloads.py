@@ -115,6 +115,58 @@ def shard_range_cells(cells, rank: int, world: int) -> tuple[int, int]:
     return e[rank], e[rank + 1]
 
 
+@dataclass
+class SeqSet:
+    """One set of sequences for the score-matrix calls (include/seqalign_hip.h `seqalign_seqset_t`): a byte arena and
+    per-sequence (off, len)."""
+    arena: np.ndarray   # uint8
+    off: np.ndarray     # uint64 [n]
+    len: np.ndarray     # uint32 [n]
+
+    @property
+    def n_seqs(self) -> int:
+        return int(self.len.shape[0])
+
+    def seq(self, i: int) -> bytes:
+        o, n = int(self.off[i]), int(self.len[i])
+        return self.arena[o:o + n].tobytes()
+
+
+def seqset_from(seqs: list[bytes]) -> SeqSet:
+    """A SeqSet holding `seqs` back to back, in order."""
+    lens = np.asarray([len(s) for s in seqs], np.uint32)
+    off = np.zeros(len(seqs), np.uint64)
+    if len(seqs) > 1:
+        off[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    arena = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8).copy()
+    return SeqSet(arena, off, lens)
+
+
+def random_set(n_seqs: int, seed: int, min_len: int, max_len: int, alphabet: bytes = b"ACGT") -> SeqSet:
+    """Seeded ragged set: lengths uniform in [min_len, max_len], letters iid over `alphabet` (b"ACGT": DNA; AMINO20's
+    bytes: protein)."""
+    rng = Rng(seed)
+    alpha = np.frombuffer(alphabet, dtype=np.uint8)
+    lens = (min_len + rng.below(max_len - min_len + 1, n_seqs)).astype(np.uint32)
+    total = int(lens.sum(dtype=np.uint64))
+    arena = np.empty(total + 1, np.uint8)
+    arena[:total] = alpha[rng.below(len(alpha), total).astype(np.int64)]
+    arena[total] = 0
+    off = np.zeros(n_seqs, np.uint64)
+    if n_seqs > 1:
+        off[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    return SeqSet(arena, off, lens)
+
+
+def cross_batch(queries: SeqSet, targets: SeqSet) -> Batch:
+    """The batch a score-matrix call stands for: pair q * n_targets + t = (query q, target t), one arena holding both sets."""
+    nq, nt = queries.n_seqs, targets.n_seqs
+    shift = np.uint64(queries.arena.nbytes)
+    arena = np.concatenate([queries.arena, targets.arena])
+    return Batch(arena, np.repeat(queries.off, nt), np.repeat(queries.len, nt),
+                 np.tile(targets.off + shift, nq), np.tile(targets.len, nq))
+
+
 def from_pairs(pairs: list[tuple[bytes, bytes]]) -> Batch:
     chunks, off_a, len_a, off_b, len_b = [], [], [], [], []
     pos = 0
