@@ -470,6 +470,7 @@ enum {
   SEQALIGN_K_SCORE_ROWS,           /* score only (seqalign_*_score_batch), one pair per wave, rows <= 1 024 columns */
   SEQALIGN_K_SCORE_STRIPS,         /* ... wider rows: strips of 512 columns, one wave each (items: pairs)          */
   SEQALIGN_K_SCORE_CROSS,          /* score only over two sets (seqalign_*_score_cross), one wave per (query, target) */
+  SEQALIGN_K_SCORE_SELECT,         /* top-k search (seqalign_*_score_search): a tile's best targets per query (items: rows) */
   SEQALIGN_K_COUNT
 };
 #define SEQALIGN_K_MAX 32
@@ -567,6 +568,36 @@ int seqalign_nw_score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
 int seqalign_sw_score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
                                   const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score,
                                   uint32_t *out_end_a, uint32_t *out_end_b);
+/* ---- top-k score search: the best targets of every query ------------------------------------------------------------ */
+#define SEQALIGN_SEARCH_MAX_K 1024
+typedef struct {
+  uint32_t target;       /* index into the target set */
+  int32_t score;
+  uint32_t end_a, end_b; /* SW: as seqalign_sw_score_cross (1-based best cell; 0, 0 when score 0); NW: 0, 0 */
+} seqalign_search_hit_t;
+/* For query q: every target t with score[q][t] >= min_score, where score is what seqalign_*_score_cross returns on the same
+ * sets, ordered by score descending, then target ascending; the first min(k, count) go to hits[q * k ...] with the cross
+ * call's end_a / end_b, and n_hits[q] is how many were written (slots past it are unspecified).  The order is total: the
+ * result does not depend on tiling, chunk_bytes or the number of contexts.  min_score INT32_MIN: no filter.  Only the hit
+ * lists leave the device (selection runs there per tile; queries over 1 024 columns are selected on the host).
+ * SEQALIGN_E_ARG: NULL arguments, k == 0 or k > SEQALIGN_SEARCH_MAX_K, n_targets > UINT32_MAX, n_queries x n_targets
+ * overflowing uint64_t -- all before any array is read.  No targets: SEQALIGN_OK with every n_hits[q] = 0.  No queries:
+ * SEQALIGN_OK, nothing written.  A character pair without a score: SEQALIGN_E_UNKNOWN_PAIR, named as the cross call
+ * names it. */
+int seqalign_nw_score_search(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                             const scoring_t *scoring, uint32_t k, int32_t min_score, seqalign_search_hit_t *hits,
+                             uint32_t *n_hits);
+int seqalign_sw_score_search(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                             const scoring_t *scoring, uint32_t k, int32_t min_score, seqalign_search_hit_t *hits,
+                             uint32_t *n_hits);
+/* ... over several contexts: contiguous query ranges cut as seqalign_*_score_cross_multi cuts them; results exactly the
+ * single-context call's */
+int seqalign_nw_score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                   const seqalign_seqset_t *targets, const scoring_t *scoring, uint32_t k, int32_t min_score,
+                                   seqalign_search_hit_t *hits, uint32_t *n_hits);
+int seqalign_sw_score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                   const seqalign_seqset_t *targets, const scoring_t *scoring, uint32_t k, int32_t min_score,
+                                   seqalign_search_hit_t *hits, uint32_t *n_hits);
 /* Kernel time of the score-only call (seq-align_amd/tools/score_bench.py): the batch is packed and uploaded once (it must
  * fit one chunk), then its score kernels run `repeats` times, each launch between two HIP events: ms_each[r]. */
 int seqalign_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int is_sw,

@@ -14,6 +14,12 @@
 //
 // Longer queries: seqalign_*_score_batch's strips, on explicit pair lists (a few long queries x a slice of the targets),
 // results scattered into the matrix.  Such a pair is over 1 024 x len_b cells: building its descriptor costs nothing next to it.
+//
+// Top-k search (seqalign_*_score_search) runs the same tiles; only the end of a tile differs.  Instead of the rows going
+// home, score_select_kernel (sa_score_select.hip) merges each row's best entries into its query's running list on the device
+// ([nq][k] keys, ends, counts, reserved with the other buffers), and after a query range's last target range only the lists
+// come home: nq x (16 k + 4) bytes.  The tile cut counts the lists as part of each query's bytes.  Long queries' rows come
+// home through the score batches anyway; their top k is taken on the host with the same key.
 #include "sa_ctx.hpp"
 
 using namespace sa_host;
@@ -55,6 +61,27 @@ struct FailPair {
   bool any() const { return key != ~0ull; }
 };
 
+// the search's order: ascending keys are score descending, then target ascending
+inline uint32_t key_u(int32_t s) { return ~((uint32_t)s ^ 0x80000000u); }
+inline uint64_t hit_key(int32_t s, uint64_t t) { return ((uint64_t)key_u(s) << 32) | t; }
+
+struct SearchOut {   // seqalign_*_score_search's outputs
+  uint32_t k;
+  int32_t min_score;
+  seqalign_search_hit_t *hits;   // [n_queries * k]
+  uint32_t *n_hits;              // [n_queries]
+  // query q's list from sorted keys and their ends
+  void put(uint64_t q, uint32_t n, const uint64_t *key, const uint32_t *ea, const uint32_t *eb) const {
+    n_hits[q] = n;
+    seqalign_search_hit_t *h = hits + q * k;
+    for (uint32_t i = 0; i < n; ++i) {
+      h[i].target = (uint32_t)key[i];
+      h[i].score = (int32_t)(~(uint32_t)(key[i] >> 32) ^ 0x80000000u);
+      h[i].end_a = ea[i]; h[i].end_b = eb[i];
+    }
+  }
+};
+
 struct CrossCall {
   seqalign_ctx *ctx;
   const seqalign_seqset_t *Q, *T;
@@ -64,8 +91,10 @@ struct CrossCall {
   uint32_t *out_end_a, *out_end_b;
   uint64_t nT;
   FailPair fail;
+  const SearchOut *search = nullptr;   // set: top-k search, the matrix outputs are unused
 
   uint64_t result_bytes() const { return is_sw ? 12 : 4; }
+  uint64_t list_bytes() const { return search ? 16ull * search->k + 4 : 0; }   // one query's running list
 
   // queries <= SA_SCORE_ROW_MAX: the cross kernel, tile by tile
   int run_short(const std::vector<uint64_t> &qs) {
@@ -81,20 +110,22 @@ struct CrossCall {
     uint64_t tb_max = 0, nt_max = 0;
     for (const Range &r : t_ranges) { tb_max = std::max(tb_max, r.bytes); nt_max = std::max(nt_max, r.count); }
     const uint64_t t_room = tb_max + nt_max * kSeqBytes;
-    const std::vector<Range> q_ranges = cut_ranges(Q, qs, budget > t_room ? budget - t_room : 0, nt_max * rp,
+    const std::vector<Range> q_ranges = cut_ranges(Q, qs, budget > t_room ? budget - t_room : 0, nt_max * rp + list_bytes(),
                                                    std::max<uint64_t>(1, kTileMaxPairs / nt_max));
     uint64_t qb_max = 0, nq_max = 0;
     for (const Range &r : q_ranges) { qb_max = std::max(qb_max, r.bytes); nq_max = std::max(nq_max, r.count); }
 
     // every buffer at its largest before anything goes up (a DevBuf that grows loses its contents): sequences, targets
     // first; descriptors off_t, off_q (u64), len_t, t_order, len_q, q_list (u32); results: err_flag, -, err_pair (u64), then
-    // score, end_a, end_b
+    // score, end_a, end_b; search: the running lists of a query range (keys u64 [nq * k], end_a, end_b u32 [nq * k], counts
+    // u32 [nq]), and at home the 16 bytes of err_flag / err_pair followed by the lists
     const uint64_t q_at = (tb_max + 15) & ~(uint64_t)15;
     const uint64_t desc_bytes = 16 * (nt_max + nq_max);
-    const uint64_t res_bytes = 16 + rp * nq_max * nt_max;
+    const uint64_t res_bytes = 16 + rp * nq_max * nt_max, lists_bytes = list_bytes() * nq_max;
     if ((rc = ctx->arena.reserve(q_at + qb_max + 16)) || (rc = ctx->off_a.reserve(desc_bytes)) ||
         (rc = ctx->best_score.reserve(res_bytes)) || (rc = ctx->h_arena.reserve(q_at + qb_max + 16)) ||
-        (rc = ctx->h_desc.reserve(desc_bytes)) || (rc = ctx->h_misc.reserve(res_bytes)))
+        (rc = ctx->h_desc.reserve(desc_bytes)) || (rc = ctx->h_misc.reserve(search ? 16 + lists_bytes : res_bytes)) ||
+        (search && (rc = ctx->search_list.reserve(lists_bytes))))
       return rc;
     uint8_t *h_seq = ctx->h_arena.as<uint8_t>();
     uint64_t *h_off_t = ctx->h_desc.as<uint64_t>(), *h_off_q = h_off_t + nt_max;
@@ -151,6 +182,10 @@ struct CrossCall {
         HIP_TRY(hipMemcpyAsync(d_qlist, h_qlist, 4 * nq, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(d_res, 0, 8, st));
         HIP_TRY(hipMemsetAsync(d_res + 2, 0xff, 8, st));
+        // search: the query range's lists, laid out for its nq (keys, end_a, end_b, counts), empty at its first target range
+        uint8_t *d_lists = ctx->search_list.as<uint8_t>();
+        const uint64_t nk = search ? nq * search->k : 0;
+        if (search && &tr == &t_ranges.front()) HIP_TRY(hipMemsetAsync(d_lists + 16 * nk, 0, 4 * nq, st));
 
         const uint64_t n = nq * nt;
         for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) {
@@ -171,8 +206,39 @@ struct CrossCall {
           if (e != hipSuccess) return fail_hip(e, "score cross kernel launch");
         }
 
-        // results home; rows into the matrix
         uint32_t *h = ctx->h_misc.as<uint32_t>();
+        if (search) {
+          // the rows into the running lists; the error word home, and after the last target range the lists
+          SaScoreSelectParams sp;
+          memset(&sp, 0, sizeof(sp));
+          sp.score = reinterpret_cast<const int32_t *>(d_res + 4);
+          if (is_sw) { sp.end_a = d_res + 4 + n; sp.end_b = d_res + 4 + 2 * n; }
+          sp.nq = (uint32_t)nq; sp.n_t = (uint32_t)nt; sp.t_base = (uint32_t)tr.first;
+          sp.k = search->k; sp.u_max = key_u(search->min_score);
+          sp.list_key = reinterpret_cast<unsigned long long *>(d_lists);
+          sp.list_ea = reinterpret_cast<uint32_t *>(d_lists + 8 * nk); sp.list_eb = sp.list_ea + nk;
+          sp.list_n = sp.list_eb + nk;
+          const hipError_t e = sa_launch_score_select(sp, st);
+          if (e != hipSuccess) return fail_hip(e, "score select kernel launch");
+          const bool last = &tr == &t_ranges.back();
+          HIP_TRY(hipMemcpyAsync(h, d_res, 16, hipMemcpyDeviceToHost, st));
+          if (last) HIP_TRY(hipMemcpyAsync(h + 4, d_lists, 16 * nk + 4 * nq, hipMemcpyDeviceToHost, st));
+          HIP_TRY(stream_wait_spinning(st));
+          if (h[0]) {
+            uint64_t key;
+            memcpy(&key, h + 2, 8);
+            fail.offer(qs[qr.first + key / nt], tr.first + key % nt, nT);
+          }
+          if (!last || fail.any()) continue;
+          const uint64_t *hk = reinterpret_cast<const uint64_t *>(h + 4);
+          const uint32_t *hea = h + 4 + 2 * nk, *heb = hea + nk, *hn = heb + nk;
+          const uint32_t K = search->k;
+          for (uint64_t j = 0; j < nq; ++j)
+            search->put(qs[qr.first + j], hn[j], hk + j * K, hea + j * K, heb + j * K);
+          continue;
+        }
+
+        // results home; rows into the matrix
         HIP_TRY(hipMemcpyAsync(h, d_res, 16 + rp * n, hipMemcpyDeviceToHost, st));
         HIP_TRY(stream_wait_spinning(st));
         if (h[0]) {
@@ -213,6 +279,10 @@ struct CrossCall {
     for (uint64_t t = 0; t < nT; ++t) memcpy(arena.data() + at_t[t], T->arena + T->off[t], T->len[t]);
 
     const uint64_t t_slice = std::min(nT, kLongSlicePairs), q_rows = std::max<uint64_t>(1, kLongSlicePairs / nT);
+    // search: each long query's best (key, end_a, end_b) so far, cut back to k after every slice
+    struct Hit { uint64_t key; uint32_t ea, eb; };
+    std::vector<std::vector<Hit>> best(search ? qs.size() : 0);
+    const auto by_key = [](const Hit &x, const Hit &y) { return x.key < y.key; };
     std::vector<uint64_t> off_a, off_b;
     std::vector<uint32_t> len_a, len_b, ea, eb;
     std::vector<int32_t> sc;
@@ -237,6 +307,17 @@ struct CrossCall {
           continue;
         }
         if (rc) return rc;
+        if (search) {
+          for (uint64_t k = 0; k < n; ++k)
+            if (sc[k] >= search->min_score) best[g0 + k / nt].push_back({hit_key(sc[k], t0 + k % nt), ea[k], eb[k]});
+          for (uint64_t g = g0; g < g1; ++g) {
+            std::vector<Hit> &b = best[g];
+            if (b.size() <= search->k) continue;
+            std::nth_element(b.begin(), b.begin() + search->k, b.end(), by_key);
+            b.resize(search->k);
+          }
+          continue;
+        }
         for (uint64_t k = 0; k < n; ++k) {
           const uint64_t at = qs[g0 + k / nt] * nT + t0 + k % nt;
           out_score[at] = sc[k];
@@ -244,6 +325,32 @@ struct CrossCall {
         }
       }
       if (fail.any()) break;
+    }
+    if (search && !fail.any()) {
+      std::vector<uint64_t> key;
+      std::vector<uint32_t> ea_, eb_;
+      for (uint64_t g = 0; g < qs.size(); ++g) {
+        std::vector<Hit> &b = best[g];
+        std::sort(b.begin(), b.end(), by_key);
+        key.resize(b.size()); ea_.resize(b.size()); eb_.resize(b.size());
+        for (size_t i = 0; i < b.size(); ++i) { key[i] = b[i].key; ea_[i] = b[i].ea; eb_[i] = b[i].eb; }
+        search->put(qs[g], (uint32_t)b.size(), key.data(), ea_.data(), eb_.data());
+      }
+    }
+    return SEQALIGN_OK;
+  }
+
+  // both paths, then the failing pair's message -- q_base: what the message adds to a query index (the *_multi calls)
+  int run(uint64_t q_base) {
+    int rc;
+    std::vector<uint64_t> short_q, long_q;
+    for (uint64_t q = 0; q < Q->n_seqs; ++q) (Q->len[q] > SA_SCORE_ROW_MAX ? long_q : short_q).push_back(q);
+    if (!short_q.empty() && (rc = run_short(short_q))) return rc;
+    if (!long_q.empty() && (rc = run_long(long_q))) return rc;
+    if (fail.any()) {
+      set_last_error("query " + std::to_string(q_base + fail.q) + ", target " + std::to_string(fail.t) +
+                     ": a character pair without a score");
+      return SEQALIGN_E_UNKNOWN_PAIR;
     }
     return SEQALIGN_OK;
   }
@@ -274,16 +381,39 @@ int sa_host::score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *quer
   HIP_TRY(hipSetDevice(ctx->device));
   StreamSyncOnExit sync(ctx->stream);
   CrossCall call{ctx, queries, targets, scoring, is_sw, out_score, out_end_a, out_end_b, targets->n_seqs, FailPair()};
-  std::vector<uint64_t> short_q, long_q;
-  for (uint64_t q = 0; q < queries->n_seqs; ++q) (queries->len[q] > SA_SCORE_ROW_MAX ? long_q : short_q).push_back(q);
-  if (!short_q.empty() && (rc = call.run_short(short_q))) return rc;
-  if (!long_q.empty() && (rc = call.run_long(long_q))) return rc;
-  if (call.fail.any()) {
-    set_last_error("query " + std::to_string(q_base + call.fail.q) + ", target " + std::to_string(call.fail.t) +
-                   ": a character pair without a score");
-    return SEQALIGN_E_UNKNOWN_PAIR;
+  return call.run(q_base);
+}
+
+int sa_host::score_search_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets, uint32_t k) {
+  if (k == 0 || k > SEQALIGN_SEARCH_MAX_K) {
+    set_last_error("score search: k must be 1 .. " + std::to_string(SEQALIGN_SEARCH_MAX_K));
+    return SEQALIGN_E_ARG;
+  }
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  if (targets->n_seqs > UINT32_MAX) {
+    set_last_error("score search: more than UINT32_MAX targets");
+    return SEQALIGN_E_ARG;
   }
   return SEQALIGN_OK;
+}
+
+int sa_host::score_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                               const scoring_t *scoring, bool is_sw, uint32_t k, int32_t min_score,
+                               seqalign_search_hit_t *hits, uint32_t *n_hits, uint64_t q_base) {
+  int rc = score_search_check(queries, targets, k);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  if (!queries->n_seqs) return SEQALIGN_OK;
+  if (!targets->n_seqs) {
+    memset(n_hits, 0, 4 * queries->n_seqs);
+    return SEQALIGN_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  StreamSyncOnExit sync(ctx->stream);
+  const SearchOut out{k, min_score, hits, n_hits};
+  CrossCall call{ctx, queries, targets, scoring, is_sw, nullptr, nullptr, nullptr, targets->n_seqs, FailPair(), &out};
+  return call.run(q_base);
 }
 
 extern "C" int seqalign_nw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
@@ -296,4 +426,18 @@ extern "C" int seqalign_sw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqse
                                        const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
   if (!ctx || !scoring || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
   return score_cross_call(ctx, queries, targets, scoring, true, out_score, out_end_a, out_end_b, 0);
+}
+
+extern "C" int seqalign_nw_score_search(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                        const scoring_t *scoring, uint32_t k, int32_t min_score, seqalign_search_hit_t *hits,
+                                        uint32_t *n_hits) {
+  if (!ctx || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
+  return score_search_call(ctx, queries, targets, scoring, false, k, min_score, hits, n_hits, 0);
+}
+
+extern "C" int seqalign_sw_score_search(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                        const scoring_t *scoring, uint32_t k, int32_t min_score, seqalign_search_hit_t *hits,
+                                        uint32_t *n_hits) {
+  if (!ctx || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
+  return score_search_call(ctx, queries, targets, scoring, true, k, min_score, hits, n_hits, 0);
 }

@@ -6,7 +6,8 @@
 //   sa_batch.hip      host-level chunking, seqalign_fill_batch, seqalign_nw_batch
 //   sa_batch_sw.hip   seqalign_sw_batch (best hit / device enumeration / host enumeration)
 //   sa_batch_score.hip seqalign_nw_score_batch / seqalign_sw_score_batch (score only)
-//   sa_batch_score_cross.hip seqalign_nw_score_cross / seqalign_sw_score_cross (score only, every query x every target)
+//   sa_batch_score_cross.hip seqalign_nw_score_cross / seqalign_sw_score_cross (score only, every query x every target),
+//                     and seqalign_*_score_search (the best k targets of every query; sa_score_select.hip selects)
 //   sa_multi.hip      the same calls over several contexts (GPUs) from one process
 #pragma once
 #include <hip/hip_runtime.h>
@@ -373,6 +374,7 @@ struct seqalign_ctx {
   sa_host::DevBuf e[14];                                 // device SW enumeration scratch (see sw_chunk_device_enumerate)
   sa_host::DevBuf strip_progress;                        // sa_fill_strips.hip: rows done per (pair, strip)
   sa_host::DevBuf score_handoff;                         // sa_score.hip's strips: the last column of every strip but the last
+  sa_host::DevBuf search_list;                           // seqalign_*_score_search: the running top-k lists of a query range
   sa_host::HostBuf h_desc, h_arena, h_M, h_A, h_B, h_misc, h_ta, h_tb, h_tmeta;
   // the last scorings uploaded through cached_scoring (host-level entry points, legacy single-pair path): [is_sw]
   seqalign_call_info_t call_info = {};   // what the last call launched (seqalign_ctx_last_call_info)
@@ -413,6 +415,12 @@ int score_cross_check(const seqalign_seqset_t *queries, const seqalign_seqset_t 
 int score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                      const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b,
                      uint64_t q_base);   // sa_async.hip: drain the submitted jobs, join the lanes (seqalign_ctx_destroy)
+// ... and the top-k search (seqalign_*_score_search) on the same tiles: its checks (E_ARG: k, the sets, n_targets), and
+// one context's call
+int score_search_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets, uint32_t k);
+int score_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                      const scoring_t *scoring, bool is_sw, uint32_t k, int32_t min_score, seqalign_search_hit_t *hits,
+                      uint32_t *n_hits, uint64_t q_base);
 
 struct CigarScope {   // RAII: the call's output format, put back on every way out
   seqalign_ctx *ctx;

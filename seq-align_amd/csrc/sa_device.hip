@@ -78,7 +78,7 @@ extern "C" const char *seqalign_kernel_kind_name(int kind) {
       "fill_sw_dirs", "fill_sw_dirs_x2", "fill_sw_best_x2", "sw_reduce", "sw_box", "sweep_regs", "sweep_lds", "sweep_strips",
       "sweep_dirs", "sweep_dirs_x2", "walk_lane", "walk_wave", "walk_dirs_lane", "walk_dirs_tile", "walk_moves_lane",
       "walk_moves_tile", "fill_nw_dirs_x4", "fill_sw_best_x4", "score_rows", "score_strips",
-      "score_cross"};
+      "score_cross", "score_select"};
   return kind >= 0 && kind < SEQALIGN_K_COUNT ? names[kind] : nullptr;
 }
 
@@ -373,6 +373,7 @@ extern "C" void seqalign_ctx_destroy(seqalign_ctx_t *ctx) {
   for (DevBuf &b : ctx->e) b.release();
   ctx->strip_progress.release();
   ctx->score_handoff.release();
+  ctx->search_list.release();
   for (HostBuf *b : {&ctx->h_one, &ctx->h_desc, &ctx->h_arena, &ctx->h_M, &ctx->h_A, &ctx->h_B, &ctx->h_misc, &ctx->h_ta,
                      &ctx->h_tb, &ctx->h_tmeta})
     b->release();

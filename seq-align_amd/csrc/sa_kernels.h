@@ -414,6 +414,22 @@ struct SaScoreCrossParams {
 };
 /* every query of the class has len_a <= max_len_a <= SA_SCORE_ROW_MAX */
 hipError_t sa_launch_score_cross(const SaScoreCrossParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream);
+/* top-k score search (seqalign_*_score_search, sa_score_select.hip): one workgroup per query row of a tile, after its
+ * score_cross launches.  Keeps the k smallest keys (~(score ^ 0x80000000)) << 32 | (t_base + t) of the row's entries with
+ * score >= min_score together with the query's running list, and writes them back sorted.  The running list's targets
+ * are all below t_base; the caller zeroed list_n before the query range's first target range. */
+struct SaScoreSelectParams {
+  const int32_t *score;              /* [q * n_t + t] the tile's rows (score_cross_kernel's layout)                       */
+  const uint32_t *end_a, *end_b;     /* same layout (SW); NULL: zeros (NW)                                                */
+  uint32_t nq, n_t;                  /* rows, and targets per row                                                         */
+  uint32_t t_base;                   /* index in the whole target set of the tile's target 0                              */
+  uint32_t k;                        /* 1 .. SEQALIGN_SEARCH_MAX_K                                                        */
+  uint32_t u_max;                    /* ~(min_score ^ 0x80000000): an entry passes when its key's high word is <= u_max    */
+  unsigned long long *list_key;      /* [nq * k] the running lists, sorted, list_n[q] of them valid                       */
+  uint32_t *list_ea, *list_eb;       /* [nq * k] their end coordinates                                                    */
+  uint32_t *list_n;                  /* [nq]                                                                              */
+};
+hipError_t sa_launch_score_select(const SaScoreSelectParams &p, hipStream_t stream);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */
 bool sa_wgstream_kernel_applicable(const SaFillParams &p, uint32_t max_len_a);
 hipError_t sa_launch_fill_wgstream(const SaFillParams &p, uint32_t max_len_a, hipStream_t stream);

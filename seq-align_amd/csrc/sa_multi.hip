@@ -231,3 +231,36 @@ extern "C" int seqalign_sw_score_cross_multi(seqalign_ctx_t *const *ctxs, int n_
   if (bad_ctx_list(ctxs, n_ctx) || !scoring || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
   return score_cross_multi(ctxs, n_ctx, queries, targets, scoring, true, out_score, out_end_a, out_end_b);
 }
+
+// top-k search: the query ranges of score_cross_multi, each context writes its queries' lists and counts
+namespace {
+int score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                       const scoring_t *scoring, bool is_sw, uint32_t k, int32_t min_score, seqalign_search_hit_t *hits,
+                       uint32_t *n_hits) {
+  int rc = score_search_check(queries, targets, k);
+  if (rc) return rc;
+  const uint64_t nq = queries->n_seqs;
+  if (!nq) return SEQALIGN_OK;
+  std::vector<uint64_t> cum(nq + 1, 0);
+  for (uint64_t q = 0; q < nq; ++q) cum[q + 1] = cum[q] + queries->len[q] + 1ull;
+  return for_each_shard(shard_edges_cum(cum, n_ctx), [&](int g, uint64_t first, uint64_t count) {
+    seqalign_seqset_t s = *queries;
+    s.n_seqs = count; s.off = queries->off + first; s.len = queries->len + first;
+    return score_search_call(ctxs[g], &s, targets, scoring, is_sw, k, min_score, hits + first * k, n_hits + first, first);
+  });
+}
+}  // namespace
+
+extern "C" int seqalign_nw_score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                              const seqalign_seqset_t *targets, const scoring_t *scoring, uint32_t k,
+                                              int32_t min_score, seqalign_search_hit_t *hits, uint32_t *n_hits) {
+  if (bad_ctx_list(ctxs, n_ctx) || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
+  return score_search_multi(ctxs, n_ctx, queries, targets, scoring, false, k, min_score, hits, n_hits);
+}
+
+extern "C" int seqalign_sw_score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                              const seqalign_seqset_t *targets, const scoring_t *scoring, uint32_t k,
+                                              int32_t min_score, seqalign_search_hit_t *hits, uint32_t *n_hits) {
+  if (bad_ctx_list(ctxs, n_ctx) || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
+  return score_search_multi(ctxs, n_ctx, queries, targets, scoring, true, k, min_score, hits, n_hits);
+}

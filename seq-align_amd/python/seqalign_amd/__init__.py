@@ -74,6 +74,12 @@ class SeqSetDesc(C.Structure):
                 ("len", C.c_void_p)]
 
 
+INT32_MIN = -2**31
+SEARCH_MAX_K = 1024   # SEQALIGN_SEARCH_MAX_K
+# seqalign_search_hit_t
+SEARCH_HIT = np.dtype([("target", np.uint32), ("score", np.int32), ("end_a", np.uint32), ("end_b", np.uint32)])
+
+
 class SwHit(C.Structure):
     """seqalign_sw_hit_t"""
     _fields_ = [("pair", C.c_uint64), ("score", C.c_int32), ("pos_a", C.c_uint32), ("pos_b", C.c_uint32),
@@ -429,6 +435,31 @@ class Context:
                                                  _ptr(end_a), _ptr(end_b)), "seqalign_sw_score_cross")
         return score, end_a, end_b
 
+    # ---- top-k score search (seqalign_nw_score_search / seqalign_sw_score_search) ------------------------------
+    def nw_score_search(self, queries, targets, scoring: Scoring, k: int, min_score: int = INT32_MIN, peers=None):
+        """seqalign_nw_score_search: (n_hits uint32[n_queries], hits SEARCH_HIT[n_queries, k]) -- per query the targets with
+        nw_score_cross's score >= min_score, score descending then target ascending, the first min(k, count) of them;
+        hits[q, n_hits[q]:] are zero."""
+        return self._score_search(queries, targets, scoring, k, min_score, peers, False)
+
+    def sw_score_search(self, queries, targets, scoring: Scoring, k: int, min_score: int = 1, peers=None):
+        """seqalign_sw_score_search: as nw_score_search over sw_score_cross's score, with its end_a / end_b."""
+        return self._score_search(queries, targets, scoring, k, min_score, peers, True)
+
+    def _score_search(self, queries, targets, scoring, k, min_score, peers, is_sw):
+        _search_args(queries, targets, scoring, k, min_score)
+        nq = queries.n_seqs
+        n_hits, hits = np.zeros(nq, np.uint32), np.zeros((nq, k), SEARCH_HIT)
+        dq, dt = seqset_desc(queries), seqset_desc(targets)
+        tail = (C.byref(dq), C.byref(dt), C.byref(scoring), C.c_uint32(k), C.c_int32(min_score), _ptr(hits), _ptr(n_hits))
+        name = "seqalign_sw_score_search" if is_sw else "seqalign_nw_score_search"
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(getattr(lib(), name + "_multi")(hs, nh, *tail), name + "_multi")
+        else:
+            _check(getattr(lib(), name)(self._h, *tail), name)
+        return n_hits, hits
+
     def score_time_ms(self, batch, scoring: Scoring, is_sw: int, repeats: int = 10) -> np.ndarray:
         """seqalign_score_time_ms: the score kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
         _score_args(batch, scoring)
@@ -571,6 +602,16 @@ def _cross_args(queries, targets, scoring):
             raise SeqAlignError(E_ARG, f"score cross: {what}.arena must be contiguous uint8")
         if n and int((s.off + s.len).max()) > s.arena.nbytes:
             raise SeqAlignError(E_ARG, f"score cross: a sequence of {what} lies outside its arena")
+
+
+def _search_args(queries, targets, scoring, k, min_score):
+    """The search wrappers' checks: _cross_args, then k in 1 .. SEARCH_MAX_K and min_score an int32."""
+    _cross_args(queries, targets, scoring)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= SEARCH_MAX_K:
+        raise SeqAlignError(E_ARG, f"score search: k must be an int in 1 .. {SEARCH_MAX_K}")
+    if isinstance(min_score, bool) or not isinstance(min_score, (int, np.integer)) or \
+            not INT32_MIN <= int(min_score) <= 2**31 - 1:
+        raise SeqAlignError(E_ARG, "score search: min_score must be an int32")
 
 
 def seqset_desc(s: "workloads.SeqSet") -> SeqSetDesc:
@@ -793,6 +834,8 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_score_batch", "seqalign_sw_score_batch", "seqalign_nw_score_batch_multi", "seqalign_sw_score_batch_multi",
     "seqalign_score_time_ms",
     "seqalign_nw_score_cross", "seqalign_sw_score_cross", "seqalign_nw_score_cross_multi", "seqalign_sw_score_cross_multi",
+    "seqalign_nw_score_search", "seqalign_sw_score_search", "seqalign_nw_score_search_multi",
+    "seqalign_sw_score_search_multi",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",
