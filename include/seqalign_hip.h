@@ -426,6 +426,7 @@ int seqalign_pool_trim(seqalign_ctx_t *ctx, uint64_t keep_bytes, uint64_t *held_
  *   arena_free_pct  10 .. 90                share of the memory free at its start that a walk of seqalign_arenas_alloc may hold (60)
  *   upload_slices   0 .. 16                 seqalign_nw_batch: slices a sub-batch's sequences are packed and uploaded in (0 = 1: measured,
  *                                           more slices cost what they overlap)
+ *   long_block_rows 0 | N >= 1              seqalign_*_align_long: rows per block and between checkpoint rows (0: sized from the chunk budget)
  *   cpl, wpb, lds_pad, reduce_depth, sweep_trace, timing   tuning experiments / development aids
  * Numbers are integers and nothing else ("abc", "1x", "" are refused, not read as 0); switches take 1 / 0, true / false, on / off,
  * yes / no.  Returns SEQALIGN_E_ARG for an unknown key or a value outside the key's range (nothing changes then). */
@@ -471,9 +472,17 @@ enum {
   SEQALIGN_K_SCORE_STRIPS,         /* ... wider rows: strips of 512 columns, one wave each (items: pairs)          */
   SEQALIGN_K_SCORE_CROSS,          /* score only over two sets (seqalign_*_score_cross), one wave per (query, target) */
   SEQALIGN_K_SCORE_SELECT,         /* top-k search (seqalign_*_score_search): a tile's best targets per query (items: rows) */
+  SEQALIGN_K_LONG_FORWARD,         /* pairs of any size (seqalign_*_align_long): score strips + checkpoint rows     */
+  SEQALIGN_K_LONG_BLOCK,           /* ... the three matrices of one block, from its checkpoint (one launch per block) */
+  SEQALIGN_K_LONG_WALK,            /* ... the traceback over one block                                              */
   SEQALIGN_K_COUNT
 };
 #define SEQALIGN_K_MAX 32
+#if defined(__cplusplus)
+static_assert(SEQALIGN_K_COUNT <= SEQALIGN_K_MAX, "seqalign_call_info_t has SEQALIGN_K_MAX slots");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(SEQALIGN_K_COUNT <= SEQALIGN_K_MAX, "seqalign_call_info_t has SEQALIGN_K_MAX slots");
+#endif
 typedef struct {
   uint32_t launches[SEQALIGN_K_MAX];
   uint64_t items[SEQALIGN_K_MAX];
@@ -539,6 +548,27 @@ int seqalign_nw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
                                   const scoring_t *scoring, int32_t *out_score);
 int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
                                   const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b);
+/* ---- long pairs: alignments past the 2^31-cell cap --------------------------------- */
+/* The alignments of seqalign_nw_batch and of seqalign_sw_batch with max_hits = 1 -- same arguments, capacities and results,
+ * byte for byte: score, both gapped strings and, SW, the hit's pos_a / pos_b / len_a / len_b / length -- for pairs of any
+ * size (len_a + len_b < 2^32 - 1, else SEQALIGN_E_TOO_LARGE).  The three matrices are never held whole: a forward pass (the
+ * score-only strips) stores M, A and B at every R-th row (12 B x (len_a + 1) per checkpoint row) and finds the SW best
+ * cell; then, block by block from the end cell, rows [checkpoint below the walk, the walk's row] x columns [0, the walk's
+ * column] are recomputed from their checkpoint and walked (alignment_reverse_move's decision order).  Device memory per pair:
+ *   12 (len_a + 1) (floor((len_b - 1) / R) + min(R, len_b) + 1) + 8 (ceil(len_a / 512) - 1) (len_b + 1) + 3 (len_a + len_b)
+ * bytes; R (rows per block, fewer than 2^31 cells) is the option long_block_rows, or (0, the default) the largest that fits
+ * the context's chunk budget (option chunk_bytes).  A pair that does not fit even so: SEQALIGN_E_NOMEM, seqalign_last_error
+ * gives the bytes needed.  Pairs run one after another, small ones included (this is for few large pairs; batches of many
+ * small pairs belong to seqalign_nw_batch / seqalign_sw_batch).  Argument checks (SEQALIGN_E_ARG, SEQALIGN_E_TOO_LARGE)
+ * come before any device work; scoring admission (SEQALIGN_E_DOMAIN) and a character pair without a score
+ * (SEQALIGN_E_UNKNOWN_PAIR, the lowest failing pair named in seqalign_last_error) are the score calls'.  SW: hit_cap or
+ * str_cap too small -- the hits that fit are delivered, *n_hits counts them, SEQALIGN_E_NOMEM.
+ * seqalign_ctx_last_call_info: kinds long_forward, long_block (one launch per block), long_walk. */
+int seqalign_nw_align_long(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                           const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score);
+int seqalign_sw_align_long(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                           const int32_t *min_score, seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits,
+                           char *out_a, char *out_b, uint64_t str_cap);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

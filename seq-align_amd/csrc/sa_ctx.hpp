@@ -8,6 +8,7 @@
 //   sa_batch_score.hip seqalign_nw_score_batch / seqalign_sw_score_batch (score only)
 //   sa_batch_score_cross.hip seqalign_nw_score_cross / seqalign_sw_score_cross (score only, every query x every target),
 //                     and seqalign_*_score_search (the best k targets of every query; sa_score_select.hip selects)
+//   sa_batch_long.hip seqalign_nw_align_long / seqalign_sw_align_long (pairs of any size: checkpoints, blocks, walks)
 //   sa_multi.hip      the same calls over several contexts (GPUs) from one process
 #pragma once
 #include <hip/hip_runtime.h>
@@ -341,6 +342,7 @@ struct SaOptions {
   uint32_t walk_stage = 1;        // walk_stage        1|0: the local tile walker writes a wave's moves as one contiguous run out of LDS (whole lines over PCIe) instead of two pieces per walk
   uint32_t walk_group = 0;        // walk_group        0|1|4|8: walks per wave of the tile walker on moves (0: four in lockstep on blocked direction bytes, else one; 1 / 4 / 8: forced)
   uint32_t async_lanes = 0;       // async_lanes       1..8 (0 = 3): batches seqalign_*_batch_submit keeps in flight per context (sa_async.hip)
+  uint32_t long_block_rows = 0;   // long_block_rows   seqalign_*_align_long: rows per block and between checkpoints (0: sized from the chunk budget)
   uint32_t arena_keep_gib = 16;   // arena_keep_gib    how much of a walk's unused chunks stays with the process (the chunk pool: large scratch
                                   //                   buffers are mapped from it instead of freshly released, not yet cleared VRAM); 0: none
 };
@@ -375,6 +377,7 @@ struct seqalign_ctx {
   sa_host::DevBuf strip_progress;                        // sa_fill_strips.hip: rows done per (pair, strip)
   sa_host::DevBuf score_handoff;                         // sa_score.hip's strips: the last column of every strip but the last
   sa_host::DevBuf search_list;                           // seqalign_*_score_search: the running top-k lists of a query range
+  sa_host::DevBuf long_ckpt, long_block;                 // seqalign_*_align_long: checkpoint rows, one block's three matrices
   sa_host::HostBuf h_desc, h_arena, h_M, h_A, h_B, h_misc, h_ta, h_tb, h_tmeta;
   // the last scorings uploaded through cached_scoring (host-level entry points, legacy single-pair path): [is_sw]
   seqalign_call_info_t call_info = {};   // what the last call launched (seqalign_ctx_last_call_info)

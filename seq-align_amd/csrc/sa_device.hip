@@ -78,7 +78,7 @@ extern "C" const char *seqalign_kernel_kind_name(int kind) {
       "fill_sw_dirs", "fill_sw_dirs_x2", "fill_sw_best_x2", "sw_reduce", "sw_box", "sweep_regs", "sweep_lds", "sweep_strips",
       "sweep_dirs", "sweep_dirs_x2", "walk_lane", "walk_wave", "walk_dirs_lane", "walk_dirs_tile", "walk_moves_lane",
       "walk_moves_tile", "fill_nw_dirs_x4", "fill_sw_best_x4", "score_rows", "score_strips",
-      "score_cross", "score_select"};
+      "score_cross", "score_select", "long_forward", "long_block", "long_walk"};
   return kind >= 0 && kind < SEQALIGN_K_COUNT ? names[kind] : nullptr;
 }
 
@@ -240,6 +240,7 @@ static bool set_option(seqalign_ctx *ctx, const char *key, const char *val) {
   if (is("walk_tile")) { if (!number(0, 64, &num) || !(num == 0 || num == 32 || num == 64)) return false; o.walk_tile = (uint32_t)num; return true; }
   if (is("walk_group")) { if (!number(0, 8, &num) || !(num == 0 || num == 1 || num == 4 || num == 8)) return false; o.walk_group = (uint32_t)num; return true; }
   if (is("arena_free_pct")) { if (!number(10, 90, &num)) return false; o.arena_free_pct = (uint32_t)num; return true; }
+  if (is("long_block_rows")) { if (!number(0, 0xFFFFFFFFll, &num)) return false; o.long_block_rows = (uint32_t)num; return true; }
   if (is("arena_quality")) {
     char *end = nullptr;
     const double q = strtod(val, &end);
@@ -286,6 +287,7 @@ static bool get_option(const seqalign_ctx *ctx, const char *key, std::string *ou
   if (is("walk_tile")) return n(o.walk_tile);
   if (is("walk_group")) return n(o.walk_group);
   if (is("arena_free_pct")) return n(o.arena_free_pct);
+  if (is("long_block_rows")) return n(o.long_block_rows);
   if (is("arena_quality")) { char buf[32]; snprintf(buf, sizeof(buf), "%.6g", (double)o.arena_quality); *out = buf; return true; }
   return false;
 }
@@ -294,7 +296,7 @@ static bool get_option(const seqalign_ctx *ctx, const char *key, std::string *ou
 // SEQALIGN_HOST_THREADS: the process-wide worker pool, sa_ctx.hpp)
 static void options_from_env(seqalign_ctx *ctx) {
   static const char *keys[] = {"kernel", "cpl", "wpb", "lds_pad", "traceback", "trace_kernel", "sweep_mode", "sweep_strip",
-                               "sweep_cpl", "sweep_ev", "sweep_trace", "sweep_dirs", "nw_dirs", "pack16", "quad", "walk_overlap", "nw_moves", "zero_copy", "reduce_depth", "timing", "chunk_bytes", "subbatches", "arena_scan_gib", "arena_quality", "arena_keep_gib", "upload_slices", "arena_free_pct", "async_lanes", "walk_group", "dirs_local", "walk_stage", "walk_tile"};
+                               "sweep_cpl", "sweep_ev", "sweep_trace", "sweep_dirs", "nw_dirs", "pack16", "quad", "walk_overlap", "nw_moves", "zero_copy", "reduce_depth", "timing", "chunk_bytes", "subbatches", "arena_scan_gib", "arena_quality", "arena_keep_gib", "upload_slices", "arena_free_pct", "async_lanes", "walk_group", "dirs_local", "walk_stage", "walk_tile", "long_block_rows"};
   for (const char *k : keys) {
     std::string name = "SEQALIGN_";
     for (const char *c = k; *c; ++c) name += (char)toupper((unsigned char)*c);
@@ -374,6 +376,8 @@ extern "C" void seqalign_ctx_destroy(seqalign_ctx_t *ctx) {
   ctx->strip_progress.release();
   ctx->score_handoff.release();
   ctx->search_list.release();
+  ctx->long_ckpt.release();
+  ctx->long_block.release();
   for (HostBuf *b : {&ctx->h_one, &ctx->h_desc, &ctx->h_arena, &ctx->h_M, &ctx->h_A, &ctx->h_B, &ctx->h_misc, &ctx->h_ta,
                      &ctx->h_tb, &ctx->h_tmeta})
     b->release();

@@ -430,6 +430,39 @@ struct SaScoreSelectParams {
   uint32_t *list_n;                  /* [nq]                                                                              */
 };
 hipError_t sa_launch_score_select(const SaScoreSelectParams &p, hipStream_t stream);
+/* alignments of pairs of any size (seqalign_*_align_long, sa_align_long.hip): ONE pair per launch, its descriptors at index 0
+ * of f's arrays.  Forward: the score-strips pipeline over the whole pair, which also stores M, A, B of every column at rows
+ * R, 2R, .. < len_b (checkpoints).  Block: M, A, B of rows [y0, y1] x columns [0, x] from the checkpoint at y0 (or row 0)
+ * into f.M / f.A / f.B at pitch x + 1.  Walk: alignment_reverse_move over the block, one lane, from the state in *walk. */
+struct SaLongWalk {
+  uint32_t x, y;                /* where the walk stands                                                                */
+  int32_t matrix, score;        /* its state                                                                           */
+  uint32_t head;                /* the strings are written backwards from out_a / out_b[len_a + len_b]                  */
+  uint32_t status;              /* 0 or SEQALIGN_E_UNKNOWN_PAIR / SEQALIGN_E_TRACEBACK                                 */
+  uint32_t started, done;       /* the end cell has been read; the walk is over                                        */
+  int32_t end_score;
+  uint32_t end_x, end_y, pad;
+};
+struct SaLongParams {
+  SaFillParams f;               /* n_pairs = 1; f.status: the lowest cell without a score (forward / block), ~0 = none */
+  uint32_t *progress;           /* [strips + 1] zeroed: rows done per strip, then the ticket counter                   */
+  uint32_t strips;              /* forward: ceil(len_a / 512) (at least 1); block: ceil(x / 512) (at least 1)          */
+  uint32_t R;                   /* rows per block; checkpoints at R, 2R, .. < len_b (R >= len_b: none)                 */
+  int32_t *ckpt;                /* checkpoint k at row (k + 1) R: M, A, B of columns 0 .. len_a, 3 (len_a + 1) int32   */
+  /* forward */
+  int32_t *handoff;             /* strips 0 .. strips - 2: rows 0 .. len_b of {max(M, A), B} of the strip's last column */
+  uint32_t *strip_best;         /* [4 * strips] SW: the best cell of strips 0 .. s                                     */
+  int32_t *result;              /* [4] score, end_a, end_b (SW: the best cell in hit order), err_flag                  */
+  /* block */
+  uint32_t y0, y1, x;
+  /* walk */
+  SaLongWalk *walk;
+  char *out_a, *out_b;          /* len_a + len_b bytes each                                                            */
+};
+#define SA_LONG_STRIP_COLS 512u
+hipError_t sa_launch_long_forward(const SaLongParams &p, bool is_sw, hipStream_t stream);
+hipError_t sa_launch_long_block(const SaLongParams &p, hipStream_t stream);
+hipError_t sa_launch_long_walk(const SaLongParams &p, hipStream_t stream);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */
 bool sa_wgstream_kernel_applicable(const SaFillParams &p, uint32_t max_len_a);
 hipError_t sa_launch_fill_wgstream(const SaFillParams &p, uint32_t max_len_a, hipStream_t stream);

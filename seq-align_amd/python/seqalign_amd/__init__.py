@@ -164,7 +164,7 @@ def batch_desc(batch: "workloads.Batch") -> BatchDesc:
 
 OPTION_DEFAULTS = {"kernel": "auto", "cpl": 0, "wpb": 0, "lds_pad": 0, "traceback": "device", "trace_kernel": "auto",
                    "sweep_mode": "auto", "sweep_strip": 0, "sweep_cpl": 0, "sweep_trace": 0, "sweep_dirs": 1, "nw_dirs": 1, "pack16": 1, "quad": 0, "walk_overlap": 0, "timing": 0, "chunk_bytes": 0,
-                   "subbatches": 0, "arena_scan_gib": 160, "arena_quality": 1.045, "arena_keep_gib": 16, "upload_slices": 0, "arena_free_pct": 60, "nw_moves": 1, "zero_copy": "auto", "sweep_ev": 1, "reduce_depth": 0, "async_lanes": 0, "walk_group": 0, "dirs_local": 1, "walk_stage": 1, "walk_tile": 0}
+                   "subbatches": 0, "arena_scan_gib": 160, "arena_quality": 1.045, "arena_keep_gib": 16, "upload_slices": 0, "arena_free_pct": 60, "nw_moves": 1, "zero_copy": "auto", "sweep_ev": 1, "reduce_depth": 0, "async_lanes": 0, "walk_group": 0, "dirs_local": 1, "walk_stage": 1, "walk_tile": 0, "long_block_rows": 0}
 
 
 K_MAX = 32
@@ -459,6 +459,53 @@ class Context:
         else:
             _check(getattr(lib(), name)(self._h, *tail), name)
         return n_hits, hits
+
+    # ---- long pairs (seqalign_nw_align_long / seqalign_sw_align_long) ---------------------------------
+    def nw_align_long(self, batch, scoring: Scoring):
+        """seqalign_nw_align_long: what nw_batch returns -- [(score, a, b)] per pair -- for pairs of any size (no 2^31-cell
+        cap: checkpoint rows and blocks recomputed from them)."""
+        _score_args(batch, scoring)
+        n = batch.n_pairs
+        caps = batch.len_a.astype(np.uint64) + batch.len_b.astype(np.uint64) + np.uint64(1)
+        str_off = np.zeros(n, np.uint64)
+        if n:
+            str_off[1:] = np.cumsum(caps)[:-1]
+        total = int(caps.sum()) + 1
+        out_a, out_b = np.zeros(total, np.uint8), np.zeros(total, np.uint8)
+        out_len, out_score = np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_align_long(self._h, C.byref(d), C.byref(scoring), _ptr(str_off), _ptr(out_a), _ptr(out_b),
+                                            _ptr(out_len), _ptr(out_score)), "seqalign_nw_align_long")
+        res = []
+        for p in range(n):
+            o, ln = int(str_off[p]), int(out_len[p])
+            res.append((int(out_score[p]), out_a[o:o + ln].tobytes(), out_b[o:o + ln].tobytes()))
+        return res
+
+    def sw_align_long(self, batch, scoring: Scoring, min_score):
+        """seqalign_sw_align_long: what sw_batch(..., max_hits=1) returns -- per pair a list of at most one hit dict --
+        for pairs of any size."""
+        _score_args(batch, scoring)
+        n = batch.n_pairs
+        ms = np.full(n, min_score, np.int32) if np.isscalar(min_score) else np.asarray(min_score, np.int32)
+        if ms.shape != (n,):
+            raise SeqAlignError(E_ARG, f"sw_align_long: min_score must be a scalar or int32[{n}]")
+        hit_cap = max(1, n)
+        str_cap = int((batch.len_a.astype(np.uint64) + batch.len_b.astype(np.uint64) + np.uint64(1)).sum()) + 1
+        hits = (SwHit * hit_cap)()
+        out_a, out_b = np.zeros(str_cap, np.uint8), np.zeros(str_cap, np.uint8)
+        n_hits = C.c_uint64(0)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_align_long(self._h, C.byref(d), C.byref(scoring), _ptr(ms), hits, C.c_uint64(hit_cap),
+                                            C.byref(n_hits), _ptr(out_a), _ptr(out_b), C.c_uint64(str_cap)),
+               "seqalign_sw_align_long")
+        per_pair = [[] for _ in range(n)]
+        for k in range(n_hits.value):
+            h = hits[k]
+            per_pair[h.pair].append(dict(score=h.score, pos_a=h.pos_a, pos_b=h.pos_b, len_a=h.len_a, len_b=h.len_b,
+                                         a=out_a[h.str_off:h.str_off + h.length].tobytes().decode(),
+                                         b=out_b[h.str_off:h.str_off + h.length].tobytes().decode()))
+        return per_pair
 
     def score_time_ms(self, batch, scoring: Scoring, is_sw: int, repeats: int = 10) -> np.ndarray:
         """seqalign_score_time_ms: the score kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
@@ -836,6 +883,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_score_cross", "seqalign_sw_score_cross", "seqalign_nw_score_cross_multi", "seqalign_sw_score_cross_multi",
     "seqalign_nw_score_search", "seqalign_sw_score_search", "seqalign_nw_score_search_multi",
     "seqalign_sw_score_search_multi",
+    "seqalign_nw_align_long", "seqalign_sw_align_long",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",
