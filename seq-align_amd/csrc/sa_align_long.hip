@@ -1,10 +1,9 @@
 // sa_align_long.hip -- alignments of pairs of any size (seqalign_nw_align_long / seqalign_sw_align_long, sa_batch_long.hip):
 // the three matrices of a pair are never held whole.  One pair at a time:
 //
-//   long_forward  the score-strips pipeline of sa_score.hip over the whole pair (tickets drawn when a workgroup starts, waits
-//                 only on lower tickets, agent-scope release / acquire of a rows-done word per strip; strip s hands strip s + 1
-//                 max(M, A) and B of its last column) -- and at rows R, 2R, .. < len_b every strip also stores M, A, B of its
-//                 columns: the checkpoints, 12 B x (len_a + 1) each.  Yields the NW score, or the SW best cell in hit order.
+//   long_forward  score_strips_kernel (sa_score.hip; the pipeline: sa_strips.hpp) over the whole pair, the ticket being the
+//                 strip -- and at rows R, 2R, .. < len_b every strip also stores M, A, B of its columns: the checkpoints,
+//                 12 B x (len_a + 1) each.  Yields the NW score, or the SW best cell in hit order.
 //   long_block    M, A, B of rows [y0, y1] x columns [0, x] -- the rows from the checkpoint at y0 (or the border row 0) down to
 //                 where the walk stands, the columns left of it -- into a block buffer at pitch x + 1.  The same pipeline
 //                 as sa_fill_strips.hip, strip s reading strip s - 1's last column back from the block; RowSweep starts from
@@ -16,7 +15,7 @@
 //                 device memory for the next block.  The strings are written backwards, as traceback_kernel writes them.
 // SW needs no second forward pass: the rectangle [0 .. end_a] x [0 .. end_b] holds the full matrix's values, and its
 // checkpoints are prefixes of the stored rows.
-#include "sa_rowsweep.hpp"
+#include "sa_strips.hpp"
 #include "sa_trace_common.hpp"
 
 namespace sa {
@@ -24,49 +23,6 @@ namespace sa {
 constexpr int kLongCPL = 8;                          // 512 columns per strip, as sa_fill_strips.hip / sa_score.hip
 constexpr uint32_t kLongCols = kWave * kLongCPL;
 static_assert(kLongCols == SA_LONG_STRIP_COLS, "strip width");
-
-__device__ __forceinline__ int long_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ unsigned long long long_wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
-// the substitution table in LDS (SA_SUBST_LDS) or where it is
-template <int SUBST>
-__device__ __forceinline__ const int32_t *long_table(const SaFillParams &p, int32_t *lds_table) {
-  if constexpr (SUBST == SA_SUBST_LDS) {
-    for (uint32_t k = threadIdx.x; k < p.K * p.K; k += blockDim.x) lds_table[k] = p.table[k];
-    __syncthreads();
-    return lds_table;
-  }
-  return p.table;
-}
-
-// the strip of this workgroup: a ticket drawn when it starts (the counter sits behind the progress words), so that strip s
-// only ever waits for a strip that is resident or done
-__device__ __forceinline__ uint32_t long_ticket(uint32_t *progress, uint32_t strips) {
-  uint32_t t = 0;
-  if (threadIdx.x == 0) t = atomicAdd(progress + strips, 1u);
-  return __builtin_amdgcn_readfirstlane(t);
-}
-
-__device__ __forceinline__ void long_wait(const uint32_t *word, uint32_t need) {
-  while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) __builtin_amdgcn_s_sleep(8);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
-__device__ __forceinline__ void long_publish(uint32_t *word, uint32_t value) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  if (threadIdx.x == 0) __hip_atomic_store(word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // my CPL columns of one row into M / A / B at dst (columns past ncol are not mine to write)
 template <int CPL>
@@ -85,10 +41,10 @@ __global__ void __launch_bounds__(kWave) long_forward_kernel(const SaLongParams 
   constexpr int CPL = kLongCPL;
   const SaFillParams &p = lp.f;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
-  const int32_t *table = long_table<SUBST>(p, lds_table);
+  const int32_t *table = stage_table<SUBST>(p, lds_table);
 
   const int lane = threadIdx.x;
-  const uint32_t strip = long_ticket(lp.progress, lp.strips);
+  const uint32_t strip = strip_ticket(lp.progress + lp.strips);   // (the counter sits behind the progress words)
   const uint32_t la = p.len_a[0], lb = p.len_b[0];
   const uint32_t i0 = strip * kLongCols;
   const uint8_t *__restrict__ sa_ = p.arena + p.off_a[0];
@@ -110,34 +66,22 @@ __global__ void __launch_bounds__(kWave) long_forward_kernel(const SaLongParams 
   RowSweep<CPL, SUBST, GENERAL> sw;
   sw.start_strip(p, k, bd, sa_, la, i0, col0, lane);
   __builtin_amdgcn_s_waitcnt(kWaitVm0);
-  int best_s[SW ? CPL : 1];
+  int best_s[SW ? CPL : 1];   // BestCells, open-coded: with the struct this kernel's SW forms ran 1 % slower (profiles/r11)
   uint32_t best_r[SW ? CPL : 1];
 #pragma unroll
   for (int c = 0; c < (SW ? CPL : 1); ++c) { best_s[c] = 0; best_r[c] = 0; }
 
-  int code = 0, fz = 0, fb = 0;   // lane q: row j0 + q's code and, from the strip to my left, max(M, A) and B
-  int oz = 0, ob = 0;             // lane q: row j0 + q's values of my last column, for the strip to my right
+  StripHandoff h;
   uint32_t to_ck = R;             // rows until the next checkpoint row
   uint64_t ck_at = (uint64_t)col0 + 1;
   for (uint32_t j = 1; j <= lb; ++j) {
     const int q = (j - 1) & (kWave - 1);
     if (q == 0) {
-      const uint32_t r = j + lane;
-      if (strip > 0) long_wait(done + strip - 1, min(j + kWave - 1, lb));
-      if (r <= lb) {
-        code = p.code[sb_[r - 1]];
-        if (strip == 0) {   // border column (reference alignment.c:72-80)
-          fz = max(k.floor_, bd.edge_gap(r));
-          fb = k.floor_;
-        } else {
-          const int2 h = *reinterpret_cast<const int2 *>(hand_in + 2ull * r);
-          fz = h.x; fb = h.y;
-        }
-      }
-      __builtin_amdgcn_s_waitcnt(kWaitVm0);
+      if (strip > 0) strip_wait(done + strip - 1, min(j + kWave - 1, lb));
+      h.load(p, k, bd, sb_, lb, strip, hand_in, j + lane);
     }
     int mv[CPL], av[CPL], bv[CPL];
-    sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(code, q), read_lane(fz, q), read_lane(fb, q), mv, av, bv);
+    sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(h.code, q), read_lane(h.fz, q), read_lane(h.fb, q), mv, av, bv);
     if constexpr (SW) {
 #pragma unroll
       for (int c = 0; c < CPL; ++c) {
@@ -153,15 +97,7 @@ __global__ void __launch_bounds__(kWave) long_forward_kernel(const SaLongParams 
         ck_at += 3ull * W;
       }
     }
-    if (!last_strip) {   // a strip that is not the last is full: lane 63's last column is the strip's
-      const int z = read_lane(max(mv[CPL - 1], av[CPL - 1]), kWave - 1), b = read_lane(bv[CPL - 1], kWave - 1);
-      oz = (lane == q) ? z : oz;
-      ob = (lane == q) ? b : ob;
-      if (q == kWave - 1 || j == lb) {
-        if (lane <= q) *reinterpret_cast<int2 *>(hand_out + 2ull * (j - q + lane)) = make_int2(oz, ob);
-        if (j != lb) long_publish(done + strip, j);   // (the last rows are published below, after the best cell)
-      }
-    }
+    if (!last_strip) h.keep<CPL>(mv, av, bv, hand_out, done + strip, lane, q, j, lb);
   }
 
   const unsigned long long err = sw.reduce_err();
@@ -175,15 +111,9 @@ __global__ void __launch_bounds__(kWave) long_forward_kernel(const SaLongParams 
 #pragma unroll
     for (int c = 0; c < CPL; ++c)   // c ascending, strict >: the lowest column wins a tie
       if (c < ncol && best_s[c] > b) { b = best_s[c]; kb = ((unsigned long long)(col0 + c + 1) << 32) | best_r[c]; }
-    int score = long_wave_max(b);
-    unsigned long long key = long_wave_min_u64(b == score && score > 0 ? kb : ~0ull);
-    if (strip > 0 && lb > 0) {   // the strips to my left: their last rows were acquired above, their best with them
-      const uint4 left = *reinterpret_cast<const uint4 *>(lp.strip_best + 4ull * (strip - 1));
-      if ((int)left.x >= score && (int)left.x > 0) {   // a tie goes to the lower column: theirs
-        score = (int)left.x;
-        key = ((unsigned long long)left.y << 32) | left.z;
-      }
-    }
+    int score = wave_max_i32(b);
+    unsigned long long key = wave_min_u64(b == score && score > 0 ? kb : ~0ull);
+    if (strip > 0 && lb > 0) merge_left_best(lp.strip_best + 4ull * (strip - 1), score, key);
     const uint32_t ea = score > 0 ? (uint32_t)(key >> 32) : 0u, eb = score > 0 ? (uint32_t)key : 0u;
     if (lane == 0) {
       if (last_strip) {
@@ -201,7 +131,7 @@ __global__ void __launch_bounds__(kWave) long_forward_kernel(const SaLongParams 
         if (col0 + c + 1 == la) lp.result[0] = sw.X[c];   // max(M, A, B) of (len_a, len_b)
     }
   }
-  if (!last_strip && lb > 0) long_publish(done + strip, lb);
+  if (!last_strip && lb > 0) strip_publish(done + strip, lb);   // the last rows (and the best cell so far)
 }
 
 // ------------------------------------------------------------------------------------------------------------ block ---
@@ -228,10 +158,10 @@ __global__ void __launch_bounds__(kWave) long_block_kernel(const SaLongParams lp
   constexpr int CPL = kLongCPL;
   const SaFillParams &p = lp.f;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
-  const int32_t *table = long_table<SUBST>(p, lds_table);
+  const int32_t *table = stage_table<SUBST>(p, lds_table);
 
   const int lane = threadIdx.x;
-  const uint32_t strip = long_ticket(lp.progress, lp.strips);
+  const uint32_t strip = strip_ticket(lp.progress + lp.strips);   // (the counter sits behind the progress words)
   const uint32_t la = p.len_a[0], lb = p.len_b[0];
   const uint32_t x = lp.x, y0 = lp.y0, y1 = lp.y1;
   const uint32_t i0 = strip * kLongCols;
@@ -282,7 +212,7 @@ __global__ void __launch_bounds__(kWave) long_block_kernel(const SaLongParams lp
       const uint32_t lr = j - y0;            // the block's row
       const int q = (lr - 1) & (kWave - 1);
       if (q == 0) {
-        if (strip > 0) long_wait(done + strip - 1, min(lr + kWave - 1, y1 - y0) + 1);
+        if (strip > 0) strip_wait(done + strip - 1, min(lr + kWave - 1, y1 - y0) + 1);
         const uint32_t r = j + lane;
         if (r <= y1) {
           code = p.code[sb_[r - 1]];
@@ -300,7 +230,7 @@ __global__ void __launch_bounds__(kWave) long_block_kernel(const SaLongParams lp
       int mv[CPL], av[CPL], bv[CPL];
       sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(code, q), read_lane(fz, q), read_lane(fb, q), mv, av, bv);
       long_store_row<CPL>(Mb, Ab, Bb, off, ncol, mv, av, bv);
-      if (!last_strip && (q == kWave - 1 || j == y1)) long_publish(done + strip, lr + 1);   // rows <= lr are written
+      if (!last_strip && (q == kWave - 1 || j == y1)) strip_publish(done + strip, lr + 1);   // rows <= lr are written
     }
     err = sw.reduce_err();
   }
@@ -375,19 +305,9 @@ __global__ void __launch_bounds__(kWave) long_walk_kernel(const SaLongParams lp)
 
 template <bool SW>
 static hipError_t launch_forward(const SaLongParams &p, hipStream_t stream) {
-  const bool general = needs_general(p.f);
-  const dim3 grid(p.strips), block(kWave);
-  const uint32_t K = p.f.K;
-  if (K <= 1) {
-    if (general) hipLaunchKernelGGL((long_forward_kernel<SA_SUBST_SIMPLE, true, SW>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((long_forward_kernel<SA_SUBST_SIMPLE, false, SW>), grid, block, 0, stream, p);
-  } else if (K <= SA_LDS_TABLE_MAX_K) {
-    const size_t lds = (size_t)K * K * sizeof(int32_t);
-    if (general) hipLaunchKernelGGL((long_forward_kernel<SA_SUBST_LDS, true, SW>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((long_forward_kernel<SA_SUBST_LDS, false, SW>), grid, block, lds, stream, p);
-  } else {
-    hipLaunchKernelGGL((long_forward_kernel<SA_SUBST_GLOBAL, true, SW>), grid, block, 0, stream, p);
-  }
+  launch_by_scoring(p.f, [&](auto subst, auto general, uint32_t table_ints) {
+    hipLaunchKernelGGL((long_forward_kernel<subst(), general(), SW>), dim3(p.strips), dim3(kWave), table_ints * sizeof(int32_t), stream, p);
+  });
   return hipGetLastError();
 }
 
@@ -403,19 +323,9 @@ hipError_t sa_launch_long_block(const SaLongParams &p, hipStream_t stream) {
   using namespace sa;
   if (p.strips == 0 || p.R == 0 || p.y1 < p.y0 || (p.y0 && p.y0 % p.R)) return hipErrorInvalidValue;
   sa_record_launch(SEQALIGN_K_LONG_BLOCK, 1);
-  const bool general = needs_general(p.f);
-  const dim3 grid(p.strips), block(kWave);
-  const uint32_t K = p.f.K;
-  if (K <= 1) {
-    if (general) hipLaunchKernelGGL((long_block_kernel<SA_SUBST_SIMPLE, true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((long_block_kernel<SA_SUBST_SIMPLE, false>), grid, block, 0, stream, p);
-  } else if (K <= SA_LDS_TABLE_MAX_K) {
-    const size_t lds = (size_t)K * K * sizeof(int32_t);
-    if (general) hipLaunchKernelGGL((long_block_kernel<SA_SUBST_LDS, true>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((long_block_kernel<SA_SUBST_LDS, false>), grid, block, lds, stream, p);
-  } else {
-    hipLaunchKernelGGL((long_block_kernel<SA_SUBST_GLOBAL, true>), grid, block, 0, stream, p);
-  }
+  launch_by_scoring(p.f, [&](auto subst, auto general, uint32_t table_ints) {
+    hipLaunchKernelGGL((long_block_kernel<subst(), general()>), dim3(p.strips), dim3(kWave), table_ints * sizeof(int32_t), stream, p);
+  });
   return hipGetLastError();
 }
 

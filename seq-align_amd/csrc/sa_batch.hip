@@ -268,7 +268,7 @@ int sa_host::fetch_status(seqalign_ctx *ctx, const Chunk &c, uint64_t *status_ou
 }
 
 int sa_host::check_batch(const seqalign_batch_t *b) {
-  if (!b || (b->n_pairs && (!b->arena || !b->off_a || !b->off_b || !b->len_a || !b->len_b))) return SEQALIGN_E_ARG;
+  if (!batch_readable(b)) return SEQALIGN_E_ARG;
   for (uint64_t p = 0; p < b->n_pairs; ++p)
     if ((uint64_t)(b->len_a[p] + 1ull) * (b->len_b[p] + 1ull) >= (1ull << 31)) return SEQALIGN_E_TOO_LARGE;
   return SEQALIGN_OK;
@@ -1159,7 +1159,7 @@ static int nw_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, con
                          const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len,
                          int32_t *out_score) {
   const seqalign_batch_t *b = batch;
-  if (!b || (b->n_pairs && (!b->arena || !b->off_a || !b->off_b || !b->len_a || !b->len_b))) return SEQALIGN_E_ARG;
+  if (!batch_readable(b)) return SEQALIGN_E_ARG;
   if (batch->n_pairs == 0) return SEQALIGN_OK;
   int rc;
   // one parallel pass over the lengths: validity (check_batch) and the sizes chunk planning needs

@@ -80,7 +80,7 @@ int choose_plan(const seqalign_ctx *ctx, uint64_t pair, uint32_t la, uint32_t lb
 
 // argument checks, before any device work
 int check_long_batch(const seqalign_batch_t *b) {
-  if (!b || (b->n_pairs && (!b->arena || !b->off_a || !b->off_b || !b->len_a || !b->len_b))) return SEQALIGN_E_ARG;
+  if (!batch_readable(b)) return SEQALIGN_E_ARG;
   for (uint64_t p = 0; p < b->n_pairs; ++p)
     if ((uint64_t)b->len_a[p] + b->len_b[p] >= 0xFFFFFFFFull) return SEQALIGN_E_TOO_LARGE;
   return SEQALIGN_OK;
@@ -114,7 +114,7 @@ struct LongPair {
     // sequences + descriptors (off_a, off_b: u64; len_a, len_b: u32) up
     if ((rc = ctx->h_arena.reserve(seq + 16)) || (rc = ctx->h_desc.reserve(64)) || (rc = ctx->h_tmeta.reserve(sizeof(LongMeta))) ||
         (rc = ctx->arena.reserve(seq + 16)) || (rc = ctx->off_a.reserve(64)) || (rc = ctx->t_meta.reserve(sizeof(LongMeta))) ||
-        (rc = ctx->strip_progress.reserve(4 * (std::max(strips_fwd, 1u) + 1) + 16 * strips_fwd + 64)) ||
+        (rc = ctx->strip_progress.reserve(sa_strip_progress_bytes(strips_fwd))) ||
         (rc = ctx->t_out_a.reserve(seq + 16)) || (rc = ctx->t_out_b.reserve(seq + 16)) ||
         (rc = ctx->long_ckpt.reserve(12 * C * pl.nck + 16)) || (rc = ctx->long_block.reserve(12 * C * pl.block_rows + 16)))
       return rc;
@@ -156,17 +156,14 @@ struct LongPair {
     if (is_sw || pl.nck) {
       p.strips = strips_fwd;
       p.handoff = strips_fwd > 1 ? ctx->score_handoff.as<int32_t>() : nullptr;
-      p.strip_best = p.progress + ((strips_fwd + 1 + 3) & ~3u);
+      p.strip_best = p.progress + sa_strip_best_word(strips_fwd);
       p.result = d_meta->result;
       HIP_TRY(hipMemsetAsync(p.progress, 0, 4 * (strips_fwd + 1), st));
       hipError_t e = sa_launch_long_forward(p, is_sw, st);
       if (e != hipSuccess) return fail_hip(e, "long forward launch");
       HIP_TRY(hipMemcpyAsync(h_meta, d_meta, sizeof(LongMeta), hipMemcpyDeviceToHost, st));
       HIP_TRY(stream_wait_spinning(st));
-      if (h_meta->result[3] || h_meta->status != ~0ull) {
-        set_last_error("pair " + std::to_string(pair) + ": a character pair without a score");
-        return SEQALIGN_E_UNKNOWN_PAIR;
-      }
+      if (h_meta->result[3] || h_meta->status != ~0ull) return fail_unknown_pair(pair);
       if (is_sw) {
         const int32_t best = h_meta->result[0];
         if (best <= 0 || best < min_score) return SEQALIGN_OK;   // no hit
@@ -193,10 +190,7 @@ struct LongPair {
       if (e != hipSuccess) return fail_hip(e, "long block / walk launch");
       HIP_TRY(hipMemcpyAsync(h_meta, d_meta, sizeof(LongMeta), hipMemcpyDeviceToHost, st));
       HIP_TRY(stream_wait_spinning(st));
-      if (first && h_meta->status != ~0ull) {   // (NW without a forward pass: its first block is the whole matrix)
-        set_last_error("pair " + std::to_string(pair) + ": a character pair without a score");
-        return SEQALIGN_E_UNKNOWN_PAIR;
-      }
+      if (first && h_meta->status != ~0ull) return fail_unknown_pair(pair);   // (NW without a forward pass: its first block is the whole matrix)
       if (h_meta->walk.status) {
         set_last_error("pair " + std::to_string(pair) + ": traceback failed");
         return (int)h_meta->walk.status;

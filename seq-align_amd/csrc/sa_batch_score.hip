@@ -78,22 +78,10 @@ struct ScoreChunkRun {
   int prepare(const seqalign_batch_t *b, const ScoreChunk &c) {
     int rc;
     n = c.count;
-    std::vector<uint8_t> cls(n);
-    uint64_t cnt[kRowClasses + 1] = {};
     uint64_t hand_total = 0;
-    for (uint64_t k = 0; k < n; ++k) {
-      const uint32_t la = b->len_a[c.first + k];
-      const int x = sa_score_row_class(la);
-      cls[k] = (uint8_t)x; cnt[x]++;
-      cls_max_a[x] = std::max(cls_max_a[x], la);
-    }
-    cls_first[0] = 0;
-    for (int x = 0; x <= kRowClasses; ++x) cls_first[x + 1] = cls_first[x] + cnt[x];
     order.resize(n);
-    { uint64_t at[kRowClasses + 1];
-      for (int x = 0; x <= kRowClasses; ++x) at[x] = cls_first[x];
-      for (uint64_t k = 0; k < n; ++k) order[at[cls[k]]++] = (uint32_t)k; }
-    const uint64_t n_strip = cnt[kStripClass];
+    sort_by_row_class(n, [&](uint64_t k) { return b->len_a[c.first + k]; }, order.data(), cls_first, cls_max_a);
+    const uint64_t n_strip = cls_first[kStripClass + 1] - cls_first[kStripClass];
     spp = n_strip ? sa_score_strips_per_pair(cls_max_a[kStripClass]) : 1;
     strip_words = ((n_strip + 7) / 8) * 8 * spp;
 
@@ -125,7 +113,7 @@ struct ScoreChunkRun {
     if ((rc = ctx->arena.reserve(c.seq_bytes + 16)) || (rc = ctx->off_a.reserve(desc_bytes)) || (rc = ctx->status.reserve(n * 8)) ||
         (rc = ctx->best_score.reserve(16 + 12 * n)))
       return rc;
-    if (n_strip && ((rc = ctx->strip_progress.reserve(4 * (strip_words + 1) + 16 * strip_words + 16)) ||
+    if (n_strip && ((rc = ctx->strip_progress.reserve(sa_strip_progress_bytes(strip_words))) ||
                     (rc = ctx->score_handoff.reserve(8 * hand_total + 16))))
       return rc;
     hipStream_t st = ctx->stream;
@@ -157,7 +145,7 @@ struct ScoreChunkRun {
       hipError_t e;
       if (x == kStripClass) {
         p.progress = ctx->strip_progress.as<uint32_t>();
-        p.strip_best = p.progress + ((strip_words + 1 + 3) & ~(uint64_t)3);
+        p.strip_best = p.progress + sa_strip_best_word(strip_words);
         p.handoff = ctx->score_handoff.as<int32_t>();
         p.handoff_off = d_hoff + s0;
         p.strips_per_pair = spp;
@@ -187,8 +175,7 @@ struct ScoreChunkRun {
       for (uint64_t s = 0; s < n; ++s)
         if (status[s] != ~0ull) worst = std::min<uint64_t>(worst, order[s]);
       if (fail_pair) *fail_pair = first + worst;
-      set_last_error("pair " + std::to_string(first + worst) + ": a character pair without a score");
-      return SEQALIGN_E_UNKNOWN_PAIR;
+      return fail_unknown_pair(first + worst);
     }
     const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
     const uint32_t *ha = h + 4 + n, *hb = h + 4 + 2 * n;
@@ -205,7 +192,7 @@ struct ScoreChunkRun {
 };
 
 int check_score_batch(const seqalign_batch_t *b) {   // check_batch without the 2^31-cell cap
-  if (!b || (b->n_pairs && (!b->arena || !b->off_a || !b->off_b || !b->len_a || !b->len_b))) return SEQALIGN_E_ARG;
+  if (!batch_readable(b)) return SEQALIGN_E_ARG;
   return SEQALIGN_OK;
 }
 

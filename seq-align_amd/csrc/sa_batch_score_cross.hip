@@ -165,17 +165,10 @@ struct CrossCall {
         }
         const uint64_t bytes = pack(Q, qs.data() + qr.first, nq, q_at, h_off_q, h_len_q);
         // the queries by row class: q_list holds class 0's, then class 1's, ...
-        uint64_t cls_first[SA_SCORE_ROW_CLASSES + 1] = {};
-        uint32_t cls_max_a[SA_SCORE_ROW_CLASSES] = {};
-        for (uint64_t k = 0; k < nq; ++k) {
-          const int x = sa_score_row_class(h_len_q[k]);
-          cls_first[x + 1]++;
-          cls_max_a[x] = std::max(cls_max_a[x], h_len_q[k]);
-        }
-        for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) cls_first[x + 1] += cls_first[x];
-        { uint64_t at[SA_SCORE_ROW_CLASSES];
-          for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) at[x] = cls_first[x];
-          for (uint64_t k = 0; k < nq; ++k) h_qlist[at[sa_score_row_class(h_len_q[k])]++] = (uint32_t)k; }
+        // (the class past the last, rows for the strips kernel, stays empty: run_short's queries are short)
+        uint64_t cls_first[SA_SCORE_ROW_CLASSES + 2];
+        uint32_t cls_max_a[SA_SCORE_ROW_CLASSES + 1];
+        sort_by_row_class(nq, [&](uint64_t k) { return h_len_q[k]; }, h_qlist, cls_first, cls_max_a);
         if (bytes) HIP_TRY(hipMemcpyAsync(d_seq + q_at, h_seq + q_at, bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_off_q, h_off_q, 8 * nq, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_len_q, h_len_q, 4 * nq, hipMemcpyHostToDevice, st));

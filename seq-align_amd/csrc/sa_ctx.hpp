@@ -499,7 +499,36 @@ bool sw_best_x2_applicable(const seqalign_ctx_t *ctx, const seqalign_dev_scoring
 int sw_traceback_dirs(seqalign_ctx_t *ctx, const seqalign_dev_scoring_t *sc, const seqalign_dev_batch_t *b, const seqalign_trace_t *t,
                       const uint8_t *dirs, const int32_t *start_score, void *stream);
 bool sw_dirs_x2_applicable(const seqalign_ctx_t *ctx, const seqalign_dev_scoring_t *scoring, uint32_t len_a, uint32_t len_b);
+// a batch whose arrays can be read: the first rule of check_batch and of its score-only and long-pair forms
+static inline bool batch_readable(const seqalign_batch_t *b) {
+  return b && (!b->n_pairs || (b->arena && b->off_a && b->off_b && b->len_a && b->len_b));
+}
 int check_batch(const seqalign_batch_t *b);
+// Counting sort of items 0 .. n - 1 by row class (sa_score_row_class of len(k)): order[] holds class 0's items, then class
+// 1's, ..., each in index order; class x has slots [cls_first[x], cls_first[x + 1]) and its longest row is cls_max_a[x].
+template <class Len>
+void sort_by_row_class(uint64_t n, Len len, uint32_t *order, uint64_t (&cls_first)[SA_SCORE_ROW_CLASSES + 2],
+                       uint32_t (&cls_max_a)[SA_SCORE_ROW_CLASSES + 1]) {
+  std::fill(std::begin(cls_first), std::end(cls_first), 0);
+  std::fill(std::begin(cls_max_a), std::end(cls_max_a), 0);
+  std::vector<uint8_t> cls(n);
+  for (uint64_t k = 0; k < n; ++k) {
+    const uint32_t la = len(k);
+    const int x = sa_score_row_class(la);
+    cls[k] = (uint8_t)x;
+    cls_first[x + 1]++;
+    cls_max_a[x] = std::max(cls_max_a[x], la);
+  }
+  for (int x = 0; x <= SA_SCORE_ROW_CLASSES; ++x) cls_first[x + 1] += cls_first[x];
+  uint64_t at[SA_SCORE_ROW_CLASSES + 1];
+  std::copy(cls_first, cls_first + SA_SCORE_ROW_CLASSES + 1, at);
+  for (uint64_t k = 0; k < n; ++k) order[at[cls[k]]++] = (uint32_t)k;
+}
+// SEQALIGN_E_UNKNOWN_PAIR for a pair of a list, with its message
+static inline int fail_unknown_pair(uint64_t pair) {
+  set_last_error("pair " + std::to_string(pair) + ": a character pair without a score");
+  return SEQALIGN_E_UNKNOWN_PAIR;
+}
 // chunked fill of a host batch with an uploaded scoring, matrices copied back (also the legacy single-pair path)
 int fill_batch_uploaded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const seqalign_dev_scoring *sc,
                         const uint64_t *mat_off, int32_t *M, int32_t *A, int32_t *B, uint64_t *status);

@@ -374,23 +374,15 @@ fill_stream_kernel(const SaFillParams p, const uint32_t table_ints) {
 
 template <int CPL, int R, int FB, int MODE, int WPB = kWavesPerBlock>
 static hipError_t launch_cpl_mode(const SaFillParams &p, hipStream_t stream) {
-  const bool general = needs_general(p);
   int wpb = WPB;   // pairs per workgroup; option "wpb" in {1,2,4,8} (tuning experiments)
   if (p.tune_wpb == 1 || p.tune_wpb == 2 || p.tune_wpb == 4 || p.tune_wpb == 8) wpb = (int)p.tune_wpb;
   const dim3 grid((p.n_pairs + wpb - 1) / wpb), block(kWave * wpb);
   size_t rings = (size_t)wpb * 3 * R * sizeof(int32_t);
   rings += p.tune_lds_pad;   // option "lds_pad": occupancy experiments
-  if (p.K <= 1) {
-    if (general) hipLaunchKernelGGL((fill_stream_kernel<CPL, SA_SUBST_SIMPLE, true, R, FB, MODE>), grid, block, rings, stream, p, 0u);
-    else hipLaunchKernelGGL((fill_stream_kernel<CPL, SA_SUBST_SIMPLE, false, R, FB, MODE>), grid, block, rings, stream, p, 0u);
-  } else if (p.K <= SA_LDS_TABLE_MAX_K) {
-    const uint32_t tints = (p.K * p.K + 3u) & ~3u;
-    const size_t lds = rings + tints * sizeof(int32_t);
-    if (general) hipLaunchKernelGGL((fill_stream_kernel<CPL, SA_SUBST_LDS, true, R, FB, MODE>), grid, block, lds, stream, p, tints);
-    else hipLaunchKernelGGL((fill_stream_kernel<CPL, SA_SUBST_LDS, false, R, FB, MODE>), grid, block, lds, stream, p, tints);
-  } else {
-    hipLaunchKernelGGL((fill_stream_kernel<CPL, SA_SUBST_GLOBAL, true, R, FB, MODE>), grid, block, rings, stream, p, 0u);
-  }
+  launch_by_scoring(p, [&](auto subst, auto general, uint32_t table_ints) {
+    const uint32_t tints = (table_ints + 3u) & ~3u;   // (the table takes whole 16-byte units of LDS)
+    hipLaunchKernelGGL((fill_stream_kernel<CPL, subst(), general(), R, FB, MODE>), grid, block, rings + tints * sizeof(int32_t), stream, p, tints);
+  });
   return hipGetLastError();
 }
 

@@ -1,31 +1,15 @@
 // sa_fill_strips.hip -- few, LONG pairs: column strips of one pair run as a
-// pipeline of waves.
+// pipeline of waves (sa_strips.hpp: the pipeline, its tickets and its waits).
 //
 // Replaces alignment_fill_matrices (reference src/alignment.c:28-168) for pairs
 // whose rows do not fit one wave; same arithmetic as the other row-sweep kernels
 // (sa_rowsweep.hpp).  sa_fill_rowscan.hip walks the 512-column strips of a pair
 // one after the other inside ONE wave: a single 10 000 x 10 000 pair keeps 1 of
-// the chip's 1024 SIMDs busy for 79 ms (1.3 GCUPS).  The only dependency between
-// strip s and strip s-1 is the boundary column (match/gap_a/gap_b of the last
-// column of s-1, row by row), so here every (pair, strip) is its own wave:
-//
-//   * strip s computes rows in chunks of 64; before a chunk it waits until strip
-//     s-1 has published that it is done with those rows (one uint32 per strip in
-//     HBM, agent-scope release/acquire), then reads the 64 boundary cells back
-//     from the matrices -- exactly what the rowscan kernel's RowFeed does;
-//   * strip s therefore runs 64 rows behind s-1: a pair with S strips takes
-//     len_b + 64*S row steps instead of len_b * S.
-//
-// Workgroup = one wave.  A workgroup does NOT take its (pair, strip) from blockIdx:
-// it draws a TICKET from an atomic counter when it starts running, and ticket =
-// (group of 8 pairs, strip, pair in group).  A strip's ticket is therefore always
-// higher than the ticket of the strip it waits for, and a ticket only exists once
-// its workgroup is resident on a CU -- so a waiting wave only ever waits for waves
-// that are running or finished, whatever order the hardware dispatches workgroups
-// in (other contexts' kernels, CU masks, preemption).  No cooperative launch, no
-// dispatch-order assumption, no watchdog.  Tickets are drawn roughly in dispatch
-// order, so one pair's strips (8 tickets apart) still tend to land on one XCD.
-#include "sa_rowsweep.hpp"
+// the chip's 1024 SIMDs busy for 79 ms (1.3 GCUPS).  Here every (pair, strip) is
+// its own wave, and what strip s needs of strip s-1 -- match/gap_a/gap_b of its
+// last column, row by row -- it reads back from the matrices once s-1 has
+// published those rows: exactly what the rowscan kernel's RowFeed does.
+#include "sa_strips.hpp"
 
 namespace sa {
 
@@ -37,20 +21,11 @@ __global__ void __launch_bounds__(kWave)
 fill_strips_kernel(const SaFillParams p, uint32_t *progress, const uint32_t strips_per_pair) {
   constexpr int CPL = kStripCPL;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
-  const int32_t *table = p.table;
-  if constexpr (SUBST == SA_SUBST_LDS) {
-    for (uint32_t k = threadIdx.x; k < p.K * p.K; k += blockDim.x) lds_table[k] = p.table[k];
-    __syncthreads();
-    table = lds_table;
-  }
+  const int32_t *table = stage_table<SUBST>(p, lds_table);
 
   const int lane = threadIdx.x;
-  // ticket = (group * strips_per_pair + strip) * 8 + pair_in_group; the counter sits behind the progress words
-  uint32_t ticket = 0;
-  if (lane == 0) ticket = atomicAdd(progress + (uint64_t)gridDim.x, 1u);
-  ticket = __builtin_amdgcn_readfirstlane(ticket);
-  const uint32_t in_group = ticket & 7u, gs = ticket >> 3;
-  const uint32_t strip = gs % strips_per_pair, pair = (gs / strips_per_pair) * 8 + in_group;
+  uint32_t strip, pair;
+  strip_of_ticket(strip_ticket(progress + (uint64_t)gridDim.x), strips_per_pair, strip, pair);
   if (pair >= p.n_pairs) return;
 
   const uint32_t la = p.len_a[pair], lb = p.len_b[pair];
@@ -100,19 +75,14 @@ fill_strips_kernel(const SaFillParams p, uint32_t *progress, const uint32_t stri
     for (uint32_t j = 1; j <= lb; ++j, off += W) {
       const int q = (j - 1) & (kWave - 1);
       if (q == 0) {
-        if (strip > 0) {   // rows j .. j+63 of the strip to my left must be in memory
-          const uint32_t need = min(j + kWave - 1, lb) + 1;
-          // (the strip to my left holds a lower ticket: it is resident or done, see the header)
-          while (__hip_atomic_load(done + strip - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need)
-            __builtin_amdgcn_s_sleep(8);
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the boundary loads below see those rows
-        }
+        // rows j .. j+63 of the strip to my left must be in memory
+        if (strip > 0) strip_wait(done + strip - 1, min(j + kWave - 1, lb) + 1);
         feed.load(p, k, bd, sb_, lb, W, i0, Mg, Ag, Bg, j + lane);
       }
       int mv[CPL], av[CPL], bv[CPL];
       sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(feed.code, q), read_lane(feed.Z, q),
              read_lane(feed.B, q), mv, av, bv);
-      if (ncol == CPL) {
+      if (ncol == CPL) {   // (open-coded, not long_store_row's form: a shared helper cost the GENERAL forms 4 more spilled SGPRs)
         store_run<CPL, true>(Mg + off, mv);
         store_run<CPL, true>(Ag + off, av);
         store_run<CPL, true>(Bg + off, bv);
@@ -121,10 +91,7 @@ fill_strips_kernel(const SaFillParams p, uint32_t *progress, const uint32_t stri
         store_partial<CPL>(Ag + off, av, ncol);
         store_partial<CPL>(Bg + off, bv, ncol);
       }
-      if (!last_strip && (q == kWave - 1 || j == lb)) {   // publish: rows <= j are written
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        if (lane == 0) __hip_atomic_store(done + strip, j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (!last_strip && (q == kWave - 1 || j == lb)) strip_publish(done + strip, j + 1);   // rows <= j are written
     }
     err = sw.reduce_err();
   }
@@ -156,17 +123,8 @@ hipError_t sa_launch_fill_strips(const SaFillParams &p, uint32_t max_len_a, uint
   hipLaunchKernelGGL(sa::strips_init_kernel, dim3((unsigned)((init_n + 255) / 256)), dim3(256), 0, stream,
                      progress, n_progress, p.status, p.n_pairs);
   const dim3 grid((unsigned)blocks), block(sa::kWave);
-  const bool general = sa::needs_general(p);
-  using namespace sa;
-  if (p.K <= 1) {
-    if (general) hipLaunchKernelGGL((fill_strips_kernel<SA_SUBST_SIMPLE, true>), grid, block, 0, stream, p, progress, spp);
-    else hipLaunchKernelGGL((fill_strips_kernel<SA_SUBST_SIMPLE, false>), grid, block, 0, stream, p, progress, spp);
-  } else if (p.K <= SA_LDS_TABLE_MAX_K) {
-    const size_t lds = (size_t)p.K * p.K * sizeof(int32_t);
-    if (general) hipLaunchKernelGGL((fill_strips_kernel<SA_SUBST_LDS, true>), grid, block, lds, stream, p, progress, spp);
-    else hipLaunchKernelGGL((fill_strips_kernel<SA_SUBST_LDS, false>), grid, block, lds, stream, p, progress, spp);
-  } else {
-    hipLaunchKernelGGL((fill_strips_kernel<SA_SUBST_GLOBAL, true>), grid, block, 0, stream, p, progress, spp);
-  }
+  sa::launch_by_scoring(p, [&](auto subst, auto general, uint32_t table_ints) {
+    hipLaunchKernelGGL((sa::fill_strips_kernel<subst(), general()>), grid, block, table_ints * sizeof(int32_t), stream, p, progress, spp);
+  });
   return hipGetLastError();
 }

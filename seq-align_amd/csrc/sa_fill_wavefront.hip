@@ -23,7 +23,7 @@
 // a 16-step window abut in L2, which merges them into full lines before they
 // reach HBM.  The row-sweep kernel (sa_fill_rowscan.hip) writes whole rows per
 // instruction instead; bench.py reports which of the two is used.
-#include "sa_fill_common.hpp"
+#include "sa_rowsweep.hpp"   // stage_table, launch_by_scoring
 
 namespace sa {
 
@@ -31,12 +31,7 @@ template <int CPL, int SUBST, bool GENERAL>
 __global__ void __launch_bounds__(kWave *kWavesPerBlock)
 fill_wavefront_kernel(const SaFillParams p) {
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
-  const int32_t *table = p.table;
-  if constexpr (SUBST == SA_SUBST_LDS) {
-    for (uint32_t k = threadIdx.x; k < p.K * p.K; k += blockDim.x) lds_table[k] = p.table[k];
-    __syncthreads();
-    table = lds_table;
-  }
+  const int32_t *table = stage_table<SUBST>(p, lds_table);
 
   const int lane = threadIdx.x & (kWave - 1);
   const uint32_t pair = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
@@ -200,19 +195,12 @@ fill_wavefront_kernel(const SaFillParams p) {
 
 template <int CPL>
 static hipError_t launch_cpl(const SaFillParams &p, hipStream_t stream) {
-  const bool general =
-      p.flags & (SA_F_NO_END_GAP | SA_F_NO_GAPS_A | SA_F_NO_GAPS_B | SA_F_HAS_SENTINEL);
+  // (not needs_general: this kernel's fast path keeps max(M, B) apart and so takes gap_open > 0 as well)
+  const bool wf_general = p.flags & (SA_F_NO_END_GAP | SA_F_NO_GAPS_A | SA_F_NO_GAPS_B | SA_F_HAS_SENTINEL);
   const dim3 grid((p.n_pairs + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
-  if (p.K <= 1) {
-    if (general) hipLaunchKernelGGL((fill_wavefront_kernel<CPL, SA_SUBST_SIMPLE, true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((fill_wavefront_kernel<CPL, SA_SUBST_SIMPLE, false>), grid, block, 0, stream, p);
-  } else if (p.K <= SA_LDS_TABLE_MAX_K) {
-    const size_t lds = (size_t)p.K * p.K * sizeof(int32_t);
-    if (general) hipLaunchKernelGGL((fill_wavefront_kernel<CPL, SA_SUBST_LDS, true>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((fill_wavefront_kernel<CPL, SA_SUBST_LDS, false>), grid, block, lds, stream, p);
-  } else {
-    hipLaunchKernelGGL((fill_wavefront_kernel<CPL, SA_SUBST_GLOBAL, true>), grid, block, 0, stream, p);
-  }
+  launch_by_scoring(p.K, wf_general, [&](auto subst, auto general, uint32_t table_ints) {
+    hipLaunchKernelGGL((fill_wavefront_kernel<CPL, subst(), general()>), grid, block, table_ints * sizeof(int32_t), stream, p);
+  });
   return hipGetLastError();
 }
 

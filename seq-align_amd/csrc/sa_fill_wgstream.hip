@@ -355,28 +355,16 @@ static hipError_t launch_wg(const SaFillParams &p, uint32_t max_len_a, hipStream
   const uint32_t R = NW > 4 ? (256 + (max_len_a + 1) + 255) / 256 * 256
                             : (256 + (max_len_a + 1) + span + 255) / 256 * 256;
   const dim3 grid(p.n_pairs), block(kWave * NW);
-  size_t lds = ((size_t)3 * R + 2 * NW * 2) * sizeof(int32_t);
-  const bool general = needs_general(p);
+  const size_t rings = ((size_t)3 * R + 2 * NW * 2) * sizeof(int32_t);
   // best-cell reporting: SW only, rows / columns that fit the packed tie-break (21 / 11+ bits)
   const bool best = p.best_score && p.best_index && (p.flags & SA_F_IS_SW);
   const bool cand = p.cand_count && p.cand_box && p.cand_rows && p.cand_rows_off && p.cand_min && (p.flags & SA_F_IS_SW);
-#define SA_WG_LAUNCH(SUBST_, GEN_, LDS_)                                                                              \
-  do {                                                                                                                \
-    if (cand) hipLaunchKernelGGL((fill_wgstream_kernel<CPL, SUBST_, NW, GEN_, 2>), grid, block, LDS_, stream, p, R);    \
-    else if (best) hipLaunchKernelGGL((fill_wgstream_kernel<CPL, SUBST_, NW, GEN_, 1>), grid, block, LDS_, stream, p, R); \
-    else hipLaunchKernelGGL((fill_wgstream_kernel<CPL, SUBST_, NW, GEN_, 0>), grid, block, LDS_, stream, p, R);         \
-  } while (0)
-  if (p.K <= 1) {
-    if (general) SA_WG_LAUNCH(SA_SUBST_SIMPLE, true, lds);
-    else SA_WG_LAUNCH(SA_SUBST_SIMPLE, false, lds);
-  } else if (p.K <= SA_LDS_TABLE_MAX_K) {
-    lds += (size_t)p.K * p.K * sizeof(int32_t);
-    if (general) SA_WG_LAUNCH(SA_SUBST_LDS, true, lds);
-    else SA_WG_LAUNCH(SA_SUBST_LDS, false, lds);
-  } else {
-    SA_WG_LAUNCH(SA_SUBST_GLOBAL, true, lds);
-  }
-#undef SA_WG_LAUNCH
+  launch_by_scoring(p, [&](auto subst, auto general, uint32_t table_ints) {
+    const size_t lds = rings + table_ints * sizeof(int32_t);
+    if (cand) hipLaunchKernelGGL((fill_wgstream_kernel<CPL, subst(), NW, general(), 2>), grid, block, lds, stream, p, R);
+    else if (best) hipLaunchKernelGGL((fill_wgstream_kernel<CPL, subst(), NW, general(), 1>), grid, block, lds, stream, p, R);
+    else hipLaunchKernelGGL((fill_wgstream_kernel<CPL, subst(), NW, general(), 0>), grid, block, lds, stream, p, R);
+  });
   return hipGetLastError();
 }
 }  // namespace sa

@@ -383,6 +383,9 @@ struct SaScoreParams {
   uint32_t *strip_best;         /* [4 * progress words] SW: the best cell of strips 0 .. s (score, column, row)        */
   uint32_t strips_per_pair;
 };
+/* One buffer holds `words` progress words, the ticket counter behind them and then, 16-byte aligned, strip_best. */
+static inline uint64_t sa_strip_best_word(uint64_t words) { return (words + 1 + 3) & ~(uint64_t)3; }
+static inline uint64_t sa_strip_progress_bytes(uint64_t words) { return 4 * sa_strip_best_word(words) + 16 * words; }
 uint32_t sa_score_strips_per_pair(uint32_t max_len_a);
 /* every pair of the launch has len_a <= SA_SCORE_ROW_MAX; max_len_a picks the columns per lane */
 hipError_t sa_launch_score_rows(const SaScoreParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream);

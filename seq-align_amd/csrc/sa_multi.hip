@@ -180,8 +180,7 @@ extern "C" int seqalign_sw_batch_cigar_multi(seqalign_ctx_t *const *ctxs, int n_
 // score only: the same contiguous ranges; every range writes its own slice of the per-pair outputs
 extern "C" int seqalign_nw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
                                              const scoring_t *scoring, int32_t *out_score) {
-  if (bad_ctx_list(ctxs, n_ctx) || !batch || !scoring || !out_score) return SEQALIGN_E_ARG;
-  if (batch->n_pairs && (!batch->arena || !batch->off_a || !batch->off_b || !batch->len_a || !batch->len_b)) return SEQALIGN_E_ARG;
+  if (bad_ctx_list(ctxs, n_ctx) || !batch_readable(batch) || !scoring || !out_score) return SEQALIGN_E_ARG;
   return for_each_shard(shard_edges(batch, n_ctx), [&](int g, uint64_t first, uint64_t count) {
     const seqalign_batch_t s = sub_batch(batch, first, count);
     return seqalign_nw_score_batch(ctxs[g], &s, scoring, out_score + first);
@@ -191,8 +190,7 @@ extern "C" int seqalign_nw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_
 extern "C" int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
                                              const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a,
                                              uint32_t *out_end_b) {
-  if (bad_ctx_list(ctxs, n_ctx) || !batch || !scoring || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
-  if (batch->n_pairs && (!batch->arena || !batch->off_a || !batch->off_b || !batch->len_a || !batch->len_b)) return SEQALIGN_E_ARG;
+  if (bad_ctx_list(ctxs, n_ctx) || !batch_readable(batch) || !scoring || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
   return for_each_shard(shard_edges(batch, n_ctx), [&](int g, uint64_t first, uint64_t count) {
     const seqalign_batch_t s = sub_batch(batch, first, count);
     return seqalign_sw_score_batch(ctxs[g], &s, scoring, out_score + first, out_end_a + first, out_end_b + first);
@@ -202,18 +200,27 @@ extern "C" int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_
 // score matrices: contiguous query ranges of nearly equal cells -- a query's cells are (len + 1) x the targets' sum of
 // (len + 1), a factor common to all, so the ranges are cut by len + 1 -- each context writes its own rows
 namespace {
+// fn(g, the range's queries as a set of their own, first) for the n_ctx query ranges
+template <class F>
+int for_each_query_shard(const seqalign_seqset_t *queries, int n_ctx, F fn) {
+  const uint64_t nq = queries->n_seqs;
+  std::vector<uint64_t> cum(nq + 1, 0);
+  for (uint64_t q = 0; q < nq; ++q) cum[q + 1] = cum[q] + queries->len[q] + 1ull;
+  return for_each_shard(shard_edges_cum(cum, n_ctx), [&](int g, uint64_t first, uint64_t count) {
+    seqalign_seqset_t s = *queries;
+    s.n_seqs = count; s.off = queries->off + first; s.len = queries->len + first;
+    return fn(g, &s, first);
+  });
+}
+
 int score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                       const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
   int rc = score_cross_check(queries, targets);
   if (rc) return rc;
   const uint64_t nq = queries->n_seqs, nt = targets->n_seqs;
   if (!nq || !nt) return SEQALIGN_OK;
-  std::vector<uint64_t> cum(nq + 1, 0);
-  for (uint64_t q = 0; q < nq; ++q) cum[q + 1] = cum[q] + queries->len[q] + 1ull;
-  return for_each_shard(shard_edges_cum(cum, n_ctx), [&](int g, uint64_t first, uint64_t count) {
-    seqalign_seqset_t s = *queries;
-    s.n_seqs = count; s.off = queries->off + first; s.len = queries->len + first;
-    return score_cross_call(ctxs[g], &s, targets, scoring, is_sw, out_score + first * nt,
+  return for_each_query_shard(queries, n_ctx, [&](int g, const seqalign_seqset_t *s, uint64_t first) {
+    return score_cross_call(ctxs[g], s, targets, scoring, is_sw, out_score + first * nt,
                             is_sw ? out_end_a + first * nt : nullptr, is_sw ? out_end_b + first * nt : nullptr, first);
   });
 }
@@ -239,14 +246,9 @@ int score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_se
                        uint32_t *n_hits) {
   int rc = score_search_check(queries, targets, k);
   if (rc) return rc;
-  const uint64_t nq = queries->n_seqs;
-  if (!nq) return SEQALIGN_OK;
-  std::vector<uint64_t> cum(nq + 1, 0);
-  for (uint64_t q = 0; q < nq; ++q) cum[q + 1] = cum[q] + queries->len[q] + 1ull;
-  return for_each_shard(shard_edges_cum(cum, n_ctx), [&](int g, uint64_t first, uint64_t count) {
-    seqalign_seqset_t s = *queries;
-    s.n_seqs = count; s.off = queries->off + first; s.len = queries->len + first;
-    return score_search_call(ctxs[g], &s, targets, scoring, is_sw, k, min_score, hits + first * k, n_hits + first, first);
+  if (!queries->n_seqs) return SEQALIGN_OK;
+  return for_each_query_shard(queries, n_ctx, [&](int g, const seqalign_seqset_t *s, uint64_t first) {
+    return score_search_call(ctxs[g], s, targets, scoring, is_sw, k, min_score, hits + first * k, n_hits + first, first);
   });
 }
 }  // namespace

@@ -33,6 +33,8 @@
 // differs; the row loop is unchanged.
 #pragma once
 
+#include <type_traits>
+
 #include "sa_fill_common.hpp"
 
 namespace sa {
@@ -55,6 +57,18 @@ __device__ __forceinline__ int wave_scan_max(int u) {
   u = max(u, dpp_mov<0x142, 0xa>(NEG, u));   // row_bcast:15 -> rows 1,3
   u = max(u, dpp_mov<0x143, 0xc>(NEG, u));   // row_bcast:31 -> rows 2,3
   return u;
+}
+
+// the substitution table where a kernel reads it: copied to LDS by the whole workgroup (SA_SUBST_LDS; a barrier, so before
+// any wave leaves), or where it is
+template <int SUBST>
+__device__ __forceinline__ const int32_t *stage_table(const SaFillParams &p, int32_t *lds_table) {
+  if constexpr (SUBST == SA_SUBST_LDS) {
+    for (uint32_t k = threadIdx.x; k < p.K * p.K; k += blockDim.x) lds_table[k] = p.table[k];
+    __syncthreads();
+    return lds_table;
+  }
+  return p.table;
 }
 
 // wave-uniform scoring constants
@@ -218,6 +232,28 @@ struct RowSweep {
 inline bool needs_general(const SaFillParams &p) {
   return (p.flags & (SA_F_NO_END_GAP | SA_F_NO_GAPS_A | SA_F_NO_GAPS_B | SA_F_HAS_SENTINEL)) ||
          p.open1 > p.ext;
+}
+
+// The kernel form a scoring needs: launch(std::integral_constant<int, SUBST>{}, std::bool_constant<GENERAL>{}, table_ints),
+// table_ints = the K * K ints an SA_SUBST_LDS kernel stages in LDS (0 otherwise).  Five forms: a table too large for LDS
+// runs the GENERAL kernel whatever the scoring.
+template <class F>
+void launch_by_scoring(uint32_t K, bool general, F &&launch) {
+  using std::bool_constant;
+  using std::integral_constant;
+  if (K <= 1) {
+    if (general) launch(integral_constant<int, SA_SUBST_SIMPLE>{}, bool_constant<true>{}, 0u);
+    else launch(integral_constant<int, SA_SUBST_SIMPLE>{}, bool_constant<false>{}, 0u);
+  } else if (K <= SA_LDS_TABLE_MAX_K) {
+    if (general) launch(integral_constant<int, SA_SUBST_LDS>{}, bool_constant<true>{}, K * K);
+    else launch(integral_constant<int, SA_SUBST_LDS>{}, bool_constant<false>{}, K * K);
+  } else {
+    launch(integral_constant<int, SA_SUBST_GLOBAL>{}, bool_constant<true>{}, 0u);
+  }
+}
+template <class F>
+void launch_by_scoring(const SaFillParams &p, F &&launch) {
+  launch_by_scoring(p.K, needs_general(p), launch);
 }
 
 // Every 64 rows lane q fetches what row j0+q needs: seq_b's code and, for strips

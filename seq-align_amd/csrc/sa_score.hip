@@ -13,65 +13,16 @@
 // Its CROSS form (seqalign_*_score_cross, kind "score_cross") takes a query and a target of two sets instead of a pair of
 // a list: same sweep, same end picks, only which sequences a wave reads and where its result goes differ.
 //
-// score_strips_kernel: wider rows, the pipeline of sa_fill_strips.hip (tickets drawn when a workgroup starts, waits only
-// on lower tickets, agent-scope release / acquire of a rows-done word per strip) -- but what strip s hands strip s + 1 is
-// not the matrices: per row, max(M, A) and B of its last column (RowSweep::row's feedZ / feedB; the up-left boundX
-// follows from them), 8 bytes into a scratch column of len_b + 1 rows.  O(strips x len_b) bytes per pair.  Published 64
-// rows at a time: lane q keeps row j0 + q's pair of values, the 64 rows leave as one coalesced 512-byte store.  SW: each
-// strip merges its best cell into the best of the strips to its left (visible: it waited for their last rows) and hands
-// that on; the last strip writes the pair's result.  Cell indices and the error key are 64-bit (len_a x len_b may pass 2^32).
-#include <type_traits>
-
-#include "sa_rowsweep.hpp"
+// score_strips_kernel: wider rows, the strips pipeline (sa_strips.hpp) -- but what strip s hands strip s + 1 is not the
+// matrices: the hand-off column (StripHandoff), O(strips x len_b) bytes per pair.  SW: each strip merges its best cell into
+// the best of the strips to its left and hands that on; the last strip writes the pair's result.  Cell indices and the
+// error key are 64-bit (len_a x len_b may pass 2^32).
+#include "sa_strips.hpp"
 
 namespace sa {
 
 constexpr int kScoreStripCPL = 8;                            // 512 columns per strip, as sa_fill_strips.hip
 constexpr uint32_t kScoreStripCols = kWave * kScoreStripCPL;
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
-// per-column running best of match_scores (SW)
-template <int CPL>
-struct BestCells {
-  int s[CPL];
-  uint32_t r[CPL];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) { s[c] = 0; r[c] = 0; }
-  }
-  __device__ __forceinline__ void row(const int (&mv)[CPL], uint32_t j) {
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-      const bool up = mv[c] > s[c];   // strict: the first (lowest) row keeps a tie
-      s[c] = up ? mv[c] : s[c];
-      r[c] = up ? j : r[c];
-    }
-  }
-  // the wave's best in hit order over my columns col0 + 1 .. (matrix column = col0 + c + 1): {score, (column << 32) | row};
-  // score 0 -> key ~0
-  __device__ __forceinline__ void reduce(uint32_t col0, int ncol, int &score, unsigned long long &key) const {
-    int b = 0;
-    unsigned long long kb = ~0ull;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c)   // c ascending, strict >: the lowest column wins a tie
-      if (c < ncol && s[c] > b) { b = s[c]; kb = ((unsigned long long)(col0 + c + 1) << 32) | r[c]; }
-    score = wave_max_i32(b);
-    key = wave_min_u64(b == score && score > 0 ? kb : ~0ull);
-  }
-};
 
 // CROSS: wave w of a launch for one row class takes target t_order[w / nq] and query q_list[w % nq].  t_order runs longest
 // first; within a class a row costs the same whatever len_a is, so a wave's cost follows its target's length and the long
@@ -82,12 +33,7 @@ __global__ void __launch_bounds__(kWave *kWavesPerBlock)
 score_rows_kernel(const std::conditional_t<CROSS, SaScoreCrossParams, SaScoreParams> sp) {
   const SaFillParams &p = sp.f;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
-  const int32_t *table = p.table;
-  if constexpr (SUBST == SA_SUBST_LDS) {
-    for (uint32_t k = threadIdx.x; k < p.K * p.K; k += blockDim.x) lds_table[k] = p.table[k];
-    __syncthreads();
-    table = lds_table;
-  }
+  const int32_t *table = stage_table<SUBST>(p, lds_table);
 
   const int lane = threadIdx.x & (kWave - 1);
   const uint32_t pair = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
@@ -172,23 +118,12 @@ score_strips_kernel(const SaScoreParams sp) {
   constexpr int CPL = kScoreStripCPL;
   const SaFillParams &p = sp.f;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
-  const int32_t *table = p.table;
-  if constexpr (SUBST == SA_SUBST_LDS) {
-    for (uint32_t k = threadIdx.x; k < p.K * p.K; k += blockDim.x) lds_table[k] = p.table[k];
-    __syncthreads();
-    table = lds_table;
-  }
+  const int32_t *table = stage_table<SUBST>(p, lds_table);
 
   const int lane = threadIdx.x;
   const uint32_t spp = sp.strips_per_pair;
-  // ticket = (group * strips_per_pair + strip) * 8 + pair_in_group; the counter sits behind the progress words
-  // (sa_fill_strips.hip: a strip's ticket is higher than that of the strip it waits for, and a ticket only exists once its
-  // workgroup is resident -- so a waiting wave waits only for waves that are running or done, whatever the dispatch order)
-  uint32_t ticket = 0;
-  if (lane == 0) ticket = atomicAdd(sp.progress + (uint64_t)gridDim.x, 1u);
-  ticket = __builtin_amdgcn_readfirstlane(ticket);
-  const uint32_t in_group = ticket & 7u, gs = ticket >> 3;
-  const uint32_t strip = gs % spp, pair = (gs / spp) * 8 + in_group;
+  uint32_t strip, pair;
+  strip_of_ticket(strip_ticket(sp.progress + (uint64_t)gridDim.x), spp, strip, pair);
   if (pair >= p.n_pairs) return;
 
   const uint32_t la = p.len_a[pair], lb = p.len_b[pair];
@@ -216,43 +151,24 @@ score_strips_kernel(const SaScoreParams sp) {
   BestCells<SW ? CPL : 1> best;
   if constexpr (SW) best.init();
 
-  int code = 0, fz = 0, fb = 0;   // lane q: row j0 + q's code and, from the strip to my left, max(M, A) and B
-  int oz = 0, ob = 0;             // lane q: row j0 + q's values of my last column, for the strip to my right
+  StripHandoff h;
   for (uint32_t j = 1; j <= lb; ++j) {
     const int q = (j - 1) & (kWave - 1);
     if (q == 0) {
-      const uint32_t r = j + lane;
-      if (strip > 0) {   // rows j .. j + 63 of the strip to my left must have been handed over
-        const uint32_t need = min(j + kWave - 1, lb);
-        while (__hip_atomic_load(done + strip - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need)
-          __builtin_amdgcn_s_sleep(8);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-      if (r <= lb) {
-        code = p.code[sb_[r - 1]];
-        if (strip == 0) {   // border column (reference alignment.c:72-80)
-          fz = max(k.floor_, bd.edge_gap(r));
-          fb = k.floor_;
-        } else {
-          const int2 h = *reinterpret_cast<const int2 *>(hand_in + 2ull * r);
-          fz = h.x; fb = h.y;
-        }
-      }
-      __builtin_amdgcn_s_waitcnt(kWaitVm0);   // once per 64 rows (see RowFeed::load)
+      // rows j .. j + 63 of the strip to my left must have been handed over
+      if (strip > 0) strip_wait(done + strip - 1, min(j + kWave - 1, lb));
+      h.load(p, k, bd, sb_, lb, strip, hand_in, j + lane);
     }
     int mv[CPL], av[CPL], bv[CPL];
-    sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(code, q), read_lane(fz, q), read_lane(fb, q), mv, av, bv);
+    sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(h.code, q), read_lane(h.fz, q), read_lane(h.fb, q), mv, av, bv);
     if constexpr (SW) best.row(mv, j);
-    if (!last_strip) {   // a strip that is not the last is full: lane 63's last column is the strip's
+    if (!last_strip) {   // StripHandoff::keep, open-coded: through the helper this kernel's SGPR counts and spills move
       const int z = read_lane(max(mv[CPL - 1], av[CPL - 1]), kWave - 1), b = read_lane(bv[CPL - 1], kWave - 1);
-      oz = (lane == q) ? z : oz;
-      ob = (lane == q) ? b : ob;
+      h.oz = (lane == q) ? z : h.oz;
+      h.ob = (lane == q) ? b : h.ob;
       if (q == kWave - 1 || j == lb) {
-        if (lane <= q) *reinterpret_cast<int2 *>(hand_out + 2ull * (j - q + lane)) = make_int2(oz, ob);
-        if (j != lb) {   // (the last rows are published below, after the best cell)
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-          if (lane == 0) __hip_atomic_store(done + strip, j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        if (lane <= q) *reinterpret_cast<int2 *>(hand_out + 2ull * (j - q + lane)) = make_int2(h.oz, h.ob);
+        if (j != lb) strip_publish(done + strip, j);   // (the last rows are published below, after the best cell)
       }
     }
   }
@@ -266,13 +182,7 @@ score_strips_kernel(const SaScoreParams sp) {
     int score;
     unsigned long long key;
     best.reduce(col0, ncol, score, key);
-    if (strip > 0 && lb > 0) {   // the strips to my left: their last rows were acquired above, their best with them
-      const uint4 left = *reinterpret_cast<const uint4 *>(sp.strip_best + 4 * (slot - 1));
-      if ((int)left.x >= score && (int)left.x > 0) {   // a tie goes to the lower column: theirs
-        score = (int)left.x;
-        key = ((unsigned long long)left.y << 32) | left.z;
-      }
-    }
+    if (strip > 0 && lb > 0) merge_left_best(sp.strip_best + 4 * (slot - 1), score, key);
     const uint32_t ea = score > 0 ? (uint32_t)(key >> 32) : 0u, eb = score > 0 ? (uint32_t)key : 0u;
     if (lane == 0) {
       if (last_strip) {
@@ -286,10 +196,7 @@ score_strips_kernel(const SaScoreParams sp) {
     for (int c = 0; c < CPL; ++c)
       if (col0 + c + 1 == la) sp.score[pair] = sw.X[c];   // max(M, A, B) of (len_a, len_b)
   }
-  if (!last_strip && lb > 0) {   // the last rows (and the best cell so far)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    if (lane == 0) __hip_atomic_store(done + strip, lb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (!last_strip && lb > 0) strip_publish(done + strip, lb);   // the last rows (and the best cell so far)
 }
 
 inline uint32_t one_wave_waves(const SaScoreParams &p) { return p.f.n_pairs; }
@@ -297,19 +204,10 @@ inline uint32_t one_wave_waves(const SaScoreCrossParams &p) { return p.n_waves; 
 
 template <int CPL, bool SW, bool CROSS, class P>
 static hipError_t launch_rows_cpl(const P &p, hipStream_t stream) {
-  const bool general = needs_general(p.f);
   const dim3 grid((one_wave_waves(p) + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
-  const uint32_t K = p.f.K;
-  if (K <= 1) {
-    if (general) hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_SIMPLE, true, SW, CROSS>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_SIMPLE, false, SW, CROSS>), grid, block, 0, stream, p);
-  } else if (K <= SA_LDS_TABLE_MAX_K) {
-    const size_t lds = (size_t)K * K * sizeof(int32_t);
-    if (general) hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_LDS, true, SW, CROSS>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_LDS, false, SW, CROSS>), grid, block, lds, stream, p);
-  } else {
-    hipLaunchKernelGGL((score_rows_kernel<CPL, SA_SUBST_GLOBAL, true, SW, CROSS>), grid, block, 0, stream, p);
-  }
+  launch_by_scoring(p.f, [&](auto subst, auto general, uint32_t table_ints) {
+    hipLaunchKernelGGL((score_rows_kernel<CPL, subst(), general(), SW, CROSS>), grid, block, table_ints * sizeof(int32_t), stream, p);
+  });
   return hipGetLastError();
 }
 
@@ -330,19 +228,9 @@ static hipError_t launch_rows(const P &p, uint32_t max_len_a, hipStream_t stream
 
 template <bool SW>
 static hipError_t launch_strips(const SaScoreParams &p, const dim3 grid, hipStream_t stream) {
-  const bool general = needs_general(p.f);
-  const dim3 block(kWave);
-  const uint32_t K = p.f.K;
-  if (K <= 1) {
-    if (general) hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_SIMPLE, true, SW>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_SIMPLE, false, SW>), grid, block, 0, stream, p);
-  } else if (K <= SA_LDS_TABLE_MAX_K) {
-    const size_t lds = (size_t)K * K * sizeof(int32_t);
-    if (general) hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_LDS, true, SW>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_LDS, false, SW>), grid, block, lds, stream, p);
-  } else {
-    hipLaunchKernelGGL((score_strips_kernel<SA_SUBST_GLOBAL, true, SW>), grid, block, 0, stream, p);
-  }
+  launch_by_scoring(p.f, [&](auto subst, auto general, uint32_t table_ints) {
+    hipLaunchKernelGGL((score_strips_kernel<subst(), general(), SW>), grid, dim3(kWave), table_ints * sizeof(int32_t), stream, p);
+  });
   return hipGetLastError();
 }
 
