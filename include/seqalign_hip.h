@@ -490,6 +490,23 @@ typedef struct {
 int seqalign_ctx_last_call_info(const seqalign_ctx_t *ctx, seqalign_call_info_t *out);
 /* "fill_stream", "fill_nw_dirs_x2", ... ; NULL for a kind that does not exist */
 const char *seqalign_kernel_kind_name(int kind);
+/* The table above is full (SEQALIGN_K_COUNT == SEQALIGN_K_MAX) and seqalign_call_info_t is ABI, so kernels added since
+ * are counted in a second record of the same shape, indexed by SEQALIGN_KX_*.  The outermost entry point of a call clears
+ * both records; a call that launches none of the kernels below leaves this one all zero. */
+enum {
+  SEQALIGN_KX_BAND_SCORE = 0,      /* banded NW, score only (seqalign_nw_score_banded), one pair per wave (items: pairs) */
+  SEQALIGN_KX_BAND_FILL,           /* banded NW, M / A / B of every band cell (seqalign_nw_align_banded)                  */
+  SEQALIGN_KX_BAND_WALK,           /* ... the traceback over a chunk's bands, one lane per pair                           */
+  SEQALIGN_KX_COUNT
+};
+#define SEQALIGN_KX_MAX 32
+typedef struct {
+  uint32_t launches[SEQALIGN_KX_MAX];
+  uint64_t items[SEQALIGN_KX_MAX];
+} seqalign_call_info_ext_t;
+int seqalign_ctx_last_call_info_ext(const seqalign_ctx_t *ctx, seqalign_call_info_ext_t *out);
+/* "band_score", "band_fill", "band_walk"; NULL for a kind that does not exist */
+const char *seqalign_kernel_kind_ext_name(int kind);
 
 /* ---- CIGAR -------------------------------------------------------------------- */
 /* The reference has no CIGAR output (its result is the pair of gapped strings, src/alignment.h:33-40); this
@@ -569,6 +586,41 @@ int seqalign_nw_align_long(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, c
 int seqalign_sw_align_long(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                            const int32_t *min_score, seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits,
                            char *out_a, char *out_b, uint64_t str_cap);
+/* ---- banded NW: score and alignment inside a diagonal band ------------------------- */
+/* Global alignment restricted to a band of diagonals, for long similar sequences.  band[p] = w (any w >= 0) gives pair p,
+ * with la = len_a, lb = len_b, the band
+ *     d_lo = max(-lb, min(0, la - lb) - w)      d_hi = min(la, max(0, la - lb) + w)
+ *     cell (i, j) (column i of seq_a, row j of seq_b) is in the band  iff  d_lo <= i - j <= d_hi;  width = d_hi - d_lo + 1
+ * so (0, 0) and (la, lb) are in every band and a band that covers the whole matrix has width la + lb + 1.  The banded
+ * matrices are the reference's recurrence (src/alignment.c:28-168, borders included) in which every cell outside the band
+ * holds the NW floor in all three matrices; the banded alignment is needleman_wunsch.c's end pick and
+ * alignment_reverse_move over those matrices.  Nothing is rounded to a kernel's frame, nothing is adaptive.  When the
+ * unbanded alignment of a pair stays inside its band, score and strings are seqalign_nw_batch's byte for byte; otherwise
+ * the score is <= the unbanded one.  A scoring that forbids moves (no_mismatches, no_gaps_in_*) may leave NO alignment
+ * inside a band: seqalign_nw_align_banded then returns SEQALIGN_E_TRACEBACK (lowest failing pair named in
+ * seqalign_last_error); seqalign_nw_score_banded returns the end cell's value as it is, below INT32_MIN / 2 then.
+ * Results, capacities and str_off exactly as seqalign_nw_score_batch / seqalign_nw_batch.  No 2^31-cell cap.
+ *   SEQALIGN_E_ARG          NULL arguments, unreadable batch
+ *   SEQALIGN_E_TOO_LARGE    a pair whose width exceeds SEQALIGN_BAND_MAX_WIDTH (found from lengths and bands alone, before
+ *                           any device work; pair named), or len_a + len_b >= 2^31
+ *   SEQALIGN_E_DOMAIN, SEQALIGN_E_NO_DEVICE   as the long calls
+ *   SEQALIGN_E_UNKNOWN_PAIR a character pair without a score INSIDE the band (lowest failing pair named); the same
+ *                           characters outside the band raise nothing
+ *   SEQALIGN_E_NOMEM        a pair that does not fit the chunk budget alone; seqalign_last_error gives the bytes needed
+ * Chunks are cut by device bytes within the option chunk_bytes.  Per pair: the score call len_a + len_b + 64; the align
+ * call 12 (len_b + 1) width (M, A, B of the band's cells: row j holds diagonals d_lo .. d_hi, cell (i, j) at
+ * j (width - 1) + i - d_lo) + 3 (len_a + len_b) + 96.
+ * seqalign_ctx_last_call_info_ext: band_score / band_fill + band_walk. */
+#define SEQALIGN_BAND_MAX_WIDTH 1024
+int seqalign_nw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                             const uint32_t *band, int32_t *out_score);
+int seqalign_nw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                             const uint32_t *band, const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len,
+                             int32_t *out_score);
+/* Timing hook (tools/align_banded_bench.py), the banded sibling of seqalign_score_time_ms: the batch (one chunk) is uploaded
+ * once, then the score call's launches run `repeats` times between HIP events; ms_each[r] = kernel time of repeat r. */
+int seqalign_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                const uint32_t *band, int repeats, float *ms_each);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

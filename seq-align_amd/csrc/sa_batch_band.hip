@@ -1,0 +1,322 @@
+// sa_batch_band.hip -- banded NW over HOST batches: seqalign_nw_score_banded, seqalign_nw_align_banded and the timing hook
+// seqalign_band_score_time_ms (the kernels: sa_band.hip; the contract: include/seqalign_hip.h).
+//
+// Everything that can be refused from lengths and bands alone is refused before any device work: the band of every pair is
+// clamped to its matrix and a width over SEQALIGN_BAND_MAX_WIDTH is SEQALIGN_E_TOO_LARGE.  Then, per chunk: the pairs are put
+// in classes by band WIDTH -- the columns per lane of the one-wave kernels, sa_score_row_class's ladder -- and the
+// descriptors laid out class by class, one launch per class; the sequences stay in pair order.  The align call fills M, A, B
+// of the band's cells (12 bytes per band cell, (len_b + 1) x width cells per pair), walks all pairs of the chunk in one
+// launch and brings home 16 bytes per pair and the strings.
+//
+// Chunks are cut by device BYTES (header: the bytes per pair); a pair that does not fit the budget alone is
+// SEQALIGN_E_NOMEM with the bytes named.
+#include "sa_ctx.hpp"
+
+using namespace sa_host;
+
+namespace {
+
+constexpr uint64_t kScorePairBytes = 64;   // descriptors (48: the align call's record, mat_off and str_off unused), status (8), score (4), slack
+constexpr uint64_t kAlignPairBytes = 96;   // descriptors (48), status (8), the walk's four words (16), slack
+constexpr uint64_t kChunkMaxPairs = (uint64_t)1 << 24;
+
+struct Band {
+  int32_t d_lo;
+  uint32_t width;
+};
+
+Band band_of(uint32_t la, uint32_t lb, uint32_t w, uint64_t *width64) {
+  const int64_t d = (int64_t)la - (int64_t)lb;
+  const int64_t d_lo = std::max<int64_t>(-(int64_t)lb, std::min<int64_t>(0, d) - (int64_t)w);
+  const int64_t d_hi = std::min<int64_t>((int64_t)la, std::max<int64_t>(0, d) + (int64_t)w);
+  *width64 = (uint64_t)(d_hi - d_lo + 1);
+  return Band{(int32_t)std::max<int64_t>(d_lo, INT32_MIN), (uint32_t)std::min<uint64_t>(*width64, 0xFFFFFFFFu)};
+}
+
+uint64_t pair_bytes(uint32_t la, uint32_t lb, uint32_t width, bool align) {
+  const uint64_t seq = (uint64_t)la + lb;
+  return align ? 12 * ((uint64_t)lb + 1) * width + 3 * seq + kAlignPairBytes : seq + kScorePairBytes;
+}
+
+// argument checks and band geometry, before any device work
+int check_band_batch(const seqalign_batch_t *b, const uint32_t *band, std::vector<Band> &geom) {
+  if (!batch_readable(b)) return SEQALIGN_E_ARG;
+  geom.resize(b->n_pairs);
+  for (uint64_t p = 0; p < b->n_pairs; ++p) {
+    const uint32_t la = b->len_a[p], lb = b->len_b[p];
+    if ((uint64_t)la + lb >= ((uint64_t)1 << 31)) {
+      set_last_error("pair " + std::to_string(p) + ": len_a + len_b is 2^31 or more");
+      return SEQALIGN_E_TOO_LARGE;
+    }
+    uint64_t width = 0;
+    geom[p] = band_of(la, lb, band[p], &width);
+    if (width > SEQALIGN_BAND_MAX_WIDTH) {
+      set_last_error("pair " + std::to_string(p) + ": a band of " + std::to_string(width) + " diagonals, at most " +
+                     std::to_string(SEQALIGN_BAND_MAX_WIDTH) + " are supported");
+      return SEQALIGN_E_TOO_LARGE;
+    }
+  }
+  return SEQALIGN_OK;
+}
+
+struct BandChunk {
+  uint64_t first = 0, count = 0, seq_bytes = 0, cells = 0;
+};
+
+int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, bool align, size_t budget, std::vector<BandChunk> &out) {
+  BandChunk c;
+  uint64_t used = 0;
+  for (uint64_t p = 0; p < b->n_pairs; ++p) {
+    const uint32_t la = b->len_a[p], lb = b->len_b[p];
+    const uint64_t need = pair_bytes(la, lb, geom[p].width, align);
+    if (need > budget) {
+      set_last_error("pair " + std::to_string(p) + ": " + std::to_string(need) + " bytes of device memory needed, the chunk budget is " +
+                     std::to_string(budget));
+      return SEQALIGN_E_NOMEM;
+    }
+    if (c.count && (used + need > budget || c.count == kChunkMaxPairs)) { out.push_back(c); c = BandChunk(); c.first = p; used = 0; }
+    used += need;
+    c.count++; c.seq_bytes += (uint64_t)la + lb;
+    c.cells += ((uint64_t)lb + 1) * geom[p].width;
+  }
+  if (c.count) out.push_back(c);
+  return SEQALIGN_OK;
+}
+
+// One chunk laid out and uploaded; launch() enqueues its kernels on ctx->stream
+struct BandChunkRun {
+  seqalign_ctx *ctx = nullptr;
+  const seqalign_dev_scoring *sc = nullptr;
+  bool align = false;
+  uint64_t n = 0, seq_bytes = 0;
+  std::vector<uint32_t> order;                          // descriptor slot -> pair of the chunk
+  std::vector<uint64_t> str_at;                         // slot -> where its strings start in the chunk's string buffers
+  uint64_t cls_first[SA_SCORE_ROW_CLASSES + 2] = {};    // class c: slots [cls_first[c], cls_first[c + 1])
+  uint32_t cls_max_w[SA_SCORE_ROW_CLASSES + 1] = {};
+  uint64_t *d_off_a = nullptr, *d_off_b = nullptr, *d_mat_off = nullptr, *d_str_off = nullptr;
+  uint32_t *d_len_a = nullptr, *d_len_b = nullptr, *d_width = nullptr;
+  int32_t *d_dlo = nullptr;
+  uint32_t *d_res = nullptr;                            // [4] header (err_flag), then score[n]
+  uint64_t cells = 0;
+
+  int prepare(const seqalign_batch_t *b, const std::vector<Band> &geom, const BandChunk &c) {
+    int rc;
+    n = c.count; seq_bytes = c.seq_bytes; cells = c.cells;
+    order.resize(n);
+    sort_by_row_class(n, [&](uint64_t k) { return geom[c.first + k].width; }, order.data(), cls_first, cls_max_w);
+
+    // pinned descriptors, slot order: off_a, off_b, mat_off, str_off (u64), len_a, len_b, width (u32), d_lo (i32)
+    const size_t desc_bytes = n * (4 * sizeof(uint64_t) + 4 * sizeof(uint32_t));
+    if ((rc = ctx->h_desc.reserve(desc_bytes)) || (rc = ctx->h_arena.reserve(seq_bytes + 16))) return rc;
+    uint64_t *h_off_a = ctx->h_desc.as<uint64_t>(), *h_off_b = h_off_a + n, *h_mat = h_off_b + n, *h_str = h_mat + n;
+    uint32_t *h_len_a = reinterpret_cast<uint32_t *>(h_str + n), *h_len_b = h_len_a + n, *h_width = h_len_b + n;
+    int32_t *h_dlo = reinterpret_cast<int32_t *>(h_width + n);
+    std::vector<uint64_t> seq_at(n);
+    { uint64_t pos = 0;
+      for (uint64_t k = 0; k < n; ++k) { seq_at[k] = pos; pos += (uint64_t)b->len_a[c.first + k] + b->len_b[c.first + k]; } }
+    str_at.resize(n);
+    uint64_t mat = 0;
+    for (uint64_t s = 0; s < n; ++s) {
+      const uint64_t k = order[s], p = c.first + k;
+      const uint32_t la = b->len_a[p], lb = b->len_b[p];
+      h_off_a[s] = seq_at[k]; h_off_b[s] = seq_at[k] + la;
+      h_len_a[s] = la; h_len_b[s] = lb;
+      h_width[s] = geom[p].width; h_dlo[s] = geom[p].d_lo;
+      h_mat[s] = mat; mat += ((uint64_t)lb + 1) * geom[p].width;
+      h_str[s] = str_at[s] = seq_at[k];   // (a pair's strings are len_a + len_b bytes at most, like its sequences)
+    }
+    uint8_t *h_seq = ctx->h_arena.as<uint8_t>();
+    constexpr uint64_t kTask = 256;
+    parallel_for((n + kTask - 1) / kTask, [&](uint64_t blk) {
+      for (uint64_t k = blk * kTask, e = std::min(n, (blk + 1) * kTask); k < e; ++k) {
+        const uint64_t p = c.first + k;
+        memcpy(h_seq + seq_at[k], b->arena + b->off_a[p], b->len_a[p]);
+        memcpy(h_seq + seq_at[k] + b->len_a[p], b->arena + b->off_b[p], b->len_b[p]);
+      }
+    });
+
+    if ((rc = ctx->arena.reserve(seq_bytes + 16)) || (rc = ctx->off_a.reserve(desc_bytes)) || (rc = ctx->status.reserve(n * 8)) ||
+        (rc = ctx->best_score.reserve(16 + 4 * n)))
+      return rc;
+    if (align && ((rc = ctx->long_block.reserve(12 * cells + 64)) || (rc = ctx->t_out_a.reserve(seq_bytes + 16)) ||
+                  (rc = ctx->t_out_b.reserve(seq_bytes + 16)) || (rc = ctx->t_meta.reserve(16 * n))))
+      return rc;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(ctx->off_a.p, h_off_a, desc_bytes, hipMemcpyHostToDevice, st));
+    if (seq_bytes) HIP_TRY(hipMemcpyAsync(ctx->arena.p, h_seq, seq_bytes, hipMemcpyHostToDevice, st));
+    d_off_a = ctx->off_a.as<uint64_t>(); d_off_b = d_off_a + n; d_mat_off = d_off_b + n; d_str_off = d_mat_off + n;
+    d_len_a = reinterpret_cast<uint32_t *>(d_str_off + n); d_len_b = d_len_a + n; d_width = d_len_b + n;
+    d_dlo = reinterpret_cast<int32_t *>(d_width + n);
+    d_res = ctx->best_score.as<uint32_t>();
+    return SEQALIGN_OK;
+  }
+
+  SaBandParams params(uint64_t s0, uint64_t m) const {
+    SaBandParams p;
+    memset(&p, 0, sizeof(p));
+    p.f = score_fill_params(sc);
+    p.f.arena = ctx->arena.as<uint8_t>();
+    p.f.off_a = d_off_a + s0; p.f.off_b = d_off_b + s0; p.f.len_a = d_len_a + s0; p.f.len_b = d_len_b + s0;
+    p.f.mat_off = d_mat_off + s0;
+    p.f.status = ctx->status.as<uint64_t>() + s0;
+    p.f.n_pairs = (uint32_t)m;
+    p.d_lo = d_dlo + s0; p.width = d_width + s0;
+    p.score = reinterpret_cast<int32_t *>(d_res + 4) + s0;
+    p.err_flag = d_res;
+    if (align) {
+      p.f.M = ctx->long_block.as<int32_t>(); p.f.A = p.f.M + cells; p.f.B = p.f.A + cells;
+      p.str_off = d_str_off + s0;
+      p.out_a = ctx->t_out_a.as<char>(); p.out_b = ctx->t_out_b.as<char>();
+      p.meta4 = ctx->t_meta.as<uint32_t>() + 4 * s0;
+    }
+    return p;
+  }
+
+  int launch() {
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemsetAsync(d_res, 0, 16, st));
+    for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) {
+      const uint64_t s0 = cls_first[x], m = cls_first[x + 1] - s0;
+      if (!m) continue;
+      const SaBandParams p = params(s0, m);
+      const hipError_t e = align ? sa_launch_band_fill(p, cls_max_w[x], st) : sa_launch_band_score(p, cls_max_w[x], st);
+      if (e != hipSuccess) return fail_hip(e, "band kernel launch");
+    }
+    if (align) {
+      const hipError_t e = sa_launch_band_walk(params(0, n), st);
+      if (e != hipSuccess) return fail_hip(e, "band walk launch");
+    }
+    return SEQALIGN_OK;
+  }
+
+  // the lowest pair of the chunk whose fill met a band cell without a score
+  int fail_from_status(uint64_t first) {
+    std::vector<uint64_t> status(n);
+    HIP_TRY(hipMemcpy(status.data(), ctx->status.p, 8 * n, hipMemcpyDeviceToHost));
+    uint64_t worst = ~0ull;
+    for (uint64_t s = 0; s < n; ++s)
+      if (status[s] != ~0ull) worst = std::min<uint64_t>(worst, order[s]);
+    return fail_unknown_pair(first + worst);
+  }
+
+  int finish_score(uint64_t first, int32_t *out_score) {
+    int rc;
+    const size_t words = 4 + n;
+    if ((rc = ctx->h_misc.reserve(4 * words))) return rc;
+    uint32_t *h = ctx->h_misc.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_wait_spinning(ctx->stream));
+    if (h[0]) return fail_from_status(first);
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
+    for (uint64_t s = 0; s < n; ++s) out_score[first + order[s]] = hs[s];
+    return SEQALIGN_OK;
+  }
+
+  int finish_align(uint64_t first, const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score) {
+    int rc;
+    if ((rc = ctx->h_tmeta.reserve(16 * n)) || (rc = ctx->h_ta.reserve(seq_bytes + 16)) || (rc = ctx->h_tb.reserve(seq_bytes + 16))) return rc;
+    hipStream_t st = ctx->stream;
+    uint32_t *meta = ctx->h_tmeta.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(meta, ctx->t_meta.p, 16 * n, hipMemcpyDeviceToHost, st));
+    if (seq_bytes) {
+      HIP_TRY(hipMemcpyAsync(ctx->h_ta.p, ctx->t_out_a.p, seq_bytes, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(ctx->h_tb.p, ctx->t_out_b.p, seq_bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(stream_wait_spinning(st));
+    uint64_t worst = ~0ull;
+    uint32_t worst_code = 0;
+    for (uint64_t s = 0; s < n; ++s)
+      if (meta[4 * s + 3] && order[s] < worst) { worst = order[s]; worst_code = meta[4 * s + 3]; }
+    if (worst != ~0ull) {
+      if (worst_code == SEQALIGN_E_UNKNOWN_PAIR) return fail_unknown_pair(first + worst);
+      set_last_error("pair " + std::to_string(first + worst) + ": traceback failed (no alignment inside the band)");
+      return (int)worst_code;
+    }
+    const char *ha = ctx->h_ta.as<char>(), *hb = ctx->h_tb.as<char>();
+    constexpr uint64_t kTask = 64;
+    parallel_for((n + kTask - 1) / kTask, [&](uint64_t blk) {
+      for (uint64_t s = blk * kTask, e = std::min(n, (blk + 1) * kTask); s < e; ++s) {
+        const uint64_t p = first + order[s];
+        const uint32_t head = meta[4 * s], len = meta[4 * s + 1];
+        memcpy(out_a + str_off[p], ha + str_at[s] + head, len);
+        memcpy(out_b + str_off[p], hb + str_at[s] + head, len);
+        out_a[str_off[p] + len] = out_b[str_off[p] + len] = '\0';
+        out_len[p] = len;
+        out_score[p] = (int32_t)meta[4 * s + 2];
+      }
+    });
+    return SEQALIGN_OK;
+  }
+};
+
+int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool align,
+              const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score) {
+  int rc;
+  if (batch->n_pairs == 0) return SEQALIGN_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  seqalign_dev_scoring *sc = nullptr;
+  if ((rc = cached_scoring(ctx, scoring, 0, &sc))) return rc;
+  std::vector<BandChunk> chunks;
+  if ((rc = plan_band_chunks(batch, geom, align, ctx->chunk_budget, chunks))) return rc;
+  StreamSyncOnExit sync(ctx->stream);
+  for (const BandChunk &c : chunks) {
+    BandChunkRun run;
+    run.ctx = ctx; run.sc = sc; run.align = align;
+    if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch())) return rc;
+    if ((rc = align ? run.finish_align(c.first, str_off, out_a, out_b, out_len, out_score) : run.finish_score(c.first, out_score))) return rc;
+  }
+  return SEQALIGN_OK;
+}
+
+}  // namespace
+
+extern "C" int seqalign_nw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                        const uint32_t *band, int32_t *out_score) {
+  if (!ctx || !batch || !scoring || !band || !out_score) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return band_call(ctx, batch, scoring, geom, false, nullptr, nullptr, nullptr, nullptr, out_score);
+}
+
+extern "C" int seqalign_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                           const uint32_t *band, int repeats, float *ms_each) {
+  if (!ctx || !batch || !scoring || !band || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom);
+  if (rc) return rc;
+  if (batch->n_pairs == 0) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);
+  HIP_TRY(hipSetDevice(ctx->device));
+  seqalign_dev_scoring *sc = nullptr;
+  if ((rc = cached_scoring(ctx, scoring, 0, &sc))) return rc;
+  std::vector<BandChunk> chunks;
+  if ((rc = plan_band_chunks(batch, geom, false, ctx->chunk_budget, chunks))) return rc;
+  if (chunks.size() != 1) { set_last_error("seqalign_band_score_time_ms: the batch does not fit one chunk"); return SEQALIGN_E_ARG; }
+  StreamSyncOnExit sync(ctx->stream);
+  BandChunkRun run;
+  run.ctx = ctx; run.sc = sc; run.align = false;
+  if ((rc = run.prepare(batch, geom, chunks[0]))) return rc;
+  EventList events;
+  for (int r = 0; r < 2 * repeats; ++r) HIP_TRY(events.add());
+  for (int r = 0; r < repeats; ++r) {
+    HIP_TRY(hipEventRecord(events.ev[2 * r], ctx->stream));
+    if ((rc = run.launch())) return rc;
+    HIP_TRY(hipEventRecord(events.ev[2 * r + 1], ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (int r = 0; r < repeats; ++r) HIP_TRY(hipEventElapsedTime(&ms_each[r], events.ev[2 * r], events.ev[2 * r + 1]));
+  return SEQALIGN_OK;
+}
+
+extern "C" int seqalign_nw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                        const uint32_t *band, const uint64_t *str_off, char *out_a, char *out_b,
+                                        uint32_t *out_len, int32_t *out_score) {
+  if (!ctx || !batch || !scoring || !band || !str_off || !out_a || !out_b || !out_len || !out_score) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return band_call(ctx, batch, scoring, geom, true, str_off, out_a, out_b, out_len, out_score);
+}

@@ -9,6 +9,7 @@
 //   sa_batch_score_cross.hip seqalign_nw_score_cross / seqalign_sw_score_cross (score only, every query x every target),
 //                     and seqalign_*_score_search (the best k targets of every query; sa_score_select.hip selects)
 //   sa_batch_long.hip seqalign_nw_align_long / seqalign_sw_align_long (pairs of any size: checkpoints, blocks, walks)
+//   sa_batch_band.hip seqalign_nw_score_banded / seqalign_nw_align_banded (NW inside a diagonal band)
 //   sa_multi.hip      the same calls over several contexts (GPUs) from one process
 #pragma once
 #include <hip/hip_runtime.h>
@@ -381,6 +382,7 @@ struct seqalign_ctx {
   sa_host::HostBuf h_desc, h_arena, h_M, h_A, h_B, h_misc, h_ta, h_tb, h_tmeta;
   // the last scorings uploaded through cached_scoring (host-level entry points, legacy single-pair path): [is_sw]
   seqalign_call_info_t call_info = {};   // what the last call launched (seqalign_ctx_last_call_info)
+  seqalign_call_info_ext_t call_info_ext = {};   // ... its second record (seqalign_ctx_last_call_info_ext)
   int call_depth = 0;                    // entry points nest (seqalign_nw_batch -> seqalign_fill_batch_device): the outermost resets
   seqalign_dev_scoring *cached[2] = {nullptr, nullptr};
   uint64_t cached_fp[2] = {0, 0};
@@ -399,6 +401,7 @@ namespace sa_host {
 struct CallScope {
   seqalign_ctx *ctx;
   seqalign_call_info_t *prev;
+  seqalign_call_info_ext_t *prev_ext;
   explicit CallScope(seqalign_ctx *c);
   ~CallScope();
   CallScope(const CallScope &) = delete;

@@ -55,21 +55,45 @@ void sa_record_launch(int kind, uint64_t items) {
   tl_recorder->items[kind] += items;
 }
 
-sa_host::CallScope::CallScope(seqalign_ctx *c) : ctx(c), prev(tl_recorder) {
+static thread_local seqalign_call_info_ext_t *tl_recorder_ext = nullptr;
+
+void sa_record_launch_ext(int kind, uint64_t items) {
+  if (!tl_recorder_ext || kind < 0 || kind >= SEQALIGN_KX_COUNT) return;
+  tl_recorder_ext->launches[kind] += 1;
+  tl_recorder_ext->items[kind] += items;
+}
+
+sa_host::CallScope::CallScope(seqalign_ctx *c) : ctx(c), prev(tl_recorder), prev_ext(tl_recorder_ext) {
   if (!ctx) return;
-  if (ctx->call_depth++ == 0) memset(&ctx->call_info, 0, sizeof(ctx->call_info));
+  if (ctx->call_depth++ == 0) {
+    memset(&ctx->call_info, 0, sizeof(ctx->call_info));
+    memset(&ctx->call_info_ext, 0, sizeof(ctx->call_info_ext));
+  }
   tl_recorder = &ctx->call_info;
+  tl_recorder_ext = &ctx->call_info_ext;
 }
 sa_host::CallScope::~CallScope() {
   if (!ctx) return;
   --ctx->call_depth;
   tl_recorder = prev;
+  tl_recorder_ext = prev_ext;
 }
 
 extern "C" int seqalign_ctx_last_call_info(const seqalign_ctx_t *ctx, seqalign_call_info_t *out) {
   if (!ctx || !out) return SEQALIGN_E_ARG;
   *out = ctx->call_info;
   return SEQALIGN_OK;
+}
+
+extern "C" int seqalign_ctx_last_call_info_ext(const seqalign_ctx_t *ctx, seqalign_call_info_ext_t *out) {
+  if (!ctx || !out) return SEQALIGN_E_ARG;
+  *out = ctx->call_info_ext;
+  return SEQALIGN_OK;
+}
+
+extern "C" const char *seqalign_kernel_kind_ext_name(int kind) {
+  static const char *names[SEQALIGN_KX_COUNT] = {"band_score", "band_fill", "band_walk"};
+  return kind >= 0 && kind < SEQALIGN_KX_COUNT ? names[kind] : nullptr;
 }
 
 extern "C" const char *seqalign_kernel_kind_name(int kind) {

@@ -466,6 +466,31 @@ struct SaLongParams {
 hipError_t sa_launch_long_forward(const SaLongParams &p, bool is_sw, hipStream_t stream);
 hipError_t sa_launch_long_block(const SaLongParams &p, hipStream_t stream);
 hipError_t sa_launch_long_walk(const SaLongParams &p, hipStream_t stream);
+/* ---- banded NW (seqalign_nw_*_banded, sa_band.hip): one wave per pair, a frame of 64 x CPL cells that follows the band down
+ * the matrix.  Pair k of a launch has the band d_lo[k] <= i - j <= d_lo[k] + width[k] - 1 (width <= SA_BAND_MAX_WIDTH; the
+ * caller clamps it to the matrix, include/seqalign_hip.h).  Score form: score[k] = the end cell's max(M, A, B).  Fill form: M, A, B of every band
+ * cell, borders included: cell (i, j) at f.mat_off[k] + j (width - 1) + i - d_lo of f.M / f.A / f.B ((len_b + 1) width cells per
+ * pair; slots whose column lies outside 0 .. len_a are not written).  Both: f.status[k] = the lowest band cell without a score
+ * (~0: none), *err_flag |= 1 when a pair has one.  Walk: one lane per pair over the fill form's cells -- a cell outside the band
+ * reads as the floor -- strings written backwards from out_a / out_b + str_off[k] + len_a + len_b, meta4[4k..] = head, length,
+ * score, status (0, SEQALIGN_E_UNKNOWN_PAIR, SEQALIGN_E_TRACEBACK). */
+#define SA_BAND_MAX_WIDTH 1024u
+struct SaBandParams {
+  SaFillParams f;
+  const int32_t *d_lo;
+  const uint32_t *width;
+  int32_t *score;
+  uint32_t *err_flag;
+  const uint64_t *str_off;
+  char *out_a, *out_b;
+  uint32_t *meta4;
+};
+/* every pair of the launch has width <= max_width <= SA_BAND_MAX_WIDTH; max_width picks the columns per lane */
+hipError_t sa_launch_band_score(const SaBandParams &p, uint32_t max_width, hipStream_t stream);
+hipError_t sa_launch_band_fill(const SaBandParams &p, uint32_t max_width, hipStream_t stream);
+hipError_t sa_launch_band_walk(const SaBandParams &p, hipStream_t stream);
+/* the second launch record (seqalign_ctx_last_call_info_ext: SEQALIGN_KX_*) */
+void sa_record_launch_ext(int kind, uint64_t items);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */
 bool sa_wgstream_kernel_applicable(const SaFillParams &p, uint32_t max_len_a);
 hipError_t sa_launch_fill_wgstream(const SaFillParams &p, uint32_t max_len_a, hipStream_t stream);

@@ -117,6 +117,7 @@ def lib():
         l.seqalign_strerror.restype = C.c_char_p
         l.seqalign_last_error.restype = C.c_char_p
         l.seqalign_kernel_kind_name.restype = C.c_char_p
+        l.seqalign_kernel_kind_ext_name.restype = C.c_char_p
         l.needleman_wunsch_new.restype = C.c_void_p
         l.smith_waterman_new.restype = C.c_void_p
         l.alignment_create.restype = C.c_void_p
@@ -173,6 +174,14 @@ K_MAX = 32
 class CallInfo(C.Structure):
     """seqalign_call_info_t (include/seqalign_hip.h)."""
     _fields_ = [("launches", C.c_uint32 * K_MAX), ("items", C.c_uint64 * K_MAX)]
+
+
+KX_MAX = 32
+
+
+class CallInfoExt(C.Structure):
+    """seqalign_call_info_ext_t (include/seqalign_hip.h): the second launch record, kinds SEQALIGN_KX_*."""
+    _fields_ = [("launches", C.c_uint32 * KX_MAX), ("items", C.c_uint64 * KX_MAX)]
 
 
 class ArenaInfo(C.Structure):
@@ -255,6 +264,12 @@ class Context:
             if info.launches[k]:
                 name = lib().seqalign_kernel_kind_name(C.c_int(k))
                 out[name.decode() if name else f"kind{k}"] = (int(info.launches[k]), int(info.items[k]))
+        ext = CallInfoExt()
+        _check(lib().seqalign_ctx_last_call_info_ext(self._h, C.byref(ext)), "seqalign_ctx_last_call_info_ext")
+        for k in range(KX_MAX):
+            if ext.launches[k]:
+                name = lib().seqalign_kernel_kind_ext_name(C.c_int(k))
+                out[name.decode() if name else f"kind_ext{k}"] = (int(ext.launches[k]), int(ext.items[k]))
         return out
 
     # ---- scoring -----------------------------------------------------------
@@ -465,22 +480,44 @@ class Context:
         """seqalign_nw_align_long: what nw_batch returns -- [(score, a, b)] per pair -- for pairs of any size (no 2^31-cell
         cap: checkpoint rows and blocks recomputed from them)."""
         _score_args(batch, scoring)
-        n = batch.n_pairs
-        caps = batch.len_a.astype(np.uint64) + batch.len_b.astype(np.uint64) + np.uint64(1)
-        str_off = np.zeros(n, np.uint64)
-        if n:
-            str_off[1:] = np.cumsum(caps)[:-1]
-        total = int(caps.sum()) + 1
-        out_a, out_b = np.zeros(total, np.uint8), np.zeros(total, np.uint8)
-        out_len, out_score = np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        str_off, out_a, out_b, out_len, out_score = _nw_string_buffers(batch)
         d = batch_desc(batch)
         _check(lib().seqalign_nw_align_long(self._h, C.byref(d), C.byref(scoring), _ptr(str_off), _ptr(out_a), _ptr(out_b),
                                             _ptr(out_len), _ptr(out_score)), "seqalign_nw_align_long")
-        res = []
-        for p in range(n):
-            o, ln = int(str_off[p]), int(out_len[p])
-            res.append((int(out_score[p]), out_a[o:o + ln].tobytes(), out_b[o:o + ln].tobytes()))
-        return res
+        return _nw_results(str_off, out_a, out_b, out_len, out_score)
+
+    # ---- banded NW (seqalign_nw_score_banded / seqalign_nw_align_banded) -------------------------------
+    def nw_score_banded(self, batch, scoring: Scoring, band) -> np.ndarray:
+        """seqalign_nw_score_banded: the global score of every pair inside its diagonal band, int32[n].  band: an int, or
+        one per pair (w >= 0; the band is d_lo = max(-lb, min(0, la - lb) - w) <= i - j <= min(la, max(0, la - lb) + w))."""
+        _score_args(batch, scoring)
+        bw = _band_arg(batch, band)
+        score = np.zeros(batch.n_pairs, np.int32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_score_banded(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(score)),
+               "seqalign_nw_score_banded")
+        return score
+
+    def nw_align_banded(self, batch, scoring: Scoring, band):
+        """seqalign_nw_align_banded: what nw_batch returns -- [(score, a, b)] per pair -- over the banded matrices.  A pair
+        with no alignment inside its band raises SeqAlignError(E_TRACEBACK)."""
+        _score_args(batch, scoring)
+        bw = _band_arg(batch, band)
+        str_off, out_a, out_b, out_len, out_score = _nw_string_buffers(batch)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_align_banded(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(str_off), _ptr(out_a),
+                                              _ptr(out_b), _ptr(out_len), _ptr(out_score)), "seqalign_nw_align_banded")
+        return _nw_results(str_off, out_a, out_b, out_len, out_score)
+
+    def band_score_time_ms(self, batch, scoring: Scoring, band, repeats: int = 10) -> np.ndarray:
+        """seqalign_band_score_time_ms: kernel time (HIP events) of nw_score_banded's launches, float32[repeats]."""
+        _score_args(batch, scoring)
+        bw = _band_arg(batch, band)
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_band_score_time_ms(self._h, C.byref(d), C.byref(scoring), _ptr(bw), C.c_int(repeats), _ptr(ms)),
+               "seqalign_band_score_time_ms")
+        return ms
 
     def sw_align_long(self, batch, scoring: Scoring, min_score):
         """seqalign_sw_align_long: what sw_batch(..., max_hits=1) returns -- per pair a list of at most one hit dict --
@@ -630,6 +667,44 @@ def _score_args(batch, scoring):
     size = batch.arena.nbytes
     if n and (int((batch.off_a + batch.len_a).max()) > size or int((batch.off_b + batch.len_b).max()) > size):
         raise SeqAlignError(E_ARG, "score: a sequence lies outside batch.arena")
+
+
+def _nw_string_buffers(batch):
+    """Output buffers of the calls that return seqalign_nw_batch's strings: str_off, out_a, out_b, out_len, out_score
+    (capacity len_a + len_b + 1 per pair)."""
+    n = batch.n_pairs
+    caps = batch.len_a.astype(np.uint64) + batch.len_b.astype(np.uint64) + np.uint64(1)
+    str_off = np.zeros(n, np.uint64)
+    if n:
+        str_off[1:] = np.cumsum(caps)[:-1]
+    total = int(caps.sum()) + 1
+    return str_off, np.zeros(total, np.uint8), np.zeros(total, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.int32)
+
+
+def _nw_results(str_off, out_a, out_b, out_len, out_score):
+    """[(score, a, b)] per pair out of those buffers."""
+    res = []
+    for p in range(len(out_len)):
+        o, ln = int(str_off[p]), int(out_len[p])
+        res.append((int(out_score[p]), out_a[o:o + ln].tobytes(), out_b[o:o + ln].tobytes()))
+    return res
+
+
+def _band_arg(batch, band) -> np.ndarray:
+    """band of the banded calls: one int for every pair, or one per pair; 0 <= w < 2^32."""
+    n = batch.n_pairs
+    try:
+        w = np.asarray(band)
+        if w.dtype.kind not in "iu" or w.ndim > 1:
+            raise ValueError
+        w = np.full(n, int(w), np.int64) if w.ndim == 0 else w.astype(np.int64)
+    except (TypeError, ValueError, OverflowError):
+        raise SeqAlignError(E_ARG, "band: an int or one int per pair") from None
+    if w.shape != (n,):
+        raise SeqAlignError(E_ARG, f"band: {w.shape[0]} entries for {n} pairs")
+    if n and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF):
+        raise SeqAlignError(E_ARG, "band: entries must be in 0 .. 2^32 - 1")
+    return np.ascontiguousarray(w.astype(np.uint32))
 
 
 def _cross_args(queries, targets, scoring):
@@ -884,6 +959,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_score_search", "seqalign_sw_score_search", "seqalign_nw_score_search_multi",
     "seqalign_sw_score_search_multi",
     "seqalign_nw_align_long", "seqalign_sw_align_long",
+    "seqalign_nw_score_banded", "seqalign_nw_align_banded", "seqalign_band_score_time_ms", "seqalign_ctx_last_call_info_ext", "seqalign_kernel_kind_ext_name",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",
