@@ -246,15 +246,7 @@ static hipError_t launch_band_cpl(const SaBandParams &p, hipStream_t stream) {
 template <bool FILL>
 static hipError_t launch_band(const SaBandParams &p, uint32_t max_width, hipStream_t stream) {
   const uint32_t need = columns_per_lane(max_width);
-  if (need <= 1) return launch_band_cpl<1, FILL>(p, stream);
-  if (need <= 2) return launch_band_cpl<2, FILL>(p, stream);
-  if (need <= 3) return launch_band_cpl<3, FILL>(p, stream);
-  if (need <= 4) return launch_band_cpl<4, FILL>(p, stream);
-  if (need <= 5) return launch_band_cpl<5, FILL>(p, stream);
-  if (need <= 6) return launch_band_cpl<6, FILL>(p, stream);
-  if (need <= 8) return launch_band_cpl<8, FILL>(p, stream);
-  if (need <= 12) return launch_band_cpl<12, FILL>(p, stream);
-  return launch_band_cpl<16, FILL>(p, stream);
+  return launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return launch_band_cpl<cpl(), FILL>(p, stream); });
 }
 
 }  // namespace sa

@@ -14,6 +14,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "sa_kernels.h"
 
 // (SA_S_* sentinels and SA_F_* flags: host/sa_internal.h, through sa_kernels.h)
@@ -112,6 +114,32 @@ inline uint32_t columns_per_lane(uint32_t max_len_a, uint32_t at_least = 0) {
   uint32_t need = (max_len_a + kWave - 1) / kWave;
   if (at_least > need && at_least <= 16) need = at_least;
   return need;
+}
+
+// The rung of a ladder of kernel instantiations that serves `need` columns per lane: the first of Rungs... (ascending) that is
+// >= need, the last one when none is (a caller that cannot serve such a `need` checks before it asks).
+template <int... Rungs>
+constexpr int pick_cpl(uint32_t need) {
+  constexpr int rungs[] = {Rungs...};
+  for (int r : rungs)
+    if ((uint32_t)r >= need) return r;
+  return rungs[sizeof...(Rungs) - 1];
+}
+// (a wrong rung gives right results from a slower kernel: no test of results sees it)
+static_assert(pick_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(1) == 1 && pick_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(3) == 3 &&
+              pick_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(7) == 8 && pick_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(9) == 12 &&
+              pick_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(13) == 16 && pick_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(17) == 16, "the full ladder");
+static_assert(pick_cpl<1, 2, 3, 4, 5, 6, 8>(7) == 8 && pick_cpl<1, 2, 3, 4, 5, 6, 8>(9) == 8, "the ladder of the whole-row kernels");
+static_assert(pick_cpl<2, 3, 4, 5, 6, 8>(0) == 2 && pick_cpl<2, 3, 4, 5, 6, 8>(1) == 2, "a ladder without its first rung");
+
+// launch(std::integral_constant<int, CPL>{}) for that rung, and what it returns (the idiom of launch_by_scoring, sa_rowsweep.hpp;
+// a left fold: the rungs are instantiated, and their kernels emitted, in ascending order)
+template <int... Rungs, class F>
+hipError_t launch_by_cpl(uint32_t need, F &&launch) {
+  const int rung = pick_cpl<Rungs...>(need);
+  hipError_t err = hipErrorInvalidValue;
+  (void)(... || (rung == Rungs && ((err = launch(std::integral_constant<int, Rungs>{})), true)));
+  return err;
 }
 
 // border values (reference alignment.c:46-81)

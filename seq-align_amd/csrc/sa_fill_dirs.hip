@@ -259,33 +259,26 @@ fill_nw_dirs_kernel(const SaFillParams p, uint8_t *__restrict__ dirs_arena) {
   nw_dirs_x1_wave<CPL, SUBST, R, LOCAL>(p, dirs_arena, pair, lane, reinterpret_cast<uint8_t *>(lds) + wave * R, table);
 }
 
-template <int CPL, int R0>
+template <int CPL>
 static hipError_t launch_nw_dirs_cpl(const SaFillParams &p, uint8_t *dirs, hipStream_t stream) {
   // (blocked direction bytes, sa_kernels.h: one block row of 64 x CPL columns per pair in LDS instead of the ring)
-  constexpr int R = (SA_DIRS_BLOCKED != 0 && kWave * CPL <= 512 && kWave * CPL * 8 > R0) ? kWave * CPL * 8 : R0;
+  constexpr int R = dirs_blocked_ring(kWave, CPL, dirs_ring(CPL));
   const int wpb = 4;
   const dim3 grid((p.n_pairs + wpb - 1) / wpb), block(kWave * wpb);
-  const size_t rings = (size_t)wpb * R;
-  const size_t lds = rings + (((size_t)p.K * p.K + 3u) & ~(size_t)3u) * sizeof(int32_t);
-  // (dirs_local: the byte's local form for the tile walkers, sa_kernels.h)
-  if (p.K <= 1 && p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_kernel<CPL, SA_SUBST_SIMPLE, R, true>), grid, block, rings, stream, p, dirs);
-  else if (p.K <= 1) hipLaunchKernelGGL((fill_nw_dirs_kernel<CPL, SA_SUBST_SIMPLE, R, false>), grid, block, rings, stream, p, dirs);
-  else if (p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_kernel<CPL, SA_SUBST_LDS, R, true>), grid, block, lds, stream, p, dirs);
-  else hipLaunchKernelGGL((fill_nw_dirs_kernel<CPL, SA_SUBST_LDS, R, false>), grid, block, lds, stream, p, dirs);
+  launch_by_dirs_form(p, dirs_x1_table_bytes(p), [&](auto subst, auto local, size_t tbl) {
+    hipLaunchKernelGGL((fill_nw_dirs_kernel<CPL, subst(), R, local()>), grid, block, (size_t)wpb * R + tbl, stream, p, dirs);
+  });
   return hipGetLastError();
 }
 
-template <int CPL, int R>
+template <int CPL>
 static hipError_t launch_dirs_cpl(const SaFillParams &p, uint8_t *dirs, hipStream_t stream) {
+  constexpr int R = dirs_ring(CPL);   // (elements: a ring of int32 scores and a ring of bytes)
   const int wpb = 4;
   const dim3 grid((p.n_pairs + wpb - 1) / wpb), block(kWave * wpb);
-  const size_t rings = (size_t)wpb * (R * 4u + R);
-  if (p.K <= 1) {
-    hipLaunchKernelGGL((fill_dirs_kernel<CPL, SA_SUBST_SIMPLE, R>), grid, block, rings, stream, p, dirs);
-  } else {
-    const size_t lds = rings + (((size_t)p.K * p.K + 3u) & ~(size_t)3u) * sizeof(int32_t);
-    hipLaunchKernelGGL((fill_dirs_kernel<CPL, SA_SUBST_LDS, R>), grid, block, lds, stream, p, dirs);
-  }
+  launch_by_dirs_subst(p, dirs_x1_table_bytes(p), [&](auto subst, size_t tbl) {
+    hipLaunchKernelGGL((fill_dirs_kernel<CPL, subst(), R>), grid, block, (size_t)wpb * (R * 4u + R) + tbl, stream, p, dirs);
+  });
   return hipGetLastError();
 }
 
@@ -302,15 +295,7 @@ hipError_t sa_launch_fill_dirs(const SaFillParams &p, uint32_t max_len_a, uint8_
   if (p.n_pairs == 0) return hipSuccess;
   sa_record_launch(SEQALIGN_K_FILL_SW_DIRS, p.n_pairs);
   const uint32_t need = sa::columns_per_lane(max_len_a + 1, p.tune_cpl);
-  if (need <= 1) return sa::launch_dirs_cpl<1, 512>(p, dirs, stream);
-  if (need <= 2) return sa::launch_dirs_cpl<2, 512>(p, dirs, stream);
-  if (need <= 3) return sa::launch_dirs_cpl<3, 512>(p, dirs, stream);
-  if (need <= 4) return sa::launch_dirs_cpl<4, 512>(p, dirs, stream);
-  if (need <= 5) return sa::launch_dirs_cpl<5, 1024>(p, dirs, stream);
-  if (need <= 6) return sa::launch_dirs_cpl<6, 1024>(p, dirs, stream);
-  if (need <= 8) return sa::launch_dirs_cpl<8, 1024>(p, dirs, stream);
-  if (need <= 12) return sa::launch_dirs_cpl<12, 1024>(p, dirs, stream);   // (rows of 513 .. 1 024 columns: round 5)
-  return sa::launch_dirs_cpl<16, 2048>(p, dirs, stream);
+  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return sa::launch_dirs_cpl<cpl()>(p, dirs, stream); });   // (12, 16: rows of 513 .. 1 024 columns, round 5)
 }
 
 // ---- Needleman-Wunsch: directions only (seqalign_nw_batch)
@@ -324,13 +309,5 @@ hipError_t sa_launch_fill_nw_dirs(const SaFillParams &p, uint32_t max_len_a, uin
   if (p.n_pairs == 0) return hipSuccess;
   sa_record_launch(SEQALIGN_K_FILL_NW_DIRS, p.n_pairs);
   const uint32_t need = sa::columns_per_lane(max_len_a + 1, sa_dirs_blocked_shape(max_len_a) ? std::min<uint32_t>(p.tune_cpl, 8u) : p.tune_cpl);
-  if (need <= 1) return sa::launch_nw_dirs_cpl<1, 512>(p, dirs, stream);
-  if (need <= 2) return sa::launch_nw_dirs_cpl<2, 512>(p, dirs, stream);
-  if (need <= 3) return sa::launch_nw_dirs_cpl<3, 512>(p, dirs, stream);
-  if (need <= 4) return sa::launch_nw_dirs_cpl<4, 512>(p, dirs, stream);
-  if (need <= 5) return sa::launch_nw_dirs_cpl<5, 1024>(p, dirs, stream);
-  if (need <= 6) return sa::launch_nw_dirs_cpl<6, 1024>(p, dirs, stream);
-  if (need <= 8) return sa::launch_nw_dirs_cpl<8, 1024>(p, dirs, stream);
-  if (need <= 12) return sa::launch_nw_dirs_cpl<12, 1024>(p, dirs, stream);   // (rows of 513 .. 1 024 columns: round 5)
-  return sa::launch_nw_dirs_cpl<16, 2048>(p, dirs, stream);
+  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return sa::launch_nw_dirs_cpl<cpl()>(p, dirs, stream); });
 }

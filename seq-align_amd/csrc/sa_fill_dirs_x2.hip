@@ -66,8 +66,6 @@
 #define SA_BEST_X4_MIN 4097u
 #endif
 namespace sa {
-// bytes of LDS per pair of the NW / best-hit fills: the ring of the row-major form, or one block row of LANES x CPL columns
-constexpr int x2_ring(int lanes, int cpl, int ring) { return (SA_DIRS_BLOCKED != 0 && lanes * cpl <= 512 && lanes * cpl * 8 > ring) ? lanes * cpl * 8 : ring; }
 constexpr bool kLdsPipe = SA_X2_LDS_PIPE != 0;        // the row profile (table scorings) a row ahead
 constexpr bool kFlushDefer = SA_X2_FLUSH_DEFER != 0;  // a ring block read at the end of one row, stored at the end of the next
 constexpr bool kNwDetrend = SA_NW_DETREND != 0;
@@ -1079,6 +1077,8 @@ __device__ __forceinline__ void sw_best_x2_wave(const SaFillParams &p, uint8_t *
   SubstX2<SUBST, CPL, (SUBST == SA_SUBST_LDS && LANES == 64)> sub;
   sub.init(p, tbl_lds, lane);
 
+  // The direction bytes' way out: nw_dirs_x2_wave's writer, line for line, and kept so -- as one shared struct it moves 204 of this
+  // file's kernels and costs one of them a wave of occupancy (profiles/r13): a fix goes into both.
   constexpr bool BLK = kDirsBlocked && LANES * CPL <= 512;   // (rows of up to 512 columns: sa_dirs_blocked_shape)
   uint8_t *ring0 = ring_wave + span * (2 * R), *ring1 = ring0 + R;
   uint32_t wv = 0, rv = 0;
@@ -1385,109 +1385,88 @@ fill_sw_best_x4x2_kernel(const SaFillParams p, uint8_t *__restrict__ dirs_arena,
   }
 }
 
-template <int CPL, int R0>
+// ---- the launches.  A grid of workgroups of four waves; LDS: the waves' rings (PAIRS per wave, R bytes each), then the table.
+// R of the NW / best-hit fills: dirs_blocked_ring (blocked direction bytes: a block row per pair instead of the ring).
+static inline dim3 x2_grid(uint32_t units) { return dim3((units + kWavesPerBlock - 1) / kWavesPerBlock); }
+
+template <int CPL>
 static hipError_t launch_sw_best_x2_cpl(const SaFillParams &p, uint8_t *dirs, hipStream_t stream) {
-  constexpr int R = x2_ring(64, CPL, R0);   // (blocked direction bytes: a block row per pair instead of the ring)
-  const int wpb = 4;
-  const uint32_t units = (p.n_pairs + 1) / 2;
-  const dim3 grid((units + wpb - 1) / wpb), block(kWave * wpb);
-  if (p.K <= 1 && p.dirs_local) hipLaunchKernelGGL((fill_sw_best_x2_kernel<CPL, SA_SUBST_SIMPLE, R, true>), grid, block, (size_t)wpb * 2 * R, stream, p, dirs);
-  else if (p.K <= 1) hipLaunchKernelGGL((fill_sw_best_x2_kernel<CPL, SA_SUBST_SIMPLE, R, false>), grid, block, (size_t)wpb * 2 * R, stream, p, dirs);
-  else if (p.dirs_local) hipLaunchKernelGGL((fill_sw_best_x2_kernel<CPL, SA_SUBST_LDS, R, true>), grid, block, (size_t)wpb * 2 * R + table_lds_bytes(p), stream, p, dirs);
-  else hipLaunchKernelGGL((fill_sw_best_x2_kernel<CPL, SA_SUBST_LDS, R, false>), grid, block, (size_t)wpb * 2 * R + table_lds_bytes(p), stream, p, dirs);
+  constexpr int R = dirs_blocked_ring(64, CPL, dirs_ring(CPL));
+  launch_by_dirs_form(p, table_lds_bytes(p), [&](auto subst, auto local, size_t tbl) {
+    hipLaunchKernelGGL((fill_sw_best_x2_kernel<CPL, subst(), R, local()>), x2_grid((p.n_pairs + 1) / 2), dim3(kWave * kWavesPerBlock), (size_t)kWavesPerBlock * 2 * R + tbl, stream, p, dirs);
+  });
   return hipGetLastError();
 }
 
-template <int CPL, int R>
+template <int CPL>
 static hipError_t launch_dirs_x2_cpl(const SaFillParams &p, uint8_t *dirs, hipStream_t stream) {
-  const int wpb = 4;
-  const uint32_t units = (p.n_pairs + 1) / 2;
-  const dim3 grid((units + wpb - 1) / wpb), block(kWave * wpb);
-  if (p.K <= 1) hipLaunchKernelGGL((fill_dirs_x2_kernel<CPL, SA_SUBST_SIMPLE, R>), grid, block, (size_t)wpb * 6 * R, stream, p, dirs);
-  else hipLaunchKernelGGL((fill_dirs_x2_kernel<CPL, SA_SUBST_LDS, R>), grid, block, (size_t)wpb * 6 * R + table_lds_bytes(p), stream, p, dirs);
+  constexpr int R = dirs_ring(CPL);   // (elements: per pair a ring of int16 scores and a ring of bytes)
+  launch_by_dirs_subst(p, table_lds_bytes(p), [&](auto subst, size_t tbl) {
+    hipLaunchKernelGGL((fill_dirs_x2_kernel<CPL, subst(), R>), x2_grid((p.n_pairs + 1) / 2), dim3(kWave * kWavesPerBlock), (size_t)kWavesPerBlock * 6 * R + tbl, stream, p, dirs);
+  });
   return hipGetLastError();
 }
 
-template <int CPL, int R0>
+template <int CPL>
 static hipError_t launch_nw_dirs_x2_cpl(const SaFillParams &p, uint8_t *dirs, hipStream_t stream) {
-  constexpr int R = x2_ring(64, CPL, R0);   // (blocked direction bytes: a block row per pair instead of the ring)
-  const int wpb = 4;
-  const uint32_t units = (p.n_pairs + 1) / 2;
-  const dim3 grid((units + wpb - 1) / wpb), block(kWave * wpb);
-  if (p.K <= 1 && p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_x2_kernel<CPL, SA_SUBST_SIMPLE, R, true>), grid, block, (size_t)wpb * 2 * R, stream, p, dirs);
-  else if (p.K <= 1) hipLaunchKernelGGL((fill_nw_dirs_x2_kernel<CPL, SA_SUBST_SIMPLE, R, false>), grid, block, (size_t)wpb * 2 * R, stream, p, dirs);
-  else if (p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_x2_kernel<CPL, SA_SUBST_LDS, R, true>), grid, block, (size_t)wpb * 2 * R + table_lds_bytes(p), stream, p, dirs);
-  else hipLaunchKernelGGL((fill_nw_dirs_x2_kernel<CPL, SA_SUBST_LDS, R, false>), grid, block, (size_t)wpb * 2 * R + table_lds_bytes(p), stream, p, dirs);
+  constexpr int R = dirs_blocked_ring(64, CPL, dirs_ring(CPL));
+  launch_by_dirs_form(p, table_lds_bytes(p), [&](auto subst, auto local, size_t tbl) {
+    hipLaunchKernelGGL((fill_nw_dirs_x2_kernel<CPL, subst(), R, local()>), x2_grid((p.n_pairs + 1) / 2), dim3(kWave * kWavesPerBlock), (size_t)kWavesPerBlock * 2 * R + tbl, stream, p, dirs);
+  });
   return hipGetLastError();
 }
 
 template <int CPL>
 static hipError_t launch_sw_best_x4_cpl(const SaFillParams &p, uint8_t *dirs, hipStream_t stream) {
-  constexpr int R = x2_ring(32, CPL, 512);
-  const int wpb = 4;
-  const uint32_t units = (p.n_pairs + 3) / 4;
-  const dim3 grid((units + wpb - 1) / wpb), block(kWave * wpb);
-  if (p.K <= 1 && p.dirs_local) hipLaunchKernelGGL((fill_sw_best_x4_kernel<CPL, SA_SUBST_SIMPLE, R, true>), grid, block, (size_t)wpb * 4 * R, stream, p, dirs);
-  else if (p.K <= 1) hipLaunchKernelGGL((fill_sw_best_x4_kernel<CPL, SA_SUBST_SIMPLE, R, false>), grid, block, (size_t)wpb * 4 * R, stream, p, dirs);
-  else if (p.dirs_local) hipLaunchKernelGGL((fill_sw_best_x4_kernel<CPL, SA_SUBST_LDS, R, true>), grid, block, (size_t)wpb * 4 * R + table_lds_bytes(p), stream, p, dirs);
-  else hipLaunchKernelGGL((fill_sw_best_x4_kernel<CPL, SA_SUBST_LDS, R, false>), grid, block, (size_t)wpb * 4 * R + table_lds_bytes(p), stream, p, dirs);
+  constexpr int R = dirs_blocked_ring(32, CPL, 512);
+  launch_by_dirs_form(p, table_lds_bytes(p), [&](auto subst, auto local, size_t tbl) {
+    hipLaunchKernelGGL((fill_sw_best_x4_kernel<CPL, subst(), R, local()>), x2_grid((p.n_pairs + 3) / 4), dim3(kWave * kWavesPerBlock), (size_t)kWavesPerBlock * 4 * R + tbl, stream, p, dirs);
+  });
   return hipGetLastError();
 }
 
 template <int CPL>
 static hipError_t launch_nw_dirs_x4_cpl(const SaFillParams &p, uint8_t *dirs, hipStream_t stream) {
-  constexpr int R = x2_ring(32, CPL, 512);   // (255 + 32 * 8 columns fit)
-  const int wpb = 4;
-  const uint32_t units = (p.n_pairs + 3) / 4;
-  const dim3 grid((units + wpb - 1) / wpb), block(kWave * wpb);
-  if (p.K <= 1 && p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_x4_kernel<CPL, SA_SUBST_SIMPLE, R, true>), grid, block, (size_t)wpb * 4 * R, stream, p, dirs);
-  else if (p.K <= 1) hipLaunchKernelGGL((fill_nw_dirs_x4_kernel<CPL, SA_SUBST_SIMPLE, R, false>), grid, block, (size_t)wpb * 4 * R, stream, p, dirs);
-  else if (p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_x4_kernel<CPL, SA_SUBST_LDS, R, true>), grid, block, (size_t)wpb * 4 * R + table_lds_bytes(p), stream, p, dirs);
-  else hipLaunchKernelGGL((fill_nw_dirs_x4_kernel<CPL, SA_SUBST_LDS, R, false>), grid, block, (size_t)wpb * 4 * R + table_lds_bytes(p), stream, p, dirs);
+  constexpr int R = dirs_blocked_ring(32, CPL, 512);   // (255 + 32 * 8 columns fit)
+  launch_by_dirs_form(p, table_lds_bytes(p), [&](auto subst, auto local, size_t tbl) {
+    hipLaunchKernelGGL((fill_nw_dirs_x4_kernel<CPL, subst(), R, local()>), x2_grid((p.n_pairs + 3) / 4), dim3(kWave * kWavesPerBlock), (size_t)kWavesPerBlock * 4 * R + tbl, stream, p, dirs);
+  });
   return hipGetLastError();
 }
 
+// (the four-per-wave waves: four pairs of 32 x CPL4 columns; the two-per-wave waves: two pairs of 64 x CPL2 in the same region)
+constexpr int x4x2_ring(int cpl4) { return dirs_blocked_ring(64, (cpl4 + 1) / 2, dirs_blocked_ring(32, cpl4, 512)); }
+
 template <int CPL4>
 static hipError_t launch_nw_dirs_x4x2_cpl(const SaFillParams &p, uint8_t *dirs, uint32_t pairs_q, hipStream_t stream) {
-  // (the four-per-wave waves: four pairs of 32 x CPL4 columns; the two-per-wave waves: two pairs of 64 x CPL2 in the same region)
-  constexpr int R = x2_ring(64, (CPL4 + 1) / 2, x2_ring(32, CPL4, 512));
-  const int wpb = 4;
-  const uint32_t q_blocks = (pairs_q / 4 + wpb - 1) / wpb, x2_blocks = ((p.n_pairs - pairs_q + 1) / 2 + wpb - 1) / wpb;
-  const dim3 grid(q_blocks + x2_blocks), block(kWave * wpb);
-  if (p.K <= 1 && p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_x4x2_kernel<CPL4, SA_SUBST_SIMPLE, R, true>), grid, block, (size_t)wpb * 4 * R, stream, p, dirs, q_blocks, pairs_q);
-  else if (p.K <= 1) hipLaunchKernelGGL((fill_nw_dirs_x4x2_kernel<CPL4, SA_SUBST_SIMPLE, R, false>), grid, block, (size_t)wpb * 4 * R, stream, p, dirs, q_blocks, pairs_q);
-  else if (p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_x4x2_kernel<CPL4, SA_SUBST_LDS, R, true>), grid, block, (size_t)wpb * 4 * R + table_lds_bytes(p), stream, p, dirs, q_blocks, pairs_q);
-  else hipLaunchKernelGGL((fill_nw_dirs_x4x2_kernel<CPL4, SA_SUBST_LDS, R, false>), grid, block, (size_t)wpb * 4 * R + table_lds_bytes(p), stream, p, dirs, q_blocks, pairs_q);
+  constexpr int R = x4x2_ring(CPL4);
+  const uint32_t q_blocks = x2_grid(pairs_q / 4).x, x2_blocks = x2_grid((p.n_pairs - pairs_q + 1) / 2).x;
+  launch_by_dirs_form(p, table_lds_bytes(p), [&](auto subst, auto local, size_t tbl) {
+    hipLaunchKernelGGL((fill_nw_dirs_x4x2_kernel<CPL4, subst(), R, local()>), dim3(q_blocks + x2_blocks), dim3(kWave * kWavesPerBlock), (size_t)kWavesPerBlock * 4 * R + tbl, stream, p, dirs, q_blocks, pairs_q);
+  });
   return hipGetLastError();
 }
 
 template <int CPL4>
 static hipError_t launch_sw_best_x4x2_cpl(const SaFillParams &p, uint8_t *dirs, uint32_t pairs_q, hipStream_t stream) {
-  constexpr int R = x2_ring(64, (CPL4 + 1) / 2, x2_ring(32, CPL4, 512));
-  const int wpb = 4;
-  const uint32_t q_blocks = (pairs_q / 4 + wpb - 1) / wpb, x2_blocks = ((p.n_pairs - pairs_q + 1) / 2 + wpb - 1) / wpb;
-  const dim3 grid(q_blocks + x2_blocks), block(kWave * wpb);
-  if (p.K <= 1 && p.dirs_local) hipLaunchKernelGGL((fill_sw_best_x4x2_kernel<CPL4, SA_SUBST_SIMPLE, R, true>), grid, block, (size_t)wpb * 4 * R, stream, p, dirs, q_blocks, pairs_q);
-  else if (p.K <= 1) hipLaunchKernelGGL((fill_sw_best_x4x2_kernel<CPL4, SA_SUBST_SIMPLE, R, false>), grid, block, (size_t)wpb * 4 * R, stream, p, dirs, q_blocks, pairs_q);
-  else if (p.dirs_local) hipLaunchKernelGGL((fill_sw_best_x4x2_kernel<CPL4, SA_SUBST_LDS, R, true>), grid, block, (size_t)wpb * 4 * R + table_lds_bytes(p), stream, p, dirs, q_blocks, pairs_q);
-  else hipLaunchKernelGGL((fill_sw_best_x4x2_kernel<CPL4, SA_SUBST_LDS, R, false>), grid, block, (size_t)wpb * 4 * R + table_lds_bytes(p), stream, p, dirs, q_blocks, pairs_q);
+  constexpr int R = x4x2_ring(CPL4);
+  const uint32_t q_blocks = x2_grid(pairs_q / 4).x, x2_blocks = x2_grid((p.n_pairs - pairs_q + 1) / 2).x;
+  launch_by_dirs_form(p, table_lds_bytes(p), [&](auto subst, auto local, size_t tbl) {
+    hipLaunchKernelGGL((fill_sw_best_x4x2_kernel<CPL4, subst(), R, local()>), dim3(q_blocks + x2_blocks), dim3(kWave * kWavesPerBlock), (size_t)kWavesPerBlock * 4 * R + tbl, stream, p, dirs, q_blocks, pairs_q);
+  });
   return hipGetLastError();
 }
 
-template <int CPL, int R0>
+template <int CPL>
 static hipError_t launch_nw_dirs_mixed_cpl(const SaFillParams &p, uint8_t *dirs, uint32_t n_modal, uint32_t n_rest, hipStream_t stream) {
-  constexpr int R = x2_ring(64, CPL, R0);
-  const int wpb = 4;
-  const uint32_t x2_blocks = ((n_modal + 1) / 2 + wpb - 1) / wpb, x1_blocks = (n_rest + wpb - 1) / wpb;
-  const dim3 grid(x2_blocks + x1_blocks), block(kWave * wpb);
-  if (p.K <= 1) {
-    if (p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_mixed_kernel<CPL, SA_SUBST_SIMPLE, R, true>), grid, block, (size_t)wpb * 2 * R, stream, p, dirs, x2_blocks, n_modal, n_rest);
-    else hipLaunchKernelGGL((fill_nw_dirs_mixed_kernel<CPL, SA_SUBST_SIMPLE, R, false>), grid, block, (size_t)wpb * 2 * R, stream, p, dirs, x2_blocks, n_modal, n_rest);
-  } else {
-    const size_t lds = std::max((size_t)wpb * 2 * R + table_lds_bytes(p), (size_t)wpb * R + (((size_t)p.K * p.K + 3u) & ~(size_t)3u) * sizeof(int32_t));
-    if (p.dirs_local) hipLaunchKernelGGL((fill_nw_dirs_mixed_kernel<CPL, SA_SUBST_LDS, R, true>), grid, block, lds, stream, p, dirs, x2_blocks, n_modal, n_rest);
-    else hipLaunchKernelGGL((fill_nw_dirs_mixed_kernel<CPL, SA_SUBST_LDS, R, false>), grid, block, lds, stream, p, dirs, x2_blocks, n_modal, n_rest);
-  }
+  constexpr int R = dirs_blocked_ring(64, CPL, dirs_ring(CPL));
+  const uint32_t x2_blocks = x2_grid((n_modal + 1) / 2).x, x1_blocks = x2_grid(n_rest).x;
+  launch_by_dirs_form(p, table_lds_bytes(p), [&](auto subst, auto local, size_t tbl) {
+    size_t lds = (size_t)kWavesPerBlock * 2 * R + tbl;
+    // (the one-pair workgroups of the grid lay their LDS out as fill_nw_dirs_kernel does: a ring per wave, then the table as int32)
+    if constexpr (subst() == SA_SUBST_LDS) lds = std::max(lds, (size_t)kWavesPerBlock * R + dirs_x1_table_bytes(p));
+    hipLaunchKernelGGL((fill_nw_dirs_mixed_kernel<CPL, subst(), R, local()>), dim3(x2_blocks + x1_blocks), dim3(kWave * kWavesPerBlock), lds, stream, p, dirs, x2_blocks, n_modal, n_rest);
+  });
   return hipGetLastError();
 }
 
@@ -1531,37 +1510,15 @@ hipError_t sa_launch_fill_nw_dirs_x2(const SaFillParams &p, uint32_t max_len_a, 
     if (p.tune_quad == 0 && pairs_q && rest && rest <= 2048u) {
       sa_record_launch(SEQALIGN_K_FILL_NW_DIRS_X4, pairs_q);
       sa_record_launch(SEQALIGN_K_FILL_NW_DIRS_X2, rest);
-      switch (c4) {
-        case 1: return sa::launch_nw_dirs_x4x2_cpl<1>(p, dirs, pairs_q, stream);
-        case 2: return sa::launch_nw_dirs_x4x2_cpl<2>(p, dirs, pairs_q, stream);
-        case 3: return sa::launch_nw_dirs_x4x2_cpl<3>(p, dirs, pairs_q, stream);
-        case 4: return sa::launch_nw_dirs_x4x2_cpl<4>(p, dirs, pairs_q, stream);
-        case 5: return sa::launch_nw_dirs_x4x2_cpl<5>(p, dirs, pairs_q, stream);
-        default: return sa::launch_nw_dirs_x4x2_cpl<6>(p, dirs, pairs_q, stream);
-      }
+      return sa::launch_by_cpl<1, 2, 3, 4, 5, 6>((uint32_t)c4, [&](auto cpl) { return sa::launch_nw_dirs_x4x2_cpl<cpl()>(p, dirs, pairs_q, stream); });
     }
     sa_record_launch(SEQALIGN_K_FILL_NW_DIRS_X4, p.n_pairs);
-    switch (c4) {
-      case 1: return sa::launch_nw_dirs_x4_cpl<1>(p, dirs, stream);
-      case 2: return sa::launch_nw_dirs_x4_cpl<2>(p, dirs, stream);
-      case 3: return sa::launch_nw_dirs_x4_cpl<3>(p, dirs, stream);
-      case 4: return sa::launch_nw_dirs_x4_cpl<4>(p, dirs, stream);
-      case 5: return sa::launch_nw_dirs_x4_cpl<5>(p, dirs, stream);
-      default: return sa::launch_nw_dirs_x4_cpl<6>(p, dirs, stream);
-    }
+    return sa::launch_by_cpl<1, 2, 3, 4, 5, 6>((uint32_t)c4, [&](auto cpl) { return sa::launch_nw_dirs_x4_cpl<cpl()>(p, dirs, stream); });
   }
   sa_record_launch(SEQALIGN_K_FILL_NW_DIRS_X2, p.n_pairs);
   // (blocked direction bytes are decided by the row's width -- host -- and by LANES x CPL <= 512 -- kernel: a forced wider CPL must not split them)
   const uint32_t need = sa::columns_per_lane(max_len_a + 1, sa_dirs_blocked_shape(max_len_a) ? std::min<uint32_t>(p.tune_cpl, 8u) : p.tune_cpl);
-  if (need <= 1) return sa::launch_nw_dirs_x2_cpl<1, 512>(p, dirs, stream);
-  if (need <= 2) return sa::launch_nw_dirs_x2_cpl<2, 512>(p, dirs, stream);
-  if (need <= 3) return sa::launch_nw_dirs_x2_cpl<3, 512>(p, dirs, stream);
-  if (need <= 4) return sa::launch_nw_dirs_x2_cpl<4, 512>(p, dirs, stream);
-  if (need <= 5) return sa::launch_nw_dirs_x2_cpl<5, 1024>(p, dirs, stream);
-  if (need <= 6) return sa::launch_nw_dirs_x2_cpl<6, 1024>(p, dirs, stream);
-  if (need <= 8) return sa::launch_nw_dirs_x2_cpl<8, 1024>(p, dirs, stream);
-  if (need <= 12) return sa::launch_nw_dirs_x2_cpl<12, 1024>(p, dirs, stream);   // (rows of 513 .. 1 024 columns: round 5)
-  return sa::launch_nw_dirs_x2_cpl<16, 2048>(p, dirs, stream);
+  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return sa::launch_nw_dirs_x2_cpl<cpl()>(p, dirs, stream); });   // (12, 16: rows of 513 .. 1 024 columns, round 5)
 }
 
 // ---- Smith-Waterman multi-hit: match_scores + directions, two pairs per wave
@@ -1575,15 +1532,7 @@ hipError_t sa_launch_fill_dirs_x2(const SaFillParams &p, uint32_t max_len_a, uin
   if (p.n_pairs == 0) return hipSuccess;
   sa_record_launch(SEQALIGN_K_FILL_SW_DIRS_X2, p.n_pairs);
   const uint32_t need = sa::columns_per_lane(max_len_a + 1, p.tune_cpl);
-  if (need <= 1) return sa::launch_dirs_x2_cpl<1, 512>(p, dirs, stream);
-  if (need <= 2) return sa::launch_dirs_x2_cpl<2, 512>(p, dirs, stream);
-  if (need <= 3) return sa::launch_dirs_x2_cpl<3, 512>(p, dirs, stream);
-  if (need <= 4) return sa::launch_dirs_x2_cpl<4, 512>(p, dirs, stream);
-  if (need <= 5) return sa::launch_dirs_x2_cpl<5, 1024>(p, dirs, stream);
-  if (need <= 6) return sa::launch_dirs_x2_cpl<6, 1024>(p, dirs, stream);
-  if (need <= 8) return sa::launch_dirs_x2_cpl<8, 1024>(p, dirs, stream);
-  if (need <= 12) return sa::launch_dirs_x2_cpl<12, 1024>(p, dirs, stream);   // (rows of 513 .. 1 024 columns: round 5)
-  return sa::launch_dirs_x2_cpl<16, 2048>(p, dirs, stream);
+  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return sa::launch_dirs_x2_cpl<cpl()>(p, dirs, stream); });   // (12, 16: rows of 513 .. 1 024 columns, round 5)
 }
 
 // ---- Smith-Waterman best hit: directions + the best cell, two pairs per wave
@@ -1606,37 +1555,15 @@ hipError_t sa_launch_fill_sw_best_x2(const SaFillParams &p, uint32_t max_len_a, 
     if (p.tune_quad == 0 && pairs_q && rest && rest <= 2048u) {
       sa_record_launch(SEQALIGN_K_FILL_SW_BEST_X4, pairs_q);
       sa_record_launch(SEQALIGN_K_FILL_SW_BEST_X2, rest);
-      switch (c4) {
-        case 1: return sa::launch_sw_best_x4x2_cpl<1>(p, dirs, pairs_q, stream);
-        case 2: return sa::launch_sw_best_x4x2_cpl<2>(p, dirs, pairs_q, stream);
-        case 3: return sa::launch_sw_best_x4x2_cpl<3>(p, dirs, pairs_q, stream);
-        case 4: return sa::launch_sw_best_x4x2_cpl<4>(p, dirs, pairs_q, stream);
-        case 5: return sa::launch_sw_best_x4x2_cpl<5>(p, dirs, pairs_q, stream);
-        default: return sa::launch_sw_best_x4x2_cpl<6>(p, dirs, pairs_q, stream);
-      }
+      return sa::launch_by_cpl<1, 2, 3, 4, 5, 6>((uint32_t)c4, [&](auto cpl) { return sa::launch_sw_best_x4x2_cpl<cpl()>(p, dirs, pairs_q, stream); });
     }
     sa_record_launch(SEQALIGN_K_FILL_SW_BEST_X4, p.n_pairs);
-    switch (c4) {
-      case 1: return sa::launch_sw_best_x4_cpl<1>(p, dirs, stream);
-      case 2: return sa::launch_sw_best_x4_cpl<2>(p, dirs, stream);
-      case 3: return sa::launch_sw_best_x4_cpl<3>(p, dirs, stream);
-      case 4: return sa::launch_sw_best_x4_cpl<4>(p, dirs, stream);
-      case 5: return sa::launch_sw_best_x4_cpl<5>(p, dirs, stream);
-      default: return sa::launch_sw_best_x4_cpl<6>(p, dirs, stream);
-    }
+    return sa::launch_by_cpl<1, 2, 3, 4, 5, 6>((uint32_t)c4, [&](auto cpl) { return sa::launch_sw_best_x4_cpl<cpl()>(p, dirs, stream); });
   }
   sa_record_launch(SEQALIGN_K_FILL_SW_BEST_X2, p.n_pairs);
   // (blocked direction bytes are decided by the row's width -- host -- and by LANES x CPL <= 512 -- kernel: a forced wider CPL must not split them)
   const uint32_t need = sa::columns_per_lane(max_len_a + 1, sa_dirs_blocked_shape(max_len_a) ? std::min<uint32_t>(p.tune_cpl, 8u) : p.tune_cpl);
-  if (need <= 1) return sa::launch_sw_best_x2_cpl<1, 512>(p, dirs, stream);
-  if (need <= 2) return sa::launch_sw_best_x2_cpl<2, 512>(p, dirs, stream);
-  if (need <= 3) return sa::launch_sw_best_x2_cpl<3, 512>(p, dirs, stream);
-  if (need <= 4) return sa::launch_sw_best_x2_cpl<4, 512>(p, dirs, stream);
-  if (need <= 5) return sa::launch_sw_best_x2_cpl<5, 1024>(p, dirs, stream);
-  if (need <= 6) return sa::launch_sw_best_x2_cpl<6, 1024>(p, dirs, stream);
-  if (need <= 8) return sa::launch_sw_best_x2_cpl<8, 1024>(p, dirs, stream);
-  if (need <= 12) return sa::launch_sw_best_x2_cpl<12, 1024>(p, dirs, stream);   // (rows of 513 .. 1 024 columns: round 5)
-  return sa::launch_sw_best_x2_cpl<16, 2048>(p, dirs, stream);
+  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return sa::launch_sw_best_x2_cpl<cpl()>(p, dirs, stream); });   // (12, 16: rows of 513 .. 1 024 columns, round 5)
 }
 
 // ---- NW, a chunk whose pairs are mostly of one shape: both kinds of waves in one grid (p.pair_list: modal pairs, then the rest)
@@ -1649,13 +1576,5 @@ hipError_t sa_launch_fill_nw_dirs_mixed(const SaFillParams &p, uint32_t max_len_
   if (n_rest) sa_record_launch(SEQALIGN_K_FILL_NW_DIRS, n_rest);
   // (blocked direction bytes are decided by the row's width -- host -- and by LANES x CPL <= 512 -- kernel: a forced wider CPL must not split them)
   const uint32_t need = sa::columns_per_lane(max_len_a + 1, sa_dirs_blocked_shape(max_len_a) ? std::min<uint32_t>(p.tune_cpl, 8u) : p.tune_cpl);   // (of the widest pair: the packed waves take it too)
-  if (need <= 1) return sa::launch_nw_dirs_mixed_cpl<1, 512>(p, dirs, n_modal, n_rest, stream);
-  if (need <= 2) return sa::launch_nw_dirs_mixed_cpl<2, 512>(p, dirs, n_modal, n_rest, stream);
-  if (need <= 3) return sa::launch_nw_dirs_mixed_cpl<3, 512>(p, dirs, n_modal, n_rest, stream);
-  if (need <= 4) return sa::launch_nw_dirs_mixed_cpl<4, 512>(p, dirs, n_modal, n_rest, stream);
-  if (need <= 5) return sa::launch_nw_dirs_mixed_cpl<5, 1024>(p, dirs, n_modal, n_rest, stream);
-  if (need <= 6) return sa::launch_nw_dirs_mixed_cpl<6, 1024>(p, dirs, n_modal, n_rest, stream);
-  if (need <= 8) return sa::launch_nw_dirs_mixed_cpl<8, 1024>(p, dirs, n_modal, n_rest, stream);
-  if (need <= 12) return sa::launch_nw_dirs_mixed_cpl<12, 1024>(p, dirs, n_modal, n_rest, stream);
-  return sa::launch_nw_dirs_mixed_cpl<16, 2048>(p, dirs, n_modal, n_rest, stream);
+  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return sa::launch_nw_dirs_mixed_cpl<cpl()>(p, dirs, n_modal, n_rest, stream); });   // (12, 16: rows of 513 .. 1 024 columns, round 5)
 }

@@ -1,11 +1,42 @@
 // sa_fill_nw_dirs_x1.hpp -- one wave's work of fill_nw_dirs_kernel (sa_fill_dirs.hip): the directions-only Needleman-Wunsch
 // fill of ONE pair.  A function of its own so that the mixed launch of sa_fill_dirs_x2.hip (pairs of the chunk's modal shape
 // two per wave, the others one per wave, in ONE grid) can call it beside the packed body.
+// In front of it, the host side that the launchers of both files share: the ring size per rung and the dispatch by kernel form.
 #pragma once
 
 #include "sa_rowsweep.hpp"
 
 namespace sa {
+
+// ---- the launch side that the direction fills share (sa_fill_dirs.hip, sa_fill_dirs_x2.hip)
+// Bytes of LDS ring per pair, by the rung of the columns-per-lane ladder: the ring holds the row that is being written and the
+// 256-byte block on its way out.
+constexpr int dirs_ring(int cpl) { return cpl <= 4 ? 512 : cpl <= 12 ? 1024 : 2048; }
+// ... of the NW / best-hit fills: that ring for row-major bytes, or -- blocked direction bytes (sa_kernels.h), rows of up to 512
+// columns -- one block row of lanes x cpl columns (8 rows) where that is more
+constexpr int dirs_blocked_ring(int lanes, int cpl, int ring) {
+  return (SA_DIRS_BLOCKED != 0 && lanes * cpl <= 512 && lanes * cpl * 8 > ring) ? lanes * cpl * 8 : ring;
+}
+// the table an SA_SUBST_LDS kernel of the one-pair fills stages behind its rings: K x K int32 in whole 16-byte units
+inline size_t dirs_x1_table_bytes(const SaFillParams &p) { return (((size_t)p.K * p.K + 3u) & ~(size_t)3u) * sizeof(int32_t); }
+// The kernel form of a direction fill: launch(std::integral_constant<int, SUBST>{}, std::bool_constant<LOCAL>{}, tbl), tbl =
+// table_bytes for an SA_SUBST_LDS kernel and 0 otherwise (the applicable-predicates admit no table beyond SA_LDS_TABLE_MAX_K);
+// LOCAL = p.dirs_local, the byte's local form for the tile walkers (sa_kernels.h).
+template <class F>
+void launch_by_dirs_form(const SaFillParams &p, size_t table_bytes, F &&launch) {
+  using std::bool_constant;
+  using std::integral_constant;
+  if (p.K <= 1 && p.dirs_local) launch(integral_constant<int, SA_SUBST_SIMPLE>{}, bool_constant<true>{}, (size_t)0);
+  else if (p.K <= 1) launch(integral_constant<int, SA_SUBST_SIMPLE>{}, bool_constant<false>{}, (size_t)0);
+  else if (p.dirs_local) launch(integral_constant<int, SA_SUBST_LDS>{}, bool_constant<true>{}, table_bytes);
+  else launch(integral_constant<int, SA_SUBST_LDS>{}, bool_constant<false>{}, table_bytes);
+}
+// the multi-hit fills have one form of the byte: launch(std::integral_constant<int, SUBST>{}, tbl)
+template <class F>
+void launch_by_dirs_subst(const SaFillParams &p, size_t table_bytes, F &&launch) {
+  if (p.K <= 1) launch(std::integral_constant<int, SA_SUBST_SIMPLE>{}, (size_t)0);
+  else launch(std::integral_constant<int, SA_SUBST_LDS>{}, table_bytes);
+}
 
 // LOCAL: the byte in its local form (sa_kernels.h: SA_LD_*) -- this cell's own five comparisons, for the tile walkers.
 template <int CPL, int SUBST, int R, bool LOCAL = false>

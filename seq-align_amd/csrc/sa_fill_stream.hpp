@@ -401,16 +401,11 @@ static hipError_t launch_stream_mode(const SaFillParams &p, uint32_t max_len_a, 
   if (need <= 8) return launch_cpl_mode<8, 2048, 256, MODE, 2>(p, stream);
   return hipErrorInvalidValue;
 #else
-  if (need <= 1) return launch_cpl_mode<1, 512, 256, MODE>(p, stream);
-  if (need <= 2) return launch_cpl_mode<2, 512, 256, MODE>(p, stream);
-  if (need <= 3) return launch_cpl_mode<3, 512, 256, MODE>(p, stream);
-  if (need <= 4) return launch_cpl_mode<4, 512, 256, MODE>(p, stream);
-  if (need <= 5) return launch_cpl_mode<5, 1024, 256, MODE>(p, stream);
-  if (need <= 6) return launch_cpl_mode<6, 1024, 256, MODE>(p, stream);
-  if (need <= 8) return launch_cpl_mode<8, 1024, 256, MODE>(p, stream);
-  // 513..1023 columns: 12 / 16 columns per lane, 24 KiB of rings per wave -> 2 pairs per workgroup
-  if (need <= 12) return launch_cpl_mode<12, 2048, 256, MODE, 2>(p, stream);
-  return launch_cpl_mode<16, 2048, 256, MODE, 2>(p, stream);
+  // up to 512 columns: four pairs per workgroup; 513..1023 columns: 12 / 16 columns per lane, 24 KiB of rings per wave -> 2 pairs per workgroup
+  return launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) {
+    constexpr int R = cpl() <= 4 ? 512 : cpl() <= 8 ? 1024 : 2048;   // ints per ring
+    return launch_cpl_mode<cpl(), R, 256, MODE, (cpl() <= 8 ? kWavesPerBlock : 2)>(p, stream);
+  });
 #endif
 }
 

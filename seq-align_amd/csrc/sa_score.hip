@@ -215,15 +215,7 @@ static hipError_t launch_rows_cpl(const P &p, hipStream_t stream) {
 template <bool SW, bool CROSS = false, class P>
 static hipError_t launch_rows(const P &p, uint32_t max_len_a, hipStream_t stream) {
   const uint32_t need = columns_per_lane(max_len_a);
-  if (need <= 1) return launch_rows_cpl<1, SW, CROSS>(p, stream);
-  if (need <= 2) return launch_rows_cpl<2, SW, CROSS>(p, stream);
-  if (need <= 3) return launch_rows_cpl<3, SW, CROSS>(p, stream);
-  if (need <= 4) return launch_rows_cpl<4, SW, CROSS>(p, stream);
-  if (need <= 5) return launch_rows_cpl<5, SW, CROSS>(p, stream);
-  if (need <= 6) return launch_rows_cpl<6, SW, CROSS>(p, stream);
-  if (need <= 8) return launch_rows_cpl<8, SW, CROSS>(p, stream);
-  if (need <= 12) return launch_rows_cpl<12, SW, CROSS>(p, stream);
-  return launch_rows_cpl<16, SW, CROSS>(p, stream);
+  return launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return launch_rows_cpl<cpl(), SW, CROSS>(p, stream); });
 }
 
 template <bool SW>

@@ -1182,15 +1182,11 @@ hipError_t sa_launch_sw_sweep(const SaSweepParams &p, hipStream_t stream) {
     if (need > 16 || p.strip_progress) return hipErrorInvalidValue;
     if (need > 8 && !(p.tune_ev && p.layout.row_bits + p.layout.col_bits + p.layout.score_bits + 2 <= 64)) return hipErrorInvalidValue;
     sa_record_launch(SEQALIGN_K_SWEEP_DIRS, p.n_pairs);
-    if (need <= 2) sa::launch_sweep_dirs<2>(p, stream);
-    else if (need <= 3) sa::launch_sweep_dirs<3>(p, stream);
-    else if (need <= 4) sa::launch_sweep_dirs<4>(p, stream);
-    else if (need <= 5) sa::launch_sweep_dirs<5>(p, stream);
-    else if (need <= 6) sa::launch_sweep_dirs<6>(p, stream);
-    else if (need <= 8) sa::launch_sweep_dirs<8>(p, stream);
-    else if (need <= 12) sa::launch_sweep_dirs_wide<12>(p, stream);   // (rows of 513 .. 1 024 columns: the ev form only)
-    else sa::launch_sweep_dirs_wide<16>(p, stream);
-    return hipGetLastError();
+    return sa::launch_by_cpl<2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) {
+      if constexpr (cpl() <= 8) sa::launch_sweep_dirs<cpl()>(p, stream);
+      else sa::launch_sweep_dirs_wide<cpl()>(p, stream);   // (rows of 513 .. 1 024 columns: the ev form only)
+      return hipGetLastError();
+    });
   }
   // Up to 512 columns a segment holds the whole row and the winners stay in registers (short sequences: the walks
   // spread over most of the row anyway).  Beyond that: many pairs -- one wave per pair, segments of 256 columns that
@@ -1209,12 +1205,10 @@ hipError_t sa_launch_sw_sweep(const SaSweepParams &p, hipStream_t stream) {
     hipLaunchKernelGGL(sa::sw_order_hits_kernel, dim3(p.n_pairs), dim3(sa::kWave), 0, stream, p);
   } else if (!forced && need <= 8) {
     // (one column per lane is not instantiated: no pair is that narrow in practice)
-    if (need <= 2) sa::launch_sweep<2, sa::SA_ROWS_REG>(p, stream);
-    else if (need <= 3) sa::launch_sweep<3, sa::SA_ROWS_REG>(p, stream);
-    else if (need <= 4) sa::launch_sweep<4, sa::SA_ROWS_REG>(p, stream);
-    else if (need <= 5) sa::launch_sweep<5, sa::SA_ROWS_REG>(p, stream);
-    else if (need <= 6) sa::launch_sweep<6, sa::SA_ROWS_REG>(p, stream);
-    else sa::launch_sweep<8, sa::SA_ROWS_REG>(p, stream);
+    return sa::launch_by_cpl<2, 3, 4, 5, 6, 8>(need, [&](auto cpl) {
+      sa::launch_sweep<cpl(), sa::SA_ROWS_REG>(p, stream);
+      return hipGetLastError();
+    });
   } else {
     const int cpl = forced ? forced : 4;
     if (!p.lds_columns) return hipErrorInvalidValue;
