@@ -1,0 +1,223 @@
+#!/usr/bin/env python3
+"""Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, *_score_cross, *_score_search,
+*_align_long and the banded NW calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
+
+    python seq-align_amd/tools/fuzz_calls.py --seconds 300
+
+tests/test_gpu_soak_calls.py runs a seeded slice of it (run(seconds, seed, max_trials)) under the `gpu` marker.
+"""
+import argparse
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[2]
+sys.path.insert(0, str(ROOT / "seq-align_amd" / "python"))
+sys.path.insert(0, str(ROOT / "tests"))
+sys.path.insert(0, str(ROOT))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402,F401
+
+import bandlib as BL  # noqa: E402
+import orclib as O  # noqa: E402
+import seqalign_amd as S  # noqa: E402
+from seqalign_amd import workloads as W  # noqa: E402
+
+
+def best_cell(M, la, lb):
+    """(score, end_a, end_b) of the SW score calls from the oracle's match_scores: score desc, column asc, row asc."""
+    Mr = np.asarray(M, np.int64).reshape(lb + 1, la + 1)
+    best = int(Mr.max())
+    if best <= 0:
+        return 0, 0, 0
+    rows, cols = np.nonzero(Mr == best)
+    k = np.lexsort((rows, cols))[0]
+    return best, int(cols[k]), int(rows[k])
+
+
+def top_k(score, end_a, end_b, k, min_score):
+    """The search calls' contract on dense matrices: per query (targets, scores, end_a, end_b), score desc then target asc."""
+    out = []
+    for row, ea, eb in zip(score, end_a, end_b):
+        idx = np.nonzero(row.astype(np.int64) >= min_score)[0]
+        order = idx[np.lexsort((idx, -row[idx].astype(np.int64)))][:k]
+        out.append((order, row[order], ea[order], eb[order]))
+    return out
+
+
+def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None):
+    """Fuzz until `seconds` have passed or `max_trials` scorings were drawn; SystemExit(1) on the first mismatch, with the
+    failing case printed.  Options it sets (long_block_rows) are put back before it returns or raises."""
+    rng = W.Rng(seed)
+    ctx = ctx or S.Context(0)
+    t_end = time.time() + seconds
+    n = {"trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0}
+
+    def rand(count, alpha=b"ACGT"):
+        return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
+
+    def fail(what, spec, *details):
+        print(f"{what} MISMATCH", spec, *details, flush=True)
+        raise SystemExit(1)
+
+    while time.time() < t_end and n["trials"] < max_trials:
+        v = rng.below(1 << 20, 16).astype(int)
+        flags = [int(v[0] >> k) & 1 for k in range(5)]
+        if v[15] % 5 < 3:
+            flags = [0, 0, 0, 0, 0]
+        match, mismatch = int(1 + v[1] % 4), -int(v[2] % 5)
+        go, ge = -int(v[3] % 8), -int(v[4] % 3)
+        if flags[2] and flags[3]:
+            mismatch = min(mismatch, go + ge)
+        case = int(v[5] & 1)
+        spec = {"init": [match, mismatch, go, ge, *flags, case], "wildcards": [["N", int(v[6] % 3) - 1]] if v[6] & 1 else []}
+        if n["trials"] % 3 == 2:      # mutations are stored as given (no case folding): in the case the lookup will ask for
+            x, y = ("A", "C") if case else ("a", "c")
+            spec["mutations"] = [[x, y, -int(1 + v[7] % 3)], [y, x, int(v[8] % 3)]]
+        sc = S.make_scoring(spec)
+        osc = O.Scoring.from_buffer_copy(bytes(sc))
+        nw_ok = min(osc.gap_open + osc.gap_extend, osc.gap_extend) >= -abs(osc.min_penalty)   # NW parity domain
+
+        pairs = []
+        wide = int(v[9] % 12) if n["trials"] % 2 else -1     # every second trial: one pair of more than 1 024 columns
+        for k in range(12):
+            kind = int(v[7] + k) % 3
+            la = int(2 + (v[8] * (k + 1)) % (260 if k % 4 else 900))
+            if k == wide:
+                la = int(1025 + v[10] % 600)
+            if kind == 0:
+                a, b = rand(la), rand(int(2 + (v[9] * (k + 3)) % 200))
+            elif kind == 1:
+                a = rand(la)
+                cut = int(v[10] % max(1, len(a)))
+                b = rand(int(v[11] % 30)) + a[cut:cut + 120] + rand(int(v[12] % 30))
+            else:
+                unit = rand(int(2 + v[13] % 7))
+                a, b = unit * int(2 + v[14] % 20), rand(3) + unit * int(2 + v[15] % 25)
+                if k == wide:
+                    a = unit * (la // len(unit) + 1)
+            if spec["wildcards"] and k % 5 == 0:
+                a = a[:len(a) // 2] + b"N" + a[len(a) // 2:]
+            if k % 4 == 1:                                    # some lower case: folded, or a mismatch when case_sensitive
+                b = b[:len(b) // 3] + b[len(b) // 3:2 * len(b) // 3].lower() + b[2 * len(b) // 3:]
+            pairs.append((a, b))
+        n["wide"] += sum(len(a) > 1024 for a, _ in pairs)
+        batch = W.from_pairs(pairs)
+        thr = int(1 + v[5] % (6 * match))
+
+        # ---- the oracle, once per pair and mode
+        fills = {}
+        for is_sw in ((0, 1) if nw_ok else (1,)):
+            for p, (a, b) in enumerate(pairs):
+                rc, M, A, B = O.oracle_fill(osc, a, b, is_sw)
+                if rc != 0:
+                    fail("ORACLE", spec, p, pairs[p])
+                fills[is_sw, p] = (M, A, B)
+
+        # ---- score only
+        if nw_ok:
+            got = ctx.nw_score(batch, sc)
+            for p in range(12):
+                M, A, B = fills[0, p]
+                if int(got[p]) != int(max(M[-1], A[-1], B[-1])):
+                    fail("NW SCORE", spec, p, pairs[p], int(got[p]))
+        s, ea, eb = ctx.sw_score(batch, sc)
+        for p, (a, b) in enumerate(pairs):
+            want = best_cell(fills[1, p][0], len(a), len(b))
+            if (int(s[p]), int(ea[p]), int(eb[p])) != want:
+                fail("SW SCORE", spec, p, pairs[p], (int(s[p]), int(ea[p]), int(eb[p])), want)
+        n["score"] += 12 * (1 + nw_ok)
+
+        # ---- score matrices and the search over them: 4 queries x 6 targets taken from the pairs
+        qi = [0, 3, 6, wide if wide >= 0 else 9]
+        ti = [1, 2, 5, 7, 10, 11]
+        queries, targets = [pairs[p][0] for p in qi], [pairs[p][1] for p in ti]
+        q, t = W.seqset_from(queries), W.seqset_from(targets)
+        k_top = (1, 3, 8)[int(v[11] % 3)]
+        for is_sw in ((0, 1) if nw_ok else (1,)):
+            dense = np.zeros((4, 6), np.int32), np.zeros((4, 6), np.uint32), np.zeros((4, 6), np.uint32)
+            for i, a in enumerate(queries):
+                for j, b in enumerate(targets):
+                    rc, M, A, B = O.oracle_fill(osc, a, b, is_sw)
+                    if rc != 0:
+                        fail("ORACLE", spec, (a, b))
+                    if is_sw:
+                        dense[0][i, j], dense[1][i, j], dense[2][i, j] = best_cell(M, len(a), len(b))
+                    else:
+                        dense[0][i, j] = max(M[-1], A[-1], B[-1])
+            if is_sw:
+                got = ctx.sw_score_cross(q, t, sc)
+            else:
+                got = (ctx.nw_score_cross(q, t, sc), dense[1], dense[2])
+            if not all(np.array_equal(g, w) for g, w in zip(got, dense)):
+                fail("SW CROSS" if is_sw else "NW CROSS", spec, queries, targets, [g.tolist() for g in got], [w.tolist() for w in dense])
+            n["cross"] += 24
+            min_score = int(np.median(dense[0][int(v[12] % 4)])) + int(v[13] % 3) - 1     # around one row's median
+            n_hits, hits = (ctx.sw_score_search if is_sw else ctx.nw_score_search)(q, t, sc, k_top, min_score=min_score)
+            for i, (tg, ws, wa, wb) in enumerate(top_k(*dense, k_top, min_score)):
+                h = hits[i, :int(n_hits[i])]
+                if not (int(n_hits[i]) == len(tg) and np.array_equal(h["target"], tg) and np.array_equal(h["score"], ws)
+                        and np.array_equal(h["end_a"], wa) and np.array_equal(h["end_b"], wb)):
+                    fail("SW SEARCH" if is_sw else "NW SEARCH", spec, "k", k_top, "min_score", min_score, "query", i, queries[i], targets,
+                         h.tolist(), (tg.tolist(), ws.tolist()))
+            n["search"] += 4
+
+        # ---- alignments of any length
+        rows = (1, 3, 17, 64, 0)[int(v[14] % 5)]
+        with ctx.options(long_block_rows=rows):
+            if nw_ok:
+                got = ctx.nw_align_long(batch, sc)
+                for p, (a, b) in enumerate(pairs):
+                    rc, s_, ra, rb = O.oracle_nw_traceback(osc, a, b, *fills[0, p])
+                    if rc != 0 or got[p] != (s_, ra, rb):
+                        fail("NW LONG", spec, "long_block_rows", rows, p, pairs[p], got[p], (s_, ra, rb))
+            got = ctx.sw_align_long(batch, sc, thr)
+            for p, (a, b) in enumerate(pairs):
+                rc, want = O.oracle_sw_hits(osc, a, b, *fills[1, p], thr, 1)
+                if rc != 0 or got[p] != want:
+                    fail("SW LONG", spec, "long_block_rows", rows, "thr", thr, p, pairs[p], got[p], want)
+        n["long"] += 12 * (1 + nw_ok)
+
+        # ---- banded NW: at most 4 pairs of at most 260 x 260, w in 0 .. 40 (the reference is Python: ~3e5 band cells a trial)
+        if nw_ok:
+            n["nw_trials"] += 1
+            small = [p for p in range(12) if max(len(pairs[p][0]), len(pairs[p][1])) <= 260][:4]
+            sub = [pairs[p] for p in small]
+            bands = [int((v[3] + 7 * p) % 41) for p in small]
+            both = [BL.expected_both(osc, a, b, w) for (a, b), w in zip(sub, bands)]
+            if sub:
+                got = ctx.nw_score_banded(W.from_pairs(sub), sc, bands)
+                if [int(x) for x in got] != [x[0] for x in both]:
+                    fail("BAND SCORE", spec, sub, bands, [int(x) for x in got], [x[0] for x in both])
+                none = [k for k, x in enumerate(both) if x[1] is None]
+                if none:            # no alignment inside the band: the call says so and names the lowest such pair
+                    try:
+                        ctx.nw_align_banded(W.from_pairs(sub), sc, bands)
+                        fail("BAND NONE", spec, sub, bands, none, "no error")
+                    except S.SeqAlignError as e:
+                        if e.code != S.E_TRACEBACK or f"pair {none[0]}:" not in str(e):
+                            fail("BAND NONE", spec, sub, bands, none, str(e))
+                    n["banded_none"] += len(none)
+                    keep = [k for k in range(len(sub)) if k not in none]
+                    sub, bands, both = [sub[k] for k in keep], [bands[k] for k in keep], [both[k] for k in keep]
+            if sub:
+                got = ctx.nw_align_banded(W.from_pairs(sub), sc, bands)
+                if got != [x[1] for x in both]:
+                    fail("BAND ALIGN", spec, sub, bands, got, [x[1] for x in both])
+            n["banded"] += len(sub)
+        n["trials"] += 1
+
+    print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
+          f"{n['score']} scores, {n['cross']} cross cells, {n['search']} searches, {n['long']} long alignments, {n['banded']} banded "
+          f"alignments (+ {n['banded_none']} with none in their band) identical to the oracle (seed {seed})", flush=True)
+    return n
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=120)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--trials", type=int, default=1 << 60)
+    args = ap.parse_args()
+    run(args.seconds, args.seed, args.trials)

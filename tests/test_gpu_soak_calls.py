@@ -1,0 +1,40 @@
+"""GPU tier: a seeded slice of seq-align_amd/tools/fuzz_calls.py, as test_gpu_soak.py runs one of fuzz_e2e.py.
+
+Random scorings (penalties, the five flags, case sensitivity, a wildcard, mutations that differ by direction) x random,
+related and tandem-repeat pairs, some wider than 1 024 columns: the score, cross, search, long and banded calls against the
+oracle and bandlib.  Bounded by trial count, so the cases are the same on every machine; the wall-clock cap is a backstop.
+A mismatch raises SystemExit(1) inside the tool with the failing case printed.
+"""
+import importlib.util
+from pathlib import Path
+
+import pytest
+
+import seqalign_amd as S
+
+pytestmark = pytest.mark.gpu
+
+TOOLS = Path(__file__).resolve().parent.parent / "seq-align_amd" / "tools"
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with S.Context(0) as c:
+        yield c
+
+
+@pytest.mark.parametrize("seed", [20261018, 11])
+def test_fuzz_calls_slice(ctx, seed):
+    spec = importlib.util.spec_from_file_location("soak_fuzz_calls", TOOLS / "fuzz_calls.py")
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    before = ctx.get_option("long_block_rows")
+    try:
+        r = fz.run(seconds=40.0, seed=seed, max_trials=40, ctx=ctx)
+    except SystemExit as e:
+        pytest.fail(f"fuzz_calls mismatch (seed {seed}); the failing case is in the captured output (exit {e.code})")
+    assert ctx.get_option("long_block_rows") == before
+    assert r["trials"] >= 15, r                    # 40 on a healthy machine; the wall-clock cap is a backstop only
+    for family in ("score", "cross", "search", "long", "banded", "nw_trials", "wide"):
+        assert r[family] > 0, (family, r)
+    assert r["score"] == 12 * (r["trials"] + r["nw_trials"]) == r["long"] and r["search"] == 4 * (r["trials"] + r["nw_trials"]), r
