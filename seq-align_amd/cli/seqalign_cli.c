@@ -434,12 +434,16 @@ static void align_sw(batch_t *bt)
   }
   hit_cap = (uint64_t)n * (cap ? cap : 1) + 16;
   if(hit_cap > bt->hit_cap) { bt->hit_cap = hit_cap + hit_cap / 4; free(bt->hits); bt->hits = malloc(bt->hit_cap * sizeof(*bt->hits)); if(!bt->hits) oom(); }
-  reserve_out(bt, str_cap + 16);
-  if(opt.cigar) {   /* (no CIGAR is longer than 2 x its columns: the strings' room holds it twice over, out_a and out_b are one allocation each) */
-    if(cap && g_nctx > 1) check(seqalign_sw_batch_cigar_multi(g_ctxs, g_nctx, &b, &scoring, bt->min_score, cap, opt.cigar, bt->hits, hit_cap, &bt->n_hits, bt->out_a, str_cap + 16), "seqalign_sw_batch_cigar_multi");
-    else if(cap) check(seqalign_sw_batch_cigar(g_ctxs[0], &b, &scoring, bt->min_score, cap, opt.cigar, bt->hits, hit_cap, &bt->n_hits, bt->out_a, str_cap + 16), "seqalign_sw_batch_cigar");
+  if(opt.cigar) {
+    /* a CIGAR can be longer than its hit's strings -- 1M1I1D per three columns, two bytes a column at worst -- so out_a alone gets twice
+     * the strings' room (out_a and out_b are separate allocations: the second is no spare room behind the first) */
+    const uint64_t cigar_cap = 2 * str_cap + 16;
+    reserve_out(bt, cigar_cap);
+    if(cap && g_nctx > 1) check(seqalign_sw_batch_cigar_multi(g_ctxs, g_nctx, &b, &scoring, bt->min_score, cap, opt.cigar, bt->hits, hit_cap, &bt->n_hits, bt->out_a, cigar_cap), "seqalign_sw_batch_cigar_multi");
+    else if(cap) check(seqalign_sw_batch_cigar(g_ctxs[0], &b, &scoring, bt->min_score, cap, opt.cigar, bt->hits, hit_cap, &bt->n_hits, bt->out_a, cigar_cap), "seqalign_sw_batch_cigar");
     return;
   }
+  reserve_out(bt, str_cap + 16);
   if(cap && g_nctx > 1) check(seqalign_sw_batch_multi(g_ctxs, g_nctx, &b, &scoring, bt->min_score, cap, bt->hits, hit_cap, &bt->n_hits, bt->out_a, bt->out_b, str_cap + 16), "seqalign_sw_batch_multi");
   else if(cap) check(seqalign_sw_batch(g_ctxs[0], &b, &scoring, bt->min_score, cap, bt->hits, hit_cap, &bt->n_hits, bt->out_a, bt->out_b, str_cap + 16), "seqalign_sw_batch");
 }

@@ -66,7 +66,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None):
         flags = [int(v[0] >> k) & 1 for k in range(5)]
         if v[15] % 5 < 3:
             flags = [0, 0, 0, 0, 0]
-        match, mismatch = int(1 + v[1] % 4), -int(v[2] % 5)
+        match, mismatch = int(1 + v[1] % 4), -int(v[2] % 13)     # (0 .. -12: below 2 (gap_open + gap_extend) in a good share of the draws -- insertion runs directly against deletion runs, tests/denselib.py)
         go, ge = -int(v[3] % 8), -int(v[4] % 3)
         if flags[2] and flags[3]:
             mismatch = min(mismatch, go + ge)

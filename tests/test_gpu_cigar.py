@@ -283,3 +283,31 @@ def test_cli_sw_cigar_lines(tmp_path):
                      for k, h in enumerate(hits)]
         assert lines == want, (extra, len(lines), len(want))
     assert any(int(l.split("\t")[1]) >= 16 for l in run_cli(SW_BIN, "--cigar", "--minscore", "6", "--file", str(fa)).splitlines())
+
+
+def test_cli_cigar_of_alternation_pairs(tmp_path):
+    """A file holding only alternation pairs, (xy)^75 against (xz)^75 (tests/denselib.py), under --match 5 --mismatch -10 --gapopen 0
+    --gapextend -1: the first pair's best hit has 223 columns and a 446-byte CIGAR, the others' 434 and more -- longer than the room
+    for the hit's two strings (len_a + len_b + 1 = 301), which is all seqalign_sw once gave the CIGAR call.  seqalign_nw on the same file: 1M1I1D per period, 450
+    bytes, through the second pass with worst-case slots."""
+    import denselib as D
+    pairs = [(b"AC" * 75, b"AG" * 75)] + [D.alternation(150, 150, k) for k in range(1, 12)]
+    fa = tmp_path / "alternation.fa"
+    fa.write_text("".join(f">a{p}\n{a.decode()}\n>b{p}\n{b.decode()}\n" for p, (a, b) in enumerate(pairs)))
+    numbers = ("--match", "5", "--mismatch", "-10", "--gapopen", "0", "--gapextend", "-1")
+    osc = D.oracle_scoring("swdense")
+    for flag, fmt in (("--cigar", M), ("--cigarx", EQX)):
+        lines = run_cli(SW_BIN, flag, "--maxhits", "1", *numbers, "--file", str(fa)).splitlines()
+        want = []
+        for p, (a, b) in enumerate(pairs):
+            rc, hits = O.oracle_sw(osc, a, b, W.default_minscore(5, len(a), len(b)), 1)
+            assert rc == 0 and len(hits) == 1 and D.count_id(hits[0]["a"], hits[0]["b"]) >= 8
+            want += [f"{p}\t{k}\t{h['score']}\t{h['pos_a']}\t{h['len_a']}\t{h['pos_b']}\t{h['len_b']}\t{py_cigar(h['a'], h['b'], fmt)}"
+                     for k, h in enumerate(hits)]
+        assert lines == want, (flag, lines[:1], want[:1])
+        assert len(want[0].split("\t")[-1]) == 446
+    lines = run_cli(NW_BIN, "--cigar", *numbers, "--file", str(fa)).splitlines()
+    for p, (a, b) in enumerate(pairs):
+        rc, s, ra, rb = O.oracle_nw(osc, a, b)
+        assert rc == 0 and lines[p] == f"{p}\ta{p}\tb{p}\t{s}\t{py_cigar(ra, rb, M)}", p
+    assert lines[0].endswith("\t" + "1M1I1D" * 75)
