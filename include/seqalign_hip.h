@@ -494,6 +494,7 @@ const char *seqalign_kernel_kind_name(int kind);
  * are counted in a second record of the same shape, indexed by SEQALIGN_KX_*.  The outermost entry point of a call clears
  * both records; a call that launches none of the kernels below leaves this one all zero. */
 enum {
+  /* (the banded SW calls are counted under these three as well: see "banded SW") */
   SEQALIGN_KX_BAND_SCORE = 0,      /* banded NW, score only (seqalign_nw_score_banded), one pair per wave (items: pairs) */
   SEQALIGN_KX_BAND_FILL,           /* banded NW, M / A / B of every band cell (seqalign_nw_align_banded)                  */
   SEQALIGN_KX_BAND_WALK,           /* ... the traceback over a chunk's bands, one lane per pair                           */
@@ -621,6 +622,50 @@ int seqalign_nw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
  * once, then the score call's launches run `repeats` times between HIP events; ms_each[r] = kernel time of repeat r. */
 int seqalign_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                 const uint32_t *band, int repeats, float *ms_each);
+/* ---- banded SW: the best local hit within a range of diagonals per pair -------------- */
+/* Local alignment restricted to the diagonals a seed or an index points at.  Pair p gets two signed bounds diag_lo[p] <=
+ * diag_hi[p]; cell (i, j) (column i of seq_a, row j of seq_b) is IN THE BAND  iff  diag_lo[p] <= i - j <= diag_hi[p].  The
+ * bounds are the caller's and may lie anywhere, wholly left or right of the main diagonal included: the band is NOT anchored
+ * to the two corners as the NW band is.  They are clipped to [-len_b, len_a] (d_lo = max(diag_lo, -len_b), d_hi = min(diag_hi,
+ * len_a)); width = d_hi - d_lo + 1 is the clipped count of diagonals.  A band that is empty after clipping (d_lo > d_hi) is
+ * legal: score 0, no hit.
+ *   The banded SW matrices are the reference's recurrence (src/alignment.c:28-168, is_sw = 1) in which every cell outside the
+ *   band holds the SW floor, 0, in all three matrices (the SW borders are 0 too: for SW "border" and "outside the band" read the
+ *   same).  The banded best hit is smith_waterman.c's first hit over those matrices: the best match_scores cell in hit order
+ *   (score descending, column ascending, index ascending), walked by alignment_reverse_move until the score is 0.  Nothing is
+ *   rounded to a kernel's frame, nothing is adaptive.
+ * What follows: a band that covers every inner cell gives the unbanded matrices; banded values are <= the unbanded ones
+ * everywhere; when the unbanded best hit's walk visits band cells only, start and end cell included, the banded hit is the
+ * unbanded one field for field and byte for byte, otherwise its score is not above it.  With gap_open + gap_extend <= 0 and
+ * gap_extend <= 0 the banded hit's own walk never leaves the band; with a positive gap_extend it can (cells outside read 0).
+ *   seqalign_sw_score_banded   seqalign_sw_score_batch's results: score, end_a, end_b of the best band cell, 1-based; 0 and
+ *                              (0, 0) when no band cell is above 0
+ *   seqalign_sw_align_banded   seqalign_sw_align_long's results and capacities: at most one hit per pair, delivered iff its
+ *                              score is > 0 and >= min_score[p], hits in pair order; hit_cap or str_cap too small: the hits
+ *                              that fit are delivered, *n_hits counts them, SEQALIGN_E_NOMEM
+ *   SEQALIGN_E_ARG          NULL arguments, unreadable batch, a pair with diag_lo > diag_hi as given (pair named)
+ *   SEQALIGN_E_TOO_LARGE    a pair whose clipped width exceeds SEQALIGN_BAND_MAX_WIDTH (pair and width named), or len_a +
+ *                           len_b >= 2^31; like SEQALIGN_E_ARG found from lengths and bounds alone, before any device work
+ *   SEQALIGN_E_DOMAIN, SEQALIGN_E_NO_DEVICE   as the other SW calls
+ *   SEQALIGN_E_UNKNOWN_PAIR a character pair without a score INSIDE the band (lowest failing pair named; such a cell keeps 0
+ *                           in match_scores); the same characters outside the band raise nothing
+ *   SEQALIGN_E_NOMEM        a pair that does not fit the chunk budget alone; seqalign_last_error gives the bytes needed
+ * No 2^31-cell cap.  Chunks are cut by device bytes within the option chunk_bytes.  Per pair: the score call len_a + len_b +
+ * 80; the align call 12 rows width + 3 (len_a + len_b) + 128, rows = the rows that have inner band cells,
+ *     max(0, min(len_b, len_a - d_lo) - max(1, 1 - d_hi) + 1)      (0 when len_a = 0 or the band is empty)
+ * (M, A, B of those rows: row j holds diagonals d_lo .. d_hi).  32 bytes per pair and the strings come home.
+ * seqalign_ctx_last_call_info_ext: the second launch record's table is pinned, so these calls add no kind -- their launches
+ * are counted under band_score / band_fill + band_walk (one band_score or band_fill launch per width class of a chunk), whose
+ * names fit; which family a record belongs to is known from the call that was made. */
+int seqalign_sw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                             const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                             uint32_t *out_end_b);
+int seqalign_sw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                             const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score, seqalign_sw_hit_t *hits,
+                             uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b, uint64_t str_cap);
+/* Timing hook (tools/align_banded_sw_bench.py), the sibling of seqalign_band_score_time_ms for seqalign_sw_score_banded */
+int seqalign_sw_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                   const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

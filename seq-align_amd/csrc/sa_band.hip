@@ -31,7 +31,24 @@
 //   launch.  reverse_move_t reads through BandAccess: a cell outside the band is the floor in all three matrices, as the
 //   contract says, so a walk that the floor's arithmetic lets out of the band (free end gaps: floor + 0 == floor) goes on
 //   exactly as the reference's would over the banded matrices.
-#include "sa_rowsweep.hpp"
+//
+// Banded SW (seqalign_sw_*_banded) is the same sweep, band_rows_kernel<.., SW = true> on SaBandSwParams, and a walk of its own
+// (band_sw_walk_kernel).  The band is the caller's -- any d_lo <= d_hi inside [-len_b, len_a] -- and every cell outside it,
+// like every border cell, holds 0 in all three matrices.  What differs from NW:
+//   Frame.  fc(j) = max(1, j + d_lo) as above, for any sign of d_lo: with d_lo >= 1 the frame moves from row 1 on, so row 0's
+//   frame starts at column d_lo; with d_hi < 0 the first row that has a band cell is 1 - d_hi and the sweep starts there, on
+//   the all-zero state (the frame still stands at column 1 then: d_lo <= d_hi < 0).  The last row swept is
+//   min(len_b, len_a - d_lo), the last that has one (sa_band_sw_rows).  Feed, entering positions and the cell above the
+//   right edge are the floor as in NW -- the SW floor, 0.
+//   Best cell.  BandBest keeps, per frame POSITION, the best match_scores value of the column that position holds and the
+//   first row that reached it; when the frame moves, the column that leaves through lane 0 is merged into a wave-uniform
+//   "retired" best (strict >: retired columns are lower than it, and they keep a tie) and the per-position bests shift with
+//   the frame.  The end pick is the retired best, then the live columns ascending: score desc, column asc, row asc.
+//   Fill form: M, A, B of rows j0 .. j1 only, row j holding diagonals d_lo .. d_hi: cell (i, j) at (j - j0) width + i - j -
+//   d_lo; no border cell is stored (BandSwAccess reads them, like the cells outside the band, as 0).  It reports the best
+//   cell itself, as the score form does.
+//   Walk: traceback_kernel's SW walk from the best cell until the score is 0, pos / len / length as it reports them.
+#include "sa_strips.hpp"   // wave_max_i32, wave_min_u64
 #include "sa_trace_common.hpp"
 
 namespace sa {
@@ -50,9 +67,54 @@ __device__ __forceinline__ void frame_shift(int (&a)[N], int enters) {
   a[N - 1] = wave_shl1(first, enters);
 }
 
-template <int CPL, int SUBST, bool GENERAL, bool FILL>
+__host__ __device__ __forceinline__ const SaBandParams &band_params(const SaBandParams &p) { return p; }
+__host__ __device__ __forceinline__ const SaBandParams &band_params(const SaBandSwParams &p) { return p.b; }
+
+// banded SW: the running best of match_scores per frame position, and of the columns that have left the frame
+template <int CPL>
+struct BandBest {
+  int s[CPL], r[CPL];                     // of the column each of my positions holds: best value, first row that reached it
+  int ret_s = 0, ret_col = 0, ret_row = 0;   // of the columns left of the frame (wave-uniform)
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) { s[c] = 0; r[c] = 0; }
+  }
+  // the frame moves off column `col`: it retires (a tie stays with the retired, lower columns), the others shift with the frame
+  __device__ __forceinline__ void retire(int col) {
+    const int s0 = read_lane(s[0], 0), r0 = read_lane(r[0], 0);
+    if (s0 > ret_s) { ret_s = s0; ret_col = col; ret_row = r0; }
+    frame_shift(s, 0);
+    frame_shift(r, 0);
+  }
+  __device__ __forceinline__ void row(const int (&mv)[CPL], uint32_t j, int ncol) {
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const bool up = c < ncol && mv[c] > s[c];   // strict: the first (lowest) row keeps a tie
+      s[c] = up ? mv[c] : s[c];
+      r[c] = up ? (int)j : r[c];
+    }
+  }
+  // the pair's best in hit order; my position c holds column col0 + c.  score 0: key ~0
+  __device__ __forceinline__ void reduce(int col0, int &score, unsigned long long &key) const {
+    int b = 0;
+    unsigned long long kb = ~0ull;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)   // c ascending, strict >: the lowest column wins a tie
+      if (s[c] > b) { b = s[c]; kb = ((unsigned long long)(uint32_t)(col0 + c) << 32) | (uint32_t)r[c]; }
+    score = wave_max_i32(b);
+    key = wave_min_u64(b == score && score > 0 ? kb : ~0ull);
+    if (ret_s >= score && ret_s > 0) {   // a tie goes to the lower column: a retired one
+      score = ret_s;
+      key = ((unsigned long long)(uint32_t)ret_col << 32) | (uint32_t)ret_row;
+    }
+  }
+};
+
+// The sweep of both band families.  SW = false: banded NW.  SW = true: banded SW (header).
+template <int CPL, int SUBST, bool GENERAL, bool FILL, bool SW = false>
 __global__ void __launch_bounds__(kWave *kWavesPerBlock)
-band_rows_kernel(const SaBandParams bp) {
+band_rows_kernel(const std::conditional_t<SW, SaBandSwParams, SaBandParams> kp) {
+  const SaBandParams &bp = band_params(kp);
   const SaFillParams &p = bp.f;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
   const int32_t *table = stage_table<SUBST>(p, lds_table);
@@ -71,10 +133,17 @@ band_rows_kernel(const SaBandParams bp) {
   const uint32_t W = la + 1;
 
   const SweepConsts k(p, table);
-  const Border bd{p.floor, p.gap_open, p.ext, false, (p.flags & SA_F_NO_START_GAP) != 0};
+  const Border bd{p.floor, p.gap_open, p.ext, SW, (p.flags & SA_F_NO_START_GAP) != 0};
+
+  // SW: the first row that has a band cell
+  const uint32_t first = (SW && d_hi < 0) ? (uint32_t)(1 - d_hi) : 1u;
 
   int32_t *Mg = nullptr, *Ag = nullptr, *Bg = nullptr;   // cell (i, j) at [j (width - 1) + i]
-  if constexpr (FILL) {
+  if constexpr (FILL && SW) {
+    const long long mo = (long long)p.mat_off[pair] - d_lo - (long long)first * width;   // row `first` is the first stored
+    Mg = p.M + mo; Ag = p.A + mo; Bg = p.B + mo;
+  }
+  if constexpr (FILL && !SW) {
     const uint64_t mo = p.mat_off[pair];
     Mg = p.M + mo - d_lo; Ag = p.A + mo - d_lo; Bg = p.B + mo - d_lo;
     // the band's border cells (reference alignment.c:46-81)
@@ -95,13 +164,17 @@ band_rows_kernel(const SaBandParams bp) {
 
   RowSweep<CPL, SUBST, GENERAL> sw;
   const int g0 = lane * CPL;   // my first frame position
-  sw.start_strip(p, k, bd, sa_, la, 0, (uint32_t)g0, lane);
+  // SW: the frame of the row before the first stands at column max(1, d_lo), over zeros
+  sw.start_strip(p, k, bd, sa_, la, 0, (uint32_t)(SW ? max(1, d_lo) - 1 + g0 : g0), lane);
   __builtin_amdgcn_s_waitcnt(kWaitVm0);   // seq_a codes landed (see RowFeed::load)
+  BandBest<SW ? CPL : 1> best;
+  if constexpr (SW) best.init();
 
-  const uint32_t rows = la ? lb : 0;   // len_a == 0: the border column is the whole matrix
+  // len_a == 0: the border column is the whole matrix.  SW: rows past the band's last cell are not swept
+  const uint32_t rows = la ? (SW ? min(lb, (uint32_t)((int)la - d_lo)) : lb) : 0;
   int code_b = 0, code_in = 0;
-  for (uint32_t j = 1; j <= rows; ++j) {
-    const int q = (j - 1) & (kWave - 1);
+  for (uint32_t j = first; j <= rows; ++j) {
+    const int q = (j - first) & (kWave - 1);
     if (q == 0) {   // every 64 rows: lane t fetches seq_b's code for row j + t and the code of the column that enters on it
       const uint32_t r = j + lane;
       code_b = code_in = 0;
@@ -122,6 +195,7 @@ band_rows_kernel(const SaBandParams bp) {
       if constexpr (GENERAL) frame_shift(sw.Y, k.floor_);
       frame_shift(sw.fa, cin & 0xff);
       if constexpr (SUBST != SA_SUBST_SIMPLE) frame_shift(sw.arow, (cin >> 8) * k.K);
+      if constexpr (SW) best.retire(fc - 1);
     }
     // the cell above the band's right edge is outside the band: the floor (header)
     const int ge = (int)j + d_hi - fc - g0;
@@ -139,6 +213,7 @@ band_rows_kernel(const SaBandParams bp) {
     const int feedZ = (jd <= 0) ? max(k.floor_, bd.edge_gap(j)) : k.floor_, feedB = k.floor_;
     int mv[CPL], av[CPL], bv[CPL];
     sw.row(k, j, lb, la, W, lane, col0, ncol, read_lane(code_b, q), feedZ, feedB, mv, av, bv);
+    if constexpr (SW) best.row(mv, j, ncol);
     if constexpr (FILL) {
       const uint64_t off = (uint64_t)j * (uint32_t)(width - 1) + col0 + 1;
       if (ncol == CPL) {
@@ -154,7 +229,17 @@ band_rows_kernel(const SaBandParams bp) {
   }
 
   const unsigned long long err = sw.reduce_err();
-  if constexpr (!FILL) {
+  if constexpr (SW) {
+    int score;
+    unsigned long long key;
+    best.reduce(max(1, (int)rows + d_lo) + g0, score, key);   // the last row's frame (no row swept: every best is 0)
+    if (lane == 0) {
+      bp.score[pair] = score;
+      kp.end_a[pair] = score > 0 ? (uint32_t)(key >> 32) : 0u;
+      kp.end_b[pair] = score > 0 ? (uint32_t)key : 0u;
+    }
+  }
+  if constexpr (!FILL && !SW) {
     if (la == 0) {   // cell (0, len_b) of the border column
       if (lane == 0) bp.score[pair] = lb == 0 ? 0 : max(k.floor_, bd.edge_gap(lb));
     } else {
@@ -233,20 +318,80 @@ __global__ void __launch_bounds__(kWave) band_walk_kernel(const SaBandParams bp)
   *reinterpret_cast<uint4 *>(bp.meta4 + 4ull * w) = make_uint4(head, la + lb - head, (uint32_t)end_score, err);
 }
 
-template <int CPL, bool FILL>
-static hipError_t launch_band_cpl(const SaBandParams &p, hipStream_t stream) {
-  const dim3 grid((p.f.n_pairs + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
-  launch_by_scoring(p.f, [&](auto subst, auto general, uint32_t table_ints) {
-    hipLaunchKernelGGL((band_rows_kernel<CPL, subst(), general(), FILL>), grid, block, table_ints * sizeof(int32_t), stream, p);
+// banded SW: border cells and cells outside the band are 0; band cell (x, y) of rows j0 .. at [(y - j0) width + x - y - d_lo]
+struct BandSwAccess {
+  const uint8_t *seq_a, *seq_b;
+  const uint16_t *code;
+  const int32_t *M, *A, *B;   // cell (x, y) at [y pitch + x]
+  uint64_t pitch;             // width - 1
+  long long d_lo, d_hi;
+  __device__ __forceinline__ int code_a(uint32_t i) const { return code[seq_a[i]]; }
+  __device__ __forceinline__ int code_b(uint32_t j) const { return code[seq_b[j]]; }
+  __device__ __forceinline__ void cell(uint32_t x, uint32_t y, int &m, int &a, int &b) const {
+    const long long d = (long long)x - (long long)y;
+    m = a = b = 0;
+    if (x > 0 && y > 0 && d >= d_lo && d <= d_hi) {
+      const uint64_t at = (uint64_t)y * pitch + x;
+      m = M[at]; a = A[at]; b = B[at];
+    }
+  }
+};
+
+// traceback_kernel's SW walk from the best cell the fill form reported, one lane per pair.  meta8[8w..]: score, status, pos_a,
+// pos_b, end_a, end_b, length, head (the strings: [head, len_a + len_b) of the pair's slot).  Score 0: no walk, length 0.
+__global__ void __launch_bounds__(kWave) band_sw_walk_kernel(const SaBandSwParams sp) {
+  const SaBandParams &bp = sp.b;
+  const SaFillParams &p = bp.f;
+  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= p.n_pairs) return;
+  const uint32_t la = p.len_a[w], lb = p.len_b[w];
+  const uint8_t *__restrict__ sa_ = p.arena + p.off_a[w];
+  const uint8_t *__restrict__ sb_ = p.arena + p.off_b[w];
+  const int d_lo = bp.d_lo[w];
+  const uint32_t width = bp.width[w];
+  const long long d_hi = (long long)d_lo + width - 1;
+  const long long first = d_hi < 0 ? 1 - d_hi : 1;
+  const long long mo = (long long)p.mat_off[w] - d_lo - first * width;
+  const BandSwAccess acc{sa_, sb_, p.code, p.M + mo, p.A + mo, p.B + mo, (uint64_t)(width - 1), (long long)d_lo, d_hi};
+  const TraceConsts k{p.code, p.table, (int)p.K, p.open1, p.ext, p.gen_eq, p.gen_ne,
+                      (p.flags & SA_F_NO_START_GAP) != 0, (p.flags & SA_F_NO_END_GAP) != 0,
+                      (p.flags & SA_F_NO_GAPS_A) != 0, (p.flags & SA_F_NO_GAPS_B) != 0};
+  char *oa = bp.out_a + bp.str_off[w];
+  char *ob = bp.out_b + bp.str_off[w];
+
+  const int end_score = bp.score[w];
+  const uint32_t end_x = sp.end_a[w], end_y = sp.end_b[w];
+  uint32_t x = end_x, y = end_y, head = la + lb, err = 0;
+  int matrix = MAT_MATCH, score = end_score;
+  // SEQALIGN_E_UNKNOWN_PAIR first, as band_walk_kernel: the pair's answer does not depend on where the cell lies
+  if (p.status[w] != ~0ull) err = SEQALIGN_E_UNKNOWN_PAIR;
+  while (!err && score > 0) {
+    if (head == 0) { err = SEQALIGN_E_TRACEBACK; break; }   // (cannot happen: every step lowers x or y)
+    --head;
+    oa[head] = (matrix == MAT_GAP_A) ? '-' : (char)sa_[x - 1];
+    ob[head] = (matrix == MAT_GAP_B) ? '-' : (char)sb_[y - 1];
+    err = reverse_move_t(acc, k, la, lb, x, y, matrix, score);
+  }
+  uint4 *out = reinterpret_cast<uint4 *>(sp.meta8 + 8ull * w);
+  out[0] = make_uint4((uint32_t)end_score, err, x, y);   // smith_waterman.c:249-255
+  out[1] = make_uint4(end_x, end_y, la + lb - head, head);
+}
+
+template <int CPL, bool FILL, bool SW, class P>
+static hipError_t launch_band_cpl(const P &p, hipStream_t stream) {
+  const SaFillParams &f = band_params(p).f;
+  const dim3 grid((f.n_pairs + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
+  launch_by_scoring(f, [&](auto subst, auto general, uint32_t table_ints) {
+    hipLaunchKernelGGL((band_rows_kernel<CPL, subst(), general(), FILL, SW>), grid, block, table_ints * sizeof(int32_t), stream, p);
   });
   return hipGetLastError();
 }
 
 // the columns per lane of the widest band (sa_score_row_class's steps)
-template <bool FILL>
-static hipError_t launch_band(const SaBandParams &p, uint32_t max_width, hipStream_t stream) {
+template <bool FILL, bool SW = false, class P>
+static hipError_t launch_band(const P &p, uint32_t max_width, hipStream_t stream) {
   const uint32_t need = columns_per_lane(max_width);
-  return launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return launch_band_cpl<cpl(), FILL>(p, stream); });
+  return launch_by_cpl<1, 2, 3, 4, 5, 6, 8, 12, 16>(need, [&](auto cpl) { return launch_band_cpl<cpl(), FILL, SW>(p, stream); });
 }
 
 }  // namespace sa
@@ -269,5 +414,27 @@ hipError_t sa_launch_band_walk(const SaBandParams &p, hipStream_t stream) {
   if (p.f.n_pairs == 0) return hipSuccess;
   sa_record_launch_ext(SEQALIGN_KX_BAND_WALK, p.f.n_pairs);
   hipLaunchKernelGGL(sa::band_walk_kernel, dim3((p.f.n_pairs + sa::kWave - 1) / sa::kWave), dim3(sa::kWave), 0, stream, p);
+  return hipGetLastError();
+}
+
+// banded SW: counted under the same three kinds (include/seqalign_hip.h: the second launch record is pinned)
+hipError_t sa_launch_band_sw_score(const SaBandSwParams &p, uint32_t max_width, hipStream_t stream) {
+  if (p.b.f.n_pairs == 0) return hipSuccess;
+  if (max_width == 0 || max_width > SA_BAND_MAX_WIDTH) return hipErrorInvalidValue;
+  sa_record_launch_ext(SEQALIGN_KX_BAND_SCORE, p.b.f.n_pairs);
+  return sa::launch_band<false, true>(p, max_width, stream);
+}
+
+hipError_t sa_launch_band_sw_fill(const SaBandSwParams &p, uint32_t max_width, hipStream_t stream) {
+  if (p.b.f.n_pairs == 0) return hipSuccess;
+  if (max_width == 0 || max_width > SA_BAND_MAX_WIDTH) return hipErrorInvalidValue;
+  sa_record_launch_ext(SEQALIGN_KX_BAND_FILL, p.b.f.n_pairs);
+  return sa::launch_band<true, true>(p, max_width, stream);
+}
+
+hipError_t sa_launch_band_sw_walk(const SaBandSwParams &p, hipStream_t stream) {
+  if (p.b.f.n_pairs == 0) return hipSuccess;
+  sa_record_launch_ext(SEQALIGN_KX_BAND_WALK, p.b.f.n_pairs);
+  hipLaunchKernelGGL(sa::band_sw_walk_kernel, dim3((p.b.f.n_pairs + sa::kWave - 1) / sa::kWave), dim3(sa::kWave), 0, stream, p);
   return hipGetLastError();
 }

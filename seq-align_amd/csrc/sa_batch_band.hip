@@ -1,5 +1,6 @@
-// sa_batch_band.hip -- banded NW over HOST batches: seqalign_nw_score_banded, seqalign_nw_align_banded and the timing hook
-// seqalign_band_score_time_ms (the kernels: sa_band.hip; the contract: include/seqalign_hip.h).
+// sa_batch_band.hip -- the banded calls over HOST batches: seqalign_nw_score_banded, seqalign_nw_align_banded and the timing
+// hook seqalign_band_score_time_ms; seqalign_sw_score_banded, seqalign_sw_align_banded and seqalign_sw_band_score_time_ms (the
+// kernels: sa_band.hip; the contracts: include/seqalign_hip.h).
 //
 // Everything that can be refused from lengths and bands alone is refused before any device work: the band of every pair is
 // clamped to its matrix and a width over SEQALIGN_BAND_MAX_WIDTH is SEQALIGN_E_TOO_LARGE.  Then, per chunk: the pairs are put
@@ -10,6 +11,11 @@
 //
 // Chunks are cut by device BYTES (header: the bytes per pair); a pair that does not fit the budget alone is
 // SEQALIGN_E_NOMEM with the bytes named.
+//
+// Banded SW runs through the same chunk plan, layout and launch loop (BandChunkRun::sw).  Its band is the caller's, clipped;
+// the align call stores only the rows that have inner band cells (sa_band_sw_rows), the fill reports the best cell, the walk
+// brings home 32 bytes per pair (score, status, pos_a, pos_b, end_a, end_b, length, head) and the strings, and the host
+// delivers the hits that reach min_score in pair order under seqalign_sw_align_long's capacity rule.
 #include "sa_ctx.hpp"
 
 using namespace sa_host;
@@ -18,11 +24,14 @@ namespace {
 
 constexpr uint64_t kScorePairBytes = 64;   // descriptors (48: the align call's record, mat_off and str_off unused), status (8), score (4), slack
 constexpr uint64_t kAlignPairBytes = 96;   // descriptors (48), status (8), the walk's four words (16), slack
+constexpr uint64_t kSwScorePairBytes = 80;   // ... and end_a, end_b (8)
+constexpr uint64_t kSwAlignPairBytes = 128;  // descriptors (48), status (8), score and end cell (12), the walk's eight words (32), slack
 constexpr uint64_t kChunkMaxPairs = (uint64_t)1 << 24;
 
 struct Band {
   int32_t d_lo;
   uint32_t width;
+  uint64_t cells;   // of one matrix in the align call
 };
 
 Band band_of(uint32_t la, uint32_t lb, uint32_t w, uint64_t *width64) {
@@ -30,12 +39,36 @@ Band band_of(uint32_t la, uint32_t lb, uint32_t w, uint64_t *width64) {
   const int64_t d_lo = std::max<int64_t>(-(int64_t)lb, std::min<int64_t>(0, d) - (int64_t)w);
   const int64_t d_hi = std::min<int64_t>((int64_t)la, std::max<int64_t>(0, d) + (int64_t)w);
   *width64 = (uint64_t)(d_hi - d_lo + 1);
-  return Band{(int32_t)std::max<int64_t>(d_lo, INT32_MIN), (uint32_t)std::min<uint64_t>(*width64, 0xFFFFFFFFu)};
+  const uint32_t width = (uint32_t)std::min<uint64_t>(*width64, 0xFFFFFFFFu);
+  return Band{(int32_t)std::max<int64_t>(d_lo, INT32_MIN), width, ((uint64_t)lb + 1) * width};
 }
 
-uint64_t pair_bytes(uint32_t la, uint32_t lb, uint32_t width, bool align) {
+// banded SW: the caller's bounds clipped to [-len_b, len_a].  A band that is empty then is given to the kernels as the one
+// diagonal len_a, which has no inner cell: score 0, nothing stored
+Band sw_band_of(uint32_t la, uint32_t lb, int32_t lo, int32_t hi, uint64_t *width64) {
+  const int64_t d_lo = std::max<int64_t>(lo, -(int64_t)lb), d_hi = std::min<int64_t>(hi, (int64_t)la);
+  if (d_lo > d_hi) { *width64 = 0; return Band{(int32_t)la, 1, 0}; }
+  *width64 = (uint64_t)(d_hi - d_lo + 1);
+  int64_t j0, j1;
+  sa_band_sw_rows(la, lb, d_lo, d_hi, &j0, &j1);
+  return Band{(int32_t)d_lo, (uint32_t)std::min<uint64_t>(*width64, 0xFFFFFFFFu), j1 < j0 ? 0 : (uint64_t)(j1 - j0 + 1) * *width64};
+}
+
+uint64_t pair_bytes(uint32_t la, uint32_t lb, uint64_t cells, bool align, bool sw) {
   const uint64_t seq = (uint64_t)la + lb;
-  return align ? 12 * ((uint64_t)lb + 1) * width + 3 * seq + kAlignPairBytes : seq + kScorePairBytes;
+  if (sw) return align ? 12 * cells + 3 * seq + kSwAlignPairBytes : seq + kSwScorePairBytes;
+  return align ? 12 * cells + 3 * seq + kAlignPairBytes : seq + kScorePairBytes;
+}
+
+int too_wide(uint64_t p, uint64_t width) {
+  set_last_error("pair " + std::to_string(p) + ": a band of " + std::to_string(width) + " diagonals, at most " +
+                 std::to_string(SEQALIGN_BAND_MAX_WIDTH) + " are supported");
+  return SEQALIGN_E_TOO_LARGE;
+}
+
+int too_long(uint64_t p) {
+  set_last_error("pair " + std::to_string(p) + ": len_a + len_b is 2^31 or more");
+  return SEQALIGN_E_TOO_LARGE;
 }
 
 // argument checks and band geometry, before any device work
@@ -44,17 +77,28 @@ int check_band_batch(const seqalign_batch_t *b, const uint32_t *band, std::vecto
   geom.resize(b->n_pairs);
   for (uint64_t p = 0; p < b->n_pairs; ++p) {
     const uint32_t la = b->len_a[p], lb = b->len_b[p];
-    if ((uint64_t)la + lb >= ((uint64_t)1 << 31)) {
-      set_last_error("pair " + std::to_string(p) + ": len_a + len_b is 2^31 or more");
-      return SEQALIGN_E_TOO_LARGE;
-    }
+    if ((uint64_t)la + lb >= ((uint64_t)1 << 31)) return too_long(p);
     uint64_t width = 0;
     geom[p] = band_of(la, lb, band[p], &width);
-    if (width > SEQALIGN_BAND_MAX_WIDTH) {
-      set_last_error("pair " + std::to_string(p) + ": a band of " + std::to_string(width) + " diagonals, at most " +
-                     std::to_string(SEQALIGN_BAND_MAX_WIDTH) + " are supported");
-      return SEQALIGN_E_TOO_LARGE;
+    if (width > SEQALIGN_BAND_MAX_WIDTH) return too_wide(p, width);
+  }
+  return SEQALIGN_OK;
+}
+
+// ... of the banded SW calls
+int check_sw_band_batch(const seqalign_batch_t *b, const int32_t *diag_lo, const int32_t *diag_hi, std::vector<Band> &geom) {
+  if (!batch_readable(b)) return SEQALIGN_E_ARG;
+  geom.resize(b->n_pairs);
+  for (uint64_t p = 0; p < b->n_pairs; ++p) {
+    const uint32_t la = b->len_a[p], lb = b->len_b[p];
+    if (diag_lo[p] > diag_hi[p]) {
+      set_last_error("pair " + std::to_string(p) + ": diag_lo " + std::to_string(diag_lo[p]) + " is above diag_hi " + std::to_string(diag_hi[p]));
+      return SEQALIGN_E_ARG;
     }
+    if ((uint64_t)la + lb >= ((uint64_t)1 << 31)) return too_long(p);
+    uint64_t width = 0;
+    geom[p] = sw_band_of(la, lb, diag_lo[p], diag_hi[p], &width);
+    if (width > SEQALIGN_BAND_MAX_WIDTH) return too_wide(p, width);
   }
   return SEQALIGN_OK;
 }
@@ -63,12 +107,12 @@ struct BandChunk {
   uint64_t first = 0, count = 0, seq_bytes = 0, cells = 0;
 };
 
-int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, bool align, size_t budget, std::vector<BandChunk> &out) {
+int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, bool align, bool sw, size_t budget, std::vector<BandChunk> &out) {
   BandChunk c;
   uint64_t used = 0;
   for (uint64_t p = 0; p < b->n_pairs; ++p) {
     const uint32_t la = b->len_a[p], lb = b->len_b[p];
-    const uint64_t need = pair_bytes(la, lb, geom[p].width, align);
+    const uint64_t need = pair_bytes(la, lb, geom[p].cells, align, sw);
     if (need > budget) {
       set_last_error("pair " + std::to_string(p) + ": " + std::to_string(need) + " bytes of device memory needed, the chunk budget is " +
                      std::to_string(budget));
@@ -77,7 +121,7 @@ int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, b
     if (c.count && (used + need > budget || c.count == kChunkMaxPairs)) { out.push_back(c); c = BandChunk(); c.first = p; used = 0; }
     used += need;
     c.count++; c.seq_bytes += (uint64_t)la + lb;
-    c.cells += ((uint64_t)lb + 1) * geom[p].width;
+    c.cells += geom[p].cells;
   }
   if (c.count) out.push_back(c);
   return SEQALIGN_OK;
@@ -87,7 +131,7 @@ int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, b
 struct BandChunkRun {
   seqalign_ctx *ctx = nullptr;
   const seqalign_dev_scoring *sc = nullptr;
-  bool align = false;
+  bool align = false, sw = false;
   uint64_t n = 0, seq_bytes = 0;
   std::vector<uint32_t> order;                          // descriptor slot -> pair of the chunk
   std::vector<uint64_t> str_at;                         // slot -> where its strings start in the chunk's string buffers
@@ -96,7 +140,7 @@ struct BandChunkRun {
   uint64_t *d_off_a = nullptr, *d_off_b = nullptr, *d_mat_off = nullptr, *d_str_off = nullptr;
   uint32_t *d_len_a = nullptr, *d_len_b = nullptr, *d_width = nullptr;
   int32_t *d_dlo = nullptr;
-  uint32_t *d_res = nullptr;                            // [4] header (err_flag), then score[n]
+  uint32_t *d_res = nullptr;                            // [4] header (err_flag), then score[n]; SW: end_a[n], end_b[n] behind it
   uint64_t cells = 0;
 
   int prepare(const seqalign_batch_t *b, const std::vector<Band> &geom, const BandChunk &c) {
@@ -122,7 +166,7 @@ struct BandChunkRun {
       h_off_a[s] = seq_at[k]; h_off_b[s] = seq_at[k] + la;
       h_len_a[s] = la; h_len_b[s] = lb;
       h_width[s] = geom[p].width; h_dlo[s] = geom[p].d_lo;
-      h_mat[s] = mat; mat += ((uint64_t)lb + 1) * geom[p].width;
+      h_mat[s] = mat; mat += geom[p].cells;
       h_str[s] = str_at[s] = seq_at[k];   // (a pair's strings are len_a + len_b bytes at most, like its sequences)
     }
     uint8_t *h_seq = ctx->h_arena.as<uint8_t>();
@@ -136,10 +180,10 @@ struct BandChunkRun {
     });
 
     if ((rc = ctx->arena.reserve(seq_bytes + 16)) || (rc = ctx->off_a.reserve(desc_bytes)) || (rc = ctx->status.reserve(n * 8)) ||
-        (rc = ctx->best_score.reserve(16 + 4 * n)))
+        (rc = ctx->best_score.reserve(16 + (sw ? 12 : 4) * n)))
       return rc;
     if (align && ((rc = ctx->long_block.reserve(12 * cells + 64)) || (rc = ctx->t_out_a.reserve(seq_bytes + 16)) ||
-                  (rc = ctx->t_out_b.reserve(seq_bytes + 16)) || (rc = ctx->t_meta.reserve(16 * n))))
+                  (rc = ctx->t_out_b.reserve(seq_bytes + 16)) || (rc = ctx->t_meta.reserve((sw ? 32 : 16) * n))))
       return rc;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(ctx->off_a.p, h_off_a, desc_bytes, hipMemcpyHostToDevice, st));
@@ -172,18 +216,33 @@ struct BandChunkRun {
     return p;
   }
 
+  SaBandSwParams sw_params(uint64_t s0, uint64_t m) const {
+    SaBandSwParams p;
+    p.b = params(s0, m);
+    p.b.meta4 = nullptr;
+    p.end_a = d_res + 4 + n + s0; p.end_b = d_res + 4 + 2 * n + s0;
+    p.meta8 = align ? ctx->t_meta.as<uint32_t>() + 8 * s0 : nullptr;
+    return p;
+  }
+
   int launch() {
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemsetAsync(d_res, 0, 16, st));
     for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) {
       const uint64_t s0 = cls_first[x], m = cls_first[x + 1] - s0;
       if (!m) continue;
-      const SaBandParams p = params(s0, m);
-      const hipError_t e = align ? sa_launch_band_fill(p, cls_max_w[x], st) : sa_launch_band_score(p, cls_max_w[x], st);
+      hipError_t e;
+      if (sw) {
+        const SaBandSwParams p = sw_params(s0, m);
+        e = align ? sa_launch_band_sw_fill(p, cls_max_w[x], st) : sa_launch_band_sw_score(p, cls_max_w[x], st);
+      } else {
+        const SaBandParams p = params(s0, m);
+        e = align ? sa_launch_band_fill(p, cls_max_w[x], st) : sa_launch_band_score(p, cls_max_w[x], st);
+      }
       if (e != hipSuccess) return fail_hip(e, "band kernel launch");
     }
     if (align) {
-      const hipError_t e = sa_launch_band_walk(params(0, n), st);
+      const hipError_t e = sw ? sa_launch_band_sw_walk(sw_params(0, n), st) : sa_launch_band_walk(params(0, n), st);
       if (e != hipSuccess) return fail_hip(e, "band walk launch");
     }
     return SEQALIGN_OK;
@@ -209,6 +268,68 @@ struct BandChunkRun {
     if (h[0]) return fail_from_status(first);
     const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
     for (uint64_t s = 0; s < n; ++s) out_score[first + order[s]] = hs[s];
+    return SEQALIGN_OK;
+  }
+
+  // banded SW: score, end_a, end_b per pair
+  int finish_sw_score(uint64_t first, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
+    int rc;
+    const size_t words = 4 + 3 * n;
+    if ((rc = ctx->h_misc.reserve(4 * words))) return rc;
+    uint32_t *h = ctx->h_misc.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_wait_spinning(ctx->stream));
+    if (h[0]) return fail_from_status(first);
+    const uint32_t *hs = h + 4, *ha = hs + n, *hb = ha + n;
+    for (uint64_t s = 0; s < n; ++s) {
+      const uint64_t p = first + order[s];
+      out_score[p] = (int32_t)hs[s]; out_end_a[p] = ha[s]; out_end_b[p] = hb[s];
+    }
+    return SEQALIGN_OK;
+  }
+
+  // banded SW: the chunk's hits in pair order, under seqalign_sw_align_long's capacity rule.  A pair's own error comes before
+  // SEQALIGN_E_NOMEM and nothing of the chunk is delivered then.
+  int finish_sw_align(uint64_t first, const int32_t *min_score, seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits,
+                      char *out_a, char *out_b, uint64_t str_cap, uint64_t *used_str) {
+    int rc;
+    if ((rc = ctx->h_tmeta.reserve(32 * n)) || (rc = ctx->h_ta.reserve(seq_bytes + 16)) || (rc = ctx->h_tb.reserve(seq_bytes + 16))) return rc;
+    hipStream_t st = ctx->stream;
+    const uint32_t *meta = ctx->h_tmeta.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(ctx->h_tmeta.p, ctx->t_meta.p, 32 * n, hipMemcpyDeviceToHost, st));
+    if (seq_bytes) {
+      HIP_TRY(hipMemcpyAsync(ctx->h_ta.p, ctx->t_out_a.p, seq_bytes, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(ctx->h_tb.p, ctx->t_out_b.p, seq_bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(stream_wait_spinning(st));
+    std::vector<uint32_t> slot_of(n);
+    uint64_t worst = ~0ull;
+    uint32_t worst_code = 0;
+    for (uint64_t s = 0; s < n; ++s) {
+      slot_of[order[s]] = (uint32_t)s;
+      if (meta[8 * s + 1] && order[s] < worst) { worst = order[s]; worst_code = meta[8 * s + 1]; }
+    }
+    if (worst != ~0ull) {
+      if (worst_code == SEQALIGN_E_UNKNOWN_PAIR) return fail_unknown_pair(first + worst);
+      set_last_error("pair " + std::to_string(first + worst) + ": traceback failed");
+      return (int)worst_code;
+    }
+    const char *ha = ctx->h_ta.as<char>(), *hb = ctx->h_tb.as<char>();
+    for (uint64_t k = 0; k < n; ++k) {
+      const uint64_t s = slot_of[k], p = first + k;
+      const uint32_t *m = meta + 8 * s;
+      const int32_t score = (int32_t)m[0];
+      if (score <= 0 || score < min_score[p]) continue;   // no hit
+      const uint32_t len = m[6], head = m[7];
+      const uint64_t took = *n_hits >= hit_cap ? 0 : put_alignment(ctx, ha + str_at[s] + head, hb + str_at[s] + head, len, out_a, out_b, *used_str,
+                                                                    str_cap > *used_str ? str_cap - *used_str : 0);
+      if (!took) return SEQALIGN_E_NOMEM;
+      seqalign_sw_hit_t &h = hits[(*n_hits)++];
+      h.pair = p; h.score = score;
+      h.pos_a = m[2]; h.pos_b = m[3]; h.len_a = m[4] - m[2]; h.len_b = m[5] - m[3];   // smith_waterman.c:251-255
+      h.length = len; h.str_off = *used_str;
+      *used_str += took;
+    }
     return SEQALIGN_OK;
   }
 
@@ -257,7 +378,7 @@ int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, 0, &sc))) return rc;
   std::vector<BandChunk> chunks;
-  if ((rc = plan_band_chunks(batch, geom, align, ctx->chunk_budget, chunks))) return rc;
+  if ((rc = plan_band_chunks(batch, geom, align, false, ctx->chunk_budget, chunks))) return rc;
   StreamSyncOnExit sync(ctx->stream);
   for (const BandChunk &c : chunks) {
     BandChunkRun run;
@@ -265,6 +386,57 @@ int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
     if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch())) return rc;
     if ((rc = align ? run.finish_align(c.first, str_off, out_a, out_b, out_len, out_score) : run.finish_score(c.first, out_score))) return rc;
   }
+  return SEQALIGN_OK;
+}
+
+int sw_band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool align,
+                 int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, const int32_t *min_score, seqalign_sw_hit_t *hits,
+                 uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b, uint64_t str_cap) {
+  int rc;
+  if (batch->n_pairs == 0) return SEQALIGN_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  seqalign_dev_scoring *sc = nullptr;
+  if ((rc = cached_scoring(ctx, scoring, 1, &sc))) return rc;
+  std::vector<BandChunk> chunks;
+  if ((rc = plan_band_chunks(batch, geom, align, true, ctx->chunk_budget, chunks))) return rc;
+  StreamSyncOnExit sync(ctx->stream);
+  uint64_t used_str = 0;
+  for (const BandChunk &c : chunks) {
+    BandChunkRun run;
+    run.ctx = ctx; run.sc = sc; run.align = align; run.sw = true;
+    if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch())) return rc;
+    if ((rc = align ? run.finish_sw_align(c.first, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, &used_str)
+                    : run.finish_sw_score(c.first, out_score, out_end_a, out_end_b)))
+      return rc;
+  }
+  return SEQALIGN_OK;
+}
+
+// the score call's launches of one chunk, `repeats` times between HIP events
+int band_time(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool sw,
+              int repeats, float *ms_each, const char *name) {
+  int rc;
+  if (batch->n_pairs == 0) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);
+  HIP_TRY(hipSetDevice(ctx->device));
+  seqalign_dev_scoring *sc = nullptr;
+  if ((rc = cached_scoring(ctx, scoring, sw ? 1 : 0, &sc))) return rc;
+  std::vector<BandChunk> chunks;
+  if ((rc = plan_band_chunks(batch, geom, false, sw, ctx->chunk_budget, chunks))) return rc;
+  if (chunks.size() != 1) { set_last_error(std::string(name) + ": the batch does not fit one chunk"); return SEQALIGN_E_ARG; }
+  StreamSyncOnExit sync(ctx->stream);
+  BandChunkRun run;
+  run.ctx = ctx; run.sc = sc; run.align = false; run.sw = sw;
+  if ((rc = run.prepare(batch, geom, chunks[0]))) return rc;
+  EventList events;
+  for (int r = 0; r < 2 * repeats; ++r) HIP_TRY(events.add());
+  for (int r = 0; r < repeats; ++r) {
+    HIP_TRY(hipEventRecord(events.ev[2 * r], ctx->stream));
+    if ((rc = run.launch())) return rc;
+    HIP_TRY(hipEventRecord(events.ev[2 * r + 1], ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (int r = 0; r < repeats; ++r) HIP_TRY(hipEventElapsedTime(&ms_each[r], events.ev[2 * r], events.ev[2 * r + 1]));
   return SEQALIGN_OK;
 }
 
@@ -286,28 +458,7 @@ extern "C" int seqalign_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_b
   std::vector<Band> geom;
   int rc = check_band_batch(batch, band, geom);
   if (rc) return rc;
-  if (batch->n_pairs == 0) return SEQALIGN_E_ARG;
-  CallScope scope(ctx);
-  HIP_TRY(hipSetDevice(ctx->device));
-  seqalign_dev_scoring *sc = nullptr;
-  if ((rc = cached_scoring(ctx, scoring, 0, &sc))) return rc;
-  std::vector<BandChunk> chunks;
-  if ((rc = plan_band_chunks(batch, geom, false, ctx->chunk_budget, chunks))) return rc;
-  if (chunks.size() != 1) { set_last_error("seqalign_band_score_time_ms: the batch does not fit one chunk"); return SEQALIGN_E_ARG; }
-  StreamSyncOnExit sync(ctx->stream);
-  BandChunkRun run;
-  run.ctx = ctx; run.sc = sc; run.align = false;
-  if ((rc = run.prepare(batch, geom, chunks[0]))) return rc;
-  EventList events;
-  for (int r = 0; r < 2 * repeats; ++r) HIP_TRY(events.add());
-  for (int r = 0; r < repeats; ++r) {
-    HIP_TRY(hipEventRecord(events.ev[2 * r], ctx->stream));
-    if ((rc = run.launch())) return rc;
-    HIP_TRY(hipEventRecord(events.ev[2 * r + 1], ctx->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  for (int r = 0; r < repeats; ++r) HIP_TRY(hipEventElapsedTime(&ms_each[r], events.ev[2 * r], events.ev[2 * r + 1]));
-  return SEQALIGN_OK;
+  return band_time(ctx, batch, scoring, geom, false, repeats, ms_each, "seqalign_band_score_time_ms");
 }
 
 extern "C" int seqalign_nw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
@@ -319,4 +470,37 @@ extern "C" int seqalign_nw_align_banded(seqalign_ctx_t *ctx, const seqalign_batc
   if (rc) return rc;
   CallScope scope(ctx);
   return band_call(ctx, batch, scoring, geom, true, str_off, out_a, out_b, out_len, out_score);
+}
+
+extern "C" int seqalign_sw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                        const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                                        uint32_t *out_end_b) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return sw_band_call(ctx, batch, scoring, geom, false, out_score, out_end_a, out_end_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0);
+}
+
+extern "C" int seqalign_sw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                        const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score,
+                                        seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b,
+                                        uint64_t str_cap) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !min_score || !hits || !n_hits || !out_a || !out_b) return SEQALIGN_E_ARG;
+  *n_hits = 0;
+  std::vector<Band> geom;
+  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return sw_band_call(ctx, batch, scoring, geom, true, nullptr, nullptr, nullptr, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap);
+}
+
+extern "C" int seqalign_sw_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                              const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom);
+  if (rc) return rc;
+  return band_time(ctx, batch, scoring, geom, true, repeats, ms_each, "seqalign_sw_band_score_time_ms");
 }

@@ -489,6 +489,25 @@ struct SaBandParams {
 hipError_t sa_launch_band_score(const SaBandParams &p, uint32_t max_width, hipStream_t stream);
 hipError_t sa_launch_band_fill(const SaBandParams &p, uint32_t max_width, hipStream_t stream);
 hipError_t sa_launch_band_walk(const SaBandParams &p, hipStream_t stream);
+/* ---- banded SW (seqalign_sw_*_banded, sa_band.hip): the same sweep over the caller's band d_lo[k] <= i - j <= d_lo[k] + width[k]
+ * - 1, already clipped to [-len_b, len_a] (1 <= width <= SA_BAND_MAX_WIDTH; a band without an inner cell is legal), every cell
+ * outside it and every border cell 0.  Both forms: b.score[k], end_a[k], end_b[k] = the best match_scores cell of the band in
+ * hit order, as SaScoreParams reports it; b.f.status / b.err_flag as above.  Fill form: M, A, B of the rows that have inner band
+ * cells (sa_band_sw_rows: j0 .. j1), cell (i, j) at b.f.mat_off[k] + (j - j0) width + i - j - d_lo.  Walk: from that best cell
+ * until the score is 0, one lane per pair; meta8[8k..] = score, status, pos_a, pos_b, end_a, end_b, length, head. */
+struct SaBandSwParams {
+  SaBandParams b;               /* b.meta4 unused */
+  uint32_t *end_a, *end_b;
+  uint32_t *meta8;
+};
+/* the rows of a banded-SW pair that have inner band cells: *j0 .. *j1 (none: *j1 < *j0) */
+static inline void sa_band_sw_rows(uint32_t len_a, uint32_t len_b, int64_t d_lo, int64_t d_hi, int64_t *j0, int64_t *j1) {
+  *j0 = d_hi < 0 ? 1 - d_hi : 1;
+  *j1 = len_a == 0 ? 0 : ((int64_t)len_a - d_lo < (int64_t)len_b ? (int64_t)len_a - d_lo : (int64_t)len_b);
+}
+hipError_t sa_launch_band_sw_score(const SaBandSwParams &p, uint32_t max_width, hipStream_t stream);
+hipError_t sa_launch_band_sw_fill(const SaBandSwParams &p, uint32_t max_width, hipStream_t stream);
+hipError_t sa_launch_band_sw_walk(const SaBandSwParams &p, hipStream_t stream);
 /* the second launch record (seqalign_ctx_last_call_info_ext: SEQALIGN_KX_*) */
 void sa_record_launch_ext(int kind, uint64_t items);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */

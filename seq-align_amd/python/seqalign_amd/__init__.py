@@ -519,6 +519,65 @@ class Context:
                "seqalign_band_score_time_ms")
         return ms
 
+    # ---- banded SW (seqalign_sw_score_banded / seqalign_sw_align_banded) -------------------------------
+    def sw_score_banded(self, batch, scoring: Scoring, diag_lo, diag_hi):
+        """seqalign_sw_score_banded: what sw_score returns -- (score int32[n], end_a uint32[n], end_b uint32[n]) -- over the
+        cells diag_lo <= i - j <= diag_hi of each pair (column i of seq_a, row j of seq_b); each bound an int or one per pair,
+        anywhere in int32, clipped to the matrix by the library."""
+        _score_args(batch, scoring)
+        lo, hi = _diag_args(batch, diag_lo, diag_hi)
+        n = batch.n_pairs
+        score, end_a, end_b = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_score_banded(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(score), _ptr(end_a),
+                                              _ptr(end_b)), "seqalign_sw_score_banded")
+        return score, end_a, end_b
+
+    def sw_align_banded(self, batch, scoring: Scoring, diag_lo, diag_hi, min_score, raw: bool = False):
+        """seqalign_sw_align_banded: what sw_batch(..., max_hits=1) returns -- per pair a list of at most one hit dict --
+        over the banded matrices.  raw=True returns (n_hits, hits array, out_a, out_b) without building Python dicts per hit
+        and, like sw_batch's, re-uses the buffers of the last raw call on the same batch."""
+        _score_args(batch, scoring)
+        lo, hi = _diag_args(batch, diag_lo, diag_hi)
+        n = batch.n_pairs
+        ms = np.full(n, min_score, np.int32) if np.isscalar(min_score) else np.asarray(min_score, np.int32)
+        if ms.shape != (n,):
+            raise SeqAlignError(E_ARG, f"sw_align_banded: min_score must be a scalar or int32[{n}]")
+        hit_cap = max(1, n)
+        str_cap = int((batch.len_a.astype(np.uint64) + batch.len_b.astype(np.uint64) + np.uint64(1)).sum()) + 1
+        cache = getattr(self, "_swband_buffers", None)
+        if raw and cache is not None and cache[0] is batch:
+            hits, out_a, out_b = cache[1]              # timing loops: same batch, same (already touched) buffers
+        else:
+            hits = (SwHit * hit_cap)()
+            out_a, out_b = np.zeros(str_cap, np.uint8), np.zeros(str_cap, np.uint8)
+            if raw:
+                self._swband_buffers = (batch, (hits, out_a, out_b))
+        n_hits = C.c_uint64(0)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_align_banded(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(ms), hits,
+                                              C.c_uint64(hit_cap), C.byref(n_hits), _ptr(out_a), _ptr(out_b), C.c_uint64(str_cap)),
+               "seqalign_sw_align_banded")
+        if raw:
+            return n_hits.value, hits, out_a, out_b
+        per_pair = [[] for _ in range(n)]
+        for k in range(n_hits.value):
+            h = hits[k]
+            per_pair[h.pair].append(dict(score=h.score, pos_a=h.pos_a, pos_b=h.pos_b, len_a=h.len_a, len_b=h.len_b,
+                                         a=out_a[h.str_off:h.str_off + h.length].tobytes().decode(),
+                                         b=out_b[h.str_off:h.str_off + h.length].tobytes().decode()))
+        return per_pair
+
+    def sw_band_score_time_ms(self, batch, scoring: Scoring, diag_lo, diag_hi, repeats: int = 10) -> np.ndarray:
+        """seqalign_sw_band_score_time_ms: kernel time (HIP events) of sw_score_banded's launches, float32[repeats]."""
+        _score_args(batch, scoring)
+        lo, hi = _diag_args(batch, diag_lo, diag_hi)
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_band_score_time_ms(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), C.c_int(repeats),
+                                                    _ptr(ms)), "seqalign_sw_band_score_time_ms")
+        return ms
+
     def sw_align_long(self, batch, scoring: Scoring, min_score):
         """seqalign_sw_align_long: what sw_batch(..., max_hits=1) returns -- per pair a list of at most one hit dict --
         for pairs of any size."""
@@ -705,6 +764,26 @@ def _band_arg(batch, band) -> np.ndarray:
     if n and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF):
         raise SeqAlignError(E_ARG, "band: entries must be in 0 .. 2^32 - 1")
     return np.ascontiguousarray(w.astype(np.uint32))
+
+
+def _diag_args(batch, diag_lo, diag_hi):
+    """diag_lo / diag_hi of the banded SW calls: each one int for every pair, or one per pair, anywhere in int32."""
+    n = batch.n_pairs
+    out = []
+    for name, bound in (("diag_lo", diag_lo), ("diag_hi", diag_hi)):
+        try:
+            w = np.asarray(bound)
+            if w.dtype.kind not in "iu" or w.ndim > 1:
+                raise ValueError
+            w = np.full(n, int(w), np.int64) if w.ndim == 0 else w.astype(np.int64)
+        except (TypeError, ValueError, OverflowError):
+            raise SeqAlignError(E_ARG, f"{name}: an int or one int per pair") from None
+        if w.shape != (n,):
+            raise SeqAlignError(E_ARG, f"{name}: {w.shape[0]} entries for {n} pairs")
+        if n and (int(w.min()) < -2 ** 31 or int(w.max()) > 2 ** 31 - 1):
+            raise SeqAlignError(E_ARG, f"{name}: entries must be in -2^31 .. 2^31 - 1")
+        out.append(np.ascontiguousarray(w.astype(np.int32)))
+    return out
 
 
 def _cross_args(queries, targets, scoring):
@@ -960,6 +1039,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_sw_score_search_multi",
     "seqalign_nw_align_long", "seqalign_sw_align_long",
     "seqalign_nw_score_banded", "seqalign_nw_align_banded", "seqalign_band_score_time_ms", "seqalign_ctx_last_call_info_ext", "seqalign_kernel_kind_ext_name",
+    "seqalign_sw_score_banded", "seqalign_sw_align_banded", "seqalign_sw_band_score_time_ms",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",
