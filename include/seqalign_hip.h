@@ -427,6 +427,8 @@ int seqalign_pool_trim(seqalign_ctx_t *ctx, uint64_t keep_bytes, uint64_t *held_
  *   upload_slices   0 .. 16                 seqalign_nw_batch: slices a sub-batch's sequences are packed and uploaded in (0 = 1: measured,
  *                                           more slices cost what they overlap)
  *   long_block_rows 0 | N >= 1              seqalign_*_align_long: rows per block and between checkpoint rows (0: sized from the chunk budget)
+ *   band_strip_cols 0 | 64 | 128 | 256 | 512   seqalign_*_banded_wide: columns per strip of the band's pipeline of waves (0: 512 from 512 pairs
+ *                                           on, else 256, see "wide banded calls")
  *   cpl, wpb, lds_pad, reduce_depth, sweep_trace, timing   tuning experiments / development aids
  * Numbers are integers and nothing else ("abc", "1x", "" are refused, not read as 0); switches take 1 / 0, true / false, on / off,
  * yes / no.  Returns SEQALIGN_E_ARG for an unknown key or a value outside the key's range (nothing changes then). */
@@ -494,7 +496,8 @@ const char *seqalign_kernel_kind_name(int kind);
  * are counted in a second record of the same shape, indexed by SEQALIGN_KX_*.  The outermost entry point of a call clears
  * both records; a call that launches none of the kernels below leaves this one all zero. */
 enum {
-  /* (the banded SW calls are counted under these three as well: see "banded SW") */
+  /* (the banded SW calls are counted under these three as well: see "banded SW"; so are the wide banded calls, whose
+   * band_score / band_fill items are the (pair, strip) waves that swept at least one row: see "wide banded calls") */
   SEQALIGN_KX_BAND_SCORE = 0,      /* banded NW, score only (seqalign_nw_score_banded), one pair per wave (items: pairs) */
   SEQALIGN_KX_BAND_FILL,           /* banded NW, M / A / B of every band cell (seqalign_nw_align_banded)                  */
   SEQALIGN_KX_BAND_WALK,           /* ... the traceback over a chunk's bands, one lane per pair                           */
@@ -666,6 +669,44 @@ int seqalign_sw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
 /* Timing hook (tools/align_banded_sw_bench.py), the sibling of seqalign_band_score_time_ms for seqalign_sw_score_banded */
 int seqalign_sw_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                    const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
+/* ---- wide banded calls: the four banded calls at any band width ---------------------- */
+/* The banded calls above hold a pair's whole band in one wave and stop at SEQALIGN_BAND_MAX_WIDTH diagonals.  These four take
+ * the argument lists of their siblings unchanged and accept ANY width: a pair's band is cut into strips of columns, one
+ * wave per strip, the waves of a pair working as a pipeline that hands a strip's last column on to the strip on its right
+ * (so one long pair, too, uses many waves).  The band definitions of "banded NW" and "banded SW" apply word for word -- the
+ * clamps, d_lo / d_hi, every cell outside the band at the floor, the end pick, the walk, the results and their capacities --
+ * and for every batch the narrow call accepts, the wide call returns the same bytes, the same status and names the same pair
+ * in seqalign_last_error.  Only the width rule differs:
+ *   SEQALIGN_E_TOO_LARGE    len_a + len_b >= 2^31 only (from lengths alone, before the context is touched)
+ *   SEQALIGN_E_ARG          as the siblings: NULL arguments, unreadable batch, (SW) diag_lo > diag_hi with the pair named
+ *   SEQALIGN_E_NOMEM        a pair that does not fit the chunk budget alone (the bytes named): the align calls are bounded by
+ *                           memory only
+ *   SEQALIGN_E_HIP          "band strip hand-off timed out" with the pair named: a wave waited for the strip on its left while
+ *                           for over 2 s NO strip of that pair published progress (only a device preempted for that long
+ *                           can cause it: some strip of a pair always runs); nothing is delivered
+ * Device bytes per pair, chunks cut within the option chunk_bytes: what the sibling call needs (see there: the align calls
+ * 12 rows width + ..., the same layout) plus the pipeline's scratch
+ *     strips (8 width + 20) + 20,      strips = max(1, ceil(len_a / S)),  S = columns per strip
+ * (chunks are also cut so that pairs-rounded-up-to-8 times the chunk's largest strip count stays within 2^28 workgroups; per
+ * strip a hand-off column of `width` entries of 8 bytes -- max(M, A) and B of the strip's last column on the rows where
+ * that cell is in the band --, a progress word and a best-cell entry; per pair two descriptors and a word that counts its strips'
+ * publications).
+ * S is the option band_strip_cols; 0, the default, takes 512 for batches of 512 pairs or more and 256 for fewer, what was
+ * fastest where it was measured.  Results do not depend on S.
+ * seqalign_ctx_last_call_info_ext: band_score, or band_fill + band_walk, one band_score / band_fill launch per chunk; their
+ * items count the (pair, strip) waves that swept at least one row -- the strips that hold a column with an inner band cell.
+ * No _multi, _submit or timing-hook variants. */
+int seqalign_nw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const uint32_t *band, int32_t *out_score);
+int seqalign_nw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const uint32_t *band, const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len,
+                                  int32_t *out_score);
+int seqalign_sw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                                  uint32_t *out_end_b);
+int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score, seqalign_sw_hit_t *hits,
+                                  uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b, uint64_t str_cap);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

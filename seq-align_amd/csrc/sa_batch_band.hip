@@ -16,6 +16,10 @@
 // the align call stores only the rows that have inner band cells (sa_band_sw_rows), the fill reports the best cell, the walk
 // brings home 32 bytes per pair (score, status, pos_a, pos_b, end_a, end_b, length, head) and the strings, and the host
 // delivers the hits that reach min_score in pair order under seqalign_sw_align_long's capacity rule.
+//
+// The wide calls (seqalign_*_banded_wide; kernel: sa_band_strips.hip) run through the same plan with a strip width
+// (BandChunkRun::wide): no width check, the pipeline's scratch added to a pair's bytes, and per chunk ONE launch over all its
+// pairs instead of one per width class; the layouts, the walks and what comes home are the narrow calls'.
 #include "sa_ctx.hpp"
 
 using namespace sa_host;
@@ -27,6 +31,10 @@ constexpr uint64_t kAlignPairBytes = 96;   // descriptors (48), status (8), the 
 constexpr uint64_t kSwScorePairBytes = 80;   // ... and end_a, end_b (8)
 constexpr uint64_t kSwAlignPairBytes = 128;  // descriptors (48), status (8), score and end cell (12), the walk's eight words (32), slack
 constexpr uint64_t kChunkMaxPairs = (uint64_t)1 << 24;
+// a wide launch has (pairs rounded up to 8) x (the chunk's largest strip count) workgroups, most of which return at once when
+// one long pair sits among many short ones: a chunk is cut before that product passes this.  One pair alone stays below it
+// (len_a < 2^31, 64 columns per strip at least: fewer than 2^25 strips, times 8)
+constexpr uint64_t kWideMaxBlocks = (uint64_t)1 << 28;
 
 struct Band {
   int32_t d_lo;
@@ -54,10 +62,31 @@ Band sw_band_of(uint32_t la, uint32_t lb, int32_t lo, int32_t hi, uint64_t *widt
   return Band{(int32_t)d_lo, (uint32_t)std::min<uint64_t>(*width64, 0xFFFFFFFFu), j1 < j0 ? 0 : (uint64_t)(j1 - j0 + 1) * *width64};
 }
 
-uint64_t pair_bytes(uint32_t la, uint32_t lb, uint64_t cells, bool align, bool sw) {
-  const uint64_t seq = (uint64_t)la + lb;
-  if (sw) return align ? 12 * cells + 3 * seq + kSwAlignPairBytes : seq + kSwScorePairBytes;
-  return align ? 12 * cells + 3 * seq + kAlignPairBytes : seq + kScorePairBytes;
+// the wide calls: a pair's strips of `cols` columns, and what they add to its bytes -- per strip a hand-off column of `width`
+// entries of 8 bytes, a progress word (4) and a best-cell entry (16), and per pair two more descriptors (16) and a front word (4)
+uint64_t wide_strips(uint32_t la, uint32_t cols) { return la ? ((uint64_t)la + cols - 1) / cols : 1; }
+uint64_t wide_bytes(uint32_t la, uint32_t width, uint32_t cols) { return wide_strips(la, cols) * (8 * (uint64_t)width + 20) + 20; }
+
+uint64_t pair_bytes(uint32_t la, uint32_t lb, const Band &g, bool align, bool sw, uint32_t wide_cols) {
+  const uint64_t seq = (uint64_t)la + lb, cells = g.cells, wide = wide_cols ? wide_bytes(la, g.width, wide_cols) : 0;
+  if (sw) return wide + (align ? 12 * cells + 3 * seq + kSwAlignPairBytes : seq + kSwScorePairBytes);
+  return wide + (align ? 12 * cells + 3 * seq + kAlignPairBytes : seq + kScorePairBytes);
+}
+
+// the (pair, strip) waves of a wide launch that sweep at least one row: the strips that hold one of the pair's columns with
+// an inner band cell, max(1, 1 + d_lo) .. min(len_a, len_b + d_hi)
+uint64_t wide_busy_strips(uint32_t la, uint32_t lb, const Band &g, uint32_t cols) {
+  const int64_t d_hi = (int64_t)g.d_lo + g.width - 1;
+  const int64_t c_lo = std::max<int64_t>(1, 1 + (int64_t)g.d_lo), c_hi = std::min<int64_t>(la, (int64_t)lb + d_hi);
+  if (la == 0 || lb == 0 || c_lo > c_hi) return 0;
+  return (uint64_t)((c_hi - 1) / cols - (c_lo - 1) / cols + 1);
+}
+
+// columns per strip of a wide call: the option band_strip_cols, or (0) what was fastest where it was measured (DESIGN.md 3.17:
+// 512 on both batches of 1 000 pairs, widths 584 and 2 049; 256 on one pair of width 1 023 and on 64 pairs of width 5 653)
+uint32_t wide_strip_cols(const seqalign_ctx *ctx, uint64_t n_pairs) {
+  if (ctx->opt.band_strip_cols) return ctx->opt.band_strip_cols;
+  return n_pairs >= 512 ? 512 : 256;
 }
 
 int too_wide(uint64_t p, uint64_t width) {
@@ -72,7 +101,7 @@ int too_long(uint64_t p) {
 }
 
 // argument checks and band geometry, before any device work
-int check_band_batch(const seqalign_batch_t *b, const uint32_t *band, std::vector<Band> &geom) {
+int check_band_batch(const seqalign_batch_t *b, const uint32_t *band, std::vector<Band> &geom, bool wide = false) {
   if (!batch_readable(b)) return SEQALIGN_E_ARG;
   geom.resize(b->n_pairs);
   for (uint64_t p = 0; p < b->n_pairs; ++p) {
@@ -80,13 +109,13 @@ int check_band_batch(const seqalign_batch_t *b, const uint32_t *band, std::vecto
     if ((uint64_t)la + lb >= ((uint64_t)1 << 31)) return too_long(p);
     uint64_t width = 0;
     geom[p] = band_of(la, lb, band[p], &width);
-    if (width > SEQALIGN_BAND_MAX_WIDTH) return too_wide(p, width);
+    if (!wide && width > SEQALIGN_BAND_MAX_WIDTH) return too_wide(p, width);
   }
   return SEQALIGN_OK;
 }
 
 // ... of the banded SW calls
-int check_sw_band_batch(const seqalign_batch_t *b, const int32_t *diag_lo, const int32_t *diag_hi, std::vector<Band> &geom) {
+int check_sw_band_batch(const seqalign_batch_t *b, const int32_t *diag_lo, const int32_t *diag_hi, std::vector<Band> &geom, bool wide = false) {
   if (!batch_readable(b)) return SEQALIGN_E_ARG;
   geom.resize(b->n_pairs);
   for (uint64_t p = 0; p < b->n_pairs; ++p) {
@@ -98,7 +127,7 @@ int check_sw_band_batch(const seqalign_batch_t *b, const int32_t *diag_lo, const
     if ((uint64_t)la + lb >= ((uint64_t)1 << 31)) return too_long(p);
     uint64_t width = 0;
     geom[p] = sw_band_of(la, lb, diag_lo[p], diag_hi[p], &width);
-    if (width > SEQALIGN_BAND_MAX_WIDTH) return too_wide(p, width);
+    if (!wide && width > SEQALIGN_BAND_MAX_WIDTH) return too_wide(p, width);
   }
   return SEQALIGN_OK;
 }
@@ -107,18 +136,23 @@ struct BandChunk {
   uint64_t first = 0, count = 0, seq_bytes = 0, cells = 0;
 };
 
-int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, bool align, bool sw, size_t budget, std::vector<BandChunk> &out) {
+int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, bool align, bool sw, size_t budget, std::vector<BandChunk> &out,
+                     uint32_t wide_cols = 0) {
   BandChunk c;
-  uint64_t used = 0;
+  uint64_t used = 0, strips_max = 0;
   for (uint64_t p = 0; p < b->n_pairs; ++p) {
     const uint32_t la = b->len_a[p], lb = b->len_b[p];
-    const uint64_t need = pair_bytes(la, lb, geom[p].cells, align, sw);
+    const uint64_t need = pair_bytes(la, lb, geom[p], align, sw, wide_cols);
+    const uint64_t strips = wide_cols ? std::max(strips_max, wide_strips(la, wide_cols)) : 0;   // the chunk's largest, with this pair
     if (need > budget) {
       set_last_error("pair " + std::to_string(p) + ": " + std::to_string(need) + " bytes of device memory needed, the chunk budget is " +
                      std::to_string(budget));
       return SEQALIGN_E_NOMEM;
     }
-    if (c.count && (used + need > budget || c.count == kChunkMaxPairs)) { out.push_back(c); c = BandChunk(); c.first = p; used = 0; }
+    if (c.count && (used + need > budget || c.count == kChunkMaxPairs || ((c.count + 8) & ~(uint64_t)7) * strips > kWideMaxBlocks)) {
+      out.push_back(c); c = BandChunk(); c.first = p; used = 0; strips_max = 0;
+    }
+    strips_max = wide_cols ? std::max(strips_max, wide_strips(la, wide_cols)) : 0;
     used += need;
     c.count++; c.seq_bytes += (uint64_t)la + lb;
     c.cells += geom[p].cells;
@@ -140,8 +174,12 @@ struct BandChunkRun {
   uint64_t *d_off_a = nullptr, *d_off_b = nullptr, *d_mat_off = nullptr, *d_str_off = nullptr;
   uint32_t *d_len_a = nullptr, *d_len_b = nullptr, *d_width = nullptr;
   int32_t *d_dlo = nullptr;
-  uint32_t *d_res = nullptr;                            // [4] header (err_flag), then score[n]; SW: end_a[n], end_b[n] behind it
+  uint32_t *d_res = nullptr;                            // [4] header (err_flag; wide: give-up word), then score[n]; SW: end_a[n], end_b[n] behind it
   uint64_t cells = 0;
+  // the wide calls: columns per strip (0: the narrow calls), one launch per chunk over all its slots
+  uint32_t wide = 0, strips_per_pair = 0;
+  uint64_t slots = 0, hand_total = 0, busy_strips = 0;
+  uint64_t *d_slot_off = nullptr, *d_hand_off = nullptr;
 
   int prepare(const seqalign_batch_t *b, const std::vector<Band> &geom, const BandChunk &c) {
     int rc;
@@ -150,11 +188,14 @@ struct BandChunkRun {
     sort_by_row_class(n, [&](uint64_t k) { return geom[c.first + k].width; }, order.data(), cls_first, cls_max_w);
 
     // pinned descriptors, slot order: off_a, off_b, mat_off, str_off (u64), len_a, len_b, width (u32), d_lo (i32)
-    const size_t desc_bytes = n * (4 * sizeof(uint64_t) + 4 * sizeof(uint32_t));
+    // the wide calls: slot_off, hand_off (u64) behind them
+    const size_t desc_bytes = n * (4 * sizeof(uint64_t) + 4 * sizeof(uint32_t) + (wide ? 2 * sizeof(uint64_t) : 0));
     if ((rc = ctx->h_desc.reserve(desc_bytes)) || (rc = ctx->h_arena.reserve(seq_bytes + 16))) return rc;
     uint64_t *h_off_a = ctx->h_desc.as<uint64_t>(), *h_off_b = h_off_a + n, *h_mat = h_off_b + n, *h_str = h_mat + n;
     uint32_t *h_len_a = reinterpret_cast<uint32_t *>(h_str + n), *h_len_b = h_len_a + n, *h_width = h_len_b + n;
     int32_t *h_dlo = reinterpret_cast<int32_t *>(h_width + n);
+    uint64_t *h_slot = reinterpret_cast<uint64_t *>(h_dlo + n), *h_hand = h_slot + n;
+    slots = hand_total = busy_strips = 0; strips_per_pair = 0;
     std::vector<uint64_t> seq_at(n);
     { uint64_t pos = 0;
       for (uint64_t k = 0; k < n; ++k) { seq_at[k] = pos; pos += (uint64_t)b->len_a[c.first + k] + b->len_b[c.first + k]; } }
@@ -168,6 +209,13 @@ struct BandChunkRun {
       h_width[s] = geom[p].width; h_dlo[s] = geom[p].d_lo;
       h_mat[s] = mat; mat += geom[p].cells;
       h_str[s] = str_at[s] = seq_at[k];   // (a pair's strings are len_a + len_b bytes at most, like its sequences)
+      if (wide) {
+        const uint64_t strips = wide_strips(la, wide);
+        h_slot[s] = slots; h_hand[s] = hand_total;
+        slots += strips; hand_total += strips * geom[p].width;
+        strips_per_pair = (uint32_t)std::max<uint64_t>(strips_per_pair, strips);
+        busy_strips += wide_busy_strips(la, lb, geom[p], wide);
+      }
     }
     uint8_t *h_seq = ctx->h_arena.as<uint8_t>();
     constexpr uint64_t kTask = 256;
@@ -185,12 +233,17 @@ struct BandChunkRun {
     if (align && ((rc = ctx->long_block.reserve(12 * cells + 64)) || (rc = ctx->t_out_a.reserve(seq_bytes + 16)) ||
                   (rc = ctx->t_out_b.reserve(seq_bytes + 16)) || (rc = ctx->t_meta.reserve((sw ? 32 : 16) * n))))
       return rc;
+    // wide: progress words, the ticket counter and the pairs' front words behind them, then (16-byte aligned) the best-cell
+    // entries; the hand-off columns
+    if (wide && ((rc = ctx->strip_progress.reserve(4 * (slots + n + 8) + 16 * slots + 16)) || (rc = ctx->score_handoff.reserve(8 * hand_total + 16))))
+      return rc;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemcpyAsync(ctx->off_a.p, h_off_a, desc_bytes, hipMemcpyHostToDevice, st));
     if (seq_bytes) HIP_TRY(hipMemcpyAsync(ctx->arena.p, h_seq, seq_bytes, hipMemcpyHostToDevice, st));
     d_off_a = ctx->off_a.as<uint64_t>(); d_off_b = d_off_a + n; d_mat_off = d_off_b + n; d_str_off = d_mat_off + n;
     d_len_a = reinterpret_cast<uint32_t *>(d_str_off + n); d_len_b = d_len_a + n; d_width = d_len_b + n;
     d_dlo = reinterpret_cast<int32_t *>(d_width + n);
+    d_slot_off = reinterpret_cast<uint64_t *>(d_dlo + n); d_hand_off = d_slot_off + n;
     d_res = ctx->best_score.as<uint32_t>();
     return SEQALIGN_OK;
   }
@@ -225,10 +278,53 @@ struct BandChunkRun {
     return p;
   }
 
+  // the wide calls: one launch over all slots of the chunk, strips_per_pair the chunk's maximum
+  int launch_wide() {
+    hipStream_t st = ctx->stream;
+    SaBandStripsParams w;
+    memset(&w, 0, sizeof(w));
+    w.s = sw_params(0, n);
+    if (!sw) { w.s.b = params(0, n); w.s.end_a = w.s.end_b = w.s.meta8 = nullptr; }
+    w.strips_per_pair = strips_per_pair;
+    w.slot_off = d_slot_off; w.hand_off = d_hand_off;
+    w.progress = ctx->strip_progress.as<uint32_t>();
+    w.ticket = w.progress + slots;
+    w.front = w.ticket + 1;
+    w.strip_best = w.progress + ((slots + n + 4) & ~(uint64_t)3);
+    w.give_up = d_res + 1;
+    w.handoff = ctx->score_handoff.as<int32_t>();
+    HIP_TRY(hipMemsetAsync(w.progress, 0, 4 * (slots + 1 + n), st));
+    HIP_TRY(hipMemsetAsync(ctx->status.p, 0xFF, 8 * n, st));
+    const hipError_t e = sa_launch_band_strips(w, wide, align, sw, busy_strips, st);
+    if (e != hipSuccess) return fail_hip(e, "band strips kernel launch");
+    return SEQALIGN_OK;
+  }
+
+  // wide: the give-up word of the header brought home in h (finish_*): slot + 1 of the first pair one of whose strips gave up
+  int fail_if_gave_up(uint64_t first, const uint32_t *h) {
+    if (!wide || !h[1]) return SEQALIGN_OK;
+    const uint64_t slot = h[1] - 1;
+    set_last_error("pair " + std::to_string(first + (slot < n ? order[slot] : 0)) + ": band strip hand-off timed out");
+    return SEQALIGN_E_HIP;
+  }
+
+  // wide align calls: the header on its way home with the walk's results (the narrow calls have no give-up word)
+  int fetch_give_up() {
+    if (!wide) return SEQALIGN_OK;
+    int rc = ctx->h_misc.reserve(16);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->h_misc.p, d_res, 16, hipMemcpyDeviceToHost, ctx->stream));
+    return SEQALIGN_OK;
+  }
+
   int launch() {
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemsetAsync(d_res, 0, 16, st));
-    for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) {
+    if (wide) {
+      int rc = launch_wide();
+      if (rc) return rc;
+    }
+    for (int x = 0; x < SA_SCORE_ROW_CLASSES && !wide; ++x) {
       const uint64_t s0 = cls_first[x], m = cls_first[x + 1] - s0;
       if (!m) continue;
       hipError_t e;
@@ -265,6 +361,7 @@ struct BandChunkRun {
     uint32_t *h = ctx->h_misc.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(stream_wait_spinning(ctx->stream));
+    if ((rc = fail_if_gave_up(first, h))) return rc;
     if (h[0]) return fail_from_status(first);
     const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
     for (uint64_t s = 0; s < n; ++s) out_score[first + order[s]] = hs[s];
@@ -279,6 +376,7 @@ struct BandChunkRun {
     uint32_t *h = ctx->h_misc.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(stream_wait_spinning(ctx->stream));
+    if ((rc = fail_if_gave_up(first, h))) return rc;
     if (h[0]) return fail_from_status(first);
     const uint32_t *hs = h + 4, *ha = hs + n, *hb = ha + n;
     for (uint64_t s = 0; s < n; ++s) {
@@ -296,12 +394,14 @@ struct BandChunkRun {
     if ((rc = ctx->h_tmeta.reserve(32 * n)) || (rc = ctx->h_ta.reserve(seq_bytes + 16)) || (rc = ctx->h_tb.reserve(seq_bytes + 16))) return rc;
     hipStream_t st = ctx->stream;
     const uint32_t *meta = ctx->h_tmeta.as<uint32_t>();
+    if ((rc = fetch_give_up())) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->h_tmeta.p, ctx->t_meta.p, 32 * n, hipMemcpyDeviceToHost, st));
     if (seq_bytes) {
       HIP_TRY(hipMemcpyAsync(ctx->h_ta.p, ctx->t_out_a.p, seq_bytes, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipMemcpyAsync(ctx->h_tb.p, ctx->t_out_b.p, seq_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(stream_wait_spinning(st));
+    if (wide && (rc = fail_if_gave_up(first, ctx->h_misc.as<uint32_t>()))) return rc;
     std::vector<uint32_t> slot_of(n);
     uint64_t worst = ~0ull;
     uint32_t worst_code = 0;
@@ -338,12 +438,14 @@ struct BandChunkRun {
     if ((rc = ctx->h_tmeta.reserve(16 * n)) || (rc = ctx->h_ta.reserve(seq_bytes + 16)) || (rc = ctx->h_tb.reserve(seq_bytes + 16))) return rc;
     hipStream_t st = ctx->stream;
     uint32_t *meta = ctx->h_tmeta.as<uint32_t>();
+    if ((rc = fetch_give_up())) return rc;
     HIP_TRY(hipMemcpyAsync(meta, ctx->t_meta.p, 16 * n, hipMemcpyDeviceToHost, st));
     if (seq_bytes) {
       HIP_TRY(hipMemcpyAsync(ctx->h_ta.p, ctx->t_out_a.p, seq_bytes, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipMemcpyAsync(ctx->h_tb.p, ctx->t_out_b.p, seq_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(stream_wait_spinning(st));
+    if (wide && (rc = fail_if_gave_up(first, ctx->h_misc.as<uint32_t>()))) return rc;
     uint64_t worst = ~0ull;
     uint32_t worst_code = 0;
     for (uint64_t s = 0; s < n; ++s)
@@ -371,18 +473,19 @@ struct BandChunkRun {
 };
 
 int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool align,
-              const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score) {
+              const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score, bool wide = false) {
   int rc;
   if (batch->n_pairs == 0) return SEQALIGN_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, 0, &sc))) return rc;
   std::vector<BandChunk> chunks;
-  if ((rc = plan_band_chunks(batch, geom, align, false, ctx->chunk_budget, chunks))) return rc;
+  const uint32_t cols = wide ? wide_strip_cols(ctx, batch->n_pairs) : 0;
+  if ((rc = plan_band_chunks(batch, geom, align, false, ctx->chunk_budget, chunks, cols))) return rc;
   StreamSyncOnExit sync(ctx->stream);
   for (const BandChunk &c : chunks) {
     BandChunkRun run;
-    run.ctx = ctx; run.sc = sc; run.align = align;
+    run.ctx = ctx; run.sc = sc; run.align = align; run.wide = cols;
     if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch())) return rc;
     if ((rc = align ? run.finish_align(c.first, str_off, out_a, out_b, out_len, out_score) : run.finish_score(c.first, out_score))) return rc;
   }
@@ -391,19 +494,20 @@ int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
 
 int sw_band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool align,
                  int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, const int32_t *min_score, seqalign_sw_hit_t *hits,
-                 uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b, uint64_t str_cap) {
+                 uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b, uint64_t str_cap, bool wide = false) {
   int rc;
   if (batch->n_pairs == 0) return SEQALIGN_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, 1, &sc))) return rc;
   std::vector<BandChunk> chunks;
-  if ((rc = plan_band_chunks(batch, geom, align, true, ctx->chunk_budget, chunks))) return rc;
+  const uint32_t cols = wide ? wide_strip_cols(ctx, batch->n_pairs) : 0;
+  if ((rc = plan_band_chunks(batch, geom, align, true, ctx->chunk_budget, chunks, cols))) return rc;
   StreamSyncOnExit sync(ctx->stream);
   uint64_t used_str = 0;
   for (const BandChunk &c : chunks) {
     BandChunkRun run;
-    run.ctx = ctx; run.sc = sc; run.align = align; run.sw = true;
+    run.ctx = ctx; run.sc = sc; run.align = align; run.sw = true; run.wide = cols;
     if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch())) return rc;
     if ((rc = align ? run.finish_sw_align(c.first, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, &used_str)
                     : run.finish_sw_score(c.first, out_score, out_end_a, out_end_b)))
@@ -503,4 +607,50 @@ extern "C" int seqalign_sw_band_score_time_ms(seqalign_ctx_t *ctx, const seqalig
   int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom);
   if (rc) return rc;
   return band_time(ctx, batch, scoring, geom, true, repeats, ms_each, "seqalign_sw_band_score_time_ms");
+}
+
+// ---- the wide banded calls: the same four contracts at any width (kernel: sa_band_strips.hip)
+extern "C" int seqalign_nw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const uint32_t *band, int32_t *out_score) {
+  if (!ctx || !batch || !scoring || !band || !out_score) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom, true);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return band_call(ctx, batch, scoring, geom, false, nullptr, nullptr, nullptr, nullptr, out_score, true);
+}
+
+extern "C" int seqalign_nw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const uint32_t *band, const uint64_t *str_off, char *out_a, char *out_b,
+                                             uint32_t *out_len, int32_t *out_score) {
+  if (!ctx || !batch || !scoring || !band || !str_off || !out_a || !out_b || !out_len || !out_score) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom, true);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return band_call(ctx, batch, scoring, geom, true, str_off, out_a, out_b, out_len, out_score, true);
+}
+
+extern "C" int seqalign_sw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                                             uint32_t *out_end_b) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom, true);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return sw_band_call(ctx, batch, scoring, geom, false, out_score, out_end_a, out_end_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, true);
+}
+
+extern "C" int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score,
+                                             seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b,
+                                             uint64_t str_cap) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !min_score || !hits || !n_hits || !out_a || !out_b) return SEQALIGN_E_ARG;
+  *n_hits = 0;
+  std::vector<Band> geom;
+  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom, true);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return sw_band_call(ctx, batch, scoring, geom, true, nullptr, nullptr, nullptr, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, true);
 }

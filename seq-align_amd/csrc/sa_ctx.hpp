@@ -344,6 +344,7 @@ struct SaOptions {
   uint32_t walk_group = 0;        // walk_group        0|1|4|8: walks per wave of the tile walker on moves (0: four in lockstep on blocked direction bytes, else one; 1 / 4 / 8: forced)
   uint32_t async_lanes = 0;       // async_lanes       1..8 (0 = 3): batches seqalign_*_batch_submit keeps in flight per context (sa_async.hip)
   uint32_t long_block_rows = 0;   // long_block_rows   seqalign_*_align_long: rows per block and between checkpoints (0: sized from the chunk budget)
+  uint32_t band_strip_cols = 0;   // band_strip_cols   seqalign_*_banded_wide: columns per strip, 64|128|256|512 (0: 512 from 512 pairs on, else 256)
   uint32_t arena_keep_gib = 16;   // arena_keep_gib    how much of a walk's unused chunks stays with the process (the chunk pool: large scratch
                                   //                   buffers are mapped from it instead of freshly released, not yet cleared VRAM); 0: none
 };

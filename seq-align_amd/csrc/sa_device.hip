@@ -265,6 +265,7 @@ static bool set_option(seqalign_ctx *ctx, const char *key, const char *val) {
   if (is("walk_group")) { if (!number(0, 8, &num) || !(num == 0 || num == 1 || num == 4 || num == 8)) return false; o.walk_group = (uint32_t)num; return true; }
   if (is("arena_free_pct")) { if (!number(10, 90, &num)) return false; o.arena_free_pct = (uint32_t)num; return true; }
   if (is("long_block_rows")) { if (!number(0, 0xFFFFFFFFll, &num)) return false; o.long_block_rows = (uint32_t)num; return true; }
+  if (is("band_strip_cols")) { if (!number(0, 512, &num) || !(num == 0 || num == 64 || num == 128 || num == 256 || num == 512)) return false; o.band_strip_cols = (uint32_t)num; return true; }
   if (is("arena_quality")) {
     char *end = nullptr;
     const double q = strtod(val, &end);
@@ -312,6 +313,7 @@ static bool get_option(const seqalign_ctx *ctx, const char *key, std::string *ou
   if (is("walk_group")) return n(o.walk_group);
   if (is("arena_free_pct")) return n(o.arena_free_pct);
   if (is("long_block_rows")) return n(o.long_block_rows);
+  if (is("band_strip_cols")) return n(o.band_strip_cols);
   if (is("arena_quality")) { char buf[32]; snprintf(buf, sizeof(buf), "%.6g", (double)o.arena_quality); *out = buf; return true; }
   return false;
 }
@@ -320,7 +322,7 @@ static bool get_option(const seqalign_ctx *ctx, const char *key, std::string *ou
 // SEQALIGN_HOST_THREADS: the process-wide worker pool, sa_ctx.hpp)
 static void options_from_env(seqalign_ctx *ctx) {
   static const char *keys[] = {"kernel", "cpl", "wpb", "lds_pad", "traceback", "trace_kernel", "sweep_mode", "sweep_strip",
-                               "sweep_cpl", "sweep_ev", "sweep_trace", "sweep_dirs", "nw_dirs", "pack16", "quad", "walk_overlap", "nw_moves", "zero_copy", "reduce_depth", "timing", "chunk_bytes", "subbatches", "arena_scan_gib", "arena_quality", "arena_keep_gib", "upload_slices", "arena_free_pct", "async_lanes", "walk_group", "dirs_local", "walk_stage", "walk_tile", "long_block_rows"};
+                               "sweep_cpl", "sweep_ev", "sweep_trace", "sweep_dirs", "nw_dirs", "pack16", "quad", "walk_overlap", "nw_moves", "zero_copy", "reduce_depth", "timing", "chunk_bytes", "subbatches", "arena_scan_gib", "arena_quality", "arena_keep_gib", "upload_slices", "arena_free_pct", "async_lanes", "walk_group", "dirs_local", "walk_stage", "walk_tile", "long_block_rows", "band_strip_cols"};
   for (const char *k : keys) {
     std::string name = "SEQALIGN_";
     for (const char *c = k; *c; ++c) name += (char)toupper((unsigned char)*c);

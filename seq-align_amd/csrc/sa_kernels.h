@@ -508,6 +508,23 @@ static inline void sa_band_sw_rows(uint32_t len_a, uint32_t len_b, int64_t d_lo,
 hipError_t sa_launch_band_sw_score(const SaBandSwParams &p, uint32_t max_width, hipStream_t stream);
 hipError_t sa_launch_band_sw_fill(const SaBandSwParams &p, uint32_t max_width, hipStream_t stream);
 hipError_t sa_launch_band_sw_walk(const SaBandSwParams &p, hipStream_t stream);
+/* ---- the wide banded calls (seqalign_*_banded_wide, sa_band_strips.hip): the same bands, matrices and layouts at any width,
+ * one wave per (pair, strip of strip_cols columns) in the strips pipeline.  s (NW: s.b alone) is the narrow launch's record;
+ * f.status must hold ~0 per pair before the launch (the strips atomicMin into it).  Pair k has max(1, ceil(len_a /
+ * strip_cols)) strips <= strips_per_pair; strip t of it owns progress word slot_off[k] + t (zero before the launch; ~0: all
+ * its rows), strip_best entry 4 (slot_off[k] + t) (SW) and the `width` int2 of handoff from hand_off[k] + t width.  *ticket
+ * (zero before the launch) deals the strips out; front[k] (zero before the launch) counts the publications of pair k's strips; *give_up (zero before the launch) becomes k + 1 for the first pair k of the launch
+ * one of whose strips ran out of its wait budget: the results are void then.
+ * The walks are sa_launch_band_walk / sa_launch_band_sw_walk over the fill form's cells. */
+struct SaBandStripsParams {
+  SaBandSwParams s;
+  uint32_t strips_per_pair;
+  const uint64_t *slot_off, *hand_off;
+  uint32_t *progress, *ticket, *front, *strip_best, *give_up;
+  int32_t *handoff;
+};
+/* strip_cols: 64 | 128 | 256 | 512; items: what the launch record counts (the (pair, strip) waves that sweep a row) */
+hipError_t sa_launch_band_strips(const SaBandStripsParams &p, uint32_t strip_cols, bool fill, bool is_sw, uint64_t items, hipStream_t stream);
 /* the second launch record (seqalign_ctx_last_call_info_ext: SEQALIGN_KX_*) */
 void sa_record_launch_ext(int kind, uint64_t items);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */

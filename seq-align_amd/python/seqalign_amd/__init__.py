@@ -165,7 +165,7 @@ def batch_desc(batch: "workloads.Batch") -> BatchDesc:
 
 OPTION_DEFAULTS = {"kernel": "auto", "cpl": 0, "wpb": 0, "lds_pad": 0, "traceback": "device", "trace_kernel": "auto",
                    "sweep_mode": "auto", "sweep_strip": 0, "sweep_cpl": 0, "sweep_trace": 0, "sweep_dirs": 1, "nw_dirs": 1, "pack16": 1, "quad": 0, "walk_overlap": 0, "timing": 0, "chunk_bytes": 0,
-                   "subbatches": 0, "arena_scan_gib": 160, "arena_quality": 1.045, "arena_keep_gib": 16, "upload_slices": 0, "arena_free_pct": 60, "nw_moves": 1, "zero_copy": "auto", "sweep_ev": 1, "reduce_depth": 0, "async_lanes": 0, "walk_group": 0, "dirs_local": 1, "walk_stage": 1, "walk_tile": 0, "long_block_rows": 0}
+                   "subbatches": 0, "arena_scan_gib": 160, "arena_quality": 1.045, "arena_keep_gib": 16, "upload_slices": 0, "arena_free_pct": 60, "nw_moves": 1, "zero_copy": "auto", "sweep_ev": 1, "reduce_depth": 0, "async_lanes": 0, "walk_group": 0, "dirs_local": 1, "walk_stage": 1, "walk_tile": 0, "long_block_rows": 0, "band_strip_cols": 0}
 
 
 K_MAX = 32
@@ -490,24 +490,46 @@ class Context:
     def nw_score_banded(self, batch, scoring: Scoring, band) -> np.ndarray:
         """seqalign_nw_score_banded: the global score of every pair inside its diagonal band, int32[n].  band: an int, or
         one per pair (w >= 0; the band is d_lo = max(-lb, min(0, la - lb) - w) <= i - j <= min(la, max(0, la - lb) + w))."""
+        return self._nw_score_banded("seqalign_nw_score_banded", batch, scoring, band)
+
+    def _nw_score_banded(self, _call: str, batch, scoring, band) -> np.ndarray:
         _score_args(batch, scoring)
         bw = _band_arg(batch, band)
         score = np.zeros(batch.n_pairs, np.int32)
         d = batch_desc(batch)
-        _check(lib().seqalign_nw_score_banded(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(score)),
-               "seqalign_nw_score_banded")
+        _check(getattr(lib(), _call)(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(score)), _call)
         return score
 
     def nw_align_banded(self, batch, scoring: Scoring, band):
         """seqalign_nw_align_banded: what nw_batch returns -- [(score, a, b)] per pair -- over the banded matrices.  A pair
         with no alignment inside its band raises SeqAlignError(E_TRACEBACK)."""
+        return self._nw_align_banded("seqalign_nw_align_banded", batch, scoring, band)
+
+    def _nw_align_banded(self, _call: str, batch, scoring, band):
         _score_args(batch, scoring)
         bw = _band_arg(batch, band)
         str_off, out_a, out_b, out_len, out_score = _nw_string_buffers(batch)
         d = batch_desc(batch)
-        _check(lib().seqalign_nw_align_banded(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(str_off), _ptr(out_a),
-                                              _ptr(out_b), _ptr(out_len), _ptr(out_score)), "seqalign_nw_align_banded")
+        _check(getattr(lib(), _call)(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(str_off), _ptr(out_a),
+                                     _ptr(out_b), _ptr(out_len), _ptr(out_score)), _call)
         return _nw_results(str_off, out_a, out_b, out_len, out_score)
+
+    # ---- the wide banded calls: the same four contracts at any band width (option band_strip_cols) ----
+    def nw_score_banded_wide(self, batch, scoring: Scoring, band) -> np.ndarray:
+        """seqalign_nw_score_banded_wide: nw_score_banded without the cap on the band's width."""
+        return self._nw_score_banded("seqalign_nw_score_banded_wide", batch, scoring, band)
+
+    def nw_align_banded_wide(self, batch, scoring: Scoring, band):
+        """seqalign_nw_align_banded_wide: nw_align_banded without the cap on the band's width."""
+        return self._nw_align_banded("seqalign_nw_align_banded_wide", batch, scoring, band)
+
+    def sw_score_banded_wide(self, batch, scoring: Scoring, diag_lo, diag_hi):
+        """seqalign_sw_score_banded_wide: sw_score_banded without the cap on the band's width."""
+        return self._sw_score_banded("seqalign_sw_score_banded_wide", batch, scoring, diag_lo, diag_hi)
+
+    def sw_align_banded_wide(self, batch, scoring: Scoring, diag_lo, diag_hi, min_score, raw: bool = False):
+        """seqalign_sw_align_banded_wide: sw_align_banded without the cap on the band's width."""
+        return self._sw_align_banded("seqalign_sw_align_banded_wide", batch, scoring, diag_lo, diag_hi, min_score, raw)
 
     def band_score_time_ms(self, batch, scoring: Scoring, band, repeats: int = 10) -> np.ndarray:
         """seqalign_band_score_time_ms: kernel time (HIP events) of nw_score_banded's launches, float32[repeats]."""
@@ -524,19 +546,25 @@ class Context:
         """seqalign_sw_score_banded: what sw_score returns -- (score int32[n], end_a uint32[n], end_b uint32[n]) -- over the
         cells diag_lo <= i - j <= diag_hi of each pair (column i of seq_a, row j of seq_b); each bound an int or one per pair,
         anywhere in int32, clipped to the matrix by the library."""
+        return self._sw_score_banded("seqalign_sw_score_banded", batch, scoring, diag_lo, diag_hi)
+
+    def _sw_score_banded(self, _call: str, batch, scoring, diag_lo, diag_hi):
         _score_args(batch, scoring)
         lo, hi = _diag_args(batch, diag_lo, diag_hi)
         n = batch.n_pairs
         score, end_a, end_b = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         d = batch_desc(batch)
-        _check(lib().seqalign_sw_score_banded(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(score), _ptr(end_a),
-                                              _ptr(end_b)), "seqalign_sw_score_banded")
+        _check(getattr(lib(), _call)(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(score), _ptr(end_a),
+                                     _ptr(end_b)), _call)
         return score, end_a, end_b
 
     def sw_align_banded(self, batch, scoring: Scoring, diag_lo, diag_hi, min_score, raw: bool = False):
         """seqalign_sw_align_banded: what sw_batch(..., max_hits=1) returns -- per pair a list of at most one hit dict --
         over the banded matrices.  raw=True returns (n_hits, hits array, out_a, out_b) without building Python dicts per hit
         and, like sw_batch's, re-uses the buffers of the last raw call on the same batch."""
+        return self._sw_align_banded("seqalign_sw_align_banded", batch, scoring, diag_lo, diag_hi, min_score, raw)
+
+    def _sw_align_banded(self, _call: str, batch, scoring, diag_lo, diag_hi, min_score, raw: bool):
         _score_args(batch, scoring)
         lo, hi = _diag_args(batch, diag_lo, diag_hi)
         n = batch.n_pairs
@@ -555,9 +583,8 @@ class Context:
                 self._swband_buffers = (batch, (hits, out_a, out_b))
         n_hits = C.c_uint64(0)
         d = batch_desc(batch)
-        _check(lib().seqalign_sw_align_banded(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(ms), hits,
-                                              C.c_uint64(hit_cap), C.byref(n_hits), _ptr(out_a), _ptr(out_b), C.c_uint64(str_cap)),
-               "seqalign_sw_align_banded")
+        _check(getattr(lib(), _call)(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(ms), hits,
+                                     C.c_uint64(hit_cap), C.byref(n_hits), _ptr(out_a), _ptr(out_b), C.c_uint64(str_cap)), _call)
         if raw:
             return n_hits.value, hits, out_a, out_b
         per_pair = [[] for _ in range(n)]
@@ -1040,6 +1067,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_align_long", "seqalign_sw_align_long",
     "seqalign_nw_score_banded", "seqalign_nw_align_banded", "seqalign_band_score_time_ms", "seqalign_ctx_last_call_info_ext", "seqalign_kernel_kind_ext_name",
     "seqalign_sw_score_banded", "seqalign_sw_align_banded", "seqalign_sw_band_score_time_ms",
+    "seqalign_nw_score_banded_wide", "seqalign_nw_align_banded_wide", "seqalign_sw_score_banded_wide", "seqalign_sw_align_banded_wide",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, *_score_cross, *_score_search,
-*_align_long and the banded NW calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+*_align_long, the banded NW calls and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
 
-tests/test_gpu_soak_calls.py runs a seeded slice of it (run(seconds, seed, max_trials)) under the `gpu` marker.
+tests/test_gpu_soak_calls.py runs a seeded slice of it (run(seconds, seed, max_trials)) under the `gpu` marker; that slice
+leaves the wide banded calls out (their Python reference on bands past 1 024 diagonals takes most of a second a trial).
 """
 import argparse
+import random
 import sys
 import time
 from pathlib import Path
@@ -20,6 +22,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402,F401
 
 import bandlib as BL  # noqa: E402
+import bandswlib as BS  # noqa: E402
 import orclib as O  # noqa: E402
 import seqalign_amd as S  # noqa: E402
 from seqalign_amd import workloads as W  # noqa: E402
@@ -46,13 +49,14 @@ def top_k(score, end_a, end_b, k, min_score):
     return out
 
 
-def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None):
+def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
     """Fuzz until `seconds` have passed or `max_trials` scorings were drawn; SystemExit(1) on the first mismatch, with the
-    failing case printed.  Options it sets (long_block_rows) are put back before it returns or raises."""
+    failing case printed.  Options it sets (long_block_rows, band_strip_cols) are put back before it returns or raises.
+    wide_calls: also the four *_banded_wide calls, on bands on both sides of 1 024 diagonals and random strip widths."""
     rng = W.Rng(seed)
     ctx = ctx or S.Context(0)
     t_end = time.time() + seconds
-    n = {"trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0}
+    n = {"trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -206,11 +210,53 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None):
                 if got != [x[1] for x in both]:
                     fail("BAND ALIGN", spec, sub, bands, got, [x[1] for x in both])
             n["banded"] += len(sub)
+
+        # ---- the wide banded calls: two small pairs (the narrow calls must agree) and one of 1 025 .. 1 624 columns whose band is
+        # 700 .. 1 500 diagonals wide, under a random strip width
+        if wide_calls:
+            small = [p for p in range(12) if max(len(pairs[p][0]), len(pairs[p][1])) <= 260][:2]
+            la = int(1025 + v[10] % 600)
+            a = rand(la)
+            long_pair = (a, BL.mutate(random.Random(int(v[11])), a, 0.08)[:la + 40])
+            sub = [pairs[p] for p in small] + [long_pair]
+            cols = (0, 64, 128, 256, 512)[int(v[12] % 5)]
+            half = int(350 + v[13] % 400)                      # the long pair: about 2 * half + 1 diagonals
+            wb = W.from_pairs(sub)
+            with ctx.options(band_strip_cols=cols):
+                if nw_ok:
+                    bands = [int((v[3] + 7 * p) % 41) for p in small] + [half]
+                    both = [BL.expected_both(osc, a, b, w) for (a, b), w in zip(sub, bands)]
+                    got = ctx.nw_score_banded_wide(wb, sc, bands)
+                    if [int(x) for x in got] != [x[0] for x in both]:
+                        fail("WIDE BAND SCORE", spec, "cols", cols, sub, bands, [int(x) for x in got], [x[0] for x in both])
+                    if small and not np.array_equal(got[:len(small)], ctx.nw_score_banded(W.from_pairs(sub[:len(small)]), sc, bands[:len(small)])):
+                        fail("WIDE / NARROW BAND SCORE", spec, "cols", cols, sub, bands)
+                    keep = [k for k, x in enumerate(both) if x[1] is not None]
+                    if keep:
+                        got = ctx.nw_align_banded_wide(W.from_pairs([sub[k] for k in keep]), sc, [bands[k] for k in keep])
+                        if got != [both[k][1] for k in keep]:
+                            fail("WIDE BAND ALIGN", spec, "cols", cols, [sub[k] for k in keep], [bands[k] for k in keep], got)
+                    n["banded_wide"] += len(keep)
+                shift = int(v[14] % 300) - 150
+                lo = [int(v[5] % 80) - 60] * len(small) + [shift - half]
+                hi = [lo[k] + int(v[6] % 90) for k in range(len(small))] + [shift + half]
+                want = [BS.expected(osc, a, b, lo[k], hi[k], thr) for k, (a, b) in enumerate(sub)]
+                s, ea, eb = ctx.sw_score_banded_wide(wb, sc, lo, hi)
+                cells = [(int(s[k]), int(ea[k]), int(eb[k])) for k in range(len(sub))]
+                if cells != [x[0] for x in want]:
+                    fail("WIDE BAND SW SCORE", spec, "cols", cols, sub, lo, hi, cells, [x[0] for x in want])
+                got = ctx.sw_align_banded_wide(wb, sc, lo, hi, thr)
+                if got != [[x[1]] if x[1] else [] for x in want]:
+                    fail("WIDE BAND SW ALIGN", spec, "cols", cols, "thr", thr, sub, lo, hi, got, [x[1] for x in want])
+                if small and got[:len(small)] != ctx.sw_align_banded(W.from_pairs(sub[:len(small)]), sc, lo[:len(small)], hi[:len(small)], thr):
+                    fail("WIDE / NARROW BAND SW ALIGN", spec, "cols", cols, sub, lo, hi)
+                n["banded_wide"] += len(sub)
         n["trials"] += 1
 
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
           f"{n['score']} scores, {n['cross']} cross cells, {n['search']} searches, {n['long']} long alignments, {n['banded']} banded "
-          f"alignments (+ {n['banded_none']} with none in their band) identical to the oracle (seed {seed})", flush=True)
+          f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results identical to the oracle "
+          f"(seed {seed})", flush=True)
     return n
 
 
@@ -219,5 +265,6 @@ if __name__ == "__main__":
     ap.add_argument("--seconds", type=float, default=120)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--trials", type=int, default=1 << 60)
+    ap.add_argument("--no-wide", action="store_true", help="leave the wide banded calls out")
     args = ap.parse_args()
-    run(args.seconds, args.seed, args.trials)
+    run(args.seconds, args.seed, args.trials, wide_calls=not args.no_wide)
