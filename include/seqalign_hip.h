@@ -569,6 +569,30 @@ int seqalign_nw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
                                   const scoring_t *scoring, int32_t *out_score);
 int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
                                   const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b);
+/* ---- SW hit spans: where the best local hit starts and ends, no traceback ------------ */
+/* Per pair the fields of the first hit of seqalign_sw_batch(min_score = 1, max_hits = 1) without its strings: score; pos_a,
+ * pos_b (0-based: the cell in which the reference's walk from the best cell reaches score 0 -- its tie order GAP_A, GAP_B,
+ * MATCH, not merely some optimal start); len_a, len_b, so that pos + len is seqalign_sw_score_batch's end_a / end_b.  All
+ * five are 0 when no cell scores above 0.  No limit on len_a * len_b: the lengths accepted are seqalign_sw_score_batch's.
+ * One forward pass carries the spans beside the scores; nothing per cell is written to device memory.  Rows of up to 512
+ * columns are swept by one wave per pair, wider rows by strips of 512 columns.  Device bytes per pair: len_a + len_b + 72,
+ * and for rows over 512 columns 32 x (strips - 1) x (len_b + 1) of hand-off plus 36 per strip, strips = ceil(len_a / 512);
+ * batches are chunked by these bytes, 20 bytes per pair and the error word come back.
+ * Argument checks, scoring admission (SEQALIGN_E_DOMAIN) and SEQALIGN_E_UNKNOWN_PAIR (the lowest failing pair's code is
+ * returned and named in seqalign_last_error) are seqalign_sw_score_batch's.  SEQALIGN_E_TRACEBACK cannot occur: in SW a
+ * positive cell always has a predecessor the walker accepts.  The launches are recorded as "score_rows" /
+ * "score_strips" (items: pairs).
+ * Not in this call: no cross, search, banded, _submit or command-line form, and no option steers it. */
+int seqalign_sw_span_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                           uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b);
+/* ... over several contexts (GPUs): contiguous ranges of nearly equal cells, results exactly the single-context call's */
+int seqalign_sw_span_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                 int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a,
+                                 uint32_t *out_len_b);
+/* Kernel time of seqalign_sw_span_batch (seq-align_amd/tools/sw_span_bench.py), the sibling of seqalign_score_time_ms: the
+ * batch (one chunk) is uploaded once, then its kernels run `repeats` times, each launch between two HIP events. */
+int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                             float *ms_each);
 /* ---- long pairs: alignments past the 2^31-cell cap --------------------------------- */
 /* The alignments of seqalign_nw_batch and of seqalign_sw_batch with max_hits = 1 -- same arguments, capacities and results,
  * byte for byte: score, both gapped strings and, SW, the hit's pos_a / pos_b / len_a / len_b / length -- for pairs of any

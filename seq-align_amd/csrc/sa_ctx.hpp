@@ -6,6 +6,7 @@
 //   sa_batch.hip      host-level chunking, seqalign_fill_batch, seqalign_nw_batch
 //   sa_batch_sw.hip   seqalign_sw_batch (best hit / device enumeration / host enumeration)
 //   sa_batch_score.hip seqalign_nw_score_batch / seqalign_sw_score_batch (score only)
+//   sa_batch_span.hip  seqalign_sw_span_batch (SW hit spans: score, start and end, no traceback)
 //   sa_batch_score_cross.hip seqalign_nw_score_cross / seqalign_sw_score_cross (score only, every query x every target),
 //                     and seqalign_*_score_search (the best k targets of every query; sa_score_select.hip selects)
 //   sa_batch_long.hip seqalign_nw_align_long / seqalign_sw_align_long (pairs of any size: checkpoints, blocks, walks)
@@ -508,25 +509,30 @@ static inline bool batch_readable(const seqalign_batch_t *b) {
   return b && (!b->n_pairs || (b->arena && b->off_a && b->off_b && b->len_a && b->len_b));
 }
 int check_batch(const seqalign_batch_t *b);
-// Counting sort of items 0 .. n - 1 by row class (sa_score_row_class of len(k)): order[] holds class 0's items, then class
+// Counting sort of items 0 .. n - 1 by row class (cls_of(len(k)): 0 .. CLASSES): order[] holds class 0's items, then class
 // 1's, ..., each in index order; class x has slots [cls_first[x], cls_first[x + 1]) and its longest row is cls_max_a[x].
-template <class Len>
-void sort_by_row_class(uint64_t n, Len len, uint32_t *order, uint64_t (&cls_first)[SA_SCORE_ROW_CLASSES + 2],
-                       uint32_t (&cls_max_a)[SA_SCORE_ROW_CLASSES + 1]) {
+template <int CLASSES, class Cls, class Len>
+void sort_by_class(uint64_t n, Cls cls_of, Len len, uint32_t *order, uint64_t (&cls_first)[CLASSES + 2], uint32_t (&cls_max_a)[CLASSES + 1]) {
   std::fill(std::begin(cls_first), std::end(cls_first), 0);
   std::fill(std::begin(cls_max_a), std::end(cls_max_a), 0);
   std::vector<uint8_t> cls(n);
   for (uint64_t k = 0; k < n; ++k) {
     const uint32_t la = len(k);
-    const int x = sa_score_row_class(la);
+    const int x = cls_of(la);
     cls[k] = (uint8_t)x;
     cls_first[x + 1]++;
     cls_max_a[x] = std::max(cls_max_a[x], la);
   }
-  for (int x = 0; x <= SA_SCORE_ROW_CLASSES; ++x) cls_first[x + 1] += cls_first[x];
-  uint64_t at[SA_SCORE_ROW_CLASSES + 1];
-  std::copy(cls_first, cls_first + SA_SCORE_ROW_CLASSES + 1, at);
+  for (int x = 0; x <= CLASSES; ++x) cls_first[x + 1] += cls_first[x];
+  uint64_t at[CLASSES + 1];
+  std::copy(cls_first, cls_first + CLASSES + 1, at);
   for (uint64_t k = 0; k < n; ++k) order[at[cls[k]]++] = (uint32_t)k;
+}
+// ... by the score kernels' classes (sa_score_row_class)
+template <class Len>
+void sort_by_row_class(uint64_t n, Len len, uint32_t *order, uint64_t (&cls_first)[SA_SCORE_ROW_CLASSES + 2],
+                       uint32_t (&cls_max_a)[SA_SCORE_ROW_CLASSES + 1]) {
+  sort_by_class<SA_SCORE_ROW_CLASSES>(n, sa_score_row_class, len, order, cls_first, cls_max_a);
 }
 // SEQALIGN_E_UNKNOWN_PAIR for a pair of a list, with its message
 static inline int fail_unknown_pair(uint64_t pair) {

@@ -402,6 +402,42 @@ static inline int sa_score_row_class(uint32_t len_a) {
   while (cpl[c] < need) ++c;
   return c;
 }
+/* ---- SW hit spans (sa_span.hip): sa_score.hip's SW sweep with the start of the best hit carried beside the scores -------
+ * Pair k of a launch: score[k], pos_a[k], pos_b[k], len_a[k], len_b[k] = the fields of the reference's first hit (all 0 when
+ * no cell is above 0); f.status / err_flag as SaScoreParams.  Rows of up to SA_SPAN_ROW_MAX columns: one wave per pair
+ * (columns per lane 1 .. 6 and 8).  Wider: strips of 512 columns handing over SA_SPAN_HANDOFF_BYTES per row. */
+#define SA_SPAN_ROW_MAX 512u
+#define SA_SPAN_HANDOFF_BYTES 32u
+#define SA_SPAN_BEST_BYTES 32u
+struct SaSpanParams {
+  SaFillParams f;
+  int32_t *score;                                 /* [n]                                                              */
+  uint32_t *pos_a, *pos_b, *len_a, *len_b;        /* [n]                                                              */
+  uint32_t *err_flag;                             /* one word, zeroed by the caller                                   */
+  /* strips only: */
+  uint32_t *progress;           /* as SaScoreParams                                                                    */
+  int32_t *handoff;             /* pair k, strip s < last: rows 0 .. len_b, SA_SPAN_HANDOFF_BYTES each, at
+                                   SA_SPAN_HANDOFF_BYTES * (handoff_off[k] + s * (len_b + 1))                           */
+  const uint64_t *handoff_off;  /* [n], in rows                                                                        */
+  uint32_t *strip_best;         /* SA_SPAN_BEST_BYTES per progress word                                                */
+  uint32_t strips_per_pair;
+};
+static inline uint64_t sa_span_progress_bytes(uint64_t words) { return 4 * sa_strip_best_word(words) + SA_SPAN_BEST_BYTES * words; }
+uint32_t sa_span_strips_per_pair(uint32_t max_len_a);
+/* every pair of the launch has len_a <= SA_SPAN_ROW_MAX; max_len_a picks the columns per lane */
+hipError_t sa_launch_span_rows(const SaSpanParams &p, uint32_t max_len_a, hipStream_t stream);
+/* the caller zeroed progress (and err_flag) and set status to ~0 */
+hipError_t sa_launch_span_strips(const SaSpanParams &p, hipStream_t stream);
+/* the one-wave span kernels' row classes, as sa_score_row_class (SA_SPAN_ROW_CLASSES: the strips kernel) */
+#define SA_SPAN_ROW_CLASSES 7
+static inline int sa_span_row_class(uint32_t len_a) {
+  static const uint32_t cpl[SA_SPAN_ROW_CLASSES] = {1, 2, 3, 4, 5, 6, 8};
+  if (len_a > SA_SPAN_ROW_MAX) return SA_SPAN_ROW_CLASSES;
+  const uint32_t need = (len_a + 63) / 64;
+  int c = 0;
+  while (cpl[c] < need) ++c;
+  return c;
+}
 /* score only over two sets (seqalign_*_score_cross): one launch per row class of the queries, one wave per (query, target).
  * f.off_a / f.len_a: the tile's queries, f.off_b / f.len_b: its targets, both into f.arena; f.n_pairs, f.status unused. */
 struct SaScoreCrossParams {

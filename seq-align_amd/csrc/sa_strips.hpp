@@ -18,7 +18,8 @@
 //
 // What strip s hands strip s + 1 differs.  The kernels that store the matrices read the left strip's last column back
 // from them (RowFeed, sa_rowsweep.hpp).  The score kernels store nothing per cell and hand over a scratch column instead
-// (StripHandoff below); SW adds the best cell so far (BestCells, merge_left_best).
+// (StripHandoff below); SW adds the best cell so far (BestCells, merge_left_best).  The span kernel (sa_span.hip) hands over
+// the same column with the spans of its two values (StripSpanHandoff, merge_left_best_span): same waits, same publishes.
 #pragma once
 
 #include "sa_rowsweep.hpp"
@@ -140,6 +141,61 @@ __device__ __forceinline__ void merge_left_best(const uint32_t *left_entry, int 
   if ((int)left.x >= score && (int)left.x > 0) {   // a tie goes to the lower column: theirs
     score = (int)left.x;
     key = ((unsigned long long)left.y << 32) | left.z;
+  }
+}
+
+// ---- the span kernel's forms (sa_span.hip) ----
+constexpr int kSpanHandoffInts = SA_SPAN_HANDOFF_BYTES / 4;   // per row of a hand-off column
+constexpr int kSpanBestWords = SA_SPAN_BEST_BYTES / 4;        // per strip_best entry
+
+// StripHandoff with spans: per row {max(M, A), B, whether max(M, A) is A's, 0} and {span of that state, span of B} of a
+// strip's last column, 32 bytes.  Moved 64 rows at a time: lane q holds row j0 + q, the 64 rows leave as 2 KiB in a row.
+struct StripSpanHandoff {
+  int code = 0;
+  int4 in0 = {0, 0, 0, 0}, in1 = {0, 0, 0, 0};     // lane q: row j0 + q, from the strip to my left
+  int4 out0 = {0, 0, 0, 0}, out1 = {0, 0, 0, 0};   // lane q: row j0 + q of my last column
+
+  // every 64 rows, after the wait: this lane's row r = j0 + lane; i0 = the column left of the strip
+  __device__ __forceinline__ void load(const SaFillParams &p, const uint8_t *__restrict__ seq_b, uint32_t lb, uint32_t strip,
+                                       uint32_t i0, const int32_t *hand_in, uint32_t r) {
+    if (r <= lb) {
+      code = p.code[seq_b[r - 1]];
+      if (strip == 0) {   // the border column holds 0: a walk that reaches (0, r) stops there
+        in0 = make_int4(0, 0, 0, 0);
+        in1 = make_int4((int)i0, (int)r, (int)i0, (int)r);
+      } else {
+        const int4 *h = reinterpret_cast<const int4 *>(hand_in + (uint64_t)kSpanHandoffInts * r);
+        in0 = h[0]; in1 = h[1];
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);   // once per 64 rows (see RowFeed::load)
+  }
+
+  // every row of a strip that is not the last; o0 / o1: the row's entry (wave-uniform).  Publishes the rows it stores to
+  // `word`, except the last ones: those wait for the best cell
+  __device__ __forceinline__ void keep(const int4 &o0, const int4 &o1, int32_t *hand_out, uint32_t *word, int lane, int q,
+                                       uint32_t j, uint32_t lb) {
+    const bool mine = lane == q;   // (member by member: a select between two vectors may go through memory)
+    out0 = make_int4(mine ? o0.x : out0.x, mine ? o0.y : out0.y, mine ? o0.z : out0.z, 0);
+    out1 = make_int4(mine ? o1.x : out1.x, mine ? o1.y : out1.y, mine ? o1.z : out1.z, mine ? o1.w : out1.w);
+    if (q == kWave - 1 || j == lb) {
+      if (lane <= q) {
+        int4 *h = reinterpret_cast<int4 *>(hand_out + (uint64_t)kSpanHandoffInts * (j - q + lane));
+        h[0] = out0; h[1] = out1;
+      }
+      if (j != lb) strip_publish(word, j);
+    }
+  }
+};
+
+// merge_left_best with the span of the best cell: an entry is {score, end_a, end_b, 0} {pos_a, pos_b, 0, 0}
+__device__ __forceinline__ void merge_left_best_span(const uint32_t *left_entry, int &score, unsigned long long &key,
+                                                     unsigned long long &span) {
+  const uint4 left = reinterpret_cast<const uint4 *>(left_entry)[0], lspan = reinterpret_cast<const uint4 *>(left_entry)[1];
+  if ((int)left.x >= score && (int)left.x > 0) {   // a tie goes to the lower column: theirs
+    score = (int)left.x;
+    key = ((unsigned long long)left.y << 32) | left.z;
+    span = ((unsigned long long)lspan.x << 32) | lspan.y;
   }
 }
 

@@ -418,6 +418,36 @@ class Context:
                    "seqalign_sw_score_batch")
         return score, end_a, end_b
 
+    # ---- SW hit spans (seqalign_sw_span_batch) ------------------------------
+    def sw_span(self, batch, scoring: Scoring, peers=None):
+        """seqalign_sw_span_batch: per pair the fields of sw_batch(min_score=1, max_hits=1)'s first hit without its strings --
+        (score int32[n], pos_a, pos_b, len_a, len_b uint32[n]); pos is 0-based, pos + len is sw_score's end; all 0 when no
+        cell scores above 0.  One forward pass, no limit on len_a * len_b."""
+        _score_args(batch, scoring)
+        n = batch.n_pairs
+        score = np.zeros(n, np.int32)
+        pos_a, pos_b, len_a, len_b = (np.zeros(n, np.uint32) for _ in range(4))
+        d = batch_desc(batch)
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(lib().seqalign_sw_span_batch_multi(hs, nh, C.byref(d), C.byref(scoring), _ptr(score), _ptr(pos_a), _ptr(pos_b),
+                                                      _ptr(len_a), _ptr(len_b)), "seqalign_sw_span_batch_multi")
+        else:
+            _check(lib().seqalign_sw_span_batch(self._h, C.byref(d), C.byref(scoring), _ptr(score), _ptr(pos_a), _ptr(pos_b),
+                                                _ptr(len_a), _ptr(len_b)), "seqalign_sw_span_batch")
+        return score, pos_a, pos_b, len_a, len_b
+
+    def sw_span_time_ms(self, batch, scoring: Scoring, repeats: int = 10) -> np.ndarray:
+        """seqalign_sw_span_time_ms: sw_span's kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
+        _score_args(batch, scoring)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "sw_span_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_span_time_ms(self._h, C.byref(d), C.byref(scoring), C.c_int(repeats), _ptr(ms)),
+               "seqalign_sw_span_time_ms")
+        return ms
+
     # ---- score matrices (seqalign_nw_score_cross / seqalign_sw_score_cross) ------------------------------
     def nw_score_cross(self, queries, targets, scoring: Scoring, peers=None) -> np.ndarray:
         """seqalign_nw_score_cross: the global score of every query against every target, int32[n_queries, n_targets] --
@@ -1061,6 +1091,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_batch_cigar", "seqalign_sw_batch_cigar", "seqalign_nw_batch_cigar_multi", "seqalign_sw_batch_cigar_multi",
     "seqalign_nw_score_batch", "seqalign_sw_score_batch", "seqalign_nw_score_batch_multi", "seqalign_sw_score_batch_multi",
     "seqalign_score_time_ms",
+    "seqalign_sw_span_batch", "seqalign_sw_span_batch_multi", "seqalign_sw_span_time_ms",
     "seqalign_nw_score_cross", "seqalign_sw_score_cross", "seqalign_nw_score_cross_multi", "seqalign_sw_score_cross_multi",
     "seqalign_nw_score_search", "seqalign_sw_score_search", "seqalign_nw_score_search_multi",
     "seqalign_sw_score_search_multi",

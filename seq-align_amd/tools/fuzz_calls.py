@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, *_score_cross, *_score_search,
-*_align_long, the banded NW calls and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+"""Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, seqalign_sw_span_batch, *_score_cross,
+*_score_search, *_align_long, the banded NW calls and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -56,7 +56,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
     rng = W.Rng(seed)
     ctx = ctx or S.Context(0)
     t_end = time.time() + seconds
-    n = {"trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0}
+    n = {"trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -132,6 +132,16 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
             if (int(s[p]), int(ea[p]), int(eb[p])) != want:
                 fail("SW SCORE", spec, p, pairs[p], (int(s[p]), int(ea[p]), int(eb[p])), want)
         n["score"] += 12 * (1 + nw_ok)
+
+        # ---- SW hit spans: the oracle's first hit without its strings
+        got = ctx.sw_span(batch, sc)
+        for p, (a, b) in enumerate(pairs):
+            rc, hits = O.oracle_sw_hits(osc, a, b, *fills[1, p], 1, 1)
+            h = hits[0] if hits else None
+            want = (h["score"], h["pos_a"], h["pos_b"], h["len_a"], h["len_b"]) if h else (0, 0, 0, 0, 0)
+            if rc != 0 or tuple(int(x[p]) for x in got) != want:
+                fail("SW SPAN", spec, p, pairs[p], tuple(int(x[p]) for x in got), want)
+        n["span"] += 12
 
         # ---- score matrices and the search over them: 4 queries x 6 targets taken from the pairs
         qi = [0, 3, 6, wide if wide >= 0 else 9]
@@ -254,7 +264,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
         n["trials"] += 1
 
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
-          f"{n['score']} scores, {n['cross']} cross cells, {n['search']} searches, {n['long']} long alignments, {n['banded']} banded "
+          f"{n['score']} scores, {n['span']} hit spans, {n['cross']} cross cells, {n['search']} searches, {n['long']} long alignments, {n['banded']} banded "
           f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results identical to the oracle "
           f"(seed {seed})", flush=True)
     return n
