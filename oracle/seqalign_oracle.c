@@ -335,7 +335,17 @@ int orc_sw_hits(const orc_scoring_t *sc, const char *a, size_t len_a,
   for (size_t p = 0; p < cells; p++)                           /* :152-156 */
     if (M[p] > 0) cand[n_cand++] = p;
   g_order.M = M; g_order.W = W;
-  qsort(cand, n_cand, sizeof(size_t), hit_cmp);                /* :159-161 */
+  if (max_hits == 1 && n_cand > 1) {
+    /* only the first candidate in hit order is fetched (nothing is marked yet, so it is never skipped): find it in one
+     * pass instead of sorting them all */
+    size_t first = 0;
+    for (size_t k = 1; k < n_cand; k++)
+      if (hit_cmp(&cand[k], &cand[first]) < 0) first = k;
+    cand[0] = cand[first];
+    n_cand = 1;
+  } else {
+    qsort(cand, n_cand, sizeof(size_t), hit_cmp);              /* :159-161 */
+  }
 
   for (size_t k = 0; k < n_cand && found < max_hits; k++) {    /* fetch :260-277 */
     const size_t end = cand[k];

@@ -10,7 +10,8 @@
 // launch and brings home 16 bytes per pair and the strings.
 //
 // Chunks are cut by device BYTES (header: the bytes per pair); a pair that does not fit the budget alone is
-// SEQALIGN_E_NOMEM with the bytes named.
+// SEQALIGN_E_NOMEM with the bytes named.  The cut, the staging of a chunk, the lowest failing pair and the timing loop are
+// sa_chunks.hpp's; what is here is the band geometry, the kernels' parameters, the wide launch and the align calls' way home.
 //
 // Banded SW runs through the same chunk plan, layout and launch loop (BandChunkRun::sw).  Its band is the caller's, clipped;
 // the align call stores only the rows that have inner band cells (sa_band_sw_rows), the fill reports the best cell, the walk
@@ -20,7 +21,7 @@
 // The wide calls (seqalign_*_banded_wide; kernel: sa_band_strips.hip) run through the same plan with a strip width
 // (BandChunkRun::wide): no width check, the pipeline's scratch added to a pair's bytes, and per chunk ONE launch over all its
 // pairs instead of one per width class; the layouts, the walks and what comes home are the narrow calls'.
-#include "sa_ctx.hpp"
+#include "sa_chunks.hpp"
 
 using namespace sa_host;
 
@@ -30,7 +31,6 @@ constexpr uint64_t kScorePairBytes = 64;   // descriptors (48: the align call's 
 constexpr uint64_t kAlignPairBytes = 96;   // descriptors (48), status (8), the walk's four words (16), slack
 constexpr uint64_t kSwScorePairBytes = 80;   // ... and end_a, end_b (8)
 constexpr uint64_t kSwAlignPairBytes = 128;  // descriptors (48), status (8), score and end cell (12), the walk's eight words (32), slack
-constexpr uint64_t kChunkMaxPairs = (uint64_t)1 << 24;
 // a wide launch has (pairs rounded up to 8) x (the chunk's largest strip count) workgroups, most of which return at once when
 // one long pair sits among many short ones: a chunk is cut before that product passes this.  One pair alone stays below it
 // (len_a < 2^31, 64 columns per strip at least: fewer than 2^25 strips, times 8)
@@ -132,33 +132,13 @@ int check_sw_band_batch(const seqalign_batch_t *b, const int32_t *diag_lo, const
   return SEQALIGN_OK;
 }
 
-struct BandChunk {
-  uint64_t first = 0, count = 0, seq_bytes = 0, cells = 0;
-};
-
-int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, bool align, bool sw, size_t budget, std::vector<BandChunk> &out,
+// cut_chunks with the banded calls' bytes per pair, the band cells summed per chunk and the wide launch's grid capped
+int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, bool align, bool sw, size_t budget, std::vector<ByteChunk> &out,
                      uint32_t wide_cols = 0) {
-  BandChunk c;
-  uint64_t used = 0, strips_max = 0;
-  for (uint64_t p = 0; p < b->n_pairs; ++p) {
-    const uint32_t la = b->len_a[p], lb = b->len_b[p];
-    const uint64_t need = pair_bytes(la, lb, geom[p], align, sw, wide_cols);
-    const uint64_t strips = wide_cols ? std::max(strips_max, wide_strips(la, wide_cols)) : 0;   // the chunk's largest, with this pair
-    if (need > budget) {
-      set_last_error("pair " + std::to_string(p) + ": " + std::to_string(need) + " bytes of device memory needed, the chunk budget is " +
-                     std::to_string(budget));
-      return SEQALIGN_E_NOMEM;
-    }
-    if (c.count && (used + need > budget || c.count == kChunkMaxPairs || ((c.count + 8) & ~(uint64_t)7) * strips > kWideMaxBlocks)) {
-      out.push_back(c); c = BandChunk(); c.first = p; used = 0; strips_max = 0;
-    }
-    strips_max = wide_cols ? std::max(strips_max, wide_strips(la, wide_cols)) : 0;
-    used += need;
-    c.count++; c.seq_bytes += (uint64_t)la + lb;
-    c.cells += geom[p].cells;
-  }
-  if (c.count) out.push_back(c);
-  return SEQALIGN_OK;
+  return cut_chunks(b, budget, [&](uint64_t p) {
+    const uint32_t la = b->len_a[p];
+    return PairNeed{pair_bytes(la, b->len_b[p], geom[p], align, sw, wide_cols), geom[p].cells, wide_cols ? wide_strips(la, wide_cols) : 0};
+  }, out, true, kWideMaxBlocks);
 }
 
 // One chunk laid out and uploaded; launch() enqueues its kernels on ctx->stream
@@ -166,70 +146,41 @@ struct BandChunkRun {
   seqalign_ctx *ctx = nullptr;
   const seqalign_dev_scoring *sc = nullptr;
   bool align = false, sw = false;
+  // classes by band width; the descriptors behind the shared ones: mat_off, str_off (wide: slot_off, hand_off), width, d_lo
+  ChunkStage<SA_SCORE_ROW_CLASSES> stage;
   uint64_t n = 0, seq_bytes = 0;
-  std::vector<uint32_t> order;                          // descriptor slot -> pair of the chunk
-  std::vector<uint64_t> str_at;                         // slot -> where its strings start in the chunk's string buffers
-  uint64_t cls_first[SA_SCORE_ROW_CLASSES + 2] = {};    // class c: slots [cls_first[c], cls_first[c + 1])
-  uint32_t cls_max_w[SA_SCORE_ROW_CLASSES + 1] = {};
-  uint64_t *d_off_a = nullptr, *d_off_b = nullptr, *d_mat_off = nullptr, *d_str_off = nullptr;
-  uint32_t *d_len_a = nullptr, *d_len_b = nullptr, *d_width = nullptr;
-  int32_t *d_dlo = nullptr;
   uint32_t *d_res = nullptr;                            // [4] header (err_flag; wide: give-up word), then score[n]; SW: end_a[n], end_b[n] behind it
   uint64_t cells = 0;
   // the wide calls: columns per strip (0: the narrow calls), one launch per chunk over all its slots
   uint32_t wide = 0, strips_per_pair = 0;
   uint64_t slots = 0, hand_total = 0, busy_strips = 0;
-  uint64_t *d_slot_off = nullptr, *d_hand_off = nullptr;
 
-  int prepare(const seqalign_batch_t *b, const std::vector<Band> &geom, const BandChunk &c) {
+  BandChunkRun(seqalign_ctx *c, const seqalign_dev_scoring *scoring, bool align_, bool sw_, uint32_t wide_cols)
+      : ctx(c), sc(scoring), align(align_), sw(sw_), wide(wide_cols) { stage.ctx = c; }
+
+  // slot -> where its strings start in the chunk's string buffers: where its sequences do (a pair's strings are len_a + len_b
+  // bytes at most); read from the pinned descriptors, which stay as laid out until the next chunk
+  uint64_t str_at(uint64_t s) const { return stage.h_off_a[s]; }
+
+  int prepare(const seqalign_batch_t *b, const std::vector<Band> &geom, const ByteChunk &c) {
     int rc;
     n = c.count; seq_bytes = c.seq_bytes; cells = c.cells;
-    order.resize(n);
-    sort_by_row_class(n, [&](uint64_t k) { return geom[c.first + k].width; }, order.data(), cls_first, cls_max_w);
-
-    // pinned descriptors, slot order: off_a, off_b, mat_off, str_off (u64), len_a, len_b, width (u32), d_lo (i32)
-    // the wide calls: slot_off, hand_off (u64) behind them
-    const size_t desc_bytes = n * (4 * sizeof(uint64_t) + 4 * sizeof(uint32_t) + (wide ? 2 * sizeof(uint64_t) : 0));
-    if ((rc = ctx->h_desc.reserve(desc_bytes)) || (rc = ctx->h_arena.reserve(seq_bytes + 16))) return rc;
-    uint64_t *h_off_a = ctx->h_desc.as<uint64_t>(), *h_off_b = h_off_a + n, *h_mat = h_off_b + n, *h_str = h_mat + n;
-    uint32_t *h_len_a = reinterpret_cast<uint32_t *>(h_str + n), *h_len_b = h_len_a + n, *h_width = h_len_b + n;
-    int32_t *h_dlo = reinterpret_cast<int32_t *>(h_width + n);
-    uint64_t *h_slot = reinterpret_cast<uint64_t *>(h_dlo + n), *h_hand = h_slot + n;
     slots = hand_total = busy_strips = 0; strips_per_pair = 0;
-    std::vector<uint64_t> seq_at(n);
-    { uint64_t pos = 0;
-      for (uint64_t k = 0; k < n; ++k) { seq_at[k] = pos; pos += (uint64_t)b->len_a[c.first + k] + b->len_b[c.first + k]; } }
-    str_at.resize(n);
     uint64_t mat = 0;
-    for (uint64_t s = 0; s < n; ++s) {
-      const uint64_t k = order[s], p = c.first + k;
+    rc = stage.lay_out(b, c, sa_score_row_class, [&](uint64_t p) { return geom[p].width; }, wide ? 4 : 2, 2, [&](uint64_t s, uint64_t p) {
       const uint32_t la = b->len_a[p], lb = b->len_b[p];
-      h_off_a[s] = seq_at[k]; h_off_b[s] = seq_at[k] + la;
-      h_len_a[s] = la; h_len_b[s] = lb;
-      h_width[s] = geom[p].width; h_dlo[s] = geom[p].d_lo;
-      h_mat[s] = mat; mat += geom[p].cells;
-      h_str[s] = str_at[s] = seq_at[k];   // (a pair's strings are len_a + len_b bytes at most, like its sequences)
+      stage.h_u32(0)[s] = geom[p].width; stage.h_u32<int32_t>(1)[s] = geom[p].d_lo;
+      stage.h_u64(0)[s] = mat; mat += geom[p].cells;
+      stage.h_u64(1)[s] = str_at(s);
       if (wide) {
         const uint64_t strips = wide_strips(la, wide);
-        h_slot[s] = slots; h_hand[s] = hand_total;
+        stage.h_u64(2)[s] = slots; stage.h_u64(3)[s] = hand_total;
         slots += strips; hand_total += strips * geom[p].width;
         strips_per_pair = (uint32_t)std::max<uint64_t>(strips_per_pair, strips);
         busy_strips += wide_busy_strips(la, lb, geom[p], wide);
       }
-    }
-    uint8_t *h_seq = ctx->h_arena.as<uint8_t>();
-    constexpr uint64_t kTask = 256;
-    parallel_for((n + kTask - 1) / kTask, [&](uint64_t blk) {
-      for (uint64_t k = blk * kTask, e = std::min(n, (blk + 1) * kTask); k < e; ++k) {
-        const uint64_t p = c.first + k;
-        memcpy(h_seq + seq_at[k], b->arena + b->off_a[p], b->len_a[p]);
-        memcpy(h_seq + seq_at[k] + b->len_a[p], b->arena + b->off_b[p], b->len_b[p]);
-      }
     });
-
-    if ((rc = ctx->arena.reserve(seq_bytes + 16)) || (rc = ctx->off_a.reserve(desc_bytes)) || (rc = ctx->status.reserve(n * 8)) ||
-        (rc = ctx->best_score.reserve(16 + (sw ? 12 : 4) * n)))
-      return rc;
+    if (rc || (rc = ctx->best_score.reserve(16 + (sw ? 12 : 4) * n))) return rc;
     if (align && ((rc = ctx->long_block.reserve(12 * cells + 64)) || (rc = ctx->t_out_a.reserve(seq_bytes + 16)) ||
                   (rc = ctx->t_out_b.reserve(seq_bytes + 16)) || (rc = ctx->t_meta.reserve((sw ? 32 : 16) * n))))
       return rc;
@@ -237,32 +188,22 @@ struct BandChunkRun {
     // entries; the hand-off columns
     if (wide && ((rc = ctx->strip_progress.reserve(4 * (slots + n + 8) + 16 * slots + 16)) || (rc = ctx->score_handoff.reserve(8 * hand_total + 16))))
       return rc;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->off_a.p, h_off_a, desc_bytes, hipMemcpyHostToDevice, st));
-    if (seq_bytes) HIP_TRY(hipMemcpyAsync(ctx->arena.p, h_seq, seq_bytes, hipMemcpyHostToDevice, st));
-    d_off_a = ctx->off_a.as<uint64_t>(); d_off_b = d_off_a + n; d_mat_off = d_off_b + n; d_str_off = d_mat_off + n;
-    d_len_a = reinterpret_cast<uint32_t *>(d_str_off + n); d_len_b = d_len_a + n; d_width = d_len_b + n;
-    d_dlo = reinterpret_cast<int32_t *>(d_width + n);
-    d_slot_off = reinterpret_cast<uint64_t *>(d_dlo + n); d_hand_off = d_slot_off + n;
     d_res = ctx->best_score.as<uint32_t>();
-    return SEQALIGN_OK;
+    return stage.upload();
   }
 
   SaBandParams params(uint64_t s0, uint64_t m) const {
     SaBandParams p;
     memset(&p, 0, sizeof(p));
     p.f = score_fill_params(sc);
-    p.f.arena = ctx->arena.as<uint8_t>();
-    p.f.off_a = d_off_a + s0; p.f.off_b = d_off_b + s0; p.f.len_a = d_len_a + s0; p.f.len_b = d_len_b + s0;
-    p.f.mat_off = d_mat_off + s0;
-    p.f.status = ctx->status.as<uint64_t>() + s0;
-    p.f.n_pairs = (uint32_t)m;
-    p.d_lo = d_dlo + s0; p.width = d_width + s0;
+    stage.set_slots(p.f, s0, m);
+    p.f.mat_off = stage.d_u64(0) + s0;
+    p.d_lo = stage.d_u32<int32_t>(1) + s0; p.width = stage.d_u32(0) + s0;
     p.score = reinterpret_cast<int32_t *>(d_res + 4) + s0;
     p.err_flag = d_res;
     if (align) {
       p.f.M = ctx->long_block.as<int32_t>(); p.f.A = p.f.M + cells; p.f.B = p.f.A + cells;
-      p.str_off = d_str_off + s0;
+      p.str_off = stage.d_u64(1) + s0;
       p.out_a = ctx->t_out_a.as<char>(); p.out_b = ctx->t_out_b.as<char>();
       p.meta4 = ctx->t_meta.as<uint32_t>() + 4 * s0;
     }
@@ -286,7 +227,7 @@ struct BandChunkRun {
     w.s = sw_params(0, n);
     if (!sw) { w.s.b = params(0, n); w.s.end_a = w.s.end_b = w.s.meta8 = nullptr; }
     w.strips_per_pair = strips_per_pair;
-    w.slot_off = d_slot_off; w.hand_off = d_hand_off;
+    w.slot_off = stage.d_u64(2); w.hand_off = stage.d_u64(3);
     w.progress = ctx->strip_progress.as<uint32_t>();
     w.ticket = w.progress + slots;
     w.front = w.ticket + 1;
@@ -301,10 +242,10 @@ struct BandChunkRun {
   }
 
   // wide: the give-up word of the header brought home in h (finish_*): slot + 1 of the first pair one of whose strips gave up
-  int fail_if_gave_up(uint64_t first, const uint32_t *h) {
+  int fail_if_gave_up(const uint32_t *h) {
     if (!wide || !h[1]) return SEQALIGN_OK;
     const uint64_t slot = h[1] - 1;
-    set_last_error("pair " + std::to_string(first + (slot < n ? order[slot] : 0)) + ": band strip hand-off timed out");
+    set_last_error("pair " + std::to_string(stage.first + (slot < n ? stage.order[slot] : 0)) + ": band strip hand-off timed out");
     return SEQALIGN_E_HIP;
   }
 
@@ -325,15 +266,15 @@ struct BandChunkRun {
       if (rc) return rc;
     }
     for (int x = 0; x < SA_SCORE_ROW_CLASSES && !wide; ++x) {
-      const uint64_t s0 = cls_first[x], m = cls_first[x + 1] - s0;
+      const uint64_t s0 = stage.cls_first[x], m = stage.class_size(x);
       if (!m) continue;
       hipError_t e;
       if (sw) {
         const SaBandSwParams p = sw_params(s0, m);
-        e = align ? sa_launch_band_sw_fill(p, cls_max_w[x], st) : sa_launch_band_sw_score(p, cls_max_w[x], st);
+        e = align ? sa_launch_band_sw_fill(p, stage.cls_max[x], st) : sa_launch_band_sw_score(p, stage.cls_max[x], st);
       } else {
         const SaBandParams p = params(s0, m);
-        e = align ? sa_launch_band_fill(p, cls_max_w[x], st) : sa_launch_band_score(p, cls_max_w[x], st);
+        e = align ? sa_launch_band_fill(p, stage.cls_max[x], st) : sa_launch_band_score(p, stage.cls_max[x], st);
       }
       if (e != hipSuccess) return fail_hip(e, "band kernel launch");
     }
@@ -344,53 +285,30 @@ struct BandChunkRun {
     return SEQALIGN_OK;
   }
 
-  // the lowest pair of the chunk whose fill met a band cell without a score
-  int fail_from_status(uint64_t first) {
-    std::vector<uint64_t> status(n);
-    HIP_TRY(hipMemcpy(status.data(), ctx->status.p, 8 * n, hipMemcpyDeviceToHost));
-    uint64_t worst = ~0ull;
-    for (uint64_t s = 0; s < n; ++s)
-      if (status[s] != ~0ull) worst = std::min<uint64_t>(worst, order[s]);
-    return fail_unknown_pair(first + worst);
-  }
-
-  int finish_score(uint64_t first, int32_t *out_score) {
+  // the score calls: score per pair, banded SW: end_a and end_b behind it; the lowest pair of the chunk whose fill met a band
+  // cell without a score named
+  int finish_score(int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
     int rc;
-    const size_t words = 4 + n;
+    const int fields = sw ? 3 : 1;
+    const size_t words = 4 + fields * n;
     if ((rc = ctx->h_misc.reserve(4 * words))) return rc;
     uint32_t *h = ctx->h_misc.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(stream_wait_spinning(ctx->stream));
-    if ((rc = fail_if_gave_up(first, h))) return rc;
-    if (h[0]) return fail_from_status(first);
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
-    for (uint64_t s = 0; s < n; ++s) out_score[first + order[s]] = hs[s];
-    return SEQALIGN_OK;
-  }
-
-  // banded SW: score, end_a, end_b per pair
-  int finish_sw_score(uint64_t first, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
-    int rc;
-    const size_t words = 4 + 3 * n;
-    if ((rc = ctx->h_misc.reserve(4 * words))) return rc;
-    uint32_t *h = ctx->h_misc.as<uint32_t>();
-    HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(stream_wait_spinning(ctx->stream));
-    if ((rc = fail_if_gave_up(first, h))) return rc;
-    if (h[0]) return fail_from_status(first);
-    const uint32_t *hs = h + 4, *ha = hs + n, *hb = ha + n;
-    for (uint64_t s = 0; s < n; ++s) {
-      const uint64_t p = first + order[s];
-      out_score[p] = (int32_t)hs[s]; out_end_a[p] = ha[s]; out_end_b[p] = hb[s];
-    }
+    if ((rc = fail_if_gave_up(h))) return rc;
+    if (h[0]) return stage.fail_from_status();
+    uint32_t *const out[2] = {out_end_a, out_end_b};
+    stage.scatter(h + 4, fields, out_score, out);
     return SEQALIGN_OK;
   }
 
   // banded SW: the chunk's hits in pair order, under seqalign_sw_align_long's capacity rule.  A pair's own error comes before
   // SEQALIGN_E_NOMEM and nothing of the chunk is delivered then.
-  int finish_sw_align(uint64_t first, const int32_t *min_score, seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits,
+  int finish_sw_align(const int32_t *min_score, seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits,
                       char *out_a, char *out_b, uint64_t str_cap, uint64_t *used_str) {
     int rc;
+    const uint64_t first = stage.first;
+    const std::vector<uint32_t> &order = stage.order;
     if ((rc = ctx->h_tmeta.reserve(32 * n)) || (rc = ctx->h_ta.reserve(seq_bytes + 16)) || (rc = ctx->h_tb.reserve(seq_bytes + 16))) return rc;
     hipStream_t st = ctx->stream;
     const uint32_t *meta = ctx->h_tmeta.as<uint32_t>();
@@ -401,7 +319,7 @@ struct BandChunkRun {
       HIP_TRY(hipMemcpyAsync(ctx->h_tb.p, ctx->t_out_b.p, seq_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(stream_wait_spinning(st));
-    if (wide && (rc = fail_if_gave_up(first, ctx->h_misc.as<uint32_t>()))) return rc;
+    if (wide && (rc = fail_if_gave_up(ctx->h_misc.as<uint32_t>()))) return rc;
     std::vector<uint32_t> slot_of(n);
     uint64_t worst = ~0ull;
     uint32_t worst_code = 0;
@@ -421,7 +339,7 @@ struct BandChunkRun {
       const int32_t score = (int32_t)m[0];
       if (score <= 0 || score < min_score[p]) continue;   // no hit
       const uint32_t len = m[6], head = m[7];
-      const uint64_t took = *n_hits >= hit_cap ? 0 : put_alignment(ctx, ha + str_at[s] + head, hb + str_at[s] + head, len, out_a, out_b, *used_str,
+      const uint64_t took = *n_hits >= hit_cap ? 0 : put_alignment(ctx, ha + str_at(s) + head, hb + str_at(s) + head, len, out_a, out_b, *used_str,
                                                                     str_cap > *used_str ? str_cap - *used_str : 0);
       if (!took) return SEQALIGN_E_NOMEM;
       seqalign_sw_hit_t &h = hits[(*n_hits)++];
@@ -433,8 +351,10 @@ struct BandChunkRun {
     return SEQALIGN_OK;
   }
 
-  int finish_align(uint64_t first, const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score) {
+  int finish_align(const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score) {
     int rc;
+    const uint64_t first = stage.first;
+    const std::vector<uint32_t> &order = stage.order;
     if ((rc = ctx->h_tmeta.reserve(16 * n)) || (rc = ctx->h_ta.reserve(seq_bytes + 16)) || (rc = ctx->h_tb.reserve(seq_bytes + 16))) return rc;
     hipStream_t st = ctx->stream;
     uint32_t *meta = ctx->h_tmeta.as<uint32_t>();
@@ -445,7 +365,7 @@ struct BandChunkRun {
       HIP_TRY(hipMemcpyAsync(ctx->h_tb.p, ctx->t_out_b.p, seq_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(stream_wait_spinning(st));
-    if (wide && (rc = fail_if_gave_up(first, ctx->h_misc.as<uint32_t>()))) return rc;
+    if (wide && (rc = fail_if_gave_up(ctx->h_misc.as<uint32_t>()))) return rc;
     uint64_t worst = ~0ull;
     uint32_t worst_code = 0;
     for (uint64_t s = 0; s < n; ++s)
@@ -461,8 +381,8 @@ struct BandChunkRun {
       for (uint64_t s = blk * kTask, e = std::min(n, (blk + 1) * kTask); s < e; ++s) {
         const uint64_t p = first + order[s];
         const uint32_t head = meta[4 * s], len = meta[4 * s + 1];
-        memcpy(out_a + str_off[p], ha + str_at[s] + head, len);
-        memcpy(out_b + str_off[p], hb + str_at[s] + head, len);
+        memcpy(out_a + str_off[p], ha + str_at(s) + head, len);
+        memcpy(out_b + str_off[p], hb + str_at(s) + head, len);
         out_a[str_off[p] + len] = out_b[str_off[p] + len] = '\0';
         out_len[p] = len;
         out_score[p] = (int32_t)meta[4 * s + 2];
@@ -472,46 +392,22 @@ struct BandChunkRun {
   }
 };
 
-int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool align,
-              const uint64_t *str_off, char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score, bool wide = false) {
+// A banded call behind its checks: every chunk prepared, launched and brought home by finish(run)
+template <class Finish>
+int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool align, bool sw,
+              bool wide, Finish finish) {
   int rc;
   if (batch->n_pairs == 0) return SEQALIGN_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
-  if ((rc = cached_scoring(ctx, scoring, 0, &sc))) return rc;
-  std::vector<BandChunk> chunks;
+  if ((rc = cached_scoring(ctx, scoring, sw ? 1 : 0, &sc))) return rc;
+  std::vector<ByteChunk> chunks;
   const uint32_t cols = wide ? wide_strip_cols(ctx, batch->n_pairs) : 0;
-  if ((rc = plan_band_chunks(batch, geom, align, false, ctx->chunk_budget, chunks, cols))) return rc;
+  if ((rc = plan_band_chunks(batch, geom, align, sw, ctx->chunk_budget, chunks, cols))) return rc;
   StreamSyncOnExit sync(ctx->stream);
-  for (const BandChunk &c : chunks) {
-    BandChunkRun run;
-    run.ctx = ctx; run.sc = sc; run.align = align; run.wide = cols;
-    if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch())) return rc;
-    if ((rc = align ? run.finish_align(c.first, str_off, out_a, out_b, out_len, out_score) : run.finish_score(c.first, out_score))) return rc;
-  }
-  return SEQALIGN_OK;
-}
-
-int sw_band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool align,
-                 int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, const int32_t *min_score, seqalign_sw_hit_t *hits,
-                 uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b, uint64_t str_cap, bool wide = false) {
-  int rc;
-  if (batch->n_pairs == 0) return SEQALIGN_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  seqalign_dev_scoring *sc = nullptr;
-  if ((rc = cached_scoring(ctx, scoring, 1, &sc))) return rc;
-  std::vector<BandChunk> chunks;
-  const uint32_t cols = wide ? wide_strip_cols(ctx, batch->n_pairs) : 0;
-  if ((rc = plan_band_chunks(batch, geom, align, true, ctx->chunk_budget, chunks, cols))) return rc;
-  StreamSyncOnExit sync(ctx->stream);
-  uint64_t used_str = 0;
-  for (const BandChunk &c : chunks) {
-    BandChunkRun run;
-    run.ctx = ctx; run.sc = sc; run.align = align; run.sw = true; run.wide = cols;
-    if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch())) return rc;
-    if ((rc = align ? run.finish_sw_align(c.first, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, &used_str)
-                    : run.finish_sw_score(c.first, out_score, out_end_a, out_end_b)))
-      return rc;
+  for (const ByteChunk &c : chunks) {
+    BandChunkRun run(ctx, sc, align, sw, cols);
+    if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch()) || (rc = finish(run))) return rc;
   }
   return SEQALIGN_OK;
 }
@@ -525,35 +421,72 @@ int band_time(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, sw ? 1 : 0, &sc))) return rc;
-  std::vector<BandChunk> chunks;
+  std::vector<ByteChunk> chunks;
   if ((rc = plan_band_chunks(batch, geom, false, sw, ctx->chunk_budget, chunks))) return rc;
   if (chunks.size() != 1) { set_last_error(std::string(name) + ": the batch does not fit one chunk"); return SEQALIGN_E_ARG; }
   StreamSyncOnExit sync(ctx->stream);
-  BandChunkRun run;
-  run.ctx = ctx; run.sc = sc; run.align = false; run.sw = sw;
+  BandChunkRun run(ctx, sc, false, sw, 0);
   if ((rc = run.prepare(batch, geom, chunks[0]))) return rc;
-  EventList events;
-  for (int r = 0; r < 2 * repeats; ++r) HIP_TRY(events.add());
-  for (int r = 0; r < repeats; ++r) {
-    HIP_TRY(hipEventRecord(events.ev[2 * r], ctx->stream));
-    if ((rc = run.launch())) return rc;
-    HIP_TRY(hipEventRecord(events.ev[2 * r + 1], ctx->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  for (int r = 0; r < repeats; ++r) HIP_TRY(hipEventElapsedTime(&ms_each[r], events.ev[2 * r], events.ev[2 * r + 1]));
-  return SEQALIGN_OK;
+  return time_launches(ctx->stream, repeats, ms_each, [&] { return run.launch(); });
+}
+
+// ---- the four contracts, each the body of its narrow call and of its wide one (any width; kernel: sa_band_strips.hip)
+int nw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const uint32_t *band, int32_t *out_score,
+                    bool wide) {
+  if (!ctx || !batch || !scoring || !band || !out_score) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom, wide);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return band_call(ctx, batch, scoring, geom, false, false, wide, [&](BandChunkRun &run) { return run.finish_score(out_score, nullptr, nullptr); });
+}
+
+int nw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const uint32_t *band, const uint64_t *str_off,
+                    char *out_a, char *out_b, uint32_t *out_len, int32_t *out_score, bool wide) {
+  if (!ctx || !batch || !scoring || !band || !str_off || !out_a || !out_b || !out_len || !out_score) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom, wide);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return band_call(ctx, batch, scoring, geom, true, false, wide,
+                   [&](BandChunkRun &run) { return run.finish_align(str_off, out_a, out_b, out_len, out_score); });
+}
+
+int sw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const int32_t *diag_lo, const int32_t *diag_hi,
+                    int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, bool wide) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom, wide);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return band_call(ctx, batch, scoring, geom, false, true, wide, [&](BandChunkRun &run) { return run.finish_score(out_score, out_end_a, out_end_b); });
+}
+
+int sw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const int32_t *diag_lo, const int32_t *diag_hi,
+                    const int32_t *min_score, seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b,
+                    uint64_t str_cap, bool wide) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !min_score || !hits || !n_hits || !out_a || !out_b) return SEQALIGN_E_ARG;
+  *n_hits = 0;
+  std::vector<Band> geom;
+  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom, wide);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  uint64_t used_str = 0;
+  return band_call(ctx, batch, scoring, geom, true, true, wide, [&](BandChunkRun &run) {
+    return run.finish_sw_align(min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, &used_str);
+  });
 }
 
 }  // namespace
 
 extern "C" int seqalign_nw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                         const uint32_t *band, int32_t *out_score) {
-  if (!ctx || !batch || !scoring || !band || !out_score) return SEQALIGN_E_ARG;
-  std::vector<Band> geom;
-  int rc = check_band_batch(batch, band, geom);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  return band_call(ctx, batch, scoring, geom, false, nullptr, nullptr, nullptr, nullptr, out_score);
+  return nw_score_banded(ctx, batch, scoring, band, out_score, false);
+}
+
+extern "C" int seqalign_nw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const uint32_t *band, int32_t *out_score) {
+  return nw_score_banded(ctx, batch, scoring, band, out_score, true);
 }
 
 extern "C" int seqalign_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
@@ -568,36 +501,39 @@ extern "C" int seqalign_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_b
 extern "C" int seqalign_nw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                         const uint32_t *band, const uint64_t *str_off, char *out_a, char *out_b,
                                         uint32_t *out_len, int32_t *out_score) {
-  if (!ctx || !batch || !scoring || !band || !str_off || !out_a || !out_b || !out_len || !out_score) return SEQALIGN_E_ARG;
-  std::vector<Band> geom;
-  int rc = check_band_batch(batch, band, geom);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  return band_call(ctx, batch, scoring, geom, true, str_off, out_a, out_b, out_len, out_score);
+  return nw_align_banded(ctx, batch, scoring, band, str_off, out_a, out_b, out_len, out_score, false);
+}
+
+extern "C" int seqalign_nw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const uint32_t *band, const uint64_t *str_off, char *out_a, char *out_b,
+                                             uint32_t *out_len, int32_t *out_score) {
+  return nw_align_banded(ctx, batch, scoring, band, str_off, out_a, out_b, out_len, out_score, true);
 }
 
 extern "C" int seqalign_sw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                         const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
                                         uint32_t *out_end_b) {
-  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
-  std::vector<Band> geom;
-  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  return sw_band_call(ctx, batch, scoring, geom, false, out_score, out_end_a, out_end_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0);
+  return sw_score_banded(ctx, batch, scoring, diag_lo, diag_hi, out_score, out_end_a, out_end_b, false);
+}
+
+extern "C" int seqalign_sw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                                             uint32_t *out_end_b) {
+  return sw_score_banded(ctx, batch, scoring, diag_lo, diag_hi, out_score, out_end_a, out_end_b, true);
 }
 
 extern "C" int seqalign_sw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                         const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score,
                                         seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b,
                                         uint64_t str_cap) {
-  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !min_score || !hits || !n_hits || !out_a || !out_b) return SEQALIGN_E_ARG;
-  *n_hits = 0;
-  std::vector<Band> geom;
-  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  return sw_band_call(ctx, batch, scoring, geom, true, nullptr, nullptr, nullptr, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap);
+  return sw_align_banded(ctx, batch, scoring, diag_lo, diag_hi, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, false);
+}
+
+extern "C" int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score,
+                                             seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b,
+                                             uint64_t str_cap) {
+  return sw_align_banded(ctx, batch, scoring, diag_lo, diag_hi, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, true);
 }
 
 extern "C" int seqalign_sw_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
@@ -607,50 +543,4 @@ extern "C" int seqalign_sw_band_score_time_ms(seqalign_ctx_t *ctx, const seqalig
   int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom);
   if (rc) return rc;
   return band_time(ctx, batch, scoring, geom, true, repeats, ms_each, "seqalign_sw_band_score_time_ms");
-}
-
-// ---- the wide banded calls: the same four contracts at any width (kernel: sa_band_strips.hip)
-extern "C" int seqalign_nw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
-                                             const uint32_t *band, int32_t *out_score) {
-  if (!ctx || !batch || !scoring || !band || !out_score) return SEQALIGN_E_ARG;
-  std::vector<Band> geom;
-  int rc = check_band_batch(batch, band, geom, true);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  return band_call(ctx, batch, scoring, geom, false, nullptr, nullptr, nullptr, nullptr, out_score, true);
-}
-
-extern "C" int seqalign_nw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
-                                             const uint32_t *band, const uint64_t *str_off, char *out_a, char *out_b,
-                                             uint32_t *out_len, int32_t *out_score) {
-  if (!ctx || !batch || !scoring || !band || !str_off || !out_a || !out_b || !out_len || !out_score) return SEQALIGN_E_ARG;
-  std::vector<Band> geom;
-  int rc = check_band_batch(batch, band, geom, true);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  return band_call(ctx, batch, scoring, geom, true, str_off, out_a, out_b, out_len, out_score, true);
-}
-
-extern "C" int seqalign_sw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
-                                             const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
-                                             uint32_t *out_end_b) {
-  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
-  std::vector<Band> geom;
-  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom, true);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  return sw_band_call(ctx, batch, scoring, geom, false, out_score, out_end_a, out_end_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, true);
-}
-
-extern "C" int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
-                                             const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score,
-                                             seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b,
-                                             uint64_t str_cap) {
-  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !min_score || !hits || !n_hits || !out_a || !out_b) return SEQALIGN_E_ARG;
-  *n_hits = 0;
-  std::vector<Band> geom;
-  int rc = check_sw_band_batch(batch, diag_lo, diag_hi, geom, true);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  return sw_band_call(ctx, batch, scoring, geom, true, nullptr, nullptr, nullptr, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, true);
 }

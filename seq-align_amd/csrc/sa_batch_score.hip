@@ -1,52 +1,22 @@
 // sa_batch_score.hip -- score only over HOST batches: seqalign_nw_score_batch, seqalign_sw_score_batch (and the timing
-// hook seqalign_score_time_ms).  No matrices, no traceback: per chunk the sequences go up, the score kernels
-// (sa_score.hip) run, 4 or 12 bytes per pair come back.
+// hook seqalign_score_time_ms), and SW hit spans: seqalign_sw_span_batch (and seqalign_sw_span_time_ms).  No matrices, no
+// traceback: per chunk the sequences go up, the score kernels (sa_score.hip) or the span kernels (sa_span.hip) run, and 4 or
+// 12 bytes per pair come back, 20 for a span (score, pos_a, pos_b, len_a, len_b), plus the error word.
 //
-// A chunk's pairs are put in classes by row width -- the columns per lane of the one-wave kernel (1 .. 16), or the strips
-// kernel for rows over 1 024 columns -- and the descriptors are laid out class by class, so that each class is one launch
-// that sizes its registers to its own widest row (a ragged batch does not run its short rows at 16 columns per lane).  The
-// sequences stay in pair order; the results are put back in pair order on the host.
+// A chunk's pairs are put in classes by row width -- the columns per lane of the one-wave kernel (score: 1 .. 16, span: 1 .. 6
+// and 8), or the strips kernel for rows over 1 024 (span: 512) columns -- and the descriptors are laid out class by class, so
+// that each class is one launch that sizes its registers to its own widest row (a ragged batch does not run its short rows at
+// 16 columns per lane).  The sequences stay in pair order; the results are put back in pair order on the host.
 //
-// Chunks are cut by device BYTES, not cells: the sequences, 64 bytes of descriptors, status and results per pair, and for
-// the strips kernel the hand-off columns (8 bytes per row and strip) -- a 100 000 x 100 000 pair is 157 MB, not 120 GB.
-#include "sa_ctx.hpp"
+// Chunks are cut by device BYTES, not cells (sa_chunks.hpp): the sequences, 64 (span: 72) bytes of descriptors, status and
+// results per pair, and for the strips kernel the hand-off columns (8 bytes per row and strip; span: 32) and 20 (span: 36)
+// bytes per strip of progress and best cell -- a 100 000 x 100 000 score pair is 157 MB, not 120 GB.
+//
+// The two families are one driver (RowChunkRun) over a traits struct each: what differs is the kernels' parameter block,
+// ladder and launch functions and the bytes named above.
+#include "sa_chunks.hpp"
 
 using namespace sa_host;
-
-namespace {
-
-constexpr int kRowClasses = SA_SCORE_ROW_CLASSES;   // sa_score.hip's instantiations (sa_score_row_class)
-constexpr int kStripClass = kRowClasses;           // rows over SA_SCORE_ROW_MAX columns
-constexpr uint64_t kPairBytes = 64;   // descriptors (32), results (12), status (8), slack
-constexpr uint64_t kChunkMaxPairs = (uint64_t)1 << 24;
-
-// hand-off columns of one pair: strips 0 .. last - 1, len_b + 1 rows each, in int2 units
-uint64_t handoff_rows(uint32_t la, uint32_t lb) {
-  return la > SA_SCORE_ROW_MAX ? (uint64_t)(sa_score_strips_per_pair(la) - 1) * ((uint64_t)lb + 1) : 0;
-}
-
-struct ScoreChunk {
-  uint64_t first = 0, count = 0, seq_bytes = 0;
-};
-
-// plan_chunks' sibling: bytes of sequences + what each pair needs besides, no per-cell term
-std::vector<ScoreChunk> plan_score_chunks(const seqalign_batch_t *b, size_t budget) {
-  std::vector<ScoreChunk> out;
-  ScoreChunk c;
-  uint64_t used = 0;
-  for (uint64_t p = 0; p < b->n_pairs; ++p) {
-    const uint32_t la = b->len_a[p], lb = b->len_b[p];
-    const uint64_t strips = la > SA_SCORE_ROW_MAX ? sa_score_strips_per_pair(la) : 0;
-    const uint64_t need = (uint64_t)la + lb + kPairBytes + 8 * handoff_rows(la, lb) + 20 * strips;
-    if (c.count && (used + need > budget || c.count == kChunkMaxPairs)) { out.push_back(c); c = ScoreChunk(); c.first = p; used = 0; }
-    used += need;
-    c.count++; c.seq_bytes += (uint64_t)la + lb;
-  }
-  if (c.count) out.push_back(c);
-  return out;
-}
-
-}  // namespace
 
 SaFillParams sa_host::score_fill_params(const seqalign_dev_scoring *s) {
   SaFillParams p;
@@ -60,161 +30,181 @@ SaFillParams sa_host::score_fill_params(const seqalign_dev_scoring *s) {
 
 namespace {
 
+struct ScoreTraits {   // sa_score.hip
+  using Params = SaScoreParams;
+  static constexpr int kRowClasses = SA_SCORE_ROW_CLASSES;   // its instantiations (sa_score_row_class)
+  static constexpr uint32_t kRowMax = SA_SCORE_ROW_MAX;
+  static constexpr uint64_t kPairBytes = 64;   // descriptors (32), results (12), status (8), slack
+  static constexpr uint64_t kHandoffBytes = 8, kBestBytes = 16;
+  static constexpr const char *kLaunch = "score kernel launch";
+  static int fields(bool is_sw) { return is_sw ? 3 : 1; }   // result words per pair: score; SW: end_a, end_b
+  static int row_class(uint32_t la) { return sa_score_row_class(la); }
+  static uint32_t strips_per_pair(uint32_t la) { return sa_score_strips_per_pair(la); }
+  static void set_results(Params &p, uint32_t *res, uint64_t n) { p.end_a = res + n; p.end_b = res + 2 * n; }
+  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool is_sw, hipStream_t st) { return sa_launch_score_rows(p, max_a, is_sw, st); }
+  static hipError_t launch_strips(const Params &p, bool is_sw, hipStream_t st) { return sa_launch_score_strips(p, is_sw, st); }
+};
+
+struct SpanTraits {   // sa_span.hip: the SW form only
+  using Params = SaSpanParams;
+  static constexpr int kRowClasses = SA_SPAN_ROW_CLASSES;   // its instantiations (sa_span_row_class)
+  static constexpr uint32_t kRowMax = SA_SPAN_ROW_MAX;
+  static constexpr uint64_t kPairBytes = 72;   // descriptors (32), results (20), status (8), slack
+  static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
+  static constexpr const char *kLaunch = "span kernel launch";
+  static int fields(bool) { return 5; }   // score, pos_a, pos_b, len_a, len_b
+  static int row_class(uint32_t la) { return sa_span_row_class(la); }
+  static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
+  static void set_results(Params &p, uint32_t *res, uint64_t n) {
+    p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
+  }
+  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_span_rows(p, max_a, st); }
+  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_span_strips(p, st); }
+};
+
+// hand-off columns of one pair: strips 0 .. last - 1, len_b + 1 rows each, in rows
+template <class T>
+uint64_t handoff_rows(uint32_t la, uint32_t lb) {
+  return la > T::kRowMax ? (uint64_t)(T::strips_per_pair(la) - 1) * ((uint64_t)lb + 1) : 0;
+}
+
+// plan_chunks' sibling: bytes of sequences + what each pair needs besides, no per-cell term.  A pair over the budget alone
+// is a chunk of its own
+template <class T>
+std::vector<ByteChunk> plan_row_chunks(const seqalign_batch_t *b, size_t budget) {
+  std::vector<ByteChunk> out;
+  (void)cut_chunks(b, budget, [&](uint64_t p) {
+    const uint32_t la = b->len_a[p], lb = b->len_b[p];
+    const uint64_t strips = la > T::kRowMax ? T::strips_per_pair(la) : 0;
+    return PairNeed{(uint64_t)la + lb + T::kPairBytes + T::kHandoffBytes * handoff_rows<T>(la, lb) + (4 + T::kBestBytes) * strips};
+  }, out);
+  return out;
+}
+
 // One chunk laid out and uploaded; launch() enqueues its kernels on ctx->stream (repeatable: it re-zeroes what they count on)
-struct ScoreChunkRun {
-  seqalign_ctx *ctx = nullptr;
+template <class T>
+struct RowChunkRun {
+  static constexpr int kStripClass = T::kRowClasses;   // rows over T::kRowMax columns
   const seqalign_dev_scoring *sc = nullptr;
   bool is_sw = false;
+  ChunkStage<T::kRowClasses> stage;   // classes by len_a; the caller's array: handoff_off
   uint64_t n = 0;
-  std::vector<uint32_t> order;                 // descriptor slot -> pair of the chunk
-  uint64_t cls_first[kRowClasses + 2] = {};    // class c: slots [cls_first[c], cls_first[c + 1])
-  uint32_t cls_max_a[kRowClasses + 1] = {};
-  uint32_t spp = 1;                            // strips per pair of the strips class
-  uint64_t strip_words = 0;                    // its progress words
-  uint64_t *d_off_a = nullptr, *d_off_b = nullptr, *d_hoff = nullptr;
-  uint32_t *d_len_a = nullptr, *d_len_b = nullptr;
-  uint32_t *d_res = nullptr;                   // [4] header (err_flag), then score[n], end_a[n], end_b[n]
+  uint32_t spp = 1;                   // strips per pair of the strips class
+  uint64_t strip_words = 0;           // its progress words
+  uint32_t *d_res = nullptr;          // [4] header (err_flag), then T::fields arrays of n words: score first
 
-  int prepare(const seqalign_batch_t *b, const ScoreChunk &c) {
+  RowChunkRun(seqalign_ctx *ctx, const seqalign_dev_scoring *scoring, bool sw) : sc(scoring), is_sw(sw) { stage.ctx = ctx; }
+
+  int prepare(const seqalign_batch_t *b, const ByteChunk &c) {
     int rc;
+    seqalign_ctx *ctx = stage.ctx;
     n = c.count;
     uint64_t hand_total = 0;
-    order.resize(n);
-    sort_by_row_class(n, [&](uint64_t k) { return b->len_a[c.first + k]; }, order.data(), cls_first, cls_max_a);
-    const uint64_t n_strip = cls_first[kStripClass + 1] - cls_first[kStripClass];
-    spp = n_strip ? sa_score_strips_per_pair(cls_max_a[kStripClass]) : 1;
-    strip_words = ((n_strip + 7) / 8) * 8 * spp;
-
-    // pinned descriptors, slot order: off_a, off_b, handoff_off (u64), len_a, len_b (u32); sequences in pair order
-    const size_t desc_bytes = n * (3 * sizeof(uint64_t) + 2 * sizeof(uint32_t));
-    if ((rc = ctx->h_desc.reserve(desc_bytes)) || (rc = ctx->h_arena.reserve(c.seq_bytes + 16))) return rc;
-    uint64_t *h_off_a = ctx->h_desc.as<uint64_t>(), *h_off_b = h_off_a + n, *h_hoff = h_off_b + n;
-    uint32_t *h_len_a = reinterpret_cast<uint32_t *>(h_hoff + n), *h_len_b = h_len_a + n;
-    std::vector<uint64_t> seq_at(n);
-    { uint64_t pos = 0;
-      for (uint64_t k = 0; k < n; ++k) { seq_at[k] = pos; pos += (uint64_t)b->len_a[c.first + k] + b->len_b[c.first + k]; } }
-    for (uint64_t s = 0; s < n; ++s) {
-      const uint64_t k = order[s], p = c.first + k;
-      const uint32_t la = b->len_a[p], lb = b->len_b[p];
-      h_off_a[s] = seq_at[k]; h_off_b[s] = seq_at[k] + la;
-      h_len_a[s] = la; h_len_b[s] = lb;
-      h_hoff[s] = hand_total; hand_total += handoff_rows(la, lb);
-    }
-    uint8_t *h_seq = ctx->h_arena.as<uint8_t>();
-    constexpr uint64_t kTask = 256;
-    parallel_for((n + kTask - 1) / kTask, [&](uint64_t blk) {
-      for (uint64_t k = blk * kTask, e = std::min(n, (blk + 1) * kTask); k < e; ++k) {
-        const uint64_t p = c.first + k;
-        memcpy(h_seq + seq_at[k], b->arena + b->off_a[p], b->len_a[p]);
-        memcpy(h_seq + seq_at[k] + b->len_a[p], b->arena + b->off_b[p], b->len_b[p]);
-      }
+    rc = stage.lay_out(b, c, T::row_class, [&](uint64_t p) { return b->len_a[p]; }, 1, 0, [&](uint64_t s, uint64_t p) {
+      stage.h_u64(0)[s] = hand_total; hand_total += handoff_rows<T>(b->len_a[p], b->len_b[p]);
     });
-
-    if ((rc = ctx->arena.reserve(c.seq_bytes + 16)) || (rc = ctx->off_a.reserve(desc_bytes)) || (rc = ctx->status.reserve(n * 8)) ||
-        (rc = ctx->best_score.reserve(16 + 12 * n)))
+    if (rc) return rc;
+    const uint64_t n_strip = stage.class_size(kStripClass);
+    spp = n_strip ? T::strips_per_pair(stage.cls_max[kStripClass]) : 1;
+    strip_words = ((n_strip + 7) / 8) * 8 * spp;
+    if ((rc = ctx->best_score.reserve(16 + 4 * T::fields(true) * n))) return rc;
+    if (n_strip && ((rc = ctx->strip_progress.reserve(4 * sa_strip_best_word(strip_words) + T::kBestBytes * strip_words)) ||
+                    (rc = ctx->score_handoff.reserve(T::kHandoffBytes * hand_total + 16))))
       return rc;
-    if (n_strip && ((rc = ctx->strip_progress.reserve(sa_strip_progress_bytes(strip_words))) ||
-                    (rc = ctx->score_handoff.reserve(8 * hand_total + 16))))
-      return rc;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(ctx->off_a.p, h_off_a, desc_bytes, hipMemcpyHostToDevice, st));
-    if (c.seq_bytes) HIP_TRY(hipMemcpyAsync(ctx->arena.p, h_seq, c.seq_bytes, hipMemcpyHostToDevice, st));
-    d_off_a = ctx->off_a.as<uint64_t>(); d_off_b = d_off_a + n; d_hoff = d_off_b + n;
-    d_len_a = reinterpret_cast<uint32_t *>(d_hoff + n); d_len_b = d_len_a + n;
     d_res = ctx->best_score.as<uint32_t>();
-    return SEQALIGN_OK;
+    return stage.upload();
   }
 
   int launch() {
+    seqalign_ctx *ctx = stage.ctx;
     hipStream_t st = ctx->stream;
     HIP_TRY(hipMemsetAsync(d_res, 0, 16, st));
     const SaFillParams f0 = score_fill_params(sc);
-    for (int x = 0; x <= kRowClasses; ++x) {
-      const uint64_t s0 = cls_first[x], m = cls_first[x + 1] - s0;
+    for (int x = 0; x <= T::kRowClasses; ++x) {
+      const uint64_t s0 = stage.cls_first[x], m = stage.class_size(x);
       if (!m) continue;
-      SaScoreParams p;
+      typename T::Params p;
       memset(&p, 0, sizeof(p));
       p.f = f0;
-      p.f.arena = ctx->arena.as<uint8_t>();
-      p.f.off_a = d_off_a + s0; p.f.off_b = d_off_b + s0; p.f.len_a = d_len_a + s0; p.f.len_b = d_len_b + s0;
-      p.f.status = ctx->status.as<uint64_t>() + s0;
-      p.f.n_pairs = (uint32_t)m;
+      stage.set_slots(p.f, s0, m);
       p.score = reinterpret_cast<int32_t *>(d_res + 4) + s0;
-      p.end_a = d_res + 4 + n + s0; p.end_b = d_res + 4 + 2 * n + s0;
+      T::set_results(p, d_res + 4 + s0, n);
       p.err_flag = d_res;
       hipError_t e;
       if (x == kStripClass) {
         p.progress = ctx->strip_progress.as<uint32_t>();
         p.strip_best = p.progress + sa_strip_best_word(strip_words);
         p.handoff = ctx->score_handoff.as<int32_t>();
-        p.handoff_off = d_hoff + s0;
+        p.handoff_off = stage.d_u64(0) + s0;
         p.strips_per_pair = spp;
         HIP_TRY(hipMemsetAsync(p.progress, 0, 4 * (strip_words + 1), st));
         HIP_TRY(hipMemsetAsync(p.f.status, 0xff, 8 * m, st));
-        e = sa_launch_score_strips(p, is_sw, st);
+        e = T::launch_strips(p, is_sw, st);
       } else {
-        e = sa_launch_score_rows(p, cls_max_a[x], is_sw, st);
+        e = T::launch_rows(p, stage.cls_max[x], is_sw, st);
       }
-      if (e != hipSuccess) return fail_hip(e, "score kernel launch");
+      if (e != hipSuccess) return fail_hip(e, T::kLaunch);
     }
     return SEQALIGN_OK;
   }
 
-  // results home, in pair order; the lowest failing pair of the chunk named
-  int finish(uint64_t first, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, uint64_t *fail_pair = nullptr) {
+  // results home, in pair order (out: the arrays behind the score); the lowest failing pair of the chunk named
+  int finish(int32_t *out_score, uint32_t *const *out, uint64_t *fail_pair) {
     int rc;
-    const size_t words = 4 + (is_sw ? 3 : 1) * n;
-    if ((rc = ctx->h_misc.reserve(std::max<size_t>(4 * words, 8 * n)))) return rc;
+    seqalign_ctx *ctx = stage.ctx;
+    const int fields = T::fields(is_sw);
+    const size_t words = 4 + fields * n;
+    if ((rc = ctx->h_misc.reserve(4 * words))) return rc;
     uint32_t *h = ctx->h_misc.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(stream_wait_spinning(ctx->stream));
-    if (h[0]) {
-      std::vector<uint64_t> status(n);
-      HIP_TRY(hipMemcpy(status.data(), ctx->status.p, 8 * n, hipMemcpyDeviceToHost));
-      uint64_t worst = ~0ull;
-      for (uint64_t s = 0; s < n; ++s)
-        if (status[s] != ~0ull) worst = std::min<uint64_t>(worst, order[s]);
-      if (fail_pair) *fail_pair = first + worst;
-      return fail_unknown_pair(first + worst);
-    }
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
-    const uint32_t *ha = h + 4 + n, *hb = h + 4 + 2 * n;
-    constexpr uint64_t kTask = 16384;
-    parallel_for((n + kTask - 1) / kTask, [&](uint64_t blk) {
-      for (uint64_t s = blk * kTask, e = std::min(n, (blk + 1) * kTask); s < e; ++s) {
-        const uint64_t p = first + order[s];
-        out_score[p] = hs[s];
-        if (is_sw) { out_end_a[p] = ha[s]; out_end_b[p] = hb[s]; }
-      }
-    });
+    if (h[0]) return stage.fail_from_status(fail_pair);
+    stage.scatter(h + 4, fields, out_score, out);
     return SEQALIGN_OK;
   }
 };
 
-int check_score_batch(const seqalign_batch_t *b) {   // check_batch without the 2^31-cell cap
-  if (!batch_readable(b)) return SEQALIGN_E_ARG;
+// seqalign_*_score_batch / seqalign_sw_span_batch behind their entry checks: every chunk prepared, launched, brought home
+template <class T>
+int row_batch_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw, int32_t *out_score,
+                   uint32_t *const *out, uint64_t *fail_pair) {
+  if (!batch_readable(batch)) return SEQALIGN_E_ARG;   // check_batch without the 2^31-cell cap
+  if (batch->n_pairs == 0) return SEQALIGN_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  int rc;
+  seqalign_dev_scoring *sc = nullptr;
+  if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
+  StreamSyncOnExit sync(ctx->stream);
+  for (const ByteChunk &c : plan_row_chunks<T>(batch, ctx->chunk_budget)) {
+    RowChunkRun<T> run(ctx, sc, is_sw);
+    if ((rc = run.prepare(batch, c)) || (rc = run.launch()) || (rc = run.finish(out_score, out, fail_pair))) return rc;
+  }
   return SEQALIGN_OK;
+}
+
+// the launches of a batch that is one chunk, `repeats` times between HIP events; `name`: the hook's, for its message
+template <class T>
+int row_time_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw, int repeats, float *ms_each,
+                  const char *name) {
+  if (!batch_readable(batch) || batch->n_pairs == 0) return SEQALIGN_E_ARG;
+  const std::vector<ByteChunk> chunks = plan_row_chunks<T>(batch, ctx->chunk_budget);
+  if (chunks.size() != 1) { set_last_error(std::string(name) + ": the batch does not fit one chunk"); return SEQALIGN_E_ARG; }
+  HIP_TRY(hipSetDevice(ctx->device));
+  int rc;
+  seqalign_dev_scoring *sc = nullptr;
+  if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
+  StreamSyncOnExit sync(ctx->stream);
+  RowChunkRun<T> run(ctx, sc, is_sw);
+  if ((rc = run.prepare(batch, chunks[0]))) return rc;
+  return time_launches(ctx->stream, repeats, ms_each, [&] { return run.launch(); });
 }
 
 }  // namespace
 
 int sa_host::score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw,
                               int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, uint64_t *fail_pair) {
-  int rc = check_score_batch(batch);
-  if (rc) return rc;
-  if (batch->n_pairs == 0) return SEQALIGN_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  seqalign_dev_scoring *sc = nullptr;
-  if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
-  StreamSyncOnExit sync(ctx->stream);
-  for (const ScoreChunk &c : plan_score_chunks(batch, ctx->chunk_budget)) {
-    ScoreChunkRun run;
-    run.ctx = ctx; run.sc = sc; run.is_sw = is_sw;
-    if ((rc = run.prepare(batch, c)) || (rc = run.launch()) ||
-        (rc = run.finish(c.first, out_score, out_end_a, out_end_b, fail_pair)))
-      return rc;
-  }
-  return SEQALIGN_OK;
+  uint32_t *const out[2] = {out_end_a, out_end_b};
+  return row_batch_call<ScoreTraits>(ctx, batch, scoring, is_sw, out_score, out, fail_pair);
 }
 
 extern "C" int seqalign_nw_score_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
@@ -235,26 +225,21 @@ extern "C" int seqalign_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_
                                       int repeats, float *ms_each) {
   if (!ctx || !scoring || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
   CallScope scope(ctx);
-  int rc = check_score_batch(batch);
-  if (rc) return rc;
-  if (batch->n_pairs == 0) return SEQALIGN_E_ARG;
-  const std::vector<ScoreChunk> chunks = plan_score_chunks(batch, ctx->chunk_budget);
-  if (chunks.size() != 1) { set_last_error("seqalign_score_time_ms: the batch does not fit one chunk"); return SEQALIGN_E_ARG; }
-  HIP_TRY(hipSetDevice(ctx->device));
-  seqalign_dev_scoring *sc = nullptr;
-  if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
-  StreamSyncOnExit sync(ctx->stream);
-  ScoreChunkRun run;
-  run.ctx = ctx; run.sc = sc; run.is_sw = is_sw != 0;
-  if ((rc = run.prepare(batch, chunks[0]))) return rc;
-  EventList events;
-  for (int r = 0; r < 2 * repeats; ++r) HIP_TRY(events.add());
-  for (int r = 0; r < repeats; ++r) {
-    HIP_TRY(hipEventRecord(events.ev[2 * r], ctx->stream));
-    if ((rc = run.launch())) return rc;
-    HIP_TRY(hipEventRecord(events.ev[2 * r + 1], ctx->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  for (int r = 0; r < repeats; ++r) HIP_TRY(hipEventElapsedTime(&ms_each[r], events.ev[2 * r], events.ev[2 * r + 1]));
-  return SEQALIGN_OK;
+  return row_time_call<ScoreTraits>(ctx, batch, scoring, is_sw != 0, repeats, ms_each, "seqalign_score_time_ms");
+}
+
+extern "C" int seqalign_sw_span_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                      int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a,
+                                      uint32_t *out_len_b) {
+  if (!ctx || !scoring || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);
+  uint32_t *const out[4] = {out_pos_a, out_pos_b, out_len_a, out_len_b};
+  return row_batch_call<SpanTraits>(ctx, batch, scoring, true, out_score, out, nullptr);
+}
+
+extern "C" int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                                        float *ms_each) {
+  if (!ctx || !scoring || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);
+  return row_time_call<SpanTraits>(ctx, batch, scoring, true, repeats, ms_each, "seqalign_sw_span_time_ms");
 }

@@ -5,12 +5,13 @@
 //                     single-pair call
 //   sa_batch.hip      host-level chunking, seqalign_fill_batch, seqalign_nw_batch
 //   sa_batch_sw.hip   seqalign_sw_batch (best hit / device enumeration / host enumeration)
-//   sa_batch_score.hip seqalign_nw_score_batch / seqalign_sw_score_batch (score only)
-//   sa_batch_span.hip  seqalign_sw_span_batch (SW hit spans: score, start and end, no traceback)
+//   sa_batch_score.hip seqalign_nw_score_batch / seqalign_sw_score_batch (score only) and seqalign_sw_span_batch (SW hit
+//                     spans: score, start and end, no traceback)
 //   sa_batch_score_cross.hip seqalign_nw_score_cross / seqalign_sw_score_cross (score only, every query x every target),
 //                     and seqalign_*_score_search (the best k targets of every query; sa_score_select.hip selects)
 //   sa_batch_long.hip seqalign_nw_align_long / seqalign_sw_align_long (pairs of any size: checkpoints, blocks, walks)
 //   sa_batch_band.hip seqalign_nw_score_banded / seqalign_nw_align_banded (NW inside a diagonal band)
+//   sa_chunks.hpp     the chunk driver that sa_batch_score.hip and sa_batch_band.hip share (chunks cut by device bytes)
 //   sa_multi.hip      the same calls over several contexts (GPUs) from one process
 #pragma once
 #include <hip/hip_runtime.h>
@@ -410,7 +411,7 @@ struct CallScope {
   CallScope &operator=(const CallScope &) = delete;
 };
 
-void async_shutdown(seqalign_ctx *ctx);
+void async_shutdown(seqalign_ctx *ctx);   // sa_async.hip: drain the submitted jobs, join the lanes (seqalign_ctx_destroy)
 
 // sa_batch_score.hip, shared with the cross calls (sa_batch_score_cross.hip): the score kernels' SaFillParams of an uploaded
 // scoring, and seqalign_*_score_batch without its entry checks -- fail_pair (optional): the failing pair it names
@@ -422,7 +423,7 @@ int score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const s
 int score_cross_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets);
 int score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                      const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b,
-                     uint64_t q_base);   // sa_async.hip: drain the submitted jobs, join the lanes (seqalign_ctx_destroy)
+                     uint64_t q_base);
 // ... and the top-k search (seqalign_*_score_search) on the same tiles: its checks (E_ARG: k, the sets, n_targets), and
 // one context's call
 int score_search_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets, uint32_t k);

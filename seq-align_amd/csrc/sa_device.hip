@@ -3,7 +3,7 @@
 // Host code above this file is C; this file is the only place that talks to the
 // HIP runtime.  No torch / C++ types cross the boundary.  No CPU fallback: when
 // the runtime or a device is missing every entry point reports it.
-#include "sa_ctx.hpp"
+#include "sa_chunks.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -706,19 +706,8 @@ extern "C" int seqalign_time_fill_ms(seqalign_ctx_t *ctx, const seqalign_dev_sco
   if (!ctx || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
   CallScope scope(ctx);
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  EventList events;   // destroyed on every exit path
-  for (int r = 0; r < 2 * repeats; ++r) HIP_TRY(events.add());
-  const std::vector<hipEvent_t> &ev = events.ev;
   StreamSyncOnExit sync(st);
-  int rc = SEQALIGN_OK;
-  for (int r = 0; r < repeats && rc == SEQALIGN_OK; ++r) {
-    HIP_TRY(hipEventRecord(ev[2 * r], st));
-    rc = seqalign_fill_batch_device(ctx, scoring, batch, kernel, st);
-    HIP_TRY(hipEventRecord(ev[2 * r + 1], st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  for (int r = 0; r < repeats && rc == SEQALIGN_OK; ++r) HIP_TRY(hipEventElapsedTime(&ms_each[r], ev[2 * r], ev[2 * r + 1]));
-  return rc;
+  return time_launches(st, repeats, ms_each, [&] { return seqalign_fill_batch_device(ctx, scoring, batch, kernel, st); });
 }
 
 static int launch_traceback(seqalign_ctx_t *ctx, const seqalign_dev_scoring_t *sc, const seqalign_dev_batch_t *b,

@@ -310,6 +310,19 @@ def test_chunks_and_memory(ctx):
     assert [int(s) for s in score] == [int(s) for s in one_chunk]
 
 
+def test_time_hook_refuses_a_batch_of_several_chunks(ctx):
+    """seqalign_band_score_time_ms times the launches of ONE chunk: a batch of more than 1 MiB at chunk_bytes = 1 MiB is
+    SEQALIGN_E_ARG with the hook's own message; at the default budget it returns `repeats` positive times."""
+    sc = S.make_scoring({"preset": "default"})
+    batch = W.from_pairs([(b"ACGT" * 50, b"ACGTTACGTACGAT" * 14)] * 4000)   # 200 + 196 + 64 bytes per pair: 1.8 MB
+    with ctx.options(chunk_bytes=1 << 20):
+        with pytest.raises(S.SeqAlignError) as err:
+            ctx.band_score_time_ms(batch, sc, 10, repeats=3)
+    assert err.value.code == S.E_ARG and "seqalign_band_score_time_ms: the batch does not fit one chunk" in str(err.value), str(err.value)
+    ms = ctx.band_score_time_ms(batch, sc, 10, repeats=3)
+    assert len(ms) == 3 and all(float(t) > 0 for t in ms), ms
+
+
 def test_unknown_pair_inside_and_outside_the_band(ctx):
     """X (in seq_a) against Y (in seq_b) has no score; every other pair of letters has one."""
     sc = S.make_scoring({"preset": "DNA_hybridization",

@@ -355,6 +355,19 @@ def test_three_chunks_give_the_same_results(ctx):
     assert [int(s) for s in score[0]] == [cell[0] for cell, hit in want]
 
 
+def test_time_hook_refuses_a_batch_of_several_chunks(ctx):
+    """seqalign_sw_band_score_time_ms times the launches of ONE chunk: a batch of more than 1 MiB at chunk_bytes = 1 MiB is
+    SEQALIGN_E_ARG with the hook's own message; at the default budget it returns `repeats` positive times."""
+    sc, _ = scoring(PLAIN)
+    batch = W.from_pairs([(b"ACGT" * 50, b"ACGTTACGTACGAT" * 14)] * 4000)   # 200 + 196 + 80 bytes per pair: 1.9 MB
+    with ctx.options(chunk_bytes=1 << 20):
+        with pytest.raises(S.SeqAlignError) as err:
+            ctx.sw_band_score_time_ms(batch, sc, -10, 10, repeats=3)
+    assert err.value.code == S.E_ARG and "seqalign_sw_band_score_time_ms: the batch does not fit one chunk" in str(err.value), str(err.value)
+    ms = ctx.sw_band_score_time_ms(batch, sc, -10, 10, repeats=3)
+    assert len(ms) == 3 and all(float(t) > 0 for t in ms), ms
+
+
 def wide_pair(batch):
     return batch.seq_a(1), batch.seq_b(1)
 

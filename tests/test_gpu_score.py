@@ -201,6 +201,78 @@ def test_unknown_character_pair_names_the_lowest_pair(ctx, is_sw):
         assert len(got) == 5 and len(set(got.tolist())) == 1
 
 
+# ---------------------------------------------------------------- 4b. several chunks --
+MIB = 1 << 20   # the smallest chunk_bytes the option accepts
+
+
+def chunked_pairs(seed, strip_len_a, n=5000):
+    """n pairs with both lengths drawn from 100 .. 300 (len_a + len_b + 64 bytes of a chunk each: three chunks of 1 MiB at
+    least), and three pairs of the strips class (len_a from strip_len_a, len_b <= 200) first, in the middle and last, so that
+    several chunks carry a strips launch."""
+    rng = W.Rng(seed)
+    letters = np.frombuffer(b"ACGT", np.uint8)
+    seq = lambda k: letters[rng.below(4, k).astype(np.int64)].tobytes()
+    lens = 100 + rng.below(201, 2 * n).astype(np.int64)
+    pairs = [(seq(int(lens[2 * k])), seq(int(lens[2 * k + 1]))) for k in range(n)]
+    strips = [(seq(la), seq(lb)) for la, lb in zip(strip_len_a, (200, 133, 57))]
+    return [strips[0]] + pairs[:n // 2] + [strips[1]] + pairs[n // 2:] + [strips[2]]
+
+
+@pytest.mark.parametrize("is_sw", [0, 1])
+def test_several_chunks_equal_the_oracle(ctx, is_sw):
+    """One batch of more than 2 MiB at chunk_bytes = 1 MiB: every pair equals the oracle, and the call launched more often
+    than at the default budget (which is how the test knows the batch was cut)."""
+    sc = S.make_scoring(SCORINGS["dna_sw" if is_sw else "dna"][0])
+    batch = W.from_pairs(chunked_pairs(1717 + is_sw, (1025, 1600, 1301)))
+    assert int(batch.len_a.sum()) + int(batch.len_b.sum()) + 64 * batch.n_pairs > 2 * MIB
+    want = oracle_want(oracle_scoring_of(sc), batch, is_sw)
+    whole = got_of(ctx, batch, sc, is_sw)
+    at_default = ctx.last_call()
+    with ctx.options(chunk_bytes=MIB):
+        cut = got_of(ctx, batch, sc, is_sw)
+        at_mib = ctx.last_call()
+    print(f"score_rows / score_strips launches: default budget {at_default}, 1 MiB {at_mib}")
+    for tag, got in (("default budget", whole), ("1 MiB", cut)):
+        bad = [(p, got[p], want[p]) for p in range(batch.n_pairs) if got[p] != want[p]]
+        assert not bad, (tag, len(bad), bad[:5])
+    assert at_mib["score_rows"][0] > at_default["score_rows"][0], (at_mib, at_default)
+    assert at_mib["score_strips"][0] > at_default["score_strips"][0] == 1, (at_mib, at_default)
+
+
+@pytest.mark.parametrize("is_sw", [0, 1])
+def test_unknown_character_pair_in_the_last_chunk(ctx, is_sw):
+    """12 000 pairs of 194 bytes each are three chunks of 1 MiB (5 405 pairs fill one): an X in two pairs of the last chunk
+    names the lower one by its number in the whole batch -- first in a narrow pair, then in a pair of the strips class."""
+    hyb = S.make_scoring({"preset": "DNA_hybridization"})
+    good = (b"ACGT" * 15, b"TTACGTACGTACGA" * 5)
+    for long_a in (0, 1500):
+        pairs = [good] * 12000
+        bad_a = b"ACGT" * (long_a // 4) if long_a else good[0]
+        pairs[11000] = (bad_a[:7] + b"X" + bad_a[8:], good[1])
+        pairs[11500] = (good[0], good[1][:20] + b"X" + good[1][21:])
+        batch = W.from_pairs(pairs)
+        with ctx.options(chunk_bytes=MIB):
+            with pytest.raises(S.SeqAlignError) as err:
+                (ctx.sw_score if is_sw else ctx.nw_score)(batch, hyb)
+            ran = ctx.last_call()
+        assert err.value.code == S.E_UNKNOWN_PAIR and "pair 11000:" in str(err.value), str(err.value)
+        assert ran["score_rows"][0] == 3 and ("score_strips" in ran) == bool(long_a), ran   # the failure came in the third chunk
+
+
+def test_time_hook_refuses_a_batch_of_several_chunks(ctx):
+    """seqalign_score_time_ms times the launches of ONE chunk: a batch of more than 1 MiB at chunk_bytes = 1 MiB is
+    SEQALIGN_E_ARG with the hook's own message; at the default budget it returns `repeats` positive times."""
+    sc = S.make_scoring({"preset": "default"})
+    batch = W.from_pairs([(b"ACGT" * 50, b"TTACGTACGTACGA" * 10)] * 4000)   # 404 bytes per pair: 1.6 MB
+    for is_sw in (0, 1):
+        with ctx.options(chunk_bytes=MIB):
+            with pytest.raises(S.SeqAlignError) as err:
+                ctx.score_time_ms(batch, sc, is_sw, repeats=3)
+        assert err.value.code == S.E_ARG and "seqalign_score_time_ms: the batch does not fit one chunk" in str(err.value), str(err.value)
+        ms = ctx.score_time_ms(batch, sc, is_sw, repeats=3)
+        assert len(ms) == 3 and all(float(t) > 0 for t in ms), ms
+
+
 # ---------------------------------------------------------------- 5. beyond the cap --
 BEYOND_CAP = r"""
 import sys, numpy as np
