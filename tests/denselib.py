@@ -300,3 +300,75 @@ def counted_sw_cases(scoring: str):
         yield "uniform:" + shape, floor, sw_uniform(shape, scoring)
         yield "ragged:" + shape, floor, sw_ragged(shape, scoring)
     yield "planted-twice", 8, sw_planted_twice(scoring)
+
+
+# ------------------------------------------------------------------------------------- the span, band and long-SW cases ---
+# tests/test_gpu_sw_span_dense.py and tests/test_gpu_band_dense.py run these lists; tests/test_span_band_dense_argument_cpu.py
+# argues on the oracle alone that they contain what those files claim.
+SPAN_STRIP_COLS = 512
+# (len_a, len_b), one per class of the span launcher: 1, 2, 3, 3, 4, 5, 6 and 8 columns per lane, and a pair of 1 100 rows (many
+# 64-row code fetches) ...
+SPAN_ROWS_SHAPES = ((60, 60), (100, 90), (130, 90), (190, 150), (250, 120), (320, 100), (384, 100), (512, 100), (150, 1100))
+# ... and rows of two to five strips; the last three run through several hand-off blocks of 64 rows
+SPAN_STRIPS_SHAPES = ((513, 150), (577, 129), (700, 64), (1100, 150), (1600, 90), (1100, 1100), (1600, 700), (2100, 300))
+SPAN_K = range(8)
+
+
+def straddling(la: int, lb: int, k: int = 0, matches: int = 1, seam: int = SPAN_STRIP_COLS):
+    """alternation's two stretches, min(la, lb) letters each and without the tail; seq_a's stands in la letters of y -- which
+    seq_b lacks -- with column `seam` in its middle (as far as la lets it): the dense hit crosses the seam wherever
+    alternation's own sits left or right of it."""
+    ua, ub, (x, y, z, w) = _units(k, matches)
+    n = min(la, lb)
+    at = max(0, min(la - n, seam - n // 2))
+    a = bytes([y]) * at + (ua * (n // len(ua) + 1))[:n] + bytes([y]) * (la - at - n)
+    return a, (ub * (lb // len(ub) + 1))[:lb]
+
+
+def span_counted(la: int, lb: int, scoring: str):
+    """The counted pairs of one span shape: alternation, k = 0 .. 7."""
+    return [alternation(la, lb, k, matches_of(scoring)) for k in SPAN_K]
+
+
+def span_seam(la: int, lb: int, scoring: str):
+    """The seam pairs of a shape of several strips: straddling, k = 0 .. 7, where the stretch can be centred on column 512
+    (not at 513 x 150: there alternation's own hits reach the last column, 513)."""
+    if la <= SPAN_STRIP_COLS or la - min(la, lb) < SPAN_STRIP_COLS - min(la, lb) // 2:
+        return []
+    return [straddling(la, lb, k, matches_of(scoring)) for k in SPAN_K]
+
+
+def span_added(la: int, lb: int, scoring: str):
+    """Spaced pairs of the shape: added to the calls, never counted."""
+    return [spaced(la, lb, 23 * la + lb + k, k, matches=matches_of(scoring)) for k in (1, 4)]
+
+
+# banded SW: (len_a, len_b) of the alternation pairs, k = 0 .. 5, and the bands (diag_lo, diag_hi) of each
+BAND_SHAPES = ((150, 150), (191, 150), (500, 500))
+BAND_K = range(6)
+
+
+def sw_bands(la: int, lb: int):
+    """The whole matrix; the excursion of the unbanded hit and one diagonal more; exactly it, (0, +1): I->D; its mirror
+    (-1, 0): the same score through D->I only; the main diagonal alone; a wide band; a band the hit's diagonals lie outside."""
+    return [(-lb, la), (-1, 1), (0, 1), (-1, 0), (0, 0), (-40, 40), (30, 60)]
+
+
+def band_pairs(la: int, lb: int, scoring: str):
+    return [alternation(la, lb, k, matches_of(scoring)) for k in BAND_K]
+
+
+def band_added(la: int, lb: int, scoring: str):
+    """Spaced pairs of the shape, added to the band calls: alternation's period is two columns (three steps), so its
+    transitions stand in every second column only; the spacers shift the stretches onto every column of a strip of 64."""
+    return [spaced(la, lb, 13 * la + k, k, matches=matches_of(scoring)) for k in (1, 4)]
+
+
+# past the narrow calls' cap of 1 024 diagonals: one pair, SW under swdense within (-600, 600), NW under cheap0 with band 600
+PAST_CAP = dict(shape=(1300, 1300), sw=("swdense", -600, 600), nw=("cheap0", 600))
+
+
+def long_sw_pairs():
+    """test_nw_align_long_seams_inside_alternating_stretches's pairs and one of three strips' width."""
+    return [alternation(150, 150, 0), alternation(191, 150, 4), alternation(500, 500, 1), spaced(300, 260, 11, 2),
+            spaced(150, 150, 12, 3), alternation(31, 40, 5)] + long_run_pairs()[:2] + [alternation(1100, 300)]
