@@ -582,7 +582,8 @@ int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
  * returned and named in seqalign_last_error) are seqalign_sw_score_batch's.  SEQALIGN_E_TRACEBACK cannot occur: in SW a
  * positive cell always has a predecessor the walker accepts.  The launches are recorded as "score_rows" /
  * "score_strips" (items: pairs).
- * Not in this call: no cross, search, banded, _submit or command-line form, and no option steers it. */
+ * Not in this call: no cross, search, _submit or command-line form, and no option steers it (banded, up to 512 diagonals:
+ * seqalign_sw_span_banded below). */
 int seqalign_sw_span_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                            uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b);
 /* ... over several contexts (GPUs): contiguous ranges of nearly equal cells, results exactly the single-context call's */
@@ -593,6 +594,38 @@ int seqalign_sw_span_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const s
  * batch (one chunk) is uploaded once, then its kernels run `repeats` times, each launch between two HIP events. */
 int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
                              float *ms_each);
+/* ---- banded SW hit spans: start and end of the best local hit inside a band, no traceback ---- */
+/* seqalign_sw_span_batch over the banded SW matrices: the five integers a mapper reports per read at the cost of a banded
+ * sweep, nothing stored per cell and no walk.
+ *   Band and matrices are seqalign_sw_score_banded's ("banded SW" below), word for word: the caller's bounds diag_lo[p] <=
+ *   diag_hi[p], anywhere in int32, clipped to [-len_b, len_a]; every cell outside the band and every border cell holds 0 in
+ *   all three matrices; a band that is empty after clipping is legal and gives five zeros.
+ *   Per pair the fields of the hit seqalign_sw_align_banded(min_score = 1) delivers, without its strings: score; pos_a, pos_b
+ *   (0-based: the cell in which alignment_reverse_move's walk from the best band cell reaches score 0, tie order GAP_A,
+ *   GAP_B, MATCH); len_a, len_b, so that pos + len is seqalign_sw_score_banded's end_a / end_b.  All five are 0 when no band
+ *   cell is above 0.  With gap_extend > 0 the start may lie one diagonal OUTSIDE the band, exactly as the align call's does:
+ *   the walk steps onto a cell that reads 0 and stops there.
+ *   SEQALIGN_E_ARG, SEQALIGN_E_DOMAIN, SEQALIGN_E_NO_DEVICE, SEQALIGN_E_NOMEM   as seqalign_sw_score_banded
+ *   SEQALIGN_E_UNKNOWN_PAIR   a character pair without a score INSIDE the band only (lowest failing pair named)
+ *   SEQALIGN_E_TOO_LARGE      a pair whose clipped width exceeds SEQALIGN_SPAN_BAND_MAX_WIDTH (pair and width named), or
+ *                             len_a + len_b >= 2^31; found from lengths and bounds alone, before any device work
+ *   SEQALIGN_E_TRACEBACK      cannot occur: a positive band cell always has a predecessor the walker accepts, a cell outside
+ *                             the band being one that holds 0 and stops the walk
+ * No 2^31-cell cap.  Device bytes per pair: len_a + len_b + 88 (the score call's and the wider result record); chunks are cut
+ * within the option chunk_bytes; 20 bytes per pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band
+ * diagonals per lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted under band_score, one
+ * per width class of a chunk.
+ * Not in this call: widths 513 .. 1 024 and a _banded_wide (strip pipeline) form -- the two-word span sweep does not fit the
+ * registers at 12 and 16 columns per lane; they wait for the one-word span -- and no cross, search, _multi,
+ * _submit or command-line form, and no option steers it. */
+#define SEQALIGN_SPAN_BAND_MAX_WIDTH 512
+int seqalign_sw_span_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                            const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
+                            uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b);
+/* Timing hook (tools/sw_span_banded_bench.py), the sibling of seqalign_sw_band_score_time_ms for seqalign_sw_span_banded:
+ * one chunk, `repeats` launches between HIP events */
+int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
 /* ---- long pairs: alignments past the 2^31-cell cap --------------------------------- */
 /* The alignments of seqalign_nw_batch and of seqalign_sw_batch with max_hits = 1 -- same arguments, capacities and results,
  * byte for byte: score, both gapped strings and, SW, the hit's pos_a / pos_b / len_a / len_b / length -- for pairs of any

@@ -544,6 +544,17 @@ static inline void sa_band_sw_rows(uint32_t len_a, uint32_t len_b, int64_t d_lo,
 hipError_t sa_launch_band_sw_score(const SaBandSwParams &p, uint32_t max_width, hipStream_t stream);
 hipError_t sa_launch_band_sw_fill(const SaBandSwParams &p, uint32_t max_width, hipStream_t stream);
 hipError_t sa_launch_band_sw_walk(const SaBandSwParams &p, hipStream_t stream);
+/* ---- banded SW hit spans (seqalign_sw_span_banded, sa_band_span.hip): the banded SW score sweep with SaSpanParams' results.
+ * Pair k of a launch has the clipped band of SaBandSwParams (1 <= width <= SA_SPAN_BAND_MAX_WIDTH); b.score[k], pos_a[k],
+ * pos_b[k], len_a[k], len_b[k] = the fields of the first hit over the banded matrices (all 0 when no band cell is above 0);
+ * b.f.status / b.err_flag as above.  b.str_off, b.out_a, b.out_b and b.meta4 are unused. */
+#define SA_SPAN_BAND_MAX_WIDTH 512u
+struct SaBandSpanParams {
+  SaBandParams b;
+  uint32_t *pos_a, *pos_b, *len_a, *len_b;
+};
+/* every pair of the launch has width <= max_width <= SA_SPAN_BAND_MAX_WIDTH; max_width picks the columns per lane */
+hipError_t sa_launch_band_span(const SaBandSpanParams &p, uint32_t max_width, hipStream_t stream);
 /* ---- the wide banded calls (seqalign_*_banded_wide, sa_band_strips.hip): the same bands, matrices and layouts at any width,
  * one wave per (pair, strip of strip_cols columns) in the strips pipeline.  s (NW: s.b alone) is the narrow launch's record;
  * f.status must hold ~0 per pair before the launch (the strips atomicMin into it).  Pair k has max(1, ceil(len_a /

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, seqalign_sw_span_batch, *_score_cross,
-*_score_search, *_align_long, the banded NW calls and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+*_score_search, *_align_long, the banded NW calls, seqalign_sw_span_banded and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -56,7 +56,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
     rng = W.Rng(seed)
     ctx = ctx or S.Context(0)
     t_end = time.time() + seconds
-    n = {"trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0}
+    n = {"trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -221,6 +221,20 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
                     fail("BAND ALIGN", spec, sub, bands, got, [x[1] for x in both])
             n["banded"] += len(sub)
 
+        # ---- banded SW hit spans: at most 4 pairs of at most 260 x 260, bounds on either side of the pair's diagonals, up to 140 wide
+        small = [p for p in range(12) if max(len(pairs[p][0]), len(pairs[p][1])) <= 260][:4]
+        if small:
+            sub = [pairs[p] for p in small]
+            lo = [int((v[5] + 31 * p) % 300) - 200 for p in small]
+            hi = [lo[k] + int((v[6] + 17 * p) % 140) for k, p in enumerate(small)]
+            hits = [BS.expected(osc, a, b, lo[k], hi[k], 1)[1] for k, (a, b) in enumerate(sub)]
+            want = [(h["score"], h["pos_a"], h["pos_b"], h["len_a"], h["len_b"]) if h else (0, 0, 0, 0, 0) for h in hits]
+            res = ctx.sw_span_banded(W.from_pairs(sub), sc, lo, hi)
+            got = [tuple(int(x[k]) for x in res) for k in range(len(sub))]
+            if got != want:
+                fail("SW SPAN BANDED", spec, sub, lo, hi, got, want)
+            n["span_banded"] += len(sub)
+
         # ---- the wide banded calls: two small pairs (the narrow calls must agree) and one of 1 025 .. 1 624 columns whose band is
         # 700 .. 1 500 diagonals wide, under a random strip width
         if wide_calls:
@@ -264,7 +278,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
         n["trials"] += 1
 
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
-          f"{n['score']} scores, {n['span']} hit spans, {n['cross']} cross cells, {n['search']} searches, {n['long']} long alignments, {n['banded']} banded "
+          f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['cross']} cross cells, {n['search']} searches, {n['long']} long alignments, {n['banded']} banded "
           f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results identical to the oracle "
           f"(seed {seed})", flush=True)
     return n
