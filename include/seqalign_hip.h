@@ -48,11 +48,26 @@ enum {
                                  here (src/alignment_scoring.c:178-181)       */
   SEQALIGN_E_DOMAIN = 6,      /* NW scoring whose gap penalties are below
                                  -|min_penalty|: signed overflow (UB) in the
-                                 reference fill                */
+                                 reference fill; or scores too
+                                 large for the row sweeps (below)              */
   SEQALIGN_E_TRACEBACK = 7,   /* src/alignment.c:328-349 would exit()         */
   SEQALIGN_E_TOO_LARGE = 8    /* one pair needs >= 2^31 cells                 */
 };
 
+/* SEQALIGN_E_DOMAIN, the second case.  The kernels de-trend gap_b along a row: they add to a cell up to `cols` times
+ * |gap_extend| before they take a maximum, a sum the reference never forms, and it must fit int32.  With la / lb the longest
+ * seq_a / seq_b of the call (score_cross, score_search: the longest query / target) and n = min(la, lb), no cell holds more than
+ *     bound = max(n P + (la + lb - 2 n) G, (la + lb) G)
+ * P = the largest substitution score above 0 (match, mismatch, every table entry), G = the largest of gap_open + gap_extend and
+ * gap_extend above 0; and
+ *     cols  = frame                         if gap_extend > 0
+ *           = min(frame, la + 1)            otherwise       (the banded calls: min(frame, la + lb + 1))
+ *     frame = 1 024; 4 096 where la >= 1 024 in the calls that fill whole matrices (seqalign_fill_batch*, seqalign_nw_batch*,
+ *             seqalign_sw_batch*, the legacy one-pair calls)
+ * A call is refused before it launches anything, with a message that names these numbers, unless
+ *     bound + cols * |gap_extend| <= INT32_MAX.
+ * Every scoring with numbers below 2^20 and gaps that cost passes on pairs of up to 1 000 letters; the narrow and the wide banded calls decide
+ * alike.  Inside the bound every result is the reference's, bit for bit, up to cell values of 2^31 - 1. */
 const char *seqalign_strerror(int code);
 /* Text of the last HIP failure on the calling thread ("" if none). */
 const char *seqalign_last_error(void);

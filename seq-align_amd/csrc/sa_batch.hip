@@ -324,6 +324,7 @@ extern "C" int seqalign_fill_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, is_sw, &sc))) return rc;
+  if ((rc = admit_batch(sc, batch, SA_FRAMES_FILL))) return rc;
   return fill_batch_uploaded(ctx, batch, sc, mat_off, M, A, B, status);
 }
 
@@ -1177,6 +1178,7 @@ static int nw_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, con
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, 0, &sc))) return rc;
+  if ((rc = admit_magnitude(sc, whole.max_a, whole.max_b, SA_FRAMES_FILL))) return rc;
   const bool on_host = traceback_on_host(ctx);
   if (!on_host && ctx->opt.nw_moves && nw_dirs_applicable(ctx, sc, whole.max_a, batch->n_pairs)) {
     // direction bytes (1 B per cell, every pair rounded up to 256 at most) + ~64 B per pair of descriptors and results:

@@ -435,6 +435,7 @@ int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, sw ? 1 : 0, &sc))) return rc;
+  if ((rc = admit_batch(sc, batch, SA_FRAMES_BAND))) return rc;
   std::vector<ByteChunk> chunks;
   const uint32_t cols = wide ? wide_strip_cols(ctx, batch->n_pairs) : 0;
   if ((rc = plan_band_chunks(batch, geom, align, sw, ctx->chunk_budget, chunks, cols, span))) return rc;
@@ -455,6 +456,7 @@ int band_time(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, sw ? 1 : 0, &sc))) return rc;
+  if ((rc = admit_batch(sc, batch, SA_FRAMES_BAND))) return rc;
   std::vector<ByteChunk> chunks;
   if ((rc = plan_band_chunks(batch, geom, false, sw, ctx->chunk_budget, chunks, 0, span))) return rc;
   if (chunks.size() != 1) { set_last_error(std::string(name) + ": the batch does not fit one chunk"); return SEQALIGN_E_ARG; }

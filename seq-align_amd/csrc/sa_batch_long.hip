@@ -226,6 +226,7 @@ int long_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
+  if ((rc = admit_batch(sc, batch, SA_FRAMES_ROWS))) return rc;
   LongPair run{ctx, sc, is_sw};
   uint64_t found = 0, used_str = 0;
   for (uint64_t p = 0; p < batch->n_pairs; ++p) {

@@ -174,6 +174,7 @@ int row_batch_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const sco
   int rc;
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
+  if ((rc = admit_batch(sc, batch, SA_FRAMES_ROWS))) return rc;
   StreamSyncOnExit sync(ctx->stream);
   for (const ByteChunk &c : plan_row_chunks<T>(batch, ctx->chunk_budget)) {
     RowChunkRun<T> run(ctx, sc, is_sw);
@@ -193,6 +194,7 @@ int row_time_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scor
   int rc;
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
+  if ((rc = admit_batch(sc, batch, SA_FRAMES_ROWS))) return rc;
   StreamSyncOnExit sync(ctx->stream);
   RowChunkRun<T> run(ctx, sc, is_sw);
   if ((rc = run.prepare(batch, chunks[0]))) return rc;

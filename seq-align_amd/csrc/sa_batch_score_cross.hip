@@ -337,6 +337,14 @@ struct CrossCall {
   int run(uint64_t q_base) {
     int rc;
     std::vector<uint64_t> short_q, long_q;
+    {   // the scoring's int32 domain over the longest query and the longest target, before anything is launched
+      seqalign_dev_scoring *sc = nullptr;
+      if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
+      uint32_t max_q = 0, max_t = 0;
+      for (uint64_t q = 0; q < Q->n_seqs; ++q) max_q = std::max(max_q, Q->len[q]);
+      for (uint64_t t = 0; t < T->n_seqs; ++t) max_t = std::max(max_t, T->len[t]);
+      if ((rc = admit_magnitude(sc, max_q, max_t, SA_FRAMES_ROWS))) return rc;
+    }
     for (uint64_t q = 0; q < Q->n_seqs; ++q) (Q->len[q] > SA_SCORE_ROW_MAX ? long_q : short_q).push_back(q);
     if (!short_q.empty() && (rc = run_short(short_q))) return rc;
     if (!long_q.empty() && (rc = run_long(long_q))) return rc;

@@ -947,6 +947,7 @@ static int sw_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, con
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, 1, &sc))) return rc;
+  if ((rc = admit_batch(sc, batch, SA_FRAMES_FILL))) return rc;
   uint64_t used_str = 0, found = 0;
   if (max_hits == 0) return SEQALIGN_OK;
   if (max_hits == 1 && !traceback_on_host(ctx)) {   // best hit only: nothing but the strings crosses PCIe

@@ -356,6 +356,7 @@ struct seqalign_dev_scoring {
   uint16_t *d_code = nullptr;
   int32_t *d_table = nullptr;
   int32_t table_abs_max = 0;   // largest |entry| of the table (sentinels excluded): the packed fills' int16 bound
+  int32_t score_pos_max = 0;   // largest substitution score above 0 (gen_eq, gen_ne, the table): the row sweeps' int32 bound
 };
 
 struct seqalign_ctx {
@@ -452,6 +453,11 @@ int reserve_arenas(seqalign_ctx *ctx, size_t bytes, bool placed = true);
 // batch after batch with one scoring_t pays for the flatten + two hipMallocs + two synchronous copies once, not per
 // call (C2: ~0.1 ms of a 1.3 ms call).  Owned by the context; valid until the next call with a different scoring.
 int cached_scoring(seqalign_ctx *ctx, const scoring_t *scoring, int is_sw, seqalign_dev_scoring **out);
+// The int32 domain of the row sweeps (sa_kernels.h: sa_domain_magnitude): SEQALIGN_OK, or SEQALIGN_E_DOMAIN with a message that
+// names the bound, for a call whose longest seq_a / seq_b are max_a / max_b letters.  Asked by every entry point before it
+// launches anything; admit_batch scans the batch's lengths for them.
+int admit_magnitude(const seqalign_dev_scoring *sc, uint64_t max_a, uint64_t max_b, SaFrames frames);
+int admit_batch(const seqalign_dev_scoring *sc, const seqalign_batch_t *batch, SaFrames frames);
 
 // the fill on device-resident data; best_score / best_index (optional, SW): filled by the fill itself
 // when the stream kernel runs (*best_done = true), otherwise the caller runs the separate reduction

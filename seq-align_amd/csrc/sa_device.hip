@@ -39,7 +39,7 @@ extern "C" const char *seqalign_strerror(int code) {
     case SEQALIGN_E_ARG: return "invalid argument";
     case SEQALIGN_E_NOMEM: return "out of memory";
     case SEQALIGN_E_UNKNOWN_PAIR: return "unknown character pair and match/mismatch not set";
-    case SEQALIGN_E_DOMAIN: return "scoring outside the defined domain (penalty below -|min_penalty|)";
+    case SEQALIGN_E_DOMAIN: return "scoring outside the defined domain (penalty below -|min_penalty|, or scores beyond the row sweeps' int32 bound)";
     case SEQALIGN_E_TRACEBACK: return "traceback failed";
     case SEQALIGN_E_TOO_LARGE: return "pair too large (>= 2^31 cells)";
   }
@@ -447,7 +447,9 @@ extern "C" int seqalign_scoring_upload(seqalign_ctx_t *ctx, const scoring_t *sco
     const int32_t v = h->flat.table[k];
     if (v == SA_S_BLOCKED || v == SA_S_UNKNOWN) continue;   // (such scorings never reach the packed fills)
     h->table_abs_max = std::max(h->table_abs_max, v < 0 ? (v == INT32_MIN ? INT32_MAX : -v) : v);
+    h->score_pos_max = std::max(h->score_pos_max, v);
   }
+  h->score_pos_max = std::max(h->score_pos_max, std::max(h->flat.gen_eq, h->flat.gen_ne));   // (sentinels are far below 0)
   *out = h;
   return SEQALIGN_OK;
 }
@@ -498,6 +500,7 @@ int sa_host::fill_device(seqalign_ctx_t *ctx, const seqalign_dev_scoring_t *scor
   if (batch->n_pairs == 0) return SEQALIGN_OK;
   if (batch->n_pairs > 0xFFFFFFFFull) return SEQALIGN_E_ARG;
   if ((uint64_t)(batch->max_len_a + 1ull) * (batch->max_len_b + 1ull) >= (1ull << 31)) return SEQALIGN_E_TOO_LARGE;
+  if (int rc = admit_magnitude(scoring, batch->max_len_a, batch->max_len_b, SA_FRAMES_FILL)) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   SaFillParams p = make_params(ctx, scoring, batch);
   hipError_t e;
@@ -847,6 +850,25 @@ int sa_host::cached_scoring(seqalign_ctx *ctx, const scoring_t *sc, int is_sw, s
   return SEQALIGN_OK;
 }
 
+int sa_host::admit_magnitude(const seqalign_dev_scoring *sc, uint64_t max_a, uint64_t max_b, SaFrames frames) {
+  const SaMagnitude m = sa_domain_magnitude(sc->score_pos_max, sc->flat.open1, sc->flat.ext, max_a, max_b, frames);
+  if (sa_domain_magnitude_fits(m)) return SEQALIGN_OK;
+  set_last_error("scoring outside the int32 domain of the row sweeps for pairs of up to " + std::to_string(max_a) + " x " +
+                 std::to_string(max_b) + " letters: the largest cell value " + std::to_string(m.bound) + " + " +
+                 std::to_string(m.cols) + " columns x |gap_extend| " + std::to_string(m.ext_abs) + " exceeds " +
+                 std::to_string(INT32_MAX) + " (include/seqalign_hip.h, SEQALIGN_E_DOMAIN)");
+  return SEQALIGN_E_DOMAIN;
+}
+
+int sa_host::admit_batch(const seqalign_dev_scoring *sc, const seqalign_batch_t *batch, SaFrames frames) {
+  uint32_t max_a = 0, max_b = 0;
+  for (uint64_t p = 0; p < batch->n_pairs; ++p) {
+    max_a = std::max(max_a, batch->len_a[p]);
+    max_b = std::max(max_b, batch->len_b[p]);
+  }
+  return admit_magnitude(sc, max_a, max_b, frames);
+}
+
 // ---- the legacy single-pair call's pinned block and the combiner of concurrent callers
 namespace {
 // OneBlock: [0, 4 KiB) the leader's descriptor arrays for up to kOneCombine requests | sequences | M | A | B
@@ -980,6 +1002,7 @@ extern "C" int sa_fill_one_pair(seqalign_ctx_t *ctx, const scoring_t *sc, int is
   HIP_TRY(hipSetDevice(ctx->device));
   seqalign_dev_scoring *dsc = nullptr;
   { int rc = cached_scoring(ctx, sc, is_sw, &dsc); if (rc) return rc; }
+  { int rc = admit_magnitude(dsc, len_a, len_b, SA_FRAMES_FILL); if (rc) return rc; }
   tm.lap("one pair: device + scoring fingerprint");
   const uint64_t cells = ((uint64_t)len_a + 1) * ((uint64_t)len_b + 1);
   if (cells >= (1ull << 31)) return SEQALIGN_E_TOO_LARGE;

@@ -33,6 +33,14 @@ constexpr int kWaitVm0 = 0x0F70;
 __device__ __forceinline__ int addw(int a, int b) {
   return (int)((unsigned)a + (unsigned)b);
 }
+// wrap-around multiply (a frame position times gap_extend): inside the admitted domain (sa_kernels.h: sa_domain_magnitude) the
+// product fits int32, and no UB here otherwise -- lanes beyond a row's last column form it too
+__device__ __forceinline__ int mulw(int a, int b) {
+  return (int)((unsigned)a * (unsigned)b);
+}
+__device__ __forceinline__ int subw(int a, int b) {
+  return (int)((unsigned)a - (unsigned)b);
+}
 __device__ __forceinline__ int max3i(int a, int b, int c) {
   return max(max(a, b), c);   // -> v_max3_i32
 }
@@ -148,7 +156,7 @@ struct Border {
   bool is_sw, no_start;
   // gap_b_scores[i] on row 0 / gap_a_scores[j*W] on column 0, index k >= 1
   __device__ __forceinline__ int edge_gap(unsigned k) const {
-    return (is_sw || no_start) ? 0 : addw(gap_open, (int)k * ext);
+    return (is_sw || no_start) ? 0 : addw(gap_open, mulw((int)k, ext));
   }
   __device__ __forceinline__ int edge_floor() const { return is_sw ? 0 : floor; }
 };

@@ -113,8 +113,8 @@ fill_dirs_kernel(const SaFillParams p, uint8_t *__restrict__ dirs_arena) {
     arow[c] = (code >> 8) * K;
     X[c] = Yp[c] = Ap[c] = 0;                               // row 0 (smith_waterman: borders are 0, alignment.c:51-57)
     T[c] = 1u; TY[c] = 2u;                                  // (A == max3 and B >= M hold on a row of zeros; never followed: scores are 0)
-    const int g_ext = (int)g * ext;                         // (ext <= 0 in this kernel's domain)
-    c1[c] = open1 - g_ext; c2[c] = 0 - g_ext; c3[c] = g_ext;   // floor = 0
+    const int g_ext = mulw((int)g, ext);                        // (ext <= 0 in this kernel's domain)
+    c1[c] = subw(open1, g_ext); c2[c] = subw(0, g_ext); c3[c] = g_ext;   // floor = 0
   }
   __builtin_amdgcn_s_waitcnt(kWaitVm0);
   const int ncol = max(0, min(CPL, (int)W - lane * CPL));

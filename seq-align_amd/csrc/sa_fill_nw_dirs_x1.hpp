@@ -117,8 +117,8 @@ __device__ __forceinline__ void nw_dirs_x1_wave(const SaFillParams &p, uint8_t *
     X[c] = max3i(mv[c], av[c], bv[c]); Yp[c] = max(mv[c], bv[c]); Ap[c] = av[c];
     T[c] = (av[c] == X[c]) ? 1u : (bv[c] == X[c]) ? 2u : 0u;
     TY[c] = (bv[c] >= mv[c]) ? 2u : 0u;
-    const int g_ext = (int)g * ext;                         // (ext <= 0 in this kernel's domain)
-    c1[c] = open1 - g_ext; c2[c] = floor_ - g_ext; c3[c] = g_ext;
+    const int g_ext = mulw((int)g, ext);                        // (ext <= 0 in this kernel's domain)
+    c1[c] = subw(open1, g_ext); c2[c] = subw(floor_, g_ext); c3[c] = g_ext;
   }
   __builtin_amdgcn_s_waitcnt(kWaitVm0);
   {

@@ -343,6 +343,34 @@ inline bool sa_domain_sw_best_x2(const SaScoringTraits &t, uint32_t la, uint32_t
          t.K <= SA_LDS_TABLE_MAX_K && t.ext <= 0 && sa_domain_nw_dirs_row(la) && lb < 32768 && sa_domain_x2_scores_fit(t, la, lb);
 }
 
+/* ---- the int32 domain of the row sweeps (include/seqalign_hip.h, SEQALIGN_E_DOMAIN) --------------------------------------
+ * Every kernel that sweeps a row de-trends gap_b (sa_rowsweep.hpp): it adds to a cell up to `cols` times |gap_extend|, a sum the
+ * reference never forms, and takes a maximum before it takes the trend back -- so that sum must fit int32, or a cell that
+ * should win the maximum loses it.  No cell of a pair of up to la x lb letters holds more than
+ *     bound = max(n P + (la + lb - 2 n) G, (la + lb) G),   n = min(la, lb),
+ * P = the largest substitution score above 0, G = the largest of gap_open + gap_extend and gap_extend above 0 (an alignment
+ * has at most n columns of two letters, and every other column is a gap column).  cols: with gap_extend <= 0 the trend grows
+ * with the position inside the frame, below the row's la + 1 columns (SA_FRAMES_BAND: below the band's at most la + lb + 1
+ * diagonals) and below the frame's width; with gap_extend > 0 it is taken from the frame's far end and is the frame's width
+ * whatever the row.  Frames are 1 024 columns at most, 4 096 where a call that fills whole matrices (SA_FRAMES_FILL) may take
+ * the workgroup fill (sa_fill_wgstream.hip: rows of 1 025 columns and more).  Admitted: bound + cols |gap_extend| <= INT32_MAX.
+ * The same bound keeps the kernels' products g * gap_extend inside int32. */
+enum SaFrames { SA_FRAMES_FILL = 0, SA_FRAMES_ROWS = 1, SA_FRAMES_BAND = 2 };
+struct SaMagnitude { uint64_t bound, cols, ext_abs; };   /* all three saturate at 2^62 */
+inline SaMagnitude sa_domain_magnitude(int32_t pos_max, int32_t open1, int32_t ext, uint64_t la, uint64_t lb, SaFrames frames) {
+  typedef unsigned __int128 u128;
+  const u128 sat = (u128)1 << 62;
+  const u128 P = pos_max > 0 ? (u128)pos_max : 0, G = (u128)(open1 > ext ? (open1 > 0 ? open1 : 0) : (ext > 0 ? ext : 0));
+  const u128 n = la < lb ? la : lb, all = (u128)la + lb;
+  const u128 mixed = n * P + (all - 2 * n) * G, gaps = all * G;
+  const u128 bound = mixed > gaps ? mixed : gaps;
+  const uint64_t cap = (frames == SA_FRAMES_FILL && la >= 1024) ? 4096 : 1024;
+  const u128 reach = frames == SA_FRAMES_BAND ? all + 1 : (u128)la + 1;
+  const uint64_t cols = ext > 0 || reach > cap ? cap : (uint64_t)reach;
+  return SaMagnitude{(uint64_t)(bound < sat ? bound : sat), cols, ext < 0 ? (uint64_t)(-(int64_t)ext) : (uint64_t)ext};
+}
+inline bool sa_domain_magnitude_fits(const SaMagnitude &m) { return m.bound + m.cols * m.ext_abs <= (uint64_t)INT32_MAX; }
+
 /* returns hipSuccess or the launch error; never synchronises */
 hipError_t sa_launch_fill_wavefront(const SaFillParams &p, uint32_t max_len_a,
                                     hipStream_t stream);

@@ -24,6 +24,12 @@
 // can wrap, no saturation is needed, and the result is the serial recurrence's
 // bit for bit.  Every other add is one the reference performs itself (value >=
 // floor plus one penalty >= -|min_penalty|).
+// The HIGH side has a condition: w(g) = cin(g) + t(g) is a sum the reference never forms, and a maximum sits between it and the
+// "+ c3" that takes t(g) back, so a w(g) that wrapped past INT32_MAX would lose the comparison it should win.  cin(g) is a
+// candidate value of a cell, so with `bound` >= every cell of the pair and t(g) <= cols * |ext| (cols: the positions g the frame
+// reaches on a real column; the whole frame for ext > 0, where t(0) = G * ext) the condition is bound + cols * |ext| <=
+// INT32_MAX.  The host checks it before every launch (sa_kernels.h: sa_domain_magnitude; SEQALIGN_E_DOMAIN otherwise).  The
+// products g * ext are formed wrap-around (mulw): inside the condition they fit, and lanes beyond the row form them too.
 // ext > 0 (legal upstream, a gap that pays): the same argument needs the trend
 // to move cin UP again, so it is taken from the right end instead -- with
 // t(g) = (G - g)*ext >= 0 for a G at or beyond the last column,
@@ -101,7 +107,7 @@ struct RowSweep {
   __device__ __forceinline__ void start_strip(const SaFillParams &p, const SweepConsts &k, const Border &bd,
                                               const uint8_t *__restrict__ seq_a, uint32_t la, uint32_t i0,
                                               uint32_t col0, int lane) {
-    trend0 = k.ext > 0 ? (kWave * CPL) * k.ext : 0;
+    trend0 = k.ext > 0 ? mulw(kWave * CPL, k.ext) : 0;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
       const uint32_t idx = col0 + c;
@@ -118,9 +124,9 @@ struct RowSweep {
           if constexpr (GENERAL) Y[c] = 0;
         }
       }
-      const int g_ext = (lane * CPL + c) * k.ext - trend0;   // -t(g)
-      c1[c] = k.open1 - g_ext;
-      c2[c] = k.floor_ - g_ext;
+      const int g_ext = subw(mulw(lane * CPL + c, k.ext), trend0);   // -t(g)
+      c1[c] = subw(k.open1, g_ext);
+      c2[c] = subw(k.floor_, g_ext);
       c3[c] = g_ext;
     }
     boundX = (i0 == 0) ? 0 : max(k.floor_, bd.edge_gap(i0));

@@ -59,7 +59,7 @@ struct SpanSweep {
 
   __device__ __forceinline__ void start_strip(const SaFillParams &p, const SweepConsts &k, const uint8_t *__restrict__ seq_a,
                                               uint32_t la, uint32_t i0, uint32_t col0, int lane) {
-    trend0 = k.ext > 0 ? (kWave * CPL) * k.ext : 0;
+    trend0 = k.ext > 0 ? mulw(kWave * CPL, k.ext) : 0;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
       const uint32_t idx = col0 + c;
@@ -69,9 +69,9 @@ struct SpanSweep {
       X[c] = 0; Ap[c] = 0;
       if constexpr (GENERAL) Y[c] = 0;
       Dx[c] = Vx[c] = idx + 1; Dy[c] = Vy[c] = 0;   // row 0 holds 0: every walk that reaches it stops there
-      const int g_ext = (lane * CPL + c) * k.ext - trend0;
-      c1[c] = k.open1 - g_ext;
-      c2[c] = -g_ext;
+      const int g_ext = subw(mulw(lane * CPL + c, k.ext), trend0);
+      c1[c] = subw(k.open1, g_ext);
+      c2[c] = subw(0, g_ext);
       c3[c] = g_ext;
       bs[c] = 0; br[c] = 0; bx[c] = 0; by[c] = 0;
     }

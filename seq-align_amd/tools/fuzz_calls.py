@@ -49,14 +49,48 @@ def top_k(score, end_a, end_b, k, min_score):
     return out
 
 
-def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
+SCALE_LOW_BITS = 8      # the drawn factors start at 2^8
+
+
+def scaled_spec(spec, f):
+    """Every number of the scoring times f: match, mismatch, the gap penalties, wildcard and mutation scores."""
+    out = dict(spec, init=[x * f for x in spec["init"][:4]] + list(spec["init"][4:]),
+               wildcards=[[c, x * f] for c, x in spec["wildcards"]])
+    if "mutations" in spec:
+        out["mutations"] = [[x, y, z * f] for x, y, z in spec["mutations"]]
+    return out
+
+
+def draw_factor(G, srng, scale, spec, peak1, la, lb):
+    """G: tests/maglib.py (the documented magnitude bound, restated).  (factor, redraws): a factor drawn log-uniformly from
+    2^8 .. scale, odd so that the low bits are populated; a draw under
+    which the exact-integer peak f * peak1 (peak1: the pairs' largest |value| at factor 1 plus the largest |penalty| -- the
+    recurrence is homogeneous) leaves int32, or which the library's documented bound refuses (include/seqalign_hip.h,
+    SEQALIGN_E_DOMAIN; maglib.admitted), is drawn again and counted."""
+    redraws = 0
+    while True:
+        u = float(srng.unit(1)[0])
+        f = int(2 ** (SCALE_LOW_BITS + u * (np.log2(scale) - SCALE_LOW_BITS))) | 1
+        big = scaled_spec(spec, f)
+        if f * peak1 <= G.INT32_MAX and all(G.admitted(big, la, lb, call) for call in ("score", "band")):
+            return f, redraws
+        redraws += 1
+
+
+def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, scale=1, dry=False):
     """Fuzz until `seconds` have passed or `max_trials` scorings were drawn; SystemExit(1) on the first mismatch, with the
     failing case printed.  Options it sets (long_block_rows, band_strip_cols) are put back before it returns or raises.
-    wide_calls: also the four *_banded_wide calls, on bands on both sides of 1 024 diagonals and random strip widths."""
+    wide_calls: also the four *_banded_wide calls, on bands on both sides of 1 024 diagonals and random strip widths.
+    scale: above 1, every trial's scoring is multiplied by a factor of up to `scale` (draw_factor; its draws come from a
+    generator of their own, and with the default of 1 the drawn stream is what it always was).  dry: draw and count only --
+    no device call -- for the CPU check of the redraw share."""
     rng = W.Rng(seed)
-    ctx = ctx or S.Context(0)
+    srng = W.Rng(seed ^ 0x5CA1E) if scale != 1 else None
+    if srng is not None:
+        import maglib as G      # only the scaled runs need it: the default run is what it was, imports included
+    ctx = ctx or (None if dry else S.Context(0))
     t_end = time.time() + seconds
-    n = {"trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0}
+    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -118,6 +152,26 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
                 if rc != 0:
                     fail("ORACLE", spec, p, pairs[p])
                 fills[is_sw, p] = (M, A, B)
+
+        if srng is not None:     # the same pairs under the scoring times a drawn factor
+            peak1 = max(G.cells_peak(*f3) for f3 in fills.values()) + max(abs(x) for x in G.numbers(spec) + [w[1] for w in spec["wildcards"]])
+            factor, redraws = draw_factor(G, srng, scale, spec, peak1, max(len(a) for a, _ in pairs), max(len(b) for _, b in pairs))
+            n["redraws"] += redraws
+            n["redrawn_trials"] += redraws > 0
+            spec = scaled_spec(spec, factor)
+            sc = S.make_scoring(spec)
+            osc = O.Scoring.from_buffer_copy(bytes(sc))
+            thr *= factor
+            if not dry:
+                for (is_sw, p) in list(fills):
+                    rc, M, A, B = O.oracle_fill(osc, *pairs[p], is_sw)
+                    if rc != 0:
+                        fail("ORACLE", spec, p, pairs[p])
+                    fills[is_sw, p] = (M, A, B)
+        if dry:
+            n["trials"] += 1
+            n["nw_trials"] += nw_ok
+            continue
 
         # ---- score only
         if nw_ok:
@@ -277,6 +331,9 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False):
                 n["banded_wide"] += len(sub)
         n["trials"] += 1
 
+    if srng is not None:
+        print(f"fuzz_calls scale up to {scale}: {n['redraws']} factors redrawn in {n['redrawn_trials']} of {n['trials']} trials "
+              f"({n['redrawn_trials'] / max(1, n['trials']):.1%} of the trials)", flush=True)
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
           f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['cross']} cross cells, {n['search']} searches, {n['long']} long alignments, {n['banded']} banded "
           f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results identical to the oracle "
@@ -290,5 +347,6 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--trials", type=int, default=1 << 60)
     ap.add_argument("--no-wide", action="store_true", help="leave the wide banded calls out")
+    ap.add_argument("--scale", type=int, default=1, help="multiply every trial's scoring by a drawn factor of up to this")
     args = ap.parse_args()
-    run(args.seconds, args.seed, args.trials, wide_calls=not args.no_wide)
+    run(args.seconds, args.seed, args.trials, wide_calls=not args.no_wide, scale=args.scale)

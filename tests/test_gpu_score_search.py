@@ -328,3 +328,109 @@ def test_launches(ctx):
     calls = ctx.last_call()
     assert set(calls) == {"score_cross", "score_select"}, calls
     assert calls["score_cross"] == (4, 5 * 50) and calls["score_select"] == (1, 5), calls
+
+
+# ---------------------------------------------------------------- 8. all 32 key bits --
+# Every search above has rows whose scores span fewer than 2 048 values, or keys so small that each radix pass has one or two
+# populated bins.  Under a scoring with large odd constants the three passes carry a prefix, a rank and a cut between them.
+MAG_SPEC = {"init": [2**20 + 7, -3 * (2**16 + 1), -5 * (2**16 + 1), -33 * (2**16 + 1), 0, 0, 0, 0, 0, 0]}
+MAG_K = (1, 7, 64, 1024)
+
+
+def related(rng, s):
+    """A relative of s: about one letter in eight substituted, one deleted."""
+    out = bytearray(s)
+    for i in rng.below(len(out), max(1, len(out) // 8)).tolist():
+        out[i] = DNA[int(rng.below(4, 1)[0])]
+    del out[int(rng.below(len(out), 1)[0])]
+    return bytes(out)
+
+
+@pytest.fixture(scope="module")
+def magnitude_sets():
+    """64 queries of 20-60 against 3 000 targets of 20-60: 600 distinct ones, each five times at scattered indices; every sixth
+    distinct target is a relative of a query."""
+    rng = W.Rng(211)
+    queries = [rand_seq(rng, int(n), DNA) for n in (20 + rng.below(41, 64)).tolist()]
+    distinct = [rand_seq(rng, int(n), DNA) for n in (20 + rng.below(41, 600)).tolist()]
+    for d in range(0, 600, 6):
+        distinct[d] = related(rng, queries[(d // 6) % 64])
+    perm = np.random.default_rng(212).permutation(3000)
+    return W.seqset_from(queries), W.seqset_from([distinct[int(perm[j]) % 600] for j in range(3000)])
+
+
+def splits_a_tie_group(dense, got, k):
+    """Queries whose k-th hit has equals among the targets left out."""
+    n_hits, hits = got
+    return [q for q in range(len(n_hits)) if int(n_hits[q]) == k and
+            (dense[0][q] == hits[q, k - 1]["score"]).sum() > (hits[q]["score"] == hits[q, k - 1]["score"]).sum()]
+
+
+@pytest.mark.parametrize("is_sw", [0, 1])
+def test_select_with_all_key_bits_in_play(ctx, magnitude_sets, is_sw):
+    """Rows whose passing scores span more than 2^11 and more than 2^22 values (three radix passes with many populated bins),
+    NW rows of both signs, and for k = 1, 7, 64 and 1 024 a cut inside a tie group: one tile, and query ranges under
+    chunk_bytes = 1 MiB, equal to each other and to the lexsort of the cross call."""
+    q, t = magnitude_sets
+    sc = S.make_scoring(MAG_SPEC)
+    floor = 1 if is_sw else INT32_MIN
+    dense = cross(ctx, q, t, sc, is_sw)
+    s = dense[0].astype(np.int64)
+    spans = [int(r[r >= floor].max() - r[r >= floor].min()) for r in s if (r >= floor).sum() > 1024]
+    assert len(spans) == q.n_seqs and max(spans) > 2**22 and min(spans) > 2**11, (len(spans), min(spans), max(spans))
+    varying = int(np.bitwise_or.reduce((s ^ s[0, 0]).ravel())) & 0xFFFFFFFF
+    # every key bit up to the highest one that differs takes both values: all 32 under NW (the first pass starts at bit 32),
+    # the 26 that 60 matches reach under SW
+    assert varying == (1 << varying.bit_length()) - 1 and varying.bit_length() >= (26 if is_sw else 32), hex(varying)
+    if not is_sw:
+        assert any((r > 0).any() and (r < 0).any() for r in s)
+    for k in MAG_K:
+        want = top_k(*dense, k, floor)
+        one = search(ctx, q, t, sc, is_sw, k, floor)
+        assert ctx.last_call()["score_select"][0] == 1
+        with ctx.options(chunk_bytes=1 << 20):
+            many = search(ctx, q, t, sc, is_sw, k, floor)
+            calls = ctx.last_call()
+        # (SW's 12 bytes per result cut the queries into ranges; NW's 4 leave this set in one tile: the 15 000 targets below)
+        assert calls["score_select"][0] >= (2 if is_sw else 1) and calls["score_select"][0] == calls["score_cross"][0], calls
+        assert_hits(one, want, f"one k={k}")
+        assert_hits(many, want, f"many k={k}")
+        assert_same(one, many)
+        assert splits_a_tie_group(dense, one, k), f"k={k}: no query's k-th hit splits a tie group"
+
+
+@pytest.mark.parametrize("is_sw", [0, 1])
+def test_select_min_score_edges_at_large_scores(ctx, magnitude_sets, is_sw):
+    """min_score at INT32_MIN, at INT32_MAX (nothing passes), at exactly a row's k-th score and one above it."""
+    q, t = magnitude_sets
+    sc = S.make_scoring(MAG_SPEC)
+    dense = cross(ctx, q, t, sc, is_sw)
+    for k in (7, 64):
+        kth = int(top_k(*dense, k, 1 if is_sw else INT32_MIN)[5][1][k - 1])
+        for min_score in (INT32_MIN, 2**31 - 1, kth, kth + 1):
+            want = top_k(*dense, k, min_score)
+            one = search(ctx, q, t, sc, is_sw, k, min_score)
+            with ctx.options(chunk_bytes=1 << 20):
+                many = search(ctx, q, t, sc, is_sw, k, min_score)
+            assert_hits(one, want, f"k={k} min={min_score}")
+            assert_same(one, many, f"k={k} min={min_score}")
+        assert int(search(ctx, q, t, sc, is_sw, k, 2**31 - 1)[0].sum()) == 0
+        assert int(search(ctx, q, t, sc, is_sw, k, kth)[0][5]) == k > int(search(ctx, q, t, sc, is_sw, k, kth + 1)[0][5])
+
+
+@pytest.mark.parametrize("is_sw", [0, 1])
+def test_select_carries_large_keys_across_target_ranges(ctx, magnitude_sets, is_sw):
+    """The same targets five times over (15 000): under chunk_bytes = 1 MiB they take several ranges, so the running lists --
+    keys with all bits in play -- go through the select again with every later range."""
+    q, t3 = magnitude_sets
+    t = W.seqset_from([t3.seq(j % 3000) for j in range(15000)])
+    sc = S.make_scoring(MAG_SPEC)
+    floor = 1 if is_sw else INT32_MIN
+    dense = cross(ctx, q, t, sc, is_sw)
+    for k in (7, 1024):
+        with ctx.options(chunk_bytes=1 << 20):
+            many = search(ctx, q, t, sc, is_sw, k, floor)
+            calls = ctx.last_call()
+        assert calls["score_select"][1] >= 2 * q.n_seqs, calls          # rows selected: every query once per target range
+        assert_hits(many, top_k(*dense, k, floor), f"k={k}")
+        assert_same(many, search(ctx, q, t, sc, is_sw, k, floor))

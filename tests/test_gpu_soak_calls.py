@@ -38,3 +38,23 @@ def test_fuzz_calls_slice(ctx, seed):
     for family in ("score", "cross", "search", "long", "banded", "nw_trials", "wide"):
         assert r[family] > 0, (family, r)
     assert r["score"] == 12 * (r["trials"] + r["nw_trials"]) == r["long"] and r["search"] == 4 * (r["trials"] + r["nw_trials"]), r
+
+
+SCALE = 1 << 23
+
+
+def test_fuzz_calls_slice_at_large_scores(ctx):
+    """The same slice with every trial's scoring multiplied by a drawn factor of 2^8 .. 2^23 (fuzz_calls.run's scale): cells
+    up to 2^31.  A factor under which the exact peak leaves int32, or which the documented magnitude bound refuses, is drawn
+    again; at most one trial in four may need that (tests/test_magnitude_argument_cpu.py checks the share on the CPU)."""
+    spec = importlib.util.spec_from_file_location("soak_fuzz_calls", TOOLS / "fuzz_calls.py")
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    try:
+        r = fz.run(seconds=40.0, seed=20261019, max_trials=40, ctx=ctx, scale=SCALE)
+    except SystemExit as e:
+        pytest.fail(f"fuzz_calls mismatch at scale {SCALE}; the failing case is in the captured output (exit {e.code})")
+    assert r["trials"] >= 15, r
+    assert 4 * r["redrawn_trials"] <= r["trials"], r
+    for family in ("score", "cross", "search", "long", "banded", "nw_trials", "wide", "span", "span_banded"):
+        assert r[family] > 0, (family, r)

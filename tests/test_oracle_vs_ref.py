@@ -9,6 +9,7 @@ import itertools
 import numpy as np
 import pytest
 
+import maglib as G
 import orclib as O
 from seqalign_amd import workloads as W
 
@@ -139,3 +140,25 @@ def test_reference_walked_hit_lists_are_current_and_equal_the_oracle_live():
             assert rc == 0 and O.ref_sw_hits(sr, a, b, thr, max_hits) == want, (spec, thr, max_hits, a, b)
             checked += len(want)
     assert checked > 200
+
+
+@pytest.mark.parametrize("fam", G.FAMILIES, ids=G.family_id)
+def test_magnitude_families_match_the_reference(fam):
+    """(needs oracle/_ref) tests/maglib.py's families -- cells from 2^15 up to 2^31 -- through the compiled reference: the
+    three matrices of every pair, the NW strings, and the first four SW hits at a threshold of four matches.  This pins the
+    oracle to the reference at these magnitudes before tests/test_gpu_magnitude.py compares the GPU with the oracle."""
+    n = 0
+    for c in G.cases_of(fam=fam):
+        so, sr = c.osc(), O.build_scoring(c.spec, "ref")
+        assert in_domain(so, c.is_sw), c.id
+        rc, M, A, B = O.oracle_fill(so, c.a, c.b, c.is_sw)
+        Mr, Ar, Br = O.ref_fill(sr, c.a, c.b, c.is_sw)
+        assert rc == 0 and np.array_equal(M, Mr) and np.array_equal(A, Ar) and np.array_equal(B, Br), c.id
+        if c.is_sw:
+            thr = 4 * c.spec["init"][0]
+            rc, want = O.oracle_sw(so, c.a, c.b, thr, 4)
+            assert rc == 0 and O.ref_sw_hits(sr, c.a, c.b, thr, 4) == want, c.id
+        else:
+            assert O.oracle_nw(so, c.a, c.b)[1:] == O.ref_nw(sr, c.a, c.b), c.id
+        n += 1
+    assert n >= 21
