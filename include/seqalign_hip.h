@@ -597,7 +597,8 @@ int seqalign_sw_score_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
  * returned and named in seqalign_last_error) are seqalign_sw_score_batch's.  SEQALIGN_E_TRACEBACK cannot occur: in SW a
  * positive cell always has a predecessor the walker accepts.  The launches are recorded as "score_rows" /
  * "score_strips" (items: pairs).
- * Not in this call: no cross, search, _submit or command-line form, and no option steers it (banded, up to 512 diagonals:
+ * Over two sets: seqalign_sw_span_cross (the span matrices) and seqalign_sw_span_search (top k with spans) below.
+ * Not in this call: no _submit or command-line form, and no option steers it (banded, up to 512 diagonals:
  * seqalign_sw_span_banded below). */
 int seqalign_sw_span_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                            uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b);
@@ -631,7 +632,8 @@ int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
  * diagonals per lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted under band_score, one
  * per width class of a chunk.
  * Not in this call: widths 513 .. 1 024 and a _banded_wide (strip pipeline) form -- the two-word span sweep does not fit the
- * registers at 12 and 16 columns per lane; they wait for the one-word span -- and no cross, search, _multi,
+ * registers at 12 and 16 columns per lane; they wait for the one-word span -- and no cross, search (the
+ * unbanded call has both: seqalign_sw_span_cross, seqalign_sw_span_search), _multi,
  * _submit or command-line form, and no option steers it. */
 #define SEQALIGN_SPAN_BAND_MAX_WIDTH 512
 int seqalign_sw_span_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
@@ -838,6 +840,45 @@ int seqalign_nw_score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const
 int seqalign_sw_score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
                                    const seqalign_seqset_t *targets, const scoring_t *scoring, uint32_t k, int32_t min_score,
                                    seqalign_search_hit_t *hits, uint32_t *n_hits);
+/* ---- SW hit spans over two sets: span matrices and a top-k search with spans ----------------------------------------- */
+/* seqalign_sw_span_cross: the result of seqalign_sw_span_batch on the batch whose pair q * n_targets + t is (query q, target
+ * t), without that batch -- five dense row-major [n_queries][n_targets] matrices; pos_a / len_a index the query, pos_b /
+ * len_b the target; score and pos + len are seqalign_sw_score_cross's score and end_a / end_b; all five are 0 where no cell
+ * is above 0.  The tiles are seqalign_sw_score_cross's with 20 result bytes per pair; queries of up to 512 columns run one
+ * wave per (query, target) (the span kernel's cross form, recorded as "score_cross"), longer ones the span strips on explicit
+ * pair lists ("score_strips").  The sweep costs what seqalign_sw_span_batch's costs, 3 - 4 x the score sweep.
+ * Argument checks (before any device work: n_queries x n_targets overflowing uint64_t, NULL arguments, readable sets),
+ * scoring admission (SEQALIGN_E_DOMAIN), empty sets (SEQALIGN_OK, nothing written) and SEQALIGN_E_UNKNOWN_PAIR ("query Q,
+ * target T: ..." for the lowest q * n_targets + t) are seqalign_sw_score_cross's.  On an error the outputs are unspecified. */
+int seqalign_sw_span_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                           const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
+                           uint32_t *out_len_a, uint32_t *out_len_b);
+/* ... over several contexts: the query ranges of seqalign_sw_score_cross_multi; results exactly the single-context call's */
+int seqalign_sw_span_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                 const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score,
+                                 uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b);
+typedef struct {
+  uint32_t target;       /* index into the target set */
+  int32_t score;
+  uint32_t pos_a, pos_b, len_a, len_b; /* seqalign_sw_span_cross's at [q][target]; five zeros when score is 0 */
+} seqalign_span_hit_t;   /* 24 bytes */
+/* seqalign_sw_span_search: seqalign_sw_score_search with the hit's start beside its end.  n_hits[q] and the target and score
+ * of every written slot are exactly that call's on the same arguments (order, min_score, k and every SEQALIGN_E_ARG case
+ * unchanged); pos / len are seqalign_sw_span_cross's at [q][target], so pos + len is the score search's end_a / end_b.  A hit
+ * of score 0 (selectable only with min_score <= 0) has five zeros.
+ * Two stages: the score search as it is, then the span sweep on the selected hits alone -- for each the prefix pair
+ * (query[0 : end_a], target[0 : end_b]), whose first hit is the full pair's, as one explicit pair list;
+ * host memory for it grows with the hits, not with the sets.  The launches: "score_cross" / "score_select" (queries over
+ * 1 024 columns: "score_strips"), then "score_rows" / "score_strips" for the prefixes.
+ * SEQALIGN_E_UNKNOWN_PAIR is the score search's and named as it names it: every (query, target) is swept in full by the
+ * first stage, so a failing pair outside the best k, or an unknown character past a selected hit's end cell, fails the call.
+ * The result does not depend on tiling, chunk_bytes or the number of contexts. */
+int seqalign_sw_span_search(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                            const scoring_t *scoring, uint32_t k, int32_t min_score, seqalign_span_hit_t *hits,
+                            uint32_t *n_hits);
+int seqalign_sw_span_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                  const seqalign_seqset_t *targets, const scoring_t *scoring, uint32_t k, int32_t min_score,
+                                  seqalign_span_hit_t *hits, uint32_t *n_hits);
 /* Kernel time of the score-only call (seq-align_amd/tools/score_bench.py): the batch is packed and uploaded once (it must
  * fit one chunk), then its score kernels run `repeats` times, each launch between two HIP events: ms_each[r]. */
 int seqalign_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int is_sw,

@@ -209,6 +209,13 @@ int sa_host::score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch
   return row_batch_call<ScoreTraits>(ctx, batch, scoring, is_sw, out_score, out, fail_pair);
 }
 
+int sa_host::span_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                             uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
+                             uint64_t *fail_pair) {
+  uint32_t *const out[4] = {out_pos_a, out_pos_b, out_len_a, out_len_b};
+  return row_batch_call<SpanTraits>(ctx, batch, scoring, true, out_score, out, fail_pair);
+}
+
 extern "C" int seqalign_nw_score_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                        int32_t *out_score) {
   if (!ctx || !scoring || !out_score) return SEQALIGN_E_ARG;
@@ -235,8 +242,7 @@ extern "C" int seqalign_sw_span_batch(seqalign_ctx_t *ctx, const seqalign_batch_
                                       uint32_t *out_len_b) {
   if (!ctx || !scoring || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b) return SEQALIGN_E_ARG;
   CallScope scope(ctx);
-  uint32_t *const out[4] = {out_pos_a, out_pos_b, out_len_a, out_len_b};
-  return row_batch_call<SpanTraits>(ctx, batch, scoring, true, out_score, out, nullptr);
+  return span_batch_impl(ctx, batch, scoring, out_score, out_pos_a, out_pos_b, out_len_a, out_len_b);
 }
 
 extern "C" int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,

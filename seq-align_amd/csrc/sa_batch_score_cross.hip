@@ -20,6 +20,14 @@
 // ([nq][k] keys, ends, counts, reserved with the other buffers), and after a query range's last target range only the lists
 // come home: nq x (16 k + 4) bytes.  The tile cut counts the lists as part of each query's bytes.  Long queries' rows come
 // home through the score batches anyway; their top k is taken on the host with the same key.
+//
+// Span matrices (seqalign_sw_span_cross) are the same tiles once more with 20 result bytes per pair: the CROSS form of the span
+// kernel (sa_span.hip) in place of the score kernel's, five rows home per query, and the short / long split at SA_SPAN_ROW_MAX
+// columns, the long queries through the span strips (span_batch_impl).
+//
+// Top-k search with spans (seqalign_sw_span_search) is two stages: the score search above, unchanged, and then
+// the span sweep on the selected hits alone -- for each the PREFIX pair (query[0 : end_a], target[0 : end_b]), whose first hit
+// is the full pair's, as an explicit pair list through span_batch_impl.
 #include "sa_ctx.hpp"
 
 using namespace sa_host;
@@ -65,19 +73,20 @@ struct FailPair {
 inline uint32_t key_u(int32_t s) { return ~((uint32_t)s ^ 0x80000000u); }
 inline uint64_t hit_key(int32_t s, uint64_t t) { return ((uint64_t)key_u(s) << 32) | t; }
 
-struct SearchOut {   // seqalign_*_score_search's outputs
+struct SearchOut {   // seqalign_*_score_search's outputs, or seqalign_sw_span_search's after its first stage
   uint32_t k;
   int32_t min_score;
   seqalign_search_hit_t *hits;   // [n_queries * k]
   uint32_t *n_hits;              // [n_queries]
+  seqalign_span_hit_t *span_hits = nullptr;   // set: these instead of `hits`, pos 0 and len = the end cell until stage 2
   // query q's list from sorted keys and their ends
   void put(uint64_t q, uint32_t n, const uint64_t *key, const uint32_t *ea, const uint32_t *eb) const {
     n_hits[q] = n;
-    seqalign_search_hit_t *h = hits + q * k;
     for (uint32_t i = 0; i < n; ++i) {
-      h[i].target = (uint32_t)key[i];
-      h[i].score = (int32_t)(~(uint32_t)(key[i] >> 32) ^ 0x80000000u);
-      h[i].end_a = ea[i]; h[i].end_b = eb[i];
+      const uint32_t target = (uint32_t)key[i];
+      const int32_t score = (int32_t)(~(uint32_t)(key[i] >> 32) ^ 0x80000000u);
+      if (span_hits) span_hits[q * k + i] = seqalign_span_hit_t{target, score, 0, 0, ea[i], eb[i]};
+      else hits[q * k + i] = seqalign_search_hit_t{target, score, ea[i], eb[i]};
     }
   }
 };
@@ -88,15 +97,18 @@ struct CrossCall {
   const scoring_t *scoring;
   bool is_sw;
   int32_t *out_score;
-  uint32_t *out_end_a, *out_end_b;
+  uint32_t *out_w[4];   // the matrices behind the score -- SW: end_a, end_b; span: pos_a, pos_b, len_a, len_b
   uint64_t nT;
   FailPair fail;
   const SearchOut *search = nullptr;   // set: top-k search, the matrix outputs are unused
+  bool span = false;                   // seqalign_sw_span_cross (is_sw set, no search)
 
-  uint64_t result_bytes() const { return is_sw ? 12 : 4; }
+  int words() const { return span ? 4 : is_sw ? 2 : 0; }   // result words per pair behind the score
+  uint64_t result_bytes() const { return 4 * (1 + (uint64_t)words()); }
+  uint32_t row_max() const { return span ? SA_SPAN_ROW_MAX : SA_SCORE_ROW_MAX; }   // the one-wave kernels' widest query
   uint64_t list_bytes() const { return search ? 16ull * search->k + 4 : 0; }   // one query's running list
 
-  // queries <= SA_SCORE_ROW_MAX: the cross kernel, tile by tile
+  // queries <= row_max(): the cross kernel, tile by tile
   int run_short(const std::vector<uint64_t> &qs) {
     int rc;
     seqalign_dev_scoring *sc = nullptr;
@@ -117,8 +129,9 @@ struct CrossCall {
 
     // every buffer at its largest before anything goes up (a DevBuf that grows loses its contents): sequences, targets
     // first; descriptors off_t, off_q (u64), len_t, t_order, len_q, q_list (u32); results: err_flag, -, err_pair (u64), then
-    // score, end_a, end_b; search: the running lists of a query range (keys u64 [nq * k], end_a, end_b u32 [nq * k], counts
-    // u32 [nq]), and at home the 16 bytes of err_flag / err_pair followed by the lists
+    // score, end_a, end_b (span: score, pos_a, pos_b, len_a, len_b); search: the running lists of a query range (keys u64
+    // [nq * k], end_a, end_b u32 [nq * k], counts u32 [nq]), and at home the 16 bytes of err_flag / err_pair followed by the
+    // lists
     const uint64_t q_at = (tb_max + 15) & ~(uint64_t)15;
     const uint64_t desc_bytes = 16 * (nt_max + nq_max);
     const uint64_t res_bytes = 16 + rp * nq_max * nt_max, lists_bytes = list_bytes() * nq_max;
@@ -165,7 +178,8 @@ struct CrossCall {
         }
         const uint64_t bytes = pack(Q, qs.data() + qr.first, nq, q_at, h_off_q, h_len_q);
         // the queries by row class: q_list holds class 0's, then class 1's, ...
-        // (the class past the last, rows for the strips kernel, stays empty: run_short's queries are short)
+        // (the class past the last, rows for the strips kernel, stays empty: run_short's queries are short; up to
+        // SA_SPAN_ROW_MAX columns the span kernels' classes are the score kernels' first SA_SPAN_ROW_CLASSES)
         uint64_t cls_first[SA_SCORE_ROW_CLASSES + 2];
         uint32_t cls_max_a[SA_SCORE_ROW_CLASSES + 1];
         sort_by_row_class(nq, [&](uint64_t k) { return h_len_q[k]; }, h_qlist, cls_first, cls_max_a);
@@ -184,6 +198,22 @@ struct CrossCall {
         for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) {
           const uint64_t m = cls_first[x + 1] - cls_first[x];
           if (!m) continue;
+          if (span) {
+            SaSpanCrossParams p;
+            memset(&p, 0, sizeof(p));
+            p.s.f = f0;
+            p.s.f.arena = d_seq;
+            p.s.f.off_a = d_off_q; p.s.f.len_a = d_len_q; p.s.f.off_b = d_off_t; p.s.f.len_b = d_len_t;
+            p.q_list = d_qlist + cls_first[x]; p.t_order = d_tord;
+            p.nq = (uint32_t)m; p.n_t = (uint32_t)nt; p.n_waves = (uint32_t)(m * nt);
+            p.s.score = reinterpret_cast<int32_t *>(d_res + 4);
+            p.s.pos_a = d_res + 4 + n; p.s.pos_b = d_res + 4 + 2 * n; p.s.len_a = d_res + 4 + 3 * n; p.s.len_b = d_res + 4 + 4 * n;
+            p.s.err_flag = d_res;
+            p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
+            const hipError_t e = sa_launch_span_cross(p, cls_max_a[x], st);
+            if (e != hipSuccess) return fail_hip(e, "span cross kernel launch");
+            continue;
+          }
           SaScoreCrossParams p;
           memset(&p, 0, sizeof(p));
           p.f = f0;
@@ -241,16 +271,13 @@ struct CrossCall {
           continue;
         }
         const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
-        const uint32_t *ha = h + 4 + n, *hb = h + 4 + 2 * n;
+        const int nw = words();
         constexpr uint64_t kRows = 64;
         parallel_for((nq + kRows - 1) / kRows, [&](uint64_t blk) {
           for (uint64_t k = blk * kRows, e = std::min(nq, (blk + 1) * kRows); k < e; ++k) {
             const uint64_t row = qs[qr.first + k] * nT + tr.first;
             memcpy(out_score + row, hs + k * nt, 4 * nt);
-            if (is_sw) {
-              memcpy(out_end_a + row, ha + k * nt, 4 * nt);
-              memcpy(out_end_b + row, hb + k * nt, 4 * nt);
-            }
+            for (int w = 0; w < nw; ++w) memcpy(out_w[w] + row, h + 4 + (w + 1) * n + k * nt, 4 * nt);
           }
         });
       }
@@ -259,7 +286,8 @@ struct CrossCall {
     return SEQALIGN_OK;
   }
 
-  // queries > SA_SCORE_ROW_MAX: score-batch slices of (a few long queries x a slice of the targets), through the strips
+  // queries > row_max(): score-batch (span: span-batch) slices of (a few long queries x a slice of the targets), through
+  // the strips
   int run_long(const std::vector<uint64_t> &qs) {
     int rc;
     // one arena of their own for the batches: the long queries, then the targets
@@ -277,14 +305,17 @@ struct CrossCall {
     std::vector<std::vector<Hit>> best(search ? qs.size() : 0);
     const auto by_key = [](const Hit &x, const Hit &y) { return x.key < y.key; };
     std::vector<uint64_t> off_a, off_b;
-    std::vector<uint32_t> len_a, len_b, ea, eb;
+    std::vector<uint32_t> len_a, len_b, w[4];   // w: the result arrays behind the score (out_w's order)
+    std::vector<uint32_t> &ea = w[0], &eb = w[1];
     std::vector<int32_t> sc;
+    const int nw = words();
     for (uint64_t g0 = 0; g0 < qs.size(); g0 += q_rows) {
       const uint64_t g1 = std::min<uint64_t>(qs.size(), g0 + q_rows);
       if (fail.any() && qs[g0] > fail.q) break;   // only higher pairs from here on
       for (uint64_t t0 = 0; t0 < nT; t0 += t_slice) {
         const uint64_t t1 = std::min(nT, t0 + t_slice), nt = t1 - t0, n = (g1 - g0) * nt;
-        off_a.resize(n); off_b.resize(n); len_a.resize(n); len_b.resize(n); sc.resize(n); ea.resize(n); eb.resize(n);
+        off_a.resize(n); off_b.resize(n); len_a.resize(n); len_b.resize(n); sc.resize(n);
+        for (int x = 0; x < std::max(nw, 2); ++x) w[x].resize(n);
         for (uint64_t k = 0; k < n; ++k) {
           const uint64_t g = g0 + k / nt, t = t0 + k % nt;
           off_a[k] = at_q[g]; len_a[k] = Q->len[qs[g]];
@@ -294,7 +325,8 @@ struct CrossCall {
         b.n_pairs = n; b.arena = arena.data(); b.arena_bytes = arena.size();
         b.off_a = off_a.data(); b.len_a = len_a.data(); b.off_b = off_b.data(); b.len_b = len_b.data();
         uint64_t bad = ~0ull;
-        rc = score_batch_impl(ctx, &b, scoring, is_sw, sc.data(), ea.data(), eb.data(), &bad);
+        rc = span ? span_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), w[2].data(), w[3].data(), &bad)
+                  : score_batch_impl(ctx, &b, scoring, is_sw, sc.data(), ea.data(), eb.data(), &bad);
         if (rc == SEQALIGN_E_UNKNOWN_PAIR && bad != ~0ull) {
           fail.offer(qs[g0 + bad / nt], t0 + bad % nt, nT);
           continue;
@@ -314,7 +346,7 @@ struct CrossCall {
         for (uint64_t k = 0; k < n; ++k) {
           const uint64_t at = qs[g0 + k / nt] * nT + t0 + k % nt;
           out_score[at] = sc[k];
-          if (is_sw) { out_end_a[at] = ea[k]; out_end_b[at] = eb[k]; }
+          for (int x = 0; x < nw; ++x) out_w[x][at] = w[x][k];
         }
       }
       if (fail.any()) break;
@@ -345,7 +377,7 @@ struct CrossCall {
       for (uint64_t t = 0; t < T->n_seqs; ++t) max_t = std::max(max_t, T->len[t]);
       if ((rc = admit_magnitude(sc, max_q, max_t, SA_FRAMES_ROWS))) return rc;
     }
-    for (uint64_t q = 0; q < Q->n_seqs; ++q) (Q->len[q] > SA_SCORE_ROW_MAX ? long_q : short_q).push_back(q);
+    for (uint64_t q = 0; q < Q->n_seqs; ++q) (Q->len[q] > row_max() ? long_q : short_q).push_back(q);
     if (!short_q.empty() && (rc = run_short(short_q))) return rc;
     if (!long_q.empty() && (rc = run_long(long_q))) return rc;
     if (fail.any()) {
@@ -381,7 +413,21 @@ int sa_host::score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *quer
   if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   StreamSyncOnExit sync(ctx->stream);
-  CrossCall call{ctx, queries, targets, scoring, is_sw, out_score, out_end_a, out_end_b, targets->n_seqs, FailPair()};
+  CrossCall call{ctx, queries, targets, scoring, is_sw, out_score, {out_end_a, out_end_b, nullptr, nullptr}, targets->n_seqs, FailPair()};
+  return call.run(q_base);
+}
+
+int sa_host::span_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                             const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
+                             uint32_t *out_len_a, uint32_t *out_len_b, uint64_t q_base) {
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  StreamSyncOnExit sync(ctx->stream);
+  CrossCall call{ctx, queries, targets, scoring, true, out_score, {out_pos_a, out_pos_b, out_len_a, out_len_b}, targets->n_seqs,
+                 FailPair(), nullptr, true};
   return call.run(q_base);
 }
 
@@ -413,8 +459,88 @@ int sa_host::score_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *que
   HIP_TRY(hipSetDevice(ctx->device));
   StreamSyncOnExit sync(ctx->stream);
   const SearchOut out{k, min_score, hits, n_hits};
-  CrossCall call{ctx, queries, targets, scoring, is_sw, nullptr, nullptr, nullptr, targets->n_seqs, FailPair(), &out};
+  CrossCall call{ctx, queries, targets, scoring, is_sw, nullptr, {nullptr, nullptr, nullptr, nullptr}, targets->n_seqs, FailPair(), &out};
   return call.run(q_base);
+}
+
+namespace {
+
+// seqalign_sw_span_search's second stage.  `hits` holds the first stage's lists with len_a / len_b = the best cell (end_a,
+// end_b) and pos 0.  Every hit above 0 becomes one pair of an explicit list: query[0 : end_a] against target[0 : end_b], whose
+// first hit is the full pair's in all five fields -- and whose row is as short as the hit allows.  What is
+// built here grows with the hits: each query that has one is copied once, up to its furthest end, and each hit's target prefix.
+int span_of_hits(seqalign_ctx_t *ctx, const seqalign_seqset_t *Q, const seqalign_seqset_t *T, const scoring_t *scoring, uint32_t k,
+                 seqalign_span_hit_t *hits, const uint32_t *n_hits, uint64_t q_base) {
+  uint64_t n = 0, bytes = 0;
+  for (uint64_t q = 0; q < Q->n_seqs; ++q) {
+    uint32_t q_end = 0;
+    for (uint32_t i = 0; i < n_hits[q]; ++i) {
+      const seqalign_span_hit_t &h = hits[q * k + i];
+      if (h.score <= 0) continue;
+      n++; bytes += h.len_b; q_end = std::max(q_end, h.len_a);
+    }
+    bytes += q_end;
+  }
+  if (!n) return SEQALIGN_OK;   // (hits of score 0 hold five zeros already)
+  std::vector<char> arena(bytes + 1);
+  std::vector<uint64_t> off_a(n), off_b(n), where(n);
+  std::vector<uint32_t> len_a(n), len_b(n), res(4 * n);
+  std::vector<int32_t> sc(n);
+  uint64_t at = 0, pos = 0;
+  for (uint64_t q = 0; q < Q->n_seqs; ++q) {
+    const uint64_t q_at = pos, first = at;
+    uint32_t q_end = 0;
+    for (uint32_t i = 0; i < n_hits[q]; ++i) {
+      const seqalign_span_hit_t &h = hits[q * k + i];
+      if (h.score <= 0) continue;
+      where[at] = q * k + i;
+      len_a[at] = h.len_a; len_b[at] = h.len_b;
+      q_end = std::max(q_end, h.len_a);
+      ++at;
+    }
+    memcpy(arena.data() + q_at, Q->arena + Q->off[q], q_end);
+    pos += q_end;
+    for (uint64_t j = first; j < at; ++j) {
+      off_a[j] = q_at; off_b[j] = pos;
+      memcpy(arena.data() + pos, T->arena + T->off[hits[where[j]].target], len_b[j]);
+      pos += len_b[j];
+    }
+  }
+  seqalign_batch_t b;
+  b.n_pairs = n; b.arena = arena.data(); b.arena_bytes = arena.size();
+  b.off_a = off_a.data(); b.len_a = len_a.data(); b.off_b = off_b.data(); b.len_b = len_b.data();
+  uint64_t bad = ~0ull;
+  const int rc = span_batch_impl(ctx, &b, scoring, sc.data(), res.data(), res.data() + n, res.data() + 2 * n, res.data() + 3 * n, &bad);
+  if (rc == SEQALIGN_E_UNKNOWN_PAIR && bad != ~0ull)   // (the first stage swept these cells and found none: kept for the message)
+    set_last_error("query " + std::to_string(q_base + where[bad] / k) + ", target " + std::to_string(hits[where[bad]].target) +
+                   ": a character pair without a score");
+  if (rc) return rc;
+  for (uint64_t j = 0; j < n; ++j) {
+    seqalign_span_hit_t &h = hits[where[j]];
+    h.pos_a = res[j]; h.pos_b = res[n + j]; h.len_a = res[2 * n + j]; h.len_b = res[3 * n + j];
+  }
+  return SEQALIGN_OK;
+}
+
+}  // namespace
+
+int sa_host::span_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                              const scoring_t *scoring, uint32_t k, int32_t min_score, seqalign_span_hit_t *hits,
+                              uint32_t *n_hits, uint64_t q_base) {
+  int rc = score_search_check(queries, targets, k);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  if (!queries->n_seqs) return SEQALIGN_OK;
+  if (!targets->n_seqs) {
+    memset(n_hits, 0, 4 * queries->n_seqs);
+    return SEQALIGN_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  StreamSyncOnExit sync(ctx->stream);
+  const SearchOut out{k, min_score, nullptr, n_hits, hits};
+  CrossCall call{ctx, queries, targets, scoring, true, nullptr, {nullptr, nullptr, nullptr, nullptr}, targets->n_seqs, FailPair(), &out};
+  if ((rc = call.run(q_base))) return rc;
+  return span_of_hits(ctx, queries, targets, scoring, k, hits, n_hits, q_base);
 }
 
 extern "C" int seqalign_nw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
@@ -441,4 +567,18 @@ extern "C" int seqalign_sw_score_search(seqalign_ctx_t *ctx, const seqalign_seqs
                                         uint32_t *n_hits) {
   if (!ctx || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
   return score_search_call(ctx, queries, targets, scoring, true, k, min_score, hits, n_hits, 0);
+}
+
+extern "C" int seqalign_sw_span_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                      const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
+                                      uint32_t *out_len_a, uint32_t *out_len_b) {
+  if (!ctx || !scoring || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b) return SEQALIGN_E_ARG;
+  return span_cross_call(ctx, queries, targets, scoring, out_score, out_pos_a, out_pos_b, out_len_a, out_len_b, 0);
+}
+
+extern "C" int seqalign_sw_span_search(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                       const scoring_t *scoring, uint32_t k, int32_t min_score, seqalign_span_hit_t *hits,
+                                       uint32_t *n_hits) {
+  if (!ctx || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
+  return span_search_call(ctx, queries, targets, scoring, k, min_score, hits, n_hits, 0);
 }

@@ -419,18 +419,30 @@ void async_shutdown(seqalign_ctx *ctx);   // sa_async.hip: drain the submitted j
 SaFillParams score_fill_params(const seqalign_dev_scoring *s);
 int score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw,
                      int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, uint64_t *fail_pair = nullptr);
+// ... and seqalign_sw_span_batch without its entry checks (the span cross and span search calls' long queries and prefix pairs)
+int span_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                    uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
+                    uint64_t *fail_pair = nullptr);
 // sa_batch_score_cross.hip: the sets' checks (E_ARG; n_queries x n_targets must fit 64 bits), and one context's cross call
 // (its own CallScope) -- q_base: what the error message adds to a query index (the *_multi calls' ranges)
 int score_cross_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets);
 int score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                      const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b,
                      uint64_t q_base);
+// ... its span form (seqalign_sw_span_cross): five matrices
+int span_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                    const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
+                    uint32_t *out_len_a, uint32_t *out_len_b, uint64_t q_base);
 // ... and the top-k search (seqalign_*_score_search) on the same tiles: its checks (E_ARG: k, the sets, n_targets), and
 // one context's call
 int score_search_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets, uint32_t k);
 int score_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                       const scoring_t *scoring, bool is_sw, uint32_t k, int32_t min_score, seqalign_search_hit_t *hits,
                       uint32_t *n_hits, uint64_t q_base);
+// ... and the search with spans (seqalign_sw_span_search): that search, then the span sweep on the selected hits' prefix pairs
+int span_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                     const scoring_t *scoring, uint32_t k, int32_t min_score, seqalign_span_hit_t *hits, uint32_t *n_hits,
+                     uint64_t q_base);
 
 struct CigarScope {   // RAII: the call's output format, put back on every way out
   seqalign_ctx *ctx;

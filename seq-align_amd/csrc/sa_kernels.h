@@ -481,6 +481,19 @@ struct SaScoreCrossParams {
 };
 /* every query of the class has len_a <= max_len_a <= SA_SCORE_ROW_MAX */
 hipError_t sa_launch_score_cross(const SaScoreCrossParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream);
+/* SW hit spans over two sets (seqalign_sw_span_cross): the span sweep of sa_span.hip's one-wave kernel with SaScoreCrossParams'
+ * wave -> (query, target) mapping.  s.f as SaScoreCrossParams::f; s.score, s.pos_a, s.pos_b, s.len_a, s.len_b: [q * n_t + t] for
+ * every query q of the tile; s.err_flag |= 1 when a pair has a cell without a score; the strips fields of s are unused. */
+struct SaSpanCrossParams {
+  SaSpanParams s;
+  const uint32_t *q_list;       /* [nq] the class's queries                                                            */
+  const uint32_t *t_order;      /* [n_t] every target of the tile, longest first                                       */
+  uint32_t nq, n_t;
+  uint32_t n_waves;             /* nq * n_t                                                                            */
+  unsigned long long *err_pair; /* min of q * n_t + t over the failing pairs; the caller set it to ~0                  */
+};
+/* every query of the class has len_a <= max_len_a <= SA_SPAN_ROW_MAX; recorded as "score_cross" (items: waves) */
+hipError_t sa_launch_span_cross(const SaSpanCrossParams &p, uint32_t max_len_a, hipStream_t stream);
 /* top-k score search (seqalign_*_score_search, sa_score_select.hip): one workgroup per query row of a tile, after its
  * score_cross launches.  Keeps the k smallest keys (~(score ^ 0x80000000)) << 32 | (t_base + t) of the row's entries with
  * score >= min_score together with the query's running list, and writes them back sorted.  The running list's targets

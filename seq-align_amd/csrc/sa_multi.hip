@@ -279,3 +279,30 @@ extern "C" int seqalign_sw_score_search_multi(seqalign_ctx_t *const *ctxs, int n
   if (bad_ctx_list(ctxs, n_ctx) || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
   return score_search_multi(ctxs, n_ctx, queries, targets, scoring, true, k, min_score, hits, n_hits);
 }
+
+// span matrices and the search with spans: the query ranges of the score forms
+extern "C" int seqalign_sw_span_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                            const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score,
+                                            uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b) {
+  if (bad_ctx_list(ctxs, n_ctx) || !scoring || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b) return SEQALIGN_E_ARG;
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  const uint64_t nt = targets->n_seqs;
+  if (!queries->n_seqs || !nt) return SEQALIGN_OK;
+  return for_each_query_shard(queries, n_ctx, [&](int g, const seqalign_seqset_t *s, uint64_t first) {
+    return span_cross_call(ctxs[g], s, targets, scoring, out_score + first * nt, out_pos_a + first * nt, out_pos_b + first * nt,
+                           out_len_a + first * nt, out_len_b + first * nt, first);
+  });
+}
+
+extern "C" int seqalign_sw_span_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
+                                             const seqalign_seqset_t *targets, const scoring_t *scoring, uint32_t k,
+                                             int32_t min_score, seqalign_span_hit_t *hits, uint32_t *n_hits) {
+  if (bad_ctx_list(ctxs, n_ctx) || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
+  int rc = score_search_check(queries, targets, k);
+  if (rc) return rc;
+  if (!queries->n_seqs) return SEQALIGN_OK;
+  return for_each_query_shard(queries, n_ctx, [&](int g, const seqalign_seqset_t *s, uint64_t first) {
+    return span_search_call(ctxs[g], s, targets, scoring, k, min_score, hits + first * k, n_hits + first, first);
+  });
+}

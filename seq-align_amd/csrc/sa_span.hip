@@ -26,25 +26,43 @@
 // span_rows_kernel: rows of up to 512 columns, one wave per pair (1 .. 6 or 8 columns per lane), 4 pairs per workgroup.
 // span_strips_kernel: wider rows, the strips pipeline of sa_strips.hpp -- the hand-off per row and strip is 32 bytes
 // (StripSpanHandoff: max(M, A) and B of the strip's last column, their spans, and whether max(M, A) came from A), the best
-// cell so far travels with its span (merge_left_best_span).  Both are recorded as "score_rows" / "score_strips".
+// cell so far travels with its span (merge_left_best_span).  Both are recorded as "score_rows" / "score_strips", the
+// one-wave kernel's CROSS form (two sets instead of a pair list) as "score_cross".
 #include "sa_span.hpp"
 
 namespace sa {
 
-template <int CPL, int SUBST, bool GENERAL>
+__device__ __forceinline__ const SaSpanParams &span_params(const SaSpanParams &p) { return p; }
+__device__ __forceinline__ const SaSpanParams &span_params(const SaSpanCrossParams &p) { return p.s; }
+
+// CROSS (seqalign_sw_span_cross, kind "score_cross"): sa_score.hip's CROSS form of this kernel -- wave w of a launch for one
+// row class takes target t_order[w / nq] and query q_list[w % nq], longest targets first, writes its five words at
+// [q * n_t + t] of the tile and leaves a failing pair's tile-local index in one 64-bit atomicMin.  Same sweep, same picks.
+template <int CPL, int SUBST, bool GENERAL, bool CROSS = false>
 __global__ void __launch_bounds__(kWave *kWavesPerBlock)
-span_rows_kernel(const SaSpanParams sp) {
+span_rows_kernel(const std::conditional_t<CROSS, SaSpanCrossParams, SaSpanParams> kp) {
+  const SaSpanParams &sp = span_params(kp);
   const SaFillParams &p = sp.f;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
   const int32_t *table = stage_table<SUBST>(p, lds_table);
 
   const int lane = threadIdx.x & (kWave - 1);
   const uint32_t pair = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
-  if (pair >= p.n_pairs) return;   // wave-uniform, after the only barrier
+  uint32_t qa = pair, tb = pair;   // descriptors of seq_a and seq_b
+  uint64_t at = pair;              // where the result goes
+  if constexpr (CROSS) {
+    if (pair >= kp.n_waves) return;   // wave-uniform, after the only barrier
+    const uint32_t ti = pair / kp.nq;
+    qa = kp.q_list[pair - ti * kp.nq];
+    tb = kp.t_order[ti];
+    at = (uint64_t)qa * kp.n_t + tb;
+  } else {
+    if (pair >= p.n_pairs) return;   // wave-uniform, after the only barrier
+  }
 
-  const uint32_t la = p.len_a[pair], lb = p.len_b[pair];
-  const uint8_t *__restrict__ sa_ = p.arena + p.off_a[pair];
-  const uint8_t *__restrict__ sb_ = p.arena + p.off_b[pair];
+  const uint32_t la = p.len_a[qa], lb = p.len_b[tb];
+  const uint8_t *__restrict__ sa_ = p.arena + p.off_a[qa];
+  const uint8_t *__restrict__ sb_ = p.arena + p.off_b[tb];
   const uint32_t W = la + 1;
   const SweepConsts k(p, table);
 
@@ -72,9 +90,16 @@ span_rows_kernel(const SaSpanParams sp) {
   unsigned long long key, span;
   sw.reduce_best(col0, ncol, score, key, span);
   if (lane == 0) {
-    span_write(sp, pair, score, key, span);
-    p.status[pair] = err;
-    if (err != ~0ull) atomicOr(sp.err_flag, 1u);
+    span_write(sp, at, score, key, span);
+    if constexpr (CROSS) {
+      if (err != ~0ull) {
+        atomicMin(kp.err_pair, (unsigned long long)at);
+        atomicOr(sp.err_flag, 1u);
+      }
+    } else {
+      p.status[pair] = err;
+      if (err != ~0ull) atomicOr(sp.err_flag, 1u);
+    }
   }
 }
 
@@ -155,11 +180,16 @@ span_strips_kernel(const SaSpanParams sp) {
   if (!last_strip && lb > 0) strip_publish(done + strip, lb);   // the last rows (and the best cell so far)
 }
 
-template <int CPL>
-static hipError_t launch_span_rows_cpl(const SaSpanParams &p, hipStream_t stream) {
-  const dim3 grid((p.f.n_pairs + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
-  launch_by_scoring(p.f, [&](auto subst, auto general, uint32_t table_ints) {
-    hipLaunchKernelGGL((span_rows_kernel<CPL, subst(), general()>), grid, block, table_ints * sizeof(int32_t), stream, p);
+inline uint32_t one_wave_waves(const SaSpanParams &p) { return p.f.n_pairs; }
+inline uint32_t one_wave_waves(const SaSpanCrossParams &p) { return p.n_waves; }
+inline const SaFillParams &fill_of(const SaSpanParams &p) { return p.f; }
+inline const SaFillParams &fill_of(const SaSpanCrossParams &p) { return p.s.f; }
+
+template <int CPL, bool CROSS, class P>
+static hipError_t launch_span_rows_cpl(const P &p, hipStream_t stream) {
+  const dim3 grid((one_wave_waves(p) + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
+  launch_by_scoring(fill_of(p), [&](auto subst, auto general, uint32_t table_ints) {
+    hipLaunchKernelGGL((span_rows_kernel<CPL, subst(), general(), CROSS>), grid, block, table_ints * sizeof(int32_t), stream, p);
   });
   return hipGetLastError();
 }
@@ -174,7 +204,14 @@ hipError_t sa_launch_span_rows(const SaSpanParams &p, uint32_t max_len_a, hipStr
   if (p.f.n_pairs == 0) return hipSuccess;
   if (max_len_a > SA_SPAN_ROW_MAX) return hipErrorInvalidValue;
   sa_record_launch(SEQALIGN_K_SCORE_ROWS, p.f.n_pairs);
-  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8>(sa::columns_per_lane(max_len_a), [&](auto cpl) { return sa::launch_span_rows_cpl<cpl()>(p, stream); });
+  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8>(sa::columns_per_lane(max_len_a), [&](auto cpl) { return sa::launch_span_rows_cpl<cpl(), false>(p, stream); });
+}
+
+hipError_t sa_launch_span_cross(const SaSpanCrossParams &p, uint32_t max_len_a, hipStream_t stream) {
+  if (p.n_waves == 0) return hipSuccess;
+  if (max_len_a > SA_SPAN_ROW_MAX || p.nq == 0) return hipErrorInvalidValue;
+  sa_record_launch(SEQALIGN_K_SCORE_CROSS, p.n_waves);
+  return sa::launch_by_cpl<1, 2, 3, 4, 5, 6, 8>(sa::columns_per_lane(max_len_a), [&](auto cpl) { return sa::launch_span_rows_cpl<cpl(), true>(p, stream); });
 }
 
 hipError_t sa_launch_span_strips(const SaSpanParams &p, hipStream_t stream) {

@@ -78,6 +78,9 @@ INT32_MIN = -2**31
 SEARCH_MAX_K = 1024   # SEQALIGN_SEARCH_MAX_K
 # seqalign_search_hit_t
 SEARCH_HIT = np.dtype([("target", np.uint32), ("score", np.int32), ("end_a", np.uint32), ("end_b", np.uint32)])
+# seqalign_span_hit_t
+SPAN_HIT = np.dtype([("target", np.uint32), ("score", np.int32), ("pos_a", np.uint32), ("pos_b", np.uint32),
+                     ("len_a", np.uint32), ("len_b", np.uint32)])
 
 
 class SwHit(C.Structure):
@@ -491,13 +494,36 @@ class Context:
         """seqalign_sw_score_search: as nw_score_search over sw_score_cross's score, with its end_a / end_b."""
         return self._score_search(queries, targets, scoring, k, min_score, peers, True)
 
-    def _score_search(self, queries, targets, scoring, k, min_score, peers, is_sw):
+    def sw_span_search(self, queries, targets, scoring: Scoring, k: int, min_score: int = 1, peers=None):
+        """seqalign_sw_span_search: (n_hits uint32[n_queries], hits SPAN_HIT[n_queries, k]) -- sw_score_search's n_hits,
+        targets and scores with sw_span_cross's pos / len at [q, target] (pos + len: the score search's end); a hit of score
+        0 has five zeros.  The score search, then the span sweep on the selected hits' prefix pairs only."""
+        return self._score_search(queries, targets, scoring, k, min_score, peers, True, span=True)
+
+    def sw_span_cross(self, queries, targets, scoring: Scoring, peers=None):
+        """seqalign_sw_span_cross: (score int32, pos_a, pos_b, len_a, len_b uint32), each [n_queries, n_targets] -- sw_span
+        on workloads.cross_batch(queries, targets) without building that batch; pos_a / len_a index the query, pos_b / len_b
+        the target; score and pos + len are sw_score_cross's."""
+        _cross_args(queries, targets, scoring)
+        shape = (queries.n_seqs, targets.n_seqs)
+        score = np.zeros(shape, np.int32)
+        pos_a, pos_b, len_a, len_b = (np.zeros(shape, np.uint32) for _ in range(4))
+        dq, dt = seqset_desc(queries), seqset_desc(targets)
+        tail = (C.byref(dq), C.byref(dt), C.byref(scoring), _ptr(score), _ptr(pos_a), _ptr(pos_b), _ptr(len_a), _ptr(len_b))
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(lib().seqalign_sw_span_cross_multi(hs, nh, *tail), "seqalign_sw_span_cross_multi")
+        else:
+            _check(lib().seqalign_sw_span_cross(self._h, *tail), "seqalign_sw_span_cross")
+        return score, pos_a, pos_b, len_a, len_b
+
+    def _score_search(self, queries, targets, scoring, k, min_score, peers, is_sw, span=False):
         _search_args(queries, targets, scoring, k, min_score)
         nq = queries.n_seqs
-        n_hits, hits = np.zeros(nq, np.uint32), np.zeros((nq, k), SEARCH_HIT)
+        n_hits, hits = np.zeros(nq, np.uint32), np.zeros((nq, k), SPAN_HIT if span else SEARCH_HIT)
         dq, dt = seqset_desc(queries), seqset_desc(targets)
         tail = (C.byref(dq), C.byref(dt), C.byref(scoring), C.c_uint32(k), C.c_int32(min_score), _ptr(hits), _ptr(n_hits))
-        name = "seqalign_sw_score_search" if is_sw else "seqalign_nw_score_search"
+        name = "seqalign_sw_span_search" if span else "seqalign_sw_score_search" if is_sw else "seqalign_nw_score_search"
         if peers:
             hs, nh = self._handles(peers)
             _check(getattr(lib(), name + "_multi")(hs, nh, *tail), name + "_multi")
@@ -1122,6 +1148,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_score_cross", "seqalign_sw_score_cross", "seqalign_nw_score_cross_multi", "seqalign_sw_score_cross_multi",
     "seqalign_nw_score_search", "seqalign_sw_score_search", "seqalign_nw_score_search_multi",
     "seqalign_sw_score_search_multi",
+    "seqalign_sw_span_cross", "seqalign_sw_span_cross_multi", "seqalign_sw_span_search", "seqalign_sw_span_search_multi",
     "seqalign_nw_align_long", "seqalign_sw_align_long",
     "seqalign_nw_score_banded", "seqalign_nw_align_banded", "seqalign_band_score_time_ms", "seqalign_ctx_last_call_info_ext", "seqalign_kernel_kind_ext_name",
     "seqalign_sw_score_banded", "seqalign_sw_align_banded", "seqalign_sw_band_score_time_ms",

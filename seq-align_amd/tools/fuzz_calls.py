@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, seqalign_sw_span_batch, *_score_cross,
-*_score_search, *_align_long, the banded NW calls, seqalign_sw_span_banded and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+*_score_search, seqalign_sw_span_cross and seqalign_sw_span_search (against sw_span on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -90,7 +90,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         import maglib as G      # only the scaled runs need it: the default run is what it was, imports included
     ctx = ctx or (None if dry else S.Context(0))
     t_end = time.time() + seconds
-    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0}
+    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -230,6 +230,22 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                     fail("SW SEARCH" if is_sw else "NW SEARCH", spec, "k", k_top, "min_score", min_score, "query", i, queries[i], targets,
                          h.tolist(), (tg.tolist(), ws.tolist()))
             n["search"] += 4
+            if not is_sw:
+                continue
+            # ---- the same sets' span matrices and search with spans: sw_span on the explicit batch, the oracle's best cells
+            want = tuple(x.reshape(4, 6) for x in ctx.sw_span(W.cross_batch(q, t), sc))
+            got = ctx.sw_span_cross(q, t, sc)
+            if not (all(np.array_equal(g, w) for g, w in zip(got, want)) and np.array_equal(got[0], dense[0])
+                    and np.array_equal(got[1] + got[3], dense[1]) and np.array_equal(got[2] + got[4], dense[2])):
+                fail("SW SPAN CROSS", spec, queries, targets, [g.tolist() for g in got], [w.tolist() for w in want])
+            n["span_cross"] += 24
+            n_span, span_hits = ctx.sw_span_search(q, t, sc, k_top, min_score=min_score)
+            for i in range(4):
+                h, hs = span_hits[i, :int(n_span[i])], hits[i, :int(n_hits[i])]
+                if not (int(n_span[i]) == int(n_hits[i]) and np.array_equal(h["target"], hs["target"]) and np.array_equal(h["score"], hs["score"])
+                        and all(np.array_equal(h[name], w[i][h["target"]]) for name, w in zip(("pos_a", "pos_b", "len_a", "len_b"), want[1:]))):
+                    fail("SW SPAN SEARCH", spec, "k", k_top, "min_score", min_score, "query", i, queries[i], targets, h.tolist(), hs.tolist())
+            n["span_search"] += 4
 
         # ---- alignments of any length
         rows = (1, 3, 17, 64, 0)[int(v[14] % 5)]
@@ -335,7 +351,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         print(f"fuzz_calls scale up to {scale}: {n['redraws']} factors redrawn in {n['redrawn_trials']} of {n['trials']} trials "
               f"({n['redrawn_trials'] / max(1, n['trials']):.1%} of the trials)", flush=True)
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
-          f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['cross']} cross cells, {n['search']} searches, {n['long']} long alignments, {n['banded']} banded "
+          f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['long']} long alignments, {n['banded']} banded "
           f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results identical to the oracle "
           f"(seed {seed})", flush=True)
     return n
