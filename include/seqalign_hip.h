@@ -610,6 +610,35 @@ int seqalign_sw_span_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const s
  * batch (one chunk) is uploaded once, then its kernels run `repeats` times, each launch between two HIP events. */
 int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
                              float *ms_each);
+/* ---- NW alignment statistics: identity counts of the global alignment, no traceback ---- */
+/* For every pair, over the alignment seqalign_nw_batch returns for it (the reference's end pick at the corner cell and
+ * alignment_reverse_move's tie order GAP_A, GAP_B, MATCH -- not merely some optimal alignment):
+ *   out_score[p]       what seqalign_nw_score_batch returns;
+ *   out_matches[p]     the columns that hold a letter of both sequences whose two letters are equal after the scoring's own case
+ *                      folding (scoring_t.case_sensitive); wildcards and substitution scores play no part;
+ *   out_mismatches[p]  the other columns that hold a letter of both.
+ * From these: aligned columns = matches + mismatches; alignment length = len_a + len_b - matches - mismatches; gap columns =
+ * len_a + len_b - 2 (matches + mismatches); identity = matches / alignment length, or over the shorter sequence, as the
+ * caller prefers.  A pair with len_a == 0 or len_b == 0 has both counts 0.
+ *   Nothing is stored per cell and nothing is walked: the two counters travel forward beside the three values of a cell
+ * (DESIGN.md 3.21).  Device memory per pair: the sequences, 64 bytes of descriptors, status and results, and for rows over 512
+ * columns 32 bytes per row and strip of 512 columns of hand-off; 12 bytes per pair come home.  No 2^31-cell cap.
+ *   Lengths, argument checks, scoring admission (SEQALIGN_E_DOMAIN) and SEQALIGN_E_UNKNOWN_PAIR are
+ * seqalign_nw_score_batch's.  SEQALIGN_E_TRACEBACK ("pair P: traceback failed") is returned for the lowest pair whose end
+ * state has no walk, in the order in which seqalign_nw_batch reports the two errors (the lowest failing pair's code; on one
+ * pair the missing score first).  Over whole matrices every pair keeps the alignment that puts all of seq_a and then all of
+ * seq_b against gaps, whatever no_mismatches / no_gaps_in_a / no_gaps_in_b forbid, so within the admitted domain no pair
+ * takes that path.  On an error the outputs are unspecified beyond the chunks already delivered.
+ *   Not here: SW statistics (they need spans and counts together), a search form, banded forms, _cross_multi, _submit, the
+ * command-line tools, gap-open counts. */
+int seqalign_nw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                            uint32_t *out_matches, uint32_t *out_mismatches);
+/* ... over several contexts (GPUs): contiguous ranges of nearly equal cells, results exactly the single-context call's */
+int seqalign_nw_stats_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
+/* Kernel time of seqalign_nw_stats_batch (seq-align_amd/tools/nw_stats_bench.py), the sibling of seqalign_sw_span_time_ms */
+int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                              float *ms_each);
 /* ---- banded SW hit spans: start and end of the best local hit inside a band, no traceback ---- */
 /* seqalign_sw_span_batch over the banded SW matrices: the five integers a mapper reports per read at the cost of a banded
  * sweep, nothing stored per cell and no walk.
@@ -853,6 +882,14 @@ int seqalign_sw_score_search_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const
 int seqalign_sw_span_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                            const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
                            uint32_t *out_len_a, uint32_t *out_len_b);
+/* Statistics matrices: seqalign_nw_stats_batch's three outputs for every query against every target, [n_queries][n_targets]
+ * each, the result of that call on the batch whose pair q * n_targets + t is (query q, target t) -- which is never built.
+ * Queries of up to 512 columns run one wave per (query, target) on tiles of the two sets, 12 result bytes per pair; longer
+ * queries run seqalign_nw_stats_batch's strips on their pairs.  Checks, admission, empty sets and the errors' "query Q, target
+ * T: ..." for the lowest q * n_targets + t are seqalign_nw_score_cross's, SEQALIGN_E_TRACEBACK as in seqalign_nw_stats_batch.
+ * There is no _cross_multi form. */
+int seqalign_nw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                            const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
 /* ... over several contexts: the query ranges of seqalign_sw_score_cross_multi; results exactly the single-context call's */
 int seqalign_sw_span_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
                                  const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score,

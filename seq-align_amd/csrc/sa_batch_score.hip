@@ -1,7 +1,9 @@
 // sa_batch_score.hip -- score only over HOST batches: seqalign_nw_score_batch, seqalign_sw_score_batch (and the timing
-// hook seqalign_score_time_ms), and SW hit spans: seqalign_sw_span_batch (and seqalign_sw_span_time_ms).  No matrices, no
-// traceback: per chunk the sequences go up, the score kernels (sa_score.hip) or the span kernels (sa_span.hip) run, and 4 or
-// 12 bytes per pair come back, 20 for a span (score, pos_a, pos_b, len_a, len_b), plus the error word.
+// hook seqalign_score_time_ms), SW hit spans: seqalign_sw_span_batch (and seqalign_sw_span_time_ms), and NW alignment statistics:
+// seqalign_nw_stats_batch (and seqalign_nw_stats_time_ms).  No matrices, no traceback: per chunk the sequences go up, the score
+// kernels (sa_score.hip), the span kernels (sa_span.hip) or the stats kernels (sa_nw_stats.hip) run, and 4 or 12 bytes per pair
+// come back, 20 for a span (score, pos_a, pos_b, len_a, len_b), 12 for statistics (score, matches, mismatches), plus the error
+// word.
 //
 // A chunk's pairs are put in classes by row width -- the columns per lane of the one-wave kernel (score: 1 .. 16, span: 1 .. 6
 // and 8), or the strips kernel for rows over 1 024 (span: 512) columns -- and the descriptors are laid out class by class, so
@@ -10,9 +12,10 @@
 //
 // Chunks are cut by device BYTES, not cells (sa_chunks.hpp): the sequences, 64 (span: 72) bytes of descriptors, status and
 // results per pair, and for the strips kernel the hand-off columns (8 bytes per row and strip; span: 32) and 20 (span: 36)
-// bytes per strip of progress and best cell -- a 100 000 x 100 000 score pair is 157 MB, not 120 GB.
+// bytes per strip of progress and best cell -- a 100 000 x 100 000 score pair is 157 MB, not 120 GB.  Statistics: 64 bytes per
+// pair, the span's 32 per row and strip, 4 per strip (no best cell).
 //
-// The two families are one driver (RowChunkRun) over a traits struct each: what differs is the kernels' parameter block,
+// The three families are one driver (RowChunkRun) over a traits struct each: what differs is the kernels' parameter block,
 // ladder and launch functions and the bytes named above.
 #include "sa_chunks.hpp"
 
@@ -37,10 +40,12 @@ struct ScoreTraits {   // sa_score.hip
   static constexpr uint64_t kPairBytes = 64;   // descriptors (32), results (12), status (8), slack
   static constexpr uint64_t kHandoffBytes = 8, kBestBytes = 16;
   static constexpr const char *kLaunch = "score kernel launch";
+  static constexpr int kMarkField = 0;         // no result word carries a mark
   static int fields(bool is_sw) { return is_sw ? 3 : 1; }   // result words per pair: score; SW: end_a, end_b
   static int row_class(uint32_t la) { return sa_score_row_class(la); }
   static uint32_t strips_per_pair(uint32_t la) { return sa_score_strips_per_pair(la); }
   static void set_results(Params &p, uint32_t *res, uint64_t n) { p.end_a = res + n; p.end_b = res + 2 * n; }
+  static void set_strip_best(Params &p, uint32_t *best) { p.strip_best = best; }
   static hipError_t launch_rows(const Params &p, uint32_t max_a, bool is_sw, hipStream_t st) { return sa_launch_score_rows(p, max_a, is_sw, st); }
   static hipError_t launch_strips(const Params &p, bool is_sw, hipStream_t st) { return sa_launch_score_strips(p, is_sw, st); }
 };
@@ -52,14 +57,33 @@ struct SpanTraits {   // sa_span.hip: the SW form only
   static constexpr uint64_t kPairBytes = 72;   // descriptors (32), results (20), status (8), slack
   static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
   static constexpr const char *kLaunch = "span kernel launch";
+  static constexpr int kMarkField = 0;
   static int fields(bool) { return 5; }   // score, pos_a, pos_b, len_a, len_b
   static int row_class(uint32_t la) { return sa_span_row_class(la); }
   static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
   static void set_results(Params &p, uint32_t *res, uint64_t n) {
     p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
   }
+  static void set_strip_best(Params &p, uint32_t *best) { p.strip_best = best; }
   static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_span_rows(p, max_a, st); }
   static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_span_strips(p, st); }
+};
+
+struct StatsTraits {   // sa_nw_stats.hip: the NW form only; classes, strips and hand-off of the span kernels, no best cell
+  using Params = SaStatsParams;
+  static constexpr int kRowClasses = SA_SPAN_ROW_CLASSES;
+  static constexpr uint32_t kRowMax = SA_SPAN_ROW_MAX;
+  static constexpr uint64_t kPairBytes = 64;   // descriptors (32), results (12), status (8), slack
+  static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = 0;
+  static constexpr const char *kLaunch = "stats kernel launch";
+  static constexpr int kMarkField = 2;         // SA_STATS_NO_WALK in the mismatch word: SEQALIGN_E_TRACEBACK
+  static int fields(bool) { return 3; }   // score, matches, mismatches
+  static int row_class(uint32_t la) { return sa_span_row_class(la); }
+  static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
+  static void set_results(Params &p, uint32_t *res, uint64_t n) { p.matches = res + n; p.mismatches = res + 2 * n; }
+  static void set_strip_best(Params &, uint32_t *) {}
+  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_stats_rows(p, max_a, st); }
+  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_stats_strips(p, st); }
 };
 
 // hand-off columns of one pair: strips 0 .. last - 1, len_b + 1 rows each, in rows
@@ -133,7 +157,7 @@ struct RowChunkRun {
       hipError_t e;
       if (x == kStripClass) {
         p.progress = ctx->strip_progress.as<uint32_t>();
-        p.strip_best = p.progress + sa_strip_best_word(strip_words);
+        T::set_strip_best(p, p.progress + sa_strip_best_word(strip_words));
         p.handoff = ctx->score_handoff.as<int32_t>();
         p.handoff_off = stage.d_u64(0) + s0;
         p.strips_per_pair = spp;
@@ -158,7 +182,22 @@ struct RowChunkRun {
     uint32_t *h = ctx->h_misc.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(stream_wait_spinning(ctx->stream));
-    if (h[0]) return stage.fail_from_status(fail_pair);
+    uint64_t unknown = ~0ull, no_walk = ~0ull;   // the chunk's lowest failing pairs, as batch indices
+    if (h[0] && (rc = stage.fail_from_status(&unknown)) != SEQALIGN_E_UNKNOWN_PAIR) return rc;
+    if constexpr (T::kMarkField > 0) {   // stats: SA_STATS_NO_WALK in the mismatch word
+      const uint32_t *w = h + 4 + (uint64_t)T::kMarkField * n;
+      for (uint64_t s = 0; s < n; ++s)
+        if (w[s] & SA_STATS_NO_WALK) no_walk = std::min<uint64_t>(no_walk, stage.first + stage.order[s]);
+    }
+    if (no_walk < unknown) {   // the lowest failing pair's code is the call's, as seqalign_nw_batch's; on one pair the fill's first
+      if (fail_pair) *fail_pair = no_walk;
+      set_last_error("pair " + std::to_string(no_walk) + ": traceback failed");
+      return SEQALIGN_E_TRACEBACK;
+    }
+    if (h[0]) {
+      if (fail_pair) *fail_pair = unknown;
+      return SEQALIGN_E_UNKNOWN_PAIR;
+    }
     stage.scatter(h + 4, fields, out_score, out);
     return SEQALIGN_OK;
   }
@@ -216,6 +255,12 @@ int sa_host::span_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
   return row_batch_call<SpanTraits>(ctx, batch, scoring, true, out_score, out, fail_pair);
 }
 
+int sa_host::stats_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                              uint32_t *out_matches, uint32_t *out_mismatches, uint64_t *fail_pair) {
+  uint32_t *const out[2] = {out_matches, out_mismatches};
+  return row_batch_call<StatsTraits>(ctx, batch, scoring, false, out_score, out, fail_pair);
+}
+
 extern "C" int seqalign_nw_score_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                        int32_t *out_score) {
   if (!ctx || !scoring || !out_score) return SEQALIGN_E_ARG;
@@ -250,4 +295,18 @@ extern "C" int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batc
   if (!ctx || !scoring || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
   CallScope scope(ctx);
   return row_time_call<SpanTraits>(ctx, batch, scoring, true, repeats, ms_each, "seqalign_sw_span_time_ms");
+}
+
+extern "C" int seqalign_nw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                       int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
+  if (!ctx || !scoring || !out_score || !out_matches || !out_mismatches || !batch_readable(batch)) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);   // (every argument checked before the context is touched)
+  return stats_batch_impl(ctx, batch, scoring, out_score, out_matches, out_mismatches);
+}
+
+extern "C" int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                                         float *ms_each) {
+  if (!ctx || !scoring || repeats <= 0 || !ms_each || !batch_readable(batch) || batch->n_pairs == 0) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);
+  return row_time_call<StatsTraits>(ctx, batch, scoring, false, repeats, ms_each, "seqalign_nw_stats_time_ms");
 }

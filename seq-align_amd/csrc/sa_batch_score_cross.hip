@@ -25,6 +25,11 @@
 // kernel (sa_span.hip) in place of the score kernel's, five rows home per query, and the short / long split at SA_SPAN_ROW_MAX
 // columns, the long queries through the span strips (span_batch_impl).
 //
+// Statistics matrices (seqalign_nw_stats_cross) are the span matrices' tiles with 12 result bytes per pair: the CROSS form of the
+// stats kernel (sa_nw_stats.hip), three rows home per query, the same split at SA_SPAN_ROW_MAX columns, the long queries through
+// the stats strips (stats_batch_impl).  A pair whose end pick has no walk (SA_STATS_NO_WALK) is SEQALIGN_E_TRACEBACK; between
+// it and a pair without a score the lower pair's code is the call's.
+//
 // Top-k search with spans (seqalign_sw_span_search) is two stages: the score search above, unchanged, and then
 // the span sweep on the selected hits alone -- for each the PREFIX pair (query[0 : end_a], target[0 : end_b]), whose first hit
 // is the full pair's, as an explicit pair list through span_batch_impl.
@@ -102,10 +107,12 @@ struct CrossCall {
   FailPair fail;
   const SearchOut *search = nullptr;   // set: top-k search, the matrix outputs are unused
   bool span = false;                   // seqalign_sw_span_cross (is_sw set, no search)
+  bool stats = false;                  // seqalign_nw_stats_cross (is_sw clear, no search): out_w = matches, mismatches
+  FailPair no_walk;                    // stats: the lowest pair whose end pick has no walk (SEQALIGN_E_TRACEBACK)
 
-  int words() const { return span ? 4 : is_sw ? 2 : 0; }   // result words per pair behind the score
+  int words() const { return span ? 4 : (is_sw || stats) ? 2 : 0; }   // result words per pair behind the score
   uint64_t result_bytes() const { return 4 * (1 + (uint64_t)words()); }
-  uint32_t row_max() const { return span ? SA_SPAN_ROW_MAX : SA_SCORE_ROW_MAX; }   // the one-wave kernels' widest query
+  uint32_t row_max() const { return (span || stats) ? SA_SPAN_ROW_MAX : SA_SCORE_ROW_MAX; }   // the one-wave kernels' widest query
   uint64_t list_bytes() const { return search ? 16ull * search->k + 4 : 0; }   // one query's running list
 
   // queries <= row_max(): the cross kernel, tile by tile
@@ -214,6 +221,22 @@ struct CrossCall {
             if (e != hipSuccess) return fail_hip(e, "span cross kernel launch");
             continue;
           }
+          if (stats) {
+            SaStatsCrossParams p;
+            memset(&p, 0, sizeof(p));
+            p.s.f = f0;
+            p.s.f.arena = d_seq;
+            p.s.f.off_a = d_off_q; p.s.f.len_a = d_len_q; p.s.f.off_b = d_off_t; p.s.f.len_b = d_len_t;
+            p.q_list = d_qlist + cls_first[x]; p.t_order = d_tord;
+            p.nq = (uint32_t)m; p.n_t = (uint32_t)nt; p.n_waves = (uint32_t)(m * nt);
+            p.s.score = reinterpret_cast<int32_t *>(d_res + 4);
+            p.s.matches = d_res + 4 + n; p.s.mismatches = d_res + 4 + 2 * n;
+            p.s.err_flag = d_res;
+            p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
+            const hipError_t e = sa_launch_stats_cross(p, cls_max_a[x], st);
+            if (e != hipSuccess) return fail_hip(e, "stats cross kernel launch");
+            continue;
+          }
           SaScoreCrossParams p;
           memset(&p, 0, sizeof(p));
           p.f = f0;
@@ -270,6 +293,12 @@ struct CrossCall {
           fail.offer(qs[qr.first + key / nt], tr.first + key % nt, nT);
           continue;
         }
+        if (stats) {   // SA_STATS_NO_WALK in a mismatch word; the tile's order is row-major, so its first is its lowest
+          const uint32_t *w = h + 4 + 2 * n;
+          uint64_t k = 0;
+          while (k < n && !(w[k] & SA_STATS_NO_WALK)) ++k;
+          if (k < n) { no_walk.offer(qs[qr.first + k / nt], tr.first + k % nt, nT); continue; }
+        }
         const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
         const int nw = words();
         constexpr uint64_t kRows = 64;
@@ -281,7 +310,7 @@ struct CrossCall {
           }
         });
       }
-      if (fail.any()) break;   // the later query ranges hold only higher pairs
+      if (fail.any() || no_walk.any()) break;   // the later query ranges hold only higher pairs
     }
     return SEQALIGN_OK;
   }
@@ -311,7 +340,7 @@ struct CrossCall {
     const int nw = words();
     for (uint64_t g0 = 0; g0 < qs.size(); g0 += q_rows) {
       const uint64_t g1 = std::min<uint64_t>(qs.size(), g0 + q_rows);
-      if (fail.any() && qs[g0] > fail.q) break;   // only higher pairs from here on
+      if ((fail.any() && qs[g0] > fail.q) || (no_walk.any() && qs[g0] > no_walk.q)) break;   // only higher pairs from here on
       for (uint64_t t0 = 0; t0 < nT; t0 += t_slice) {
         const uint64_t t1 = std::min(nT, t0 + t_slice), nt = t1 - t0, n = (g1 - g0) * nt;
         off_a.resize(n); off_b.resize(n); len_a.resize(n); len_b.resize(n); sc.resize(n);
@@ -325,8 +354,13 @@ struct CrossCall {
         b.n_pairs = n; b.arena = arena.data(); b.arena_bytes = arena.size();
         b.off_a = off_a.data(); b.len_a = len_a.data(); b.off_b = off_b.data(); b.len_b = len_b.data();
         uint64_t bad = ~0ull;
-        rc = span ? span_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), w[2].data(), w[3].data(), &bad)
-                  : score_batch_impl(ctx, &b, scoring, is_sw, sc.data(), ea.data(), eb.data(), &bad);
+        rc = span    ? span_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), w[2].data(), w[3].data(), &bad)
+             : stats ? stats_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), &bad)
+                     : score_batch_impl(ctx, &b, scoring, is_sw, sc.data(), ea.data(), eb.data(), &bad);
+        if (rc == SEQALIGN_E_TRACEBACK && bad != ~0ull) {
+          no_walk.offer(qs[g0 + bad / nt], t0 + bad % nt, nT);
+          continue;
+        }
         if (rc == SEQALIGN_E_UNKNOWN_PAIR && bad != ~0ull) {
           fail.offer(qs[g0 + bad / nt], t0 + bad % nt, nT);
           continue;
@@ -380,6 +414,10 @@ struct CrossCall {
     for (uint64_t q = 0; q < Q->n_seqs; ++q) (Q->len[q] > row_max() ? long_q : short_q).push_back(q);
     if (!short_q.empty() && (rc = run_short(short_q))) return rc;
     if (!long_q.empty() && (rc = run_long(long_q))) return rc;
+    if (no_walk.any() && no_walk.key < fail.key) {   // the lowest failing pair's code is the call's
+      set_last_error("query " + std::to_string(q_base + no_walk.q) + ", target " + std::to_string(no_walk.t) + ": traceback failed");
+      return SEQALIGN_E_TRACEBACK;
+    }
     if (fail.any()) {
       set_last_error("query " + std::to_string(q_base + fail.q) + ", target " + std::to_string(fail.t) +
                      ": a character pair without a score");
@@ -428,6 +466,20 @@ int sa_host::span_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queri
   StreamSyncOnExit sync(ctx->stream);
   CrossCall call{ctx, queries, targets, scoring, true, out_score, {out_pos_a, out_pos_b, out_len_a, out_len_b}, targets->n_seqs,
                  FailPair(), nullptr, true};
+  return call.run(q_base);
+}
+
+int sa_host::stats_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                              const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches,
+                              uint64_t q_base) {
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  StreamSyncOnExit sync(ctx->stream);
+  CrossCall call{ctx, queries, targets, scoring, false, out_score, {out_matches, out_mismatches, nullptr, nullptr}, targets->n_seqs,
+                 FailPair(), nullptr, false, true};
   return call.run(q_base);
 }
 
@@ -581,4 +633,10 @@ extern "C" int seqalign_sw_span_search(seqalign_ctx_t *ctx, const seqalign_seqse
                                        uint32_t *n_hits) {
   if (!ctx || !scoring || !hits || !n_hits) return SEQALIGN_E_ARG;
   return span_search_call(ctx, queries, targets, scoring, k, min_score, hits, n_hits, 0);
+}
+
+extern "C" int seqalign_nw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                       const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
+  if (!ctx || !scoring || !out_score || !out_matches || !out_mismatches) return SEQALIGN_E_ARG;
+  return stats_cross_call(ctx, queries, targets, scoring, out_score, out_matches, out_mismatches, 0);
 }

@@ -423,6 +423,10 @@ int score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const s
 int span_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                     uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
                     uint64_t *fail_pair = nullptr);
+// ... and seqalign_nw_stats_batch without its entry checks (the stats cross call's long queries); SEQALIGN_E_TRACEBACK names its
+// pair through fail_pair too
+int stats_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                     uint32_t *out_matches, uint32_t *out_mismatches, uint64_t *fail_pair = nullptr);
 // sa_batch_score_cross.hip: the sets' checks (E_ARG; n_queries x n_targets must fit 64 bits), and one context's cross call
 // (its own CallScope) -- q_base: what the error message adds to a query index (the *_multi calls' ranges)
 int score_cross_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets);
@@ -433,6 +437,9 @@ int score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, cons
 int span_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                     const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
                     uint32_t *out_len_a, uint32_t *out_len_b, uint64_t q_base);
+// ... its statistics form (seqalign_nw_stats_cross): three matrices
+int stats_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                     const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches, uint64_t q_base);
 // ... and the top-k search (seqalign_*_score_search) on the same tiles: its checks (E_ARG: k, the sets, n_targets), and
 // one context's call
 int score_search_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets, uint32_t k);

@@ -494,6 +494,35 @@ struct SaSpanCrossParams {
 };
 /* every query of the class has len_a <= max_len_a <= SA_SPAN_ROW_MAX; recorded as "score_cross" (items: waves) */
 hipError_t sa_launch_span_cross(const SaSpanCrossParams &p, uint32_t max_len_a, hipStream_t stream);
+/* ---- NW alignment statistics (seqalign_nw_stats_batch / _cross, sa_nw_stats.hip): sa_score.hip's NW sweep with two counters
+ * carried beside the three values of a cell.  Pair k of a launch: score[k] = SaScoreParams' NW score,
+ * matches[k] / mismatches[k] = the columns of the alignment seqalign_nw_batch returns that hold two equal / two different
+ * letters (after the scoring's case folding); bit 31 of mismatches[k] (SA_STATS_NO_WALK) = the end pick's state has no walk
+ * (SEQALIGN_E_TRACEBACK).  f.status / err_flag as SaScoreParams.  Row classes, strips, hand-off bytes and the layout of
+ * `progress` are the span kernels' (SA_SPAN_ROW_MAX, sa_span_row_class, sa_span_strips_per_pair, SA_SPAN_HANDOFF_BYTES);
+ * there is no best cell, so nothing follows the ticket counter. */
+#define SA_STATS_NO_WALK 0x80000000u
+struct SaStatsParams {
+  SaFillParams f;
+  int32_t *score;                   /* [n]                                                                             */
+  uint32_t *matches, *mismatches;   /* [n]                                                                             */
+  uint32_t *err_flag;               /* one word, zeroed by the caller                                                  */
+  /* strips only: */
+  uint32_t *progress;               /* as SaScoreParams                                                                */
+  int32_t *handoff;                 /* as SaSpanParams: per row {max(M, A), B, whether A's, 0} {the two payloads}      */
+  const uint64_t *handoff_off;      /* [n], in rows                                                                    */
+  uint32_t strips_per_pair;
+};
+struct SaStatsCrossParams {         /* SaSpanCrossParams' wave -> (query, target) mapping                              */
+  SaStatsParams s;
+  const uint32_t *q_list, *t_order;
+  uint32_t nq, n_t, n_waves;
+  unsigned long long *err_pair;
+};
+/* recorded as "score_rows" / "score_strips" / "score_cross"; the callers' duties are sa_launch_span_*'s */
+hipError_t sa_launch_stats_rows(const SaStatsParams &p, uint32_t max_len_a, hipStream_t stream);
+hipError_t sa_launch_stats_strips(const SaStatsParams &p, hipStream_t stream);
+hipError_t sa_launch_stats_cross(const SaStatsCrossParams &p, uint32_t max_len_a, hipStream_t stream);
 /* top-k score search (seqalign_*_score_search, sa_score_select.hip): one workgroup per query row of a tile, after its
  * score_cross launches.  Keeps the k smallest keys (~(score ^ 0x80000000)) << 32 | (t_base + t) of the row's entries with
  * score >= min_score together with the query's running list, and writes them back sorted.  The running list's targets

@@ -210,6 +210,17 @@ extern "C" int seqalign_sw_span_batch_multi(seqalign_ctx_t *const *ctxs, int n_c
   });
 }
 
+extern "C" int seqalign_nw_stats_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
+                                             const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches,
+                                             uint32_t *out_mismatches) {
+  if (bad_ctx_list(ctxs, n_ctx) || !batch_readable(batch) || !scoring || !out_score || !out_matches || !out_mismatches)
+    return SEQALIGN_E_ARG;
+  return for_each_shard(shard_edges(batch, n_ctx), [&](int g, uint64_t first, uint64_t count) {
+    const seqalign_batch_t s = sub_batch(batch, first, count);
+    return seqalign_nw_stats_batch(ctxs[g], &s, scoring, out_score + first, out_matches + first, out_mismatches + first);
+  });
+}
+
 // score matrices: contiguous query ranges of nearly equal cells -- a query's cells are (len + 1) x the targets' sum of
 // (len + 1), a factor common to all, so the ranges are cut by len + 1 -- each context writes its own rows
 namespace {

@@ -451,6 +451,47 @@ class Context:
                "seqalign_sw_span_time_ms")
         return ms
 
+    # ---- NW alignment statistics (seqalign_nw_stats_batch / seqalign_nw_stats_cross) ------------------------------
+    def nw_stats(self, batch, scoring: Scoring, peers=None):
+        """seqalign_nw_stats_batch: (score int32[n], matches uint32[n], mismatches uint32[n]) -- nw_score's score and, over the
+        alignment nw_batch returns for the pair, the columns that hold two equal / two different letters (after the scoring's
+        case folding).  Alignment length = len_a + len_b - matches - mismatches; identity = matches / that.  One forward pass,
+        no strings, no limit on len_a * len_b."""
+        _score_args(batch, scoring)
+        n = batch.n_pairs
+        score, matches, mismatches = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        d = batch_desc(batch)
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(lib().seqalign_nw_stats_batch_multi(hs, nh, C.byref(d), C.byref(scoring), _ptr(score), _ptr(matches),
+                                                       _ptr(mismatches)), "seqalign_nw_stats_batch_multi")
+        else:
+            _check(lib().seqalign_nw_stats_batch(self._h, C.byref(d), C.byref(scoring), _ptr(score), _ptr(matches),
+                                                 _ptr(mismatches)), "seqalign_nw_stats_batch")
+        return score, matches, mismatches
+
+    def nw_stats_time_ms(self, batch, scoring: Scoring, repeats: int = 10) -> np.ndarray:
+        """seqalign_nw_stats_time_ms: nw_stats' kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
+        _score_args(batch, scoring)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "nw_stats_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_stats_time_ms(self._h, C.byref(d), C.byref(scoring), C.c_int(repeats), _ptr(ms)),
+               "seqalign_nw_stats_time_ms")
+        return ms
+
+    def nw_stats_cross(self, queries, targets, scoring: Scoring):
+        """seqalign_nw_stats_cross: (score int32, matches uint32, mismatches uint32), each [n_queries, n_targets] -- nw_stats
+        on workloads.cross_batch(queries, targets) without building that batch."""
+        _cross_args(queries, targets, scoring)
+        shape = (queries.n_seqs, targets.n_seqs)
+        score, matches, mismatches = np.zeros(shape, np.int32), np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        dq, dt = seqset_desc(queries), seqset_desc(targets)
+        _check(lib().seqalign_nw_stats_cross(self._h, C.byref(dq), C.byref(dt), C.byref(scoring), _ptr(score), _ptr(matches),
+                                             _ptr(mismatches)), "seqalign_nw_stats_cross")
+        return score, matches, mismatches
+
     # ---- score matrices (seqalign_nw_score_cross / seqalign_sw_score_cross) ------------------------------
     def nw_score_cross(self, queries, targets, scoring: Scoring, peers=None) -> np.ndarray:
         """seqalign_nw_score_cross: the global score of every query against every target, int32[n_queries, n_targets] --
@@ -1145,6 +1186,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_score_batch", "seqalign_sw_score_batch", "seqalign_nw_score_batch_multi", "seqalign_sw_score_batch_multi",
     "seqalign_score_time_ms",
     "seqalign_sw_span_batch", "seqalign_sw_span_batch_multi", "seqalign_sw_span_time_ms",
+    "seqalign_nw_stats_batch", "seqalign_nw_stats_batch_multi", "seqalign_nw_stats_time_ms", "seqalign_nw_stats_cross",
     "seqalign_nw_score_cross", "seqalign_sw_score_cross", "seqalign_nw_score_cross_multi", "seqalign_sw_score_cross_multi",
     "seqalign_nw_score_search", "seqalign_sw_score_search", "seqalign_nw_score_search_multi",
     "seqalign_sw_score_search_multi",

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, seqalign_sw_span_batch, *_score_cross,
-*_score_search, seqalign_sw_span_cross and seqalign_sw_span_search (against sw_span on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+*_score_search, seqalign_sw_span_cross and seqalign_sw_span_search (against sw_span on the explicit batch), seqalign_nw_stats_batch
+(the columns of the oracle's strings) and seqalign_nw_stats_cross (against nw_stats on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -24,6 +25,7 @@ import torch  # noqa: E402,F401
 import bandlib as BL  # noqa: E402
 import bandswlib as BS  # noqa: E402
 import orclib as O  # noqa: E402
+import statlib as ST  # noqa: E402
 import seqalign_amd as S  # noqa: E402
 from seqalign_amd import workloads as W  # noqa: E402
 
@@ -90,7 +92,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         import maglib as G      # only the scaled runs need it: the default run is what it was, imports included
     ctx = ctx or (None if dry else S.Context(0))
     t_end = time.time() + seconds
-    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0}
+    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -197,6 +199,16 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                 fail("SW SPAN", spec, p, pairs[p], tuple(int(x[p]) for x in got), want)
         n["span"] += 12
 
+        # ---- NW statistics: the columns of the oracle's strings, counted on the host
+        if nw_ok:
+            got = ST.got_stats(ctx.nw_stats(batch, sc))
+            for p, (a, b) in enumerate(pairs):
+                rc, score, ra, rb = O.oracle_nw_traceback(osc, a, b, *fills[0, p])
+                want = (score,) + ST.count_columns(osc, ra, rb) if rc == 0 else None
+                if got[p] != want:
+                    fail("NW STATS", spec, p, pairs[p], got[p], want)
+            n["stats"] += len(pairs)
+
         # ---- score matrices and the search over them: 4 queries x 6 targets taken from the pairs
         qi = [0, 3, 6, wide if wide >= 0 else 9]
         ti = [1, 2, 5, 7, 10, 11]
@@ -231,6 +243,12 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                          h.tolist(), (tg.tolist(), ws.tolist()))
             n["search"] += 4
             if not is_sw:
+                # ---- the same sets' statistics matrices: nw_stats on the explicit batch, the oracle's scores
+                want = tuple(x.reshape(4, 6) for x in ctx.nw_stats(W.cross_batch(q, t), sc))
+                got = ctx.nw_stats_cross(q, t, sc)
+                if not (all(np.array_equal(g, w) for g, w in zip(got, want)) and np.array_equal(got[0], dense[0])):
+                    fail("NW STATS CROSS", spec, queries, targets, [g.tolist() for g in got], [w.tolist() for w in want])
+                n["stats_cross"] += 24
                 continue
             # ---- the same sets' span matrices and search with spans: sw_span on the explicit batch, the oracle's best cells
             want = tuple(x.reshape(4, 6) for x in ctx.sw_span(W.cross_batch(q, t), sc))
