@@ -629,8 +629,8 @@ int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
  * pair the missing score first).  Over whole matrices every pair keeps the alignment that puts all of seq_a and then all of
  * seq_b against gaps, whatever no_mismatches / no_gaps_in_a / no_gaps_in_b forbid, so within the admitted domain no pair
  * takes that path.  On an error the outputs are unspecified beyond the chunks already delivered.
- *   Not here: SW statistics (they need spans and counts together), a search form, banded forms, _cross_multi, _submit, the
- * command-line tools, gap-open counts. */
+ *   Not here: a search form, banded forms, _cross_multi, _submit, the command-line tools, gap-open counts.  SW statistics:
+ * seqalign_sw_stats_batch below. */
 int seqalign_nw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                             uint32_t *out_matches, uint32_t *out_mismatches);
 /* ... over several contexts (GPUs): contiguous ranges of nearly equal cells, results exactly the single-context call's */
@@ -638,6 +638,42 @@ int seqalign_nw_stats_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
                                   int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
 /* Kernel time of seqalign_nw_stats_batch (seq-align_amd/tools/nw_stats_bench.py), the sibling of seqalign_sw_span_time_ms */
 int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                              float *ms_each);
+/* ---- SW alignment statistics: hit span and identity counts of the best local hit in one pass, no traceback ---- */
+/* For every pair, over the first hit of seqalign_sw_batch(min_score = 1, max_hits = 1) -- the best cell in hit order and the
+ * walk of alignment_reverse_move from it, tie order GAP_A, GAP_B, MATCH, not merely some optimal hit:
+ *   out_score, out_pos_a, out_pos_b, out_len_a, out_len_b   exactly seqalign_sw_span_batch's five;
+ *   out_matches[p]     the columns of that hit's strings that hold a letter of both sequences whose two letters are equal
+ *                      after the scoring's own case folding (scoring_t.case_sensitive); substitution scores, wildcards and
+ *                      no_mismatches play no part in which bucket a column falls into;
+ *   out_mismatches[p]  the other columns that hold a letter of both.
+ * All seven are 0 when no cell scores above 0.  From these, BLAST-style: aligned columns = matches + mismatches; alignment
+ * length = len_a + len_b - matches - mismatches (the hit's len_a, len_b); gap columns = len_a + len_b - 2 (matches +
+ * mismatches); identity = matches / alignment length; qstart = pos_a + 1, qend = pos_a + len_a, sstart = pos_b + 1, send =
+ * pos_b + len_b.
+ *   One forward pass, nothing stored per cell and nothing walked: beside the three values of a cell travel two words, the
+ * cell in which the walk stops as x | y << 16 and matches | mismatches << 16.  So both sequences of every
+ * pair must have at most SEQALIGN_SW_STATS_MAX_LEN letters: a longer one is SEQALIGN_E_TOO_LARGE with the lowest such pair
+ * named in seqalign_last_error, found from the descriptors with the other argument checks, before the context is touched and
+ * before any device work.  There is no cap on len_a * len_b: 65 535 x 65 535 is legal.
+ *   Device bytes per pair: len_a + len_b + 80, and for rows over 512 columns 32 x (strips - 1) x (len_b + 1) of hand-off plus
+ * 36 per strip, strips = ceil(len_a / 512) -- seqalign_sw_span_batch's plus 8 bytes of results; batches are chunked by these
+ * bytes, 28 bytes per pair and the error word come back.  Argument checks, scoring admission (SEQALIGN_E_DOMAIN) and
+ * SEQALIGN_E_UNKNOWN_PAIR are seqalign_sw_span_batch's; SEQALIGN_E_TRACEBACK cannot occur.  The launches are recorded as
+ * "score_rows" / "score_strips" (items: pairs).
+ *   Not here: sequences over 65 535 letters (a four-word payload), a search form, banded forms, _cross_multi, _submit, the
+ * command-line tools, gap-open counts. */
+#define SEQALIGN_SW_STATS_MAX_LEN 65535u
+int seqalign_sw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                            uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
+                            uint32_t *out_matches, uint32_t *out_mismatches);
+/* ... over several contexts (GPUs): contiguous ranges of nearly equal cells, results exactly the single-context call's; the
+ * length limit names the pair's index in the whole batch */
+int seqalign_sw_stats_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a,
+                                  uint32_t *out_len_b, uint32_t *out_matches, uint32_t *out_mismatches);
+/* Kernel time of seqalign_sw_stats_batch (seq-align_amd/tools/sw_stats_bench.py), the sibling of seqalign_sw_span_time_ms */
+int seqalign_sw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
                               float *ms_each);
 /* ---- banded SW hit spans: start and end of the best local hit inside a band, no traceback ---- */
 /* seqalign_sw_span_batch over the banded SW matrices: the five integers a mapper reports per read at the cost of a banded
@@ -890,6 +926,16 @@ int seqalign_sw_span_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries
  * There is no _cross_multi form. */
 int seqalign_nw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                             const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
+/* SW statistics matrices: seqalign_sw_stats_batch's seven outputs for every query against every target, [n_queries][n_targets]
+ * each, the result of that call on the batch whose pair q * n_targets + t is (query q, target t) -- which is never built; pos_a
+ * and len_a are in the query.  It runs on seqalign_sw_span_cross's tiles with 28 result bytes per pair: queries of up to 512
+ * columns run one wave per (query, target), longer queries run seqalign_sw_stats_batch's strips on their pairs.  Every query and
+ * every target must have at most SEQALIGN_SW_STATS_MAX_LEN letters (SEQALIGN_E_TOO_LARGE, "query Q: ..." / "target T: ...",
+ * before the context is touched).  Checks, admission, empty sets and SEQALIGN_E_UNKNOWN_PAIR's "query Q, target T: ..." are
+ * seqalign_sw_span_cross's.  There is no _cross_multi form. */
+int seqalign_sw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                            const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
+                            uint32_t *out_len_a, uint32_t *out_len_b, uint32_t *out_matches, uint32_t *out_mismatches);
 /* ... over several contexts: the query ranges of seqalign_sw_score_cross_multi; results exactly the single-context call's */
 int seqalign_sw_span_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seqset_t *queries,
                                  const seqalign_seqset_t *targets, const scoring_t *scoring, int32_t *out_score,

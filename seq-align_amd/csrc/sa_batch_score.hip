@@ -1,9 +1,10 @@
 // sa_batch_score.hip -- score only over HOST batches: seqalign_nw_score_batch, seqalign_sw_score_batch (and the timing
 // hook seqalign_score_time_ms), SW hit spans: seqalign_sw_span_batch (and seqalign_sw_span_time_ms), and NW alignment statistics:
-// seqalign_nw_stats_batch (and seqalign_nw_stats_time_ms).  No matrices, no traceback: per chunk the sequences go up, the score
-// kernels (sa_score.hip), the span kernels (sa_span.hip) or the stats kernels (sa_nw_stats.hip) run, and 4 or 12 bytes per pair
-// come back, 20 for a span (score, pos_a, pos_b, len_a, len_b), 12 for statistics (score, matches, mismatches), plus the error
-// word.
+// seqalign_nw_stats_batch (and seqalign_nw_stats_time_ms), and SW alignment statistics: seqalign_sw_stats_batch (and
+// seqalign_sw_stats_time_ms).  No matrices, no traceback: per chunk the sequences go up, the score kernels (sa_score.hip), the span
+// kernels (sa_span.hip) or the stats kernels (sa_nw_stats.hip, sa_sw_stats.hip) run, and 4 or 12 bytes per pair come back, 20 for
+// a span (score, pos_a, pos_b, len_a, len_b), 12 for NW statistics (score, matches, mismatches), 28 for SW statistics (the span's
+// five, matches, mismatches), plus the error word.
 //
 // A chunk's pairs are put in classes by row width -- the columns per lane of the one-wave kernel (score: 1 .. 16, span: 1 .. 6
 // and 8), or the strips kernel for rows over 1 024 (span: 512) columns -- and the descriptors are laid out class by class, so
@@ -13,9 +14,10 @@
 // Chunks are cut by device BYTES, not cells (sa_chunks.hpp): the sequences, 64 (span: 72) bytes of descriptors, status and
 // results per pair, and for the strips kernel the hand-off columns (8 bytes per row and strip; span: 32) and 20 (span: 36)
 // bytes per strip of progress and best cell -- a 100 000 x 100 000 score pair is 157 MB, not 120 GB.  Statistics: 64 bytes per
-// pair, the span's 32 per row and strip, 4 per strip (no best cell).
+// pair, the span's 32 per row and strip, 4 per strip (no best cell).  SW statistics: the span's bytes plus 8 of results per pair
+// (80), its 32 per row and strip and its 36 per strip.
 //
-// The three families are one driver (RowChunkRun) over a traits struct each: what differs is the kernels' parameter block,
+// The four families are one driver (RowChunkRun) over a traits struct each: what differs is the kernels' parameter block,
 // ladder and launch functions and the bytes named above.
 #include "sa_chunks.hpp"
 
@@ -84,6 +86,26 @@ struct StatsTraits {   // sa_nw_stats.hip: the NW form only; classes, strips and
   static void set_strip_best(Params &, uint32_t *) {}
   static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_stats_rows(p, max_a, st); }
   static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_stats_strips(p, st); }
+};
+
+struct SwStatsTraits {   // sa_sw_stats.hip: the span kernels' classes, strips, hand-off and best-cell bytes; seven result words
+  using Params = SaSwStatsParams;
+  static constexpr int kRowClasses = SA_SPAN_ROW_CLASSES;
+  static constexpr uint32_t kRowMax = SA_SPAN_ROW_MAX;
+  static constexpr uint64_t kPairBytes = 80;   // descriptors (32), results (28), status (8), slack
+  static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
+  static constexpr const char *kLaunch = "sw stats kernel launch";
+  static constexpr int kMarkField = 0;
+  static int fields(bool) { return 7; }   // score, pos_a, pos_b, len_a, len_b, matches, mismatches
+  static int row_class(uint32_t la) { return sa_span_row_class(la); }
+  static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
+  static void set_results(Params &p, uint32_t *res, uint64_t n) {
+    p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
+    p.matches = res + 5 * n; p.mismatches = res + 6 * n;
+  }
+  static void set_strip_best(Params &p, uint32_t *best) { p.strip_best = best; }
+  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_sw_stats_rows(p, max_a, st); }
+  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_sw_stats_strips(p, st); }
 };
 
 // hand-off columns of one pair: strips 0 .. last - 1, len_b + 1 rows each, in rows
@@ -261,6 +283,24 @@ int sa_host::stats_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch
   return row_batch_call<StatsTraits>(ctx, batch, scoring, false, out_score, out, fail_pair);
 }
 
+// seqalign_sw_stats_*'s length limit: a coordinate and a counter are 16 bits each in the kernels' payload words
+int sa_host::sw_stats_check_batch(const seqalign_batch_t *batch) {
+  for (uint64_t p = 0; p < batch->n_pairs; ++p)
+    if (batch->len_a[p] > SEQALIGN_SW_STATS_MAX_LEN || batch->len_b[p] > SEQALIGN_SW_STATS_MAX_LEN) {
+      const bool in_a = batch->len_a[p] > SEQALIGN_SW_STATS_MAX_LEN;
+      set_last_error("pair " + std::to_string(p) + ": " + (in_a ? "seq_a" : "seq_b") + " has " +
+                     std::to_string(in_a ? batch->len_a[p] : batch->len_b[p]) + " letters, SW statistics take at most " +
+                     std::to_string(SEQALIGN_SW_STATS_MAX_LEN));
+      return SEQALIGN_E_TOO_LARGE;
+    }
+  return SEQALIGN_OK;
+}
+
+int sa_host::sw_stats_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                                 uint32_t *const *out, uint64_t *fail_pair) {
+  return row_batch_call<SwStatsTraits>(ctx, batch, scoring, true, out_score, out, fail_pair);
+}
+
 extern "C" int seqalign_nw_score_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                        int32_t *out_score) {
   if (!ctx || !scoring || !out_score) return SEQALIGN_E_ARG;
@@ -309,4 +349,28 @@ extern "C" int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_bat
   if (!ctx || !scoring || repeats <= 0 || !ms_each || !batch_readable(batch) || batch->n_pairs == 0) return SEQALIGN_E_ARG;
   CallScope scope(ctx);
   return row_time_call<StatsTraits>(ctx, batch, scoring, false, repeats, ms_each, "seqalign_nw_stats_time_ms");
+}
+
+extern "C" int seqalign_sw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                       int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a,
+                                       uint32_t *out_len_b, uint32_t *out_matches, uint32_t *out_mismatches) {
+  if (!scoring || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b || !out_matches || !out_mismatches ||
+      !batch_readable(batch))
+    return SEQALIGN_E_ARG;
+  int rc = sw_stats_check_batch(batch);   // (before the context is looked at: the limit is the arguments' own)
+  if (rc) return rc;
+  if (!ctx) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);
+  uint32_t *const out[6] = {out_pos_a, out_pos_b, out_len_a, out_len_b, out_matches, out_mismatches};
+  return sw_stats_batch_impl(ctx, batch, scoring, out_score, out);
+}
+
+extern "C" int seqalign_sw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                                         float *ms_each) {
+  if (!scoring || repeats <= 0 || !ms_each || !batch_readable(batch) || batch->n_pairs == 0) return SEQALIGN_E_ARG;
+  int rc = sw_stats_check_batch(batch);
+  if (rc) return rc;
+  if (!ctx) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);
+  return row_time_call<SwStatsTraits>(ctx, batch, scoring, true, repeats, ms_each, "seqalign_sw_stats_time_ms");
 }

@@ -30,6 +30,10 @@
 // the stats strips (stats_batch_impl).  A pair whose end pick has no walk (SA_STATS_NO_WALK) is SEQALIGN_E_TRACEBACK; between
 // it and a pair without a score the lower pair's code is the call's.
 //
+// SW statistics matrices (seqalign_sw_stats_cross) are the span matrices' tiles once more with 28 result bytes per pair: the CROSS
+// form of the SW stats kernel (sa_sw_stats.hip), seven rows home per query, the long queries through its strips
+// (sw_stats_batch_impl).  Every query and every target has at most SEQALIGN_SW_STATS_MAX_LEN letters (checked at the entry).
+//
 // Top-k search with spans (seqalign_sw_span_search) is two stages: the score search above, unchanged, and then
 // the span sweep on the selected hits alone -- for each the PREFIX pair (query[0 : end_a], target[0 : end_b]), whose first hit
 // is the full pair's, as an explicit pair list through span_batch_impl.
@@ -102,17 +106,18 @@ struct CrossCall {
   const scoring_t *scoring;
   bool is_sw;
   int32_t *out_score;
-  uint32_t *out_w[4];   // the matrices behind the score -- SW: end_a, end_b; span: pos_a, pos_b, len_a, len_b
+  uint32_t *out_w[6];   // the matrices behind the score -- SW: end_a, end_b; span: pos_a, pos_b, len_a, len_b; SW stats: + counts
   uint64_t nT;
   FailPair fail;
   const SearchOut *search = nullptr;   // set: top-k search, the matrix outputs are unused
   bool span = false;                   // seqalign_sw_span_cross (is_sw set, no search)
   bool stats = false;                  // seqalign_nw_stats_cross (is_sw clear, no search): out_w = matches, mismatches
   FailPair no_walk;                    // stats: the lowest pair whose end pick has no walk (SEQALIGN_E_TRACEBACK)
+  bool sw_stats = false;               // seqalign_sw_stats_cross (is_sw set, no search): out_w = the span's four, matches, mismatches
 
-  int words() const { return span ? 4 : (is_sw || stats) ? 2 : 0; }   // result words per pair behind the score
+  int words() const { return sw_stats ? 6 : span ? 4 : (is_sw || stats) ? 2 : 0; }   // result words per pair behind the score
   uint64_t result_bytes() const { return 4 * (1 + (uint64_t)words()); }
-  uint32_t row_max() const { return (span || stats) ? SA_SPAN_ROW_MAX : SA_SCORE_ROW_MAX; }   // the one-wave kernels' widest query
+  uint32_t row_max() const { return (span || stats || sw_stats) ? SA_SPAN_ROW_MAX : SA_SCORE_ROW_MAX; }   // the one-wave kernels' widest query
   uint64_t list_bytes() const { return search ? 16ull * search->k + 4 : 0; }   // one query's running list
 
   // queries <= row_max(): the cross kernel, tile by tile
@@ -219,6 +224,23 @@ struct CrossCall {
             p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
             const hipError_t e = sa_launch_span_cross(p, cls_max_a[x], st);
             if (e != hipSuccess) return fail_hip(e, "span cross kernel launch");
+            continue;
+          }
+          if (sw_stats) {
+            SaSwStatsCrossParams p;
+            memset(&p, 0, sizeof(p));
+            p.s.f = f0;
+            p.s.f.arena = d_seq;
+            p.s.f.off_a = d_off_q; p.s.f.len_a = d_len_q; p.s.f.off_b = d_off_t; p.s.f.len_b = d_len_t;
+            p.q_list = d_qlist + cls_first[x]; p.t_order = d_tord;
+            p.nq = (uint32_t)m; p.n_t = (uint32_t)nt; p.n_waves = (uint32_t)(m * nt);
+            p.s.score = reinterpret_cast<int32_t *>(d_res + 4);
+            p.s.pos_a = d_res + 4 + n; p.s.pos_b = d_res + 4 + 2 * n; p.s.len_a = d_res + 4 + 3 * n; p.s.len_b = d_res + 4 + 4 * n;
+            p.s.matches = d_res + 4 + 5 * n; p.s.mismatches = d_res + 4 + 6 * n;
+            p.s.err_flag = d_res;
+            p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
+            const hipError_t e = sa_launch_sw_stats_cross(p, cls_max_a[x], st);
+            if (e != hipSuccess) return fail_hip(e, "sw stats cross kernel launch");
             continue;
           }
           if (stats) {
@@ -334,7 +356,7 @@ struct CrossCall {
     std::vector<std::vector<Hit>> best(search ? qs.size() : 0);
     const auto by_key = [](const Hit &x, const Hit &y) { return x.key < y.key; };
     std::vector<uint64_t> off_a, off_b;
-    std::vector<uint32_t> len_a, len_b, w[4];   // w: the result arrays behind the score (out_w's order)
+    std::vector<uint32_t> len_a, len_b, w[6];   // w: the result arrays behind the score (out_w's order)
     std::vector<uint32_t> &ea = w[0], &eb = w[1];
     std::vector<int32_t> sc;
     const int nw = words();
@@ -354,7 +376,9 @@ struct CrossCall {
         b.n_pairs = n; b.arena = arena.data(); b.arena_bytes = arena.size();
         b.off_a = off_a.data(); b.len_a = len_a.data(); b.off_b = off_b.data(); b.len_b = len_b.data();
         uint64_t bad = ~0ull;
-        rc = span    ? span_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), w[2].data(), w[3].data(), &bad)
+        uint32_t *const w6[6] = {w[0].data(), w[1].data(), w[2].data(), w[3].data(), w[4].data(), w[5].data()};
+        rc = sw_stats ? sw_stats_batch_impl(ctx, &b, scoring, sc.data(), w6, &bad)
+             : span  ? span_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), w[2].data(), w[3].data(), &bad)
              : stats ? stats_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), &bad)
                      : score_batch_impl(ctx, &b, scoring, is_sw, sc.data(), ea.data(), eb.data(), &bad);
         if (rc == SEQALIGN_E_TRACEBACK && bad != ~0ull) {
@@ -480,6 +504,17 @@ int sa_host::stats_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *quer
   StreamSyncOnExit sync(ctx->stream);
   CrossCall call{ctx, queries, targets, scoring, false, out_score, {out_matches, out_mismatches, nullptr, nullptr}, targets->n_seqs,
                  FailPair(), nullptr, false, true};
+  return call.run(q_base);
+}
+
+int sa_host::sw_stats_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                 const scoring_t *scoring, int32_t *out_score, uint32_t *const *out_w, uint64_t q_base) {
+  CallScope scope(ctx);
+  if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  StreamSyncOnExit sync(ctx->stream);
+  CrossCall call{ctx, queries, targets, scoring, true, out_score, {out_w[0], out_w[1], out_w[2], out_w[3], out_w[4], out_w[5]},
+                 targets->n_seqs, FailPair(), nullptr, false, false, FailPair(), true};
   return call.run(q_base);
 }
 
@@ -639,4 +674,27 @@ extern "C" int seqalign_nw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqse
                                        const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
   if (!ctx || !scoring || !out_score || !out_matches || !out_mismatches) return SEQALIGN_E_ARG;
   return stats_cross_call(ctx, queries, targets, scoring, out_score, out_matches, out_mismatches, 0);
+}
+
+// seqalign_sw_stats_*'s length limit over a set (sa_host::sw_stats_check_batch): the lowest sequence over it is named
+static int sw_stats_check_set(const seqalign_seqset_t *s, const char *what) {
+  for (uint64_t i = 0; i < s->n_seqs; ++i)
+    if (s->len[i] > SEQALIGN_SW_STATS_MAX_LEN) {
+      set_last_error(std::string(what) + " " + std::to_string(i) + ": " + std::to_string(s->len[i]) +
+                     " letters, SW statistics take at most " + std::to_string(SEQALIGN_SW_STATS_MAX_LEN));
+      return SEQALIGN_E_TOO_LARGE;
+    }
+  return SEQALIGN_OK;
+}
+
+extern "C" int seqalign_sw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                       const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
+                                       uint32_t *out_len_a, uint32_t *out_len_b, uint32_t *out_matches, uint32_t *out_mismatches) {
+  if (!scoring || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b || !out_matches || !out_mismatches)
+    return SEQALIGN_E_ARG;
+  int rc = score_cross_check(queries, targets);
+  if (rc || (rc = sw_stats_check_set(queries, "query")) || (rc = sw_stats_check_set(targets, "target"))) return rc;
+  if (!ctx) return SEQALIGN_E_ARG;   // (the limit is the arguments' own: found before the context is looked at)
+  uint32_t *const out_w[6] = {out_pos_a, out_pos_b, out_len_a, out_len_b, out_matches, out_mismatches};
+  return sw_stats_cross_call(ctx, queries, targets, scoring, out_score, out_w, 0);
 }

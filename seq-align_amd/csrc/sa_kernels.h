@@ -523,6 +523,26 @@ struct SaStatsCrossParams {         /* SaSpanCrossParams' wave -> (query, target
 hipError_t sa_launch_stats_rows(const SaStatsParams &p, uint32_t max_len_a, hipStream_t stream);
 hipError_t sa_launch_stats_strips(const SaStatsParams &p, hipStream_t stream);
 hipError_t sa_launch_stats_cross(const SaStatsCrossParams &p, uint32_t max_len_a, hipStream_t stream);
+/* ---- SW alignment statistics (seqalign_sw_stats_batch / _cross, sa_sw_stats.hip): the span sweep's SW arithmetic with the
+ * span in ONE word and the two counters in the other.  Pair k of a launch: SaSpanParams' five results, and
+ * matches[k] / mismatches[k] = the columns of that hit's strings that hold two equal / two different letters (after the
+ * scoring's case folding).  Both sequences of every pair have at most SA_SW_STATS_MAX_LEN letters (the caller's duty): a
+ * coordinate and a counter are 16 bits each.  Everything else -- row classes, strips, hand-off, progress and strip_best
+ * layout -- is SaSpanParams'; a strip_best entry is {score, end_a, end_b, 0} {x | y << 16, matches | mismatches << 16, 0, 0}. */
+#define SA_SW_STATS_MAX_LEN SEQALIGN_SW_STATS_MAX_LEN
+struct SaSwStatsParams : SaSpanParams {
+  uint32_t *matches, *mismatches;   /* [n]                                                                             */
+};
+struct SaSwStatsCrossParams {       /* SaSpanCrossParams' wave -> (query, target) mapping                              */
+  SaSwStatsParams s;
+  const uint32_t *q_list, *t_order;
+  uint32_t nq, n_t, n_waves;
+  unsigned long long *err_pair;
+};
+/* recorded as "score_rows" / "score_strips" / "score_cross"; the callers' duties are sa_launch_span_*'s */
+hipError_t sa_launch_sw_stats_rows(const SaSwStatsParams &p, uint32_t max_len_a, hipStream_t stream);
+hipError_t sa_launch_sw_stats_strips(const SaSwStatsParams &p, hipStream_t stream);
+hipError_t sa_launch_sw_stats_cross(const SaSwStatsCrossParams &p, uint32_t max_len_a, hipStream_t stream);
 /* top-k score search (seqalign_*_score_search, sa_score_select.hip): one workgroup per query row of a tile, after its
  * score_cross launches.  Keeps the k smallest keys (~(score ^ 0x80000000)) << 32 | (t_base + t) of the row's entries with
  * score >= min_score together with the query's running list, and writes them back sorted.  The running list's targets

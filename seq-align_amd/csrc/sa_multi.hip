@@ -221,6 +221,23 @@ extern "C" int seqalign_nw_stats_batch_multi(seqalign_ctx_t *const *ctxs, int n_
   });
 }
 
+extern "C" int seqalign_sw_stats_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_batch_t *batch,
+                                             const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
+                                             uint32_t *out_len_a, uint32_t *out_len_b, uint32_t *out_matches,
+                                             uint32_t *out_mismatches) {
+  if (!ctxs || n_ctx <= 0 || !batch_readable(batch) || !scoring || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b ||
+      !out_matches || !out_mismatches)
+    return SEQALIGN_E_ARG;
+  int rc = sw_stats_check_batch(batch);   // (the whole batch's pair index, before any context is looked at)
+  if (rc) return rc;
+  if (bad_ctx_list(ctxs, n_ctx)) return SEQALIGN_E_ARG;
+  return for_each_shard(shard_edges(batch, n_ctx), [&](int g, uint64_t first, uint64_t count) {
+    const seqalign_batch_t s = sub_batch(batch, first, count);
+    return seqalign_sw_stats_batch(ctxs[g], &s, scoring, out_score + first, out_pos_a + first, out_pos_b + first, out_len_a + first,
+                                   out_len_b + first, out_matches + first, out_mismatches + first);
+  });
+}
+
 // score matrices: contiguous query ranges of nearly equal cells -- a query's cells are (len + 1) x the targets' sum of
 // (len + 1), a factor common to all, so the ranges are cut by len + 1 -- each context writes its own rows
 namespace {

@@ -1,0 +1,209 @@
+// sa_sw_stats.hpp -- the arithmetic of the SW statistics sweeps (sa_sw_stats.hip): SwStatSweep, one matrix row per step, SpanSweep's
+// SW values and tie rules (sa_span.hpp) with another meaning in the two payload words beside each of match, gap_a and gap_b:
+//   word 0  x | y << 16                   the cell in which the walk that starts in that state stops (SpanSweep's two words in one),
+//   word 1  matches | mismatches << 16    the letter columns of that walk, split as StatSweep splits them (sa_nw_stats.hpp).
+// Both sequences have at most SA_SW_STATS_MAX_LEN = 65 535 letters, so a coordinate fits 16 bits, and matches + mismatches <=
+// min(len_a, len_b) <= 65 535, so neither half of word 1 carries into the other: a match state's step is one add of 1 or 0x10000.
+// The scan's element, its merge and the feed of a strip are sa_span.hpp's: in a SpanCand / SpanFeed here x is word 0 and y word 1.
+// The definition and the tie argument are in sa_sw_stats.hip's header.
+#pragma once
+#include "sa_span.hpp"
+
+namespace sa {
+
+// a state that stops in cell (x, y) -- value <= 0, a border cell, a forced gap_b, the floor candidate of its own cell -- has
+// counted nothing
+__device__ __forceinline__ uint32_t sw_stat_cell(uint32_t x, uint32_t y) { return x | (y << 16); }
+
+template <int CPL, int SUBST, bool GENERAL>
+struct SwStatSweep {
+  int fa[CPL], arow[CPL];
+  int X[CPL], Ap[CPL];
+  int Y[GENERAL ? CPL : 1];
+  int c1[CPL], c2[CPL], c3[CPL];
+  uint32_t Ds[CPL], Dc[CPL], Vs[CPL], Vc[CPL];   // previous row: the diagonal and the vertical feed, {stop cell, counts} each
+  int boundX;                                    // max3 of the cell left of the strip on the previous row ...
+  uint32_t boundDs, boundDc;                     // ... and its diagonal feed
+  int trend0;
+  unsigned long long err = ~0ull;
+  // the running best of match_scores per column (BestCells), with the two words of that cell's match state
+  int bs[CPL];
+  uint32_t br[CPL], bw0[CPL], bw1[CPL];
+
+  __device__ __forceinline__ void start_strip(const SaFillParams &p, const SweepConsts &k, const uint8_t *__restrict__ seq_a,
+                                              uint32_t la, uint32_t i0, uint32_t col0, int lane) {
+    trend0 = k.ext > 0 ? mulw(kWave * CPL, k.ext) : 0;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const uint32_t idx = col0 + c;
+      const int code = idx < la ? (int)p.code[seq_a[idx]] : 0;
+      fa[c] = code & 0xff;
+      arow[c] = (code >> 8) * k.K;
+      X[c] = 0; Ap[c] = 0;
+      if constexpr (GENERAL) Y[c] = 0;
+      Ds[c] = Vs[c] = sw_stat_cell(idx + 1, 0); Dc[c] = Vc[c] = 0;   // row 0 holds 0: every walk that reaches it stops there
+      const int g_ext = subw(mulw(lane * CPL + c, k.ext), trend0);
+      c1[c] = subw(k.open1, g_ext);
+      c2[c] = subw(0, g_ext);
+      c3[c] = g_ext;
+      bs[c] = 0; br[c] = 0; bw0[c] = 0; bw1[c] = 0;
+    }
+    boundX = 0; boundDs = sw_stat_cell(i0, 0); boundDc = 0;
+  }
+
+  // Row j.  f: the cell left of the strip on this row.  Leaves the last column's hand-off in `out` (lane 63's is the strip's).
+  __device__ __forceinline__ void row(const SweepConsts &k, uint32_t j, uint32_t lb, uint32_t la, uint32_t W, int lane,
+                                      uint32_t col0, int ncol, int code_b, const SpanFeed &f, SpanFeed &out) {
+    int xd = wave_shr1(X[CPL - 1], boundX);
+    uint32_t ds = (uint32_t)wave_shr1((int)Ds[CPL - 1], (int)boundDs), dc = (uint32_t)wave_shr1((int)Dc[CPL - 1], (int)boundDc);
+    {   // the boundary cell of this row, for the next one: A > B > M over {max(M, A) and whose it is, B}
+      boundX = max(f.z, f.b);
+      const bool zwins = f.from_a ? f.z >= f.b : f.z > f.b;
+      boundDs = zwins ? f.zx : f.bx;
+      boundDc = zwins ? f.zy : f.by;
+    }
+    const int fb = code_b & 0xff;
+    const uint32_t jhi = j << 16;
+    int mv[CPL], av[CPL], bv[CPL];
+    uint32_t ms[CPL], mc[CPL], as[CPL], ac[CPL];
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const uint32_t gx = col0 + c + 1;
+      const int s = subst_score<SUBST>(fa[c], arow[c], code_b, k.table, k.gen_eq, k.gen_ne);
+      int m, a;
+      bool a_free = false;   // gap_a of the last column under no_end_gap_penalty: max3 of the cell above, no penalty
+      if constexpr (GENERAL) {
+        const int a_norm = max3i(addw(Y[c], k.open1), addw(Ap[c], k.ext), 0);
+        m = (s == SA_S_BLOCKED) ? 0 : max(addw(xd, s), 0);
+        if (s == SA_S_UNKNOWN && c < ncol) {
+          m = 0;
+          err = min(err, (unsigned long long)j * W + gx);
+        }
+        const bool last_col = (gx == la);
+        a_free = last_col && k.no_end;
+        a = a_free ? max(Y[c], Ap[c]) : (!k.no_gaps_a || last_col) ? a_norm : 0;
+      } else {
+        m = max(addw(xd, s), 0);
+        a = max3i(addw(X[c], k.open1), addw(Ap[c], k.ext), 0);
+      }
+      const uint32_t here = gx | jhi;
+      ms[c] = m > 0 ? ds : here;
+      mc[c] = m > 0 ? dc + (fa[c] == fb ? 1u : 0x10000u) : 0u;   // the cell's own letters: one match or one mismatch
+      as[c] = a > 0 ? (a_free ? Ds[c] : Vs[c]) : here;
+      ac[c] = a > 0 ? (a_free ? Dc[c] : Vc[c]) : 0u;
+      xd = X[c]; ds = Ds[c]; dc = Dc[c];
+      mv[c] = m; av[c] = a;
+      const bool up = m > bs[c];   // strict: the first (lowest) row keeps a tie
+      bs[c] = up ? m : bs[c]; br[c] = up ? j : br[c]; bw0[c] = up ? ms[c] : bw0[c]; bw1[c] = up ? mc[c] : bw1[c];
+    }
+
+    // gap_b
+    bool free_row = false, forced = false;
+    if constexpr (GENERAL) {
+      const bool last_row = (j == lb);
+      free_row = last_row && k.no_end;
+      forced = k.no_gaps_b && !last_row;
+    }
+    uint32_t bss[CPL], bcs[CPL];
+    if (forced) {
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) { bv[c] = 0; bss[c] = (col0 + c + 1) | jhi; bcs[c] = 0u; }
+    } else {
+      // max(M, A) of the column to my left, whose it is, and its payload
+      const bool la_from_a = av[CPL - 1] >= mv[CPL - 1];
+      int zl = wave_shr1(max(mv[CPL - 1], av[CPL - 1]), f.z);
+      int zl_a = wave_shr1((int)la_from_a, f.from_a);
+      uint32_t zls = (uint32_t)wave_shr1((int)(la_from_a ? as[CPL - 1] : ms[CPL - 1]), (int)f.zx);
+      uint32_t zlc = (uint32_t)wave_shr1((int)(la_from_a ? ac[CPL - 1] : mc[CPL - 1]), (int)f.zy);
+      SpanCand P[CPL];
+      const bool floor_pays = !free_row && k.ext > 0;   // only then can the floor of a cell feed a positive cell to its right
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        SpanCand w{free_row ? zl : addw(zl, c1[c]), zl_a, zls, zlc};
+        if (floor_pays) {   // the floor of this very cell: it wins a tie with the opening that enters here
+          const bool fl = c2[c] >= w.v;
+          w = SpanCand{fl ? c2[c] : w.v, fl ? 1 : w.nm, fl ? (col0 + c + 1) | jhi : w.x, fl ? 0u : w.y};
+        }
+        if (c == 0) {   // lane 0 continues the previous strip's chain: B(left) + ext, de-trended at g = 0
+          const SpanCand carry{free_row ? f.b : addw(addw(f.b, k.ext), trend0), 1, f.bx, f.by};
+          const SpanCand wc = span_merge(carry, w);
+          const bool l0 = lane == 0;   // (member by member: a select between two structs goes through memory)
+          w = SpanCand{l0 ? wc.v : w.v, l0 ? wc.nm : w.nm, l0 ? wc.x : w.x, l0 ? wc.y : w.y};
+        }
+        P[c] = (c == 0) ? w : span_merge(P[c - 1], w);
+        const bool fa_ = av[c] >= mv[c];
+        zl = max(mv[c], av[c]); zl_a = fa_;
+        zls = fa_ ? as[c] : ms[c]; zlc = fa_ ? ac[c] : mc[c];
+      }
+      const SpanCand incl = wave_scan_span(P[CPL - 1]);
+      const SpanCand e{wave_shr1(incl.v, INT32_MIN), 0, (uint32_t)wave_shr1((int)incl.x, 0), (uint32_t)wave_shr1((int)incl.y, 0)};
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const SpanCand pm = span_merge(e, P[c]);
+        bv[c] = max(free_row ? pm.v : addw(pm.v, c3[c]), 0);   // (the clamp: the floor is not among the candidates unless it pays)
+        bss[c] = bv[c] > 0 ? pm.x : (col0 + c + 1) | jhi;
+        bcs[c] = bv[c] > 0 ? pm.y : 0u;
+      }
+    }
+
+    // the feeds of the next row
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int mb = max(mv[c], bv[c]);
+      const bool b_over_m = bv[c] >= mv[c];
+      const uint32_t ls = b_over_m ? bss[c] : ms[c], lc = b_over_m ? bcs[c] : mc[c];
+      const bool d_a = av[c] >= mb, v_a = addw(av[c], k.ext) >= addw(mb, k.open1);
+      Ds[c] = d_a ? as[c] : ls; Dc[c] = d_a ? ac[c] : lc;
+      Vs[c] = v_a ? as[c] : ls; Vc[c] = v_a ? ac[c] : lc;
+      X[c] = max(av[c], mb);
+      if constexpr (GENERAL) Y[c] = mb;
+      Ap[c] = av[c];
+    }
+    const bool o_a = av[CPL - 1] >= mv[CPL - 1];
+    out.z = max(mv[CPL - 1], av[CPL - 1]); out.b = bv[CPL - 1]; out.from_a = o_a;
+    out.zx = o_a ? as[CPL - 1] : ms[CPL - 1]; out.zy = o_a ? ac[CPL - 1] : mc[CPL - 1];
+    out.bx = bss[CPL - 1]; out.by = bcs[CPL - 1];
+  }
+
+  __device__ __forceinline__ unsigned long long reduce_err() {
+    unsigned long long e = err;
+    if constexpr (GENERAL) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) e = min(e, __shfl_xor(e, o));
+    }
+    return e;
+  }
+
+  // SpanSweep::reduce_best with the two words of the winning cell: {score, (column << 32) | row, (word 0 << 32) | word 1}
+  __device__ __forceinline__ void reduce_best(uint32_t col0, int ncol, int &score, unsigned long long &key,
+                                              unsigned long long &words) const {
+    int b = 0;
+    unsigned long long kb = ~0ull, wb = 0;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)   // c ascending, strict >: the lowest column wins a tie
+      if (c < ncol && bs[c] > b) {
+        b = bs[c];
+        kb = ((unsigned long long)(col0 + c + 1) << 32) | br[c];
+        wb = ((unsigned long long)bw0[c] << 32) | bw1[c];
+      }
+    score = wave_max_i32(b);
+    const unsigned long long mine = (b == score && score > 0) ? kb : ~0ull;
+    key = wave_min_u64(mine);
+    words = wave_min_u64((mine == key && score > 0) ? wb : ~0ull);   // one lane holds the key
+  }
+};
+
+// the seven results of one pair from the best cell's key and its two packed words
+__device__ __forceinline__ void sw_stats_write(const SaSwStatsParams &sp, uint64_t at, int score, unsigned long long key,
+                                               unsigned long long words) {
+  const bool hit = score > 0;
+  const uint32_t ea = hit ? (uint32_t)(key >> 32) : 0u, eb = hit ? (uint32_t)key : 0u;
+  const uint32_t w0 = hit ? (uint32_t)(words >> 32) : 0u, w1 = hit ? (uint32_t)words : 0u;
+  const uint32_t pa = w0 & 0xffffu, pb = w0 >> 16;
+  sp.score[at] = hit ? score : 0;
+  sp.pos_a[at] = pa; sp.pos_b[at] = pb;
+  sp.len_a[at] = ea - pa; sp.len_b[at] = eb - pb;
+  sp.matches[at] = w1 & 0xffffu; sp.mismatches[at] = w1 >> 16;
+}
+
+}  // namespace sa

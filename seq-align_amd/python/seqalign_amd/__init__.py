@@ -76,6 +76,7 @@ class SeqSetDesc(C.Structure):
 
 INT32_MIN = -2**31
 SEARCH_MAX_K = 1024   # SEQALIGN_SEARCH_MAX_K
+SW_STATS_MAX_LEN = 65535   # SEQALIGN_SW_STATS_MAX_LEN
 # seqalign_search_hit_t
 SEARCH_HIT = np.dtype([("target", np.uint32), ("score", np.int32), ("end_a", np.uint32), ("end_b", np.uint32)])
 # seqalign_span_hit_t
@@ -492,6 +493,54 @@ class Context:
                                              _ptr(mismatches)), "seqalign_nw_stats_cross")
         return score, matches, mismatches
 
+    # ---- SW alignment statistics (seqalign_sw_stats_batch / seqalign_sw_stats_cross) ------------------------------
+    def sw_stats(self, batch, scoring: Scoring, peers=None):
+        """seqalign_sw_stats_batch: (score int32[n], pos_a, pos_b, len_a, len_b, matches, mismatches uint32[n]) -- sw_span's
+        five and, over that hit's strings, the columns that hold two equal / two different letters (after the scoring's case
+        folding).  Alignment length = len_a + len_b - matches - mismatches; identity = matches / that.  All 0 when no cell
+        scores above 0.  One forward pass, no strings, no limit on len_a * len_b; both sequences of every pair have at most
+        SW_STATS_MAX_LEN letters (E_TOO_LARGE)."""
+        _score_args(batch, scoring)
+        _sw_stats_lengths("sw_stats", "pair", ("seq_a", batch.len_a), ("seq_b", batch.len_b))
+        n = batch.n_pairs
+        score = np.zeros(n, np.int32)
+        words = tuple(np.zeros(n, np.uint32) for _ in range(6))
+        d = batch_desc(batch)
+        tail = (C.byref(d), C.byref(scoring), _ptr(score)) + tuple(_ptr(w) for w in words)
+        if peers:
+            hs, nh = self._handles(peers)
+            _check(lib().seqalign_sw_stats_batch_multi(hs, nh, *tail), "seqalign_sw_stats_batch_multi")
+        else:
+            _check(lib().seqalign_sw_stats_batch(self._h, *tail), "seqalign_sw_stats_batch")
+        return (score,) + words
+
+    def sw_stats_time_ms(self, batch, scoring: Scoring, repeats: int = 10) -> np.ndarray:
+        """seqalign_sw_stats_time_ms: sw_stats' kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
+        _score_args(batch, scoring)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "sw_stats_time_ms: repeats must be > 0")
+        _sw_stats_lengths("sw_stats_time_ms", "pair", ("seq_a", batch.len_a), ("seq_b", batch.len_b))
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_stats_time_ms(self._h, C.byref(d), C.byref(scoring), C.c_int(repeats), _ptr(ms)),
+               "seqalign_sw_stats_time_ms")
+        return ms
+
+    def sw_stats_cross(self, queries, targets, scoring: Scoring):
+        """seqalign_sw_stats_cross: (score int32, pos_a, pos_b, len_a, len_b, matches, mismatches uint32), each [n_queries,
+        n_targets] -- sw_stats on workloads.cross_batch(queries, targets) without building that batch; pos_a / len_a are in
+        the query."""
+        _cross_args(queries, targets, scoring)
+        _sw_stats_lengths("sw_stats_cross", "query", (None, queries.len))
+        _sw_stats_lengths("sw_stats_cross", "target", (None, targets.len))
+        shape = (queries.n_seqs, targets.n_seqs)
+        score = np.zeros(shape, np.int32)
+        words = tuple(np.zeros(shape, np.uint32) for _ in range(6))
+        dq, dt = seqset_desc(queries), seqset_desc(targets)
+        _check(lib().seqalign_sw_stats_cross(self._h, C.byref(dq), C.byref(dt), C.byref(scoring), _ptr(score),
+                                             *(_ptr(w) for w in words)), "seqalign_sw_stats_cross")
+        return (score,) + words
+
     # ---- score matrices (seqalign_nw_score_cross / seqalign_sw_score_cross) ------------------------------
     def nw_score_cross(self, queries, targets, scoring: Scoring, peers=None) -> np.ndarray:
         """seqalign_nw_score_cross: the global score of every query against every target, int32[n_queries, n_targets] --
@@ -879,6 +928,17 @@ def _score_args(batch, scoring):
         raise SeqAlignError(E_ARG, "score: a sequence lies outside batch.arena")
 
 
+def _sw_stats_lengths(call, what, *arrays):
+    """The SW statistics calls' length limit (SEQALIGN_SW_STATS_MAX_LEN), as the library raises it: the lowest entry named."""
+    over = [np.flatnonzero(a > SW_STATS_MAX_LEN) for _, a in arrays]
+    first = min((int(o[0]) for o in over if len(o)), default=None)
+    if first is None:
+        return
+    name, a = next((nm, a) for (nm, a), o in zip(arrays, over) if len(o) and int(o[0]) == first)
+    has = f"{name} has " if name else ""
+    raise SeqAlignError(E_TOO_LARGE, f"{call}: {what} {first}: {has}{int(a[first])} letters, SW statistics take at most {SW_STATS_MAX_LEN}")
+
+
 def _nw_string_buffers(batch):
     """Output buffers of the calls that return seqalign_nw_batch's strings: str_off, out_a, out_b, out_len, out_score
     (capacity len_a + len_b + 1 per pair)."""
@@ -1187,6 +1247,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_score_time_ms",
     "seqalign_sw_span_batch", "seqalign_sw_span_batch_multi", "seqalign_sw_span_time_ms",
     "seqalign_nw_stats_batch", "seqalign_nw_stats_batch_multi", "seqalign_nw_stats_time_ms", "seqalign_nw_stats_cross",
+    "seqalign_sw_stats_batch", "seqalign_sw_stats_batch_multi", "seqalign_sw_stats_time_ms", "seqalign_sw_stats_cross",
     "seqalign_nw_score_cross", "seqalign_sw_score_cross", "seqalign_nw_score_cross_multi", "seqalign_sw_score_cross_multi",
     "seqalign_nw_score_search", "seqalign_sw_score_search", "seqalign_nw_score_search_multi",
     "seqalign_sw_score_search_multi",

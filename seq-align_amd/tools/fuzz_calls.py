@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, seqalign_sw_span_batch, *_score_cross,
 *_score_search, seqalign_sw_span_cross and seqalign_sw_span_search (against sw_span on the explicit batch), seqalign_nw_stats_batch
-(the columns of the oracle's strings) and seqalign_nw_stats_cross (against nw_stats on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+(the columns of the oracle's strings) and seqalign_nw_stats_cross (against nw_stats on the explicit batch), seqalign_sw_stats_batch
+(the oracle's first hit and its counted strings) and seqalign_sw_stats_cross (against sw_stats on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -92,7 +93,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         import maglib as G      # only the scaled runs need it: the default run is what it was, imports included
     ctx = ctx or (None if dry else S.Context(0))
     t_end = time.time() + seconds
-    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0}
+    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -189,15 +190,20 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                 fail("SW SCORE", spec, p, pairs[p], (int(s[p]), int(ea[p]), int(eb[p])), want)
         n["score"] += 12 * (1 + nw_ok)
 
-        # ---- SW hit spans: the oracle's first hit without its strings
+        # ---- SW hit spans: the oracle's first hit without its strings; SW statistics: that hit and its strings' counted columns
         got = ctx.sw_span(batch, sc)
+        got7 = ctx.sw_stats(batch, sc)
         for p, (a, b) in enumerate(pairs):
             rc, hits = O.oracle_sw_hits(osc, a, b, *fills[1, p], 1, 1)
             h = hits[0] if hits else None
             want = (h["score"], h["pos_a"], h["pos_b"], h["len_a"], h["len_b"]) if h else (0, 0, 0, 0, 0)
             if rc != 0 or tuple(int(x[p]) for x in got) != want:
                 fail("SW SPAN", spec, p, pairs[p], tuple(int(x[p]) for x in got), want)
+            want7 = want + (ST.count_columns(osc, h["a"].encode(), h["b"].encode()) if h else (0, 0))
+            if tuple(int(x[p]) for x in got7) != want7:
+                fail("SW STATS", spec, p, pairs[p], tuple(int(x[p]) for x in got7), want7)
         n["span"] += 12
+        n["sw_stats"] += len(pairs)
 
         # ---- NW statistics: the columns of the oracle's strings, counted on the host
         if nw_ok:
@@ -257,6 +263,12 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                     and np.array_equal(got[1] + got[3], dense[1]) and np.array_equal(got[2] + got[4], dense[2])):
                 fail("SW SPAN CROSS", spec, queries, targets, [g.tolist() for g in got], [w.tolist() for w in want])
             n["span_cross"] += 24
+            # ---- the same sets' SW statistics matrices: sw_stats on the explicit batch, the span matrices just checked
+            want7 = tuple(x.reshape(4, 6) for x in ctx.sw_stats(W.cross_batch(q, t), sc))
+            got7 = ctx.sw_stats_cross(q, t, sc)
+            if not (all(np.array_equal(g, w) for g, w in zip(got7, want7)) and all(np.array_equal(g, w) for g, w in zip(got7[:5], got))):
+                fail("SW STATS CROSS", spec, queries, targets, [g.tolist() for g in got7], [w.tolist() for w in want7])
+            n["sw_stats_cross"] += 24
             n_span, span_hits = ctx.sw_span_search(q, t, sc, k_top, min_score=min_score)
             for i in range(4):
                 h, hs = span_hits[i, :int(n_span[i])], hits[i, :int(n_hits[i])]
@@ -369,7 +381,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         print(f"fuzz_calls scale up to {scale}: {n['redraws']} factors redrawn in {n['redrawn_trials']} of {n['trials']} trials "
               f"({n['redrawn_trials'] / max(1, n['trials']):.1%} of the trials)", flush=True)
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
-          f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['long']} long alignments, {n['banded']} banded "
+          f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['stats']} NW and {n['sw_stats']} SW statistics, {n['stats_cross']} NW and {n['sw_stats_cross']} SW statistics cross cells, {n['long']} long alignments, {n['banded']} banded "
           f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results identical to the oracle "
           f"(seed {seed})", flush=True)
     return n
