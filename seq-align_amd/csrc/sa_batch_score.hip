@@ -17,9 +17,9 @@
 // pair, the span's 32 per row and strip, 4 per strip (no best cell).  SW statistics: the span's bytes plus 8 of results per pair
 // (80), its 32 per row and strip and its 36 per strip.
 //
-// The four families are one driver (RowChunkRun) over a traits struct each: what differs is the kernels' parameter block,
-// ladder and launch functions and the bytes named above.
-#include "sa_chunks.hpp"
+// The four families are one driver (RowChunkRun) over a traits struct each (sa_row_families.hpp, shared with the cross driver):
+// what differs is the kernels' parameter block, ladder and launch functions and the bytes named above.
+#include "sa_row_families.hpp"
 
 using namespace sa_host;
 
@@ -34,79 +34,6 @@ SaFillParams sa_host::score_fill_params(const seqalign_dev_scoring *s) {
 }
 
 namespace {
-
-struct ScoreTraits {   // sa_score.hip
-  using Params = SaScoreParams;
-  static constexpr int kRowClasses = SA_SCORE_ROW_CLASSES;   // its instantiations (sa_score_row_class)
-  static constexpr uint32_t kRowMax = SA_SCORE_ROW_MAX;
-  static constexpr uint64_t kPairBytes = 64;   // descriptors (32), results (12), status (8), slack
-  static constexpr uint64_t kHandoffBytes = 8, kBestBytes = 16;
-  static constexpr const char *kLaunch = "score kernel launch";
-  static constexpr int kMarkField = 0;         // no result word carries a mark
-  static int fields(bool is_sw) { return is_sw ? 3 : 1; }   // result words per pair: score; SW: end_a, end_b
-  static int row_class(uint32_t la) { return sa_score_row_class(la); }
-  static uint32_t strips_per_pair(uint32_t la) { return sa_score_strips_per_pair(la); }
-  static void set_results(Params &p, uint32_t *res, uint64_t n) { p.end_a = res + n; p.end_b = res + 2 * n; }
-  static void set_strip_best(Params &p, uint32_t *best) { p.strip_best = best; }
-  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool is_sw, hipStream_t st) { return sa_launch_score_rows(p, max_a, is_sw, st); }
-  static hipError_t launch_strips(const Params &p, bool is_sw, hipStream_t st) { return sa_launch_score_strips(p, is_sw, st); }
-};
-
-struct SpanTraits {   // sa_span.hip: the SW form only
-  using Params = SaSpanParams;
-  static constexpr int kRowClasses = SA_SPAN_ROW_CLASSES;   // its instantiations (sa_span_row_class)
-  static constexpr uint32_t kRowMax = SA_SPAN_ROW_MAX;
-  static constexpr uint64_t kPairBytes = 72;   // descriptors (32), results (20), status (8), slack
-  static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
-  static constexpr const char *kLaunch = "span kernel launch";
-  static constexpr int kMarkField = 0;
-  static int fields(bool) { return 5; }   // score, pos_a, pos_b, len_a, len_b
-  static int row_class(uint32_t la) { return sa_span_row_class(la); }
-  static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
-  static void set_results(Params &p, uint32_t *res, uint64_t n) {
-    p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
-  }
-  static void set_strip_best(Params &p, uint32_t *best) { p.strip_best = best; }
-  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_span_rows(p, max_a, st); }
-  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_span_strips(p, st); }
-};
-
-struct StatsTraits {   // sa_nw_stats.hip: the NW form only; classes, strips and hand-off of the span kernels, no best cell
-  using Params = SaStatsParams;
-  static constexpr int kRowClasses = SA_SPAN_ROW_CLASSES;
-  static constexpr uint32_t kRowMax = SA_SPAN_ROW_MAX;
-  static constexpr uint64_t kPairBytes = 64;   // descriptors (32), results (12), status (8), slack
-  static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = 0;
-  static constexpr const char *kLaunch = "stats kernel launch";
-  static constexpr int kMarkField = 2;         // SA_STATS_NO_WALK in the mismatch word: SEQALIGN_E_TRACEBACK
-  static int fields(bool) { return 3; }   // score, matches, mismatches
-  static int row_class(uint32_t la) { return sa_span_row_class(la); }
-  static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
-  static void set_results(Params &p, uint32_t *res, uint64_t n) { p.matches = res + n; p.mismatches = res + 2 * n; }
-  static void set_strip_best(Params &, uint32_t *) {}
-  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_stats_rows(p, max_a, st); }
-  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_stats_strips(p, st); }
-};
-
-struct SwStatsTraits {   // sa_sw_stats.hip: the span kernels' classes, strips, hand-off and best-cell bytes; seven result words
-  using Params = SaSwStatsParams;
-  static constexpr int kRowClasses = SA_SPAN_ROW_CLASSES;
-  static constexpr uint32_t kRowMax = SA_SPAN_ROW_MAX;
-  static constexpr uint64_t kPairBytes = 80;   // descriptors (32), results (28), status (8), slack
-  static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
-  static constexpr const char *kLaunch = "sw stats kernel launch";
-  static constexpr int kMarkField = 0;
-  static int fields(bool) { return 7; }   // score, pos_a, pos_b, len_a, len_b, matches, mismatches
-  static int row_class(uint32_t la) { return sa_span_row_class(la); }
-  static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
-  static void set_results(Params &p, uint32_t *res, uint64_t n) {
-    p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
-    p.matches = res + 5 * n; p.mismatches = res + 6 * n;
-  }
-  static void set_strip_best(Params &p, uint32_t *best) { p.strip_best = best; }
-  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_sw_stats_rows(p, max_a, st); }
-  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_sw_stats_strips(p, st); }
-};
 
 // hand-off columns of one pair: strips 0 .. last - 1, len_b + 1 rows each, in rows
 template <class T>
@@ -225,10 +152,12 @@ struct RowChunkRun {
   }
 };
 
-// seqalign_*_score_batch / seqalign_sw_span_batch behind their entry checks: every chunk prepared, launched, brought home
+}  // namespace
+
+// seqalign_*_score_batch / seqalign_sw_span_batch / seqalign_*_stats_batch behind their entry checks (sa_row_families.hpp)
 template <class T>
-int row_batch_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw, int32_t *out_score,
-                   uint32_t *const *out, uint64_t *fail_pair) {
+int sa_host::row_batch_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw,
+                            int32_t *out_score, uint32_t *const *out, uint64_t *fail_pair) {
   if (!batch_readable(batch)) return SEQALIGN_E_ARG;   // check_batch without the 2^31-cell cap
   if (batch->n_pairs == 0) return SEQALIGN_OK;
   HIP_TRY(hipSetDevice(ctx->device));
@@ -243,6 +172,12 @@ int row_batch_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const sco
   }
   return SEQALIGN_OK;
 }
+template int sa_host::row_batch_call<ScoreTraits>(seqalign_ctx_t *, const seqalign_batch_t *, const scoring_t *, bool, int32_t *, uint32_t *const *, uint64_t *);
+template int sa_host::row_batch_call<SpanTraits>(seqalign_ctx_t *, const seqalign_batch_t *, const scoring_t *, bool, int32_t *, uint32_t *const *, uint64_t *);
+template int sa_host::row_batch_call<StatsTraits>(seqalign_ctx_t *, const seqalign_batch_t *, const scoring_t *, bool, int32_t *, uint32_t *const *, uint64_t *);
+template int sa_host::row_batch_call<SwStatsTraits>(seqalign_ctx_t *, const seqalign_batch_t *, const scoring_t *, bool, int32_t *, uint32_t *const *, uint64_t *);
+
+namespace {
 
 // the launches of a batch that is one chunk, `repeats` times between HIP events; `name`: the hook's, for its message
 template <class T>
@@ -277,12 +212,6 @@ int sa_host::span_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
   return row_batch_call<SpanTraits>(ctx, batch, scoring, true, out_score, out, fail_pair);
 }
 
-int sa_host::stats_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
-                              uint32_t *out_matches, uint32_t *out_mismatches, uint64_t *fail_pair) {
-  uint32_t *const out[2] = {out_matches, out_mismatches};
-  return row_batch_call<StatsTraits>(ctx, batch, scoring, false, out_score, out, fail_pair);
-}
-
 // seqalign_sw_stats_*'s length limit: a coordinate and a counter are 16 bits each in the kernels' payload words
 int sa_host::sw_stats_check_batch(const seqalign_batch_t *batch) {
   for (uint64_t p = 0; p < batch->n_pairs; ++p)
@@ -294,11 +223,6 @@ int sa_host::sw_stats_check_batch(const seqalign_batch_t *batch) {
       return SEQALIGN_E_TOO_LARGE;
     }
   return SEQALIGN_OK;
-}
-
-int sa_host::sw_stats_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
-                                 uint32_t *const *out, uint64_t *fail_pair) {
-  return row_batch_call<SwStatsTraits>(ctx, batch, scoring, true, out_score, out, fail_pair);
 }
 
 extern "C" int seqalign_nw_score_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
@@ -341,7 +265,8 @@ extern "C" int seqalign_nw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch
                                        int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
   if (!ctx || !scoring || !out_score || !out_matches || !out_mismatches || !batch_readable(batch)) return SEQALIGN_E_ARG;
   CallScope scope(ctx);   // (every argument checked before the context is touched)
-  return stats_batch_impl(ctx, batch, scoring, out_score, out_matches, out_mismatches);
+  uint32_t *const out[2] = {out_matches, out_mismatches};
+  return row_batch_call<StatsTraits>(ctx, batch, scoring, false, out_score, out);
 }
 
 extern "C" int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
@@ -362,7 +287,7 @@ extern "C" int seqalign_sw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch
   if (!ctx) return SEQALIGN_E_ARG;
   CallScope scope(ctx);
   uint32_t *const out[6] = {out_pos_a, out_pos_b, out_len_a, out_len_b, out_matches, out_mismatches};
-  return sw_stats_batch_impl(ctx, batch, scoring, out_score, out);
+  return row_batch_call<SwStatsTraits>(ctx, batch, scoring, true, out_score, out);
 }
 
 extern "C" int seqalign_sw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,

@@ -23,21 +23,24 @@
 //
 // Span matrices (seqalign_sw_span_cross) are the same tiles once more with 20 result bytes per pair: the CROSS form of the span
 // kernel (sa_span.hip) in place of the score kernel's, five rows home per query, and the short / long split at SA_SPAN_ROW_MAX
-// columns, the long queries through the span strips (span_batch_impl).
+// columns, the long queries through the span strips (row_batch_call<SpanTraits>).
 //
 // Statistics matrices (seqalign_nw_stats_cross) are the span matrices' tiles with 12 result bytes per pair: the CROSS form of the
 // stats kernel (sa_nw_stats.hip), three rows home per query, the same split at SA_SPAN_ROW_MAX columns, the long queries through
-// the stats strips (stats_batch_impl).  A pair whose end pick has no walk (SA_STATS_NO_WALK) is SEQALIGN_E_TRACEBACK; between
-// it and a pair without a score the lower pair's code is the call's.
+// the stats strips (row_batch_call<StatsTraits>).  A pair whose end pick has no walk (SA_STATS_NO_WALK) is SEQALIGN_E_TRACEBACK;
+// between it and a pair without a score the lower pair's code is the call's.
 //
 // SW statistics matrices (seqalign_sw_stats_cross) are the span matrices' tiles once more with 28 result bytes per pair: the CROSS
 // form of the SW stats kernel (sa_sw_stats.hip), seven rows home per query, the long queries through its strips
-// (sw_stats_batch_impl).  Every query and every target has at most SEQALIGN_SW_STATS_MAX_LEN letters (checked at the entry).
+// (row_batch_call<SwStatsTraits>).  Every query and every target has at most SEQALIGN_SW_STATS_MAX_LEN letters (checked at the entry).
 //
 // Top-k search with spans (seqalign_sw_span_search) is two stages: the score search above, unchanged, and then
 // the span sweep on the selected hits alone -- for each the PREFIX pair (query[0 : end_a], target[0 : end_b]), whose first hit
 // is the full pair's, as an explicit pair list through span_batch_impl.
-#include "sa_ctx.hpp"
+//
+// The four families are one driver, CrossCall<R>, over the batch driver's traits structs (sa_row_families.hpp): one parameter
+// block per row class, R's CROSS launch, R's result layout, R's batch call for the long queries.
+#include "sa_row_families.hpp"
 
 using namespace sa_host;
 
@@ -100,27 +103,25 @@ struct SearchOut {   // seqalign_*_score_search's outputs, or seqalign_sw_span_s
   }
 };
 
+// One cross call of family R (sa_row_families.hpp): its tiles through R's CROSS kernel, its long queries through R's batch call
+template <class R>
 struct CrossCall {
   seqalign_ctx *ctx;
   const seqalign_seqset_t *Q, *T;
   const scoring_t *scoring;
   bool is_sw;
   int32_t *out_score;
-  uint32_t *out_w[6];   // the matrices behind the score -- SW: end_a, end_b; span: pos_a, pos_b, len_a, len_b; SW stats: + counts
+  uint32_t *const *out_w;   // the matrices behind the score, fields() - 1 of them in R::set_results' order
   uint64_t nT;
-  FailPair fail;
-  const SearchOut *search = nullptr;   // set: top-k search, the matrix outputs are unused
-  bool span = false;                   // seqalign_sw_span_cross (is_sw set, no search)
-  bool stats = false;                  // seqalign_nw_stats_cross (is_sw clear, no search): out_w = matches, mismatches
-  FailPair no_walk;                    // stats: the lowest pair whose end pick has no walk (SEQALIGN_E_TRACEBACK)
-  bool sw_stats = false;               // seqalign_sw_stats_cross (is_sw set, no search): out_w = the span's four, matches, mismatches
+  const SearchOut *search = nullptr;   // set: top-k search (the score family only), the matrix outputs are unused
+  FailPair fail;                       // the lowest pair without a score
+  FailPair no_walk;                    // R::kMarkField: the lowest pair whose end pick has no walk (SEQALIGN_E_TRACEBACK)
 
-  int words() const { return sw_stats ? 6 : span ? 4 : (is_sw || stats) ? 2 : 0; }   // result words per pair behind the score
-  uint64_t result_bytes() const { return 4 * (1 + (uint64_t)words()); }
-  uint32_t row_max() const { return (span || stats || sw_stats) ? SA_SPAN_ROW_MAX : SA_SCORE_ROW_MAX; }   // the one-wave kernels' widest query
+  int fields() const { return R::fields(is_sw); }   // result words per pair, the score first
+  uint64_t result_bytes() const { return 4 * (uint64_t)fields(); }
   uint64_t list_bytes() const { return search ? 16ull * search->k + 4 : 0; }   // one query's running list
 
-  // queries <= row_max(): the cross kernel, tile by tile
+  // queries <= R::kRowMax: the cross kernel, tile by tile
   int run_short(const std::vector<uint64_t> &qs) {
     int rc;
     seqalign_dev_scoring *sc = nullptr;
@@ -210,68 +211,19 @@ struct CrossCall {
         for (int x = 0; x < SA_SCORE_ROW_CLASSES; ++x) {
           const uint64_t m = cls_first[x + 1] - cls_first[x];
           if (!m) continue;
-          if (span) {
-            SaSpanCrossParams p;
-            memset(&p, 0, sizeof(p));
-            p.s.f = f0;
-            p.s.f.arena = d_seq;
-            p.s.f.off_a = d_off_q; p.s.f.len_a = d_len_q; p.s.f.off_b = d_off_t; p.s.f.len_b = d_len_t;
-            p.q_list = d_qlist + cls_first[x]; p.t_order = d_tord;
-            p.nq = (uint32_t)m; p.n_t = (uint32_t)nt; p.n_waves = (uint32_t)(m * nt);
-            p.s.score = reinterpret_cast<int32_t *>(d_res + 4);
-            p.s.pos_a = d_res + 4 + n; p.s.pos_b = d_res + 4 + 2 * n; p.s.len_a = d_res + 4 + 3 * n; p.s.len_b = d_res + 4 + 4 * n;
-            p.s.err_flag = d_res;
-            p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
-            const hipError_t e = sa_launch_span_cross(p, cls_max_a[x], st);
-            if (e != hipSuccess) return fail_hip(e, "span cross kernel launch");
-            continue;
-          }
-          if (sw_stats) {
-            SaSwStatsCrossParams p;
-            memset(&p, 0, sizeof(p));
-            p.s.f = f0;
-            p.s.f.arena = d_seq;
-            p.s.f.off_a = d_off_q; p.s.f.len_a = d_len_q; p.s.f.off_b = d_off_t; p.s.f.len_b = d_len_t;
-            p.q_list = d_qlist + cls_first[x]; p.t_order = d_tord;
-            p.nq = (uint32_t)m; p.n_t = (uint32_t)nt; p.n_waves = (uint32_t)(m * nt);
-            p.s.score = reinterpret_cast<int32_t *>(d_res + 4);
-            p.s.pos_a = d_res + 4 + n; p.s.pos_b = d_res + 4 + 2 * n; p.s.len_a = d_res + 4 + 3 * n; p.s.len_b = d_res + 4 + 4 * n;
-            p.s.matches = d_res + 4 + 5 * n; p.s.mismatches = d_res + 4 + 6 * n;
-            p.s.err_flag = d_res;
-            p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
-            const hipError_t e = sa_launch_sw_stats_cross(p, cls_max_a[x], st);
-            if (e != hipSuccess) return fail_hip(e, "sw stats cross kernel launch");
-            continue;
-          }
-          if (stats) {
-            SaStatsCrossParams p;
-            memset(&p, 0, sizeof(p));
-            p.s.f = f0;
-            p.s.f.arena = d_seq;
-            p.s.f.off_a = d_off_q; p.s.f.len_a = d_len_q; p.s.f.off_b = d_off_t; p.s.f.len_b = d_len_t;
-            p.q_list = d_qlist + cls_first[x]; p.t_order = d_tord;
-            p.nq = (uint32_t)m; p.n_t = (uint32_t)nt; p.n_waves = (uint32_t)(m * nt);
-            p.s.score = reinterpret_cast<int32_t *>(d_res + 4);
-            p.s.matches = d_res + 4 + n; p.s.mismatches = d_res + 4 + 2 * n;
-            p.s.err_flag = d_res;
-            p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
-            const hipError_t e = sa_launch_stats_cross(p, cls_max_a[x], st);
-            if (e != hipSuccess) return fail_hip(e, "stats cross kernel launch");
-            continue;
-          }
-          SaScoreCrossParams p;
+          typename R::CrossParams p;
           memset(&p, 0, sizeof(p));
-          p.f = f0;
-          p.f.arena = d_seq;
-          p.f.off_a = d_off_q; p.f.len_a = d_len_q; p.f.off_b = d_off_t; p.f.len_b = d_len_t;
+          p.s.f = f0;
+          p.s.f.arena = d_seq;
+          p.s.f.off_a = d_off_q; p.s.f.len_a = d_len_q; p.s.f.off_b = d_off_t; p.s.f.len_b = d_len_t;
           p.q_list = d_qlist + cls_first[x]; p.t_order = d_tord;
           p.nq = (uint32_t)m; p.n_t = (uint32_t)nt; p.n_waves = (uint32_t)(m * nt);
-          p.score = reinterpret_cast<int32_t *>(d_res + 4);
-          p.end_a = d_res + 4 + n; p.end_b = d_res + 4 + 2 * n;
-          p.err_flag = d_res;
+          p.s.score = reinterpret_cast<int32_t *>(d_res + 4);
+          R::set_results(p.s, d_res + 4, n);
+          p.s.err_flag = d_res;
           p.err_pair = reinterpret_cast<unsigned long long *>(d_res + 2);
-          const hipError_t e = sa_launch_score_cross(p, cls_max_a[x], is_sw, st);
-          if (e != hipSuccess) return fail_hip(e, "score cross kernel launch");
+          const hipError_t e = R::launch_cross(p, cls_max_a[x], is_sw, st);
+          if (e != hipSuccess) return fail_hip(e, R::kLaunchCross);
         }
 
         uint32_t *h = ctx->h_misc.as<uint32_t>();
@@ -315,14 +267,14 @@ struct CrossCall {
           fail.offer(qs[qr.first + key / nt], tr.first + key % nt, nT);
           continue;
         }
-        if (stats) {   // SA_STATS_NO_WALK in a mismatch word; the tile's order is row-major, so its first is its lowest
-          const uint32_t *w = h + 4 + 2 * n;
+        if constexpr (R::kMarkField > 0) {   // SA_STATS_NO_WALK in a mismatch word; the tile's order is row-major: its first is its lowest
+          const uint32_t *w = h + 4 + (uint64_t)R::kMarkField * n;
           uint64_t k = 0;
           while (k < n && !(w[k] & SA_STATS_NO_WALK)) ++k;
           if (k < n) { no_walk.offer(qs[qr.first + k / nt], tr.first + k % nt, nT); continue; }
         }
         const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
-        const int nw = words();
+        const int nw = fields() - 1;
         constexpr uint64_t kRows = 64;
         parallel_for((nq + kRows - 1) / kRows, [&](uint64_t blk) {
           for (uint64_t k = blk * kRows, e = std::min(nq, (blk + 1) * kRows); k < e; ++k) {
@@ -337,8 +289,8 @@ struct CrossCall {
     return SEQALIGN_OK;
   }
 
-  // queries > row_max(): score-batch (span: span-batch) slices of (a few long queries x a slice of the targets), through
-  // the strips
+  // queries > R::kRowMax: slices of (a few long queries x a slice of the targets) as explicit batches through R's batch call,
+  // that is through the strips
   int run_long(const std::vector<uint64_t> &qs) {
     int rc;
     // one arena of their own for the batches: the long queries, then the targets
@@ -359,7 +311,7 @@ struct CrossCall {
     std::vector<uint32_t> len_a, len_b, w[6];   // w: the result arrays behind the score (out_w's order)
     std::vector<uint32_t> &ea = w[0], &eb = w[1];
     std::vector<int32_t> sc;
-    const int nw = words();
+    const int nw = fields() - 1;
     for (uint64_t g0 = 0; g0 < qs.size(); g0 += q_rows) {
       const uint64_t g1 = std::min<uint64_t>(qs.size(), g0 + q_rows);
       if ((fail.any() && qs[g0] > fail.q) || (no_walk.any() && qs[g0] > no_walk.q)) break;   // only higher pairs from here on
@@ -377,10 +329,7 @@ struct CrossCall {
         b.off_a = off_a.data(); b.len_a = len_a.data(); b.off_b = off_b.data(); b.len_b = len_b.data();
         uint64_t bad = ~0ull;
         uint32_t *const w6[6] = {w[0].data(), w[1].data(), w[2].data(), w[3].data(), w[4].data(), w[5].data()};
-        rc = sw_stats ? sw_stats_batch_impl(ctx, &b, scoring, sc.data(), w6, &bad)
-             : span  ? span_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), w[2].data(), w[3].data(), &bad)
-             : stats ? stats_batch_impl(ctx, &b, scoring, sc.data(), w[0].data(), w[1].data(), &bad)
-                     : score_batch_impl(ctx, &b, scoring, is_sw, sc.data(), ea.data(), eb.data(), &bad);
+        rc = row_batch_call<R>(ctx, &b, scoring, is_sw, sc.data(), w6, &bad);
         if (rc == SEQALIGN_E_TRACEBACK && bad != ~0ull) {
           no_walk.offer(qs[g0 + bad / nt], t0 + bad % nt, nT);
           continue;
@@ -435,7 +384,7 @@ struct CrossCall {
       for (uint64_t t = 0; t < T->n_seqs; ++t) max_t = std::max(max_t, T->len[t]);
       if ((rc = admit_magnitude(sc, max_q, max_t, SA_FRAMES_ROWS))) return rc;
     }
-    for (uint64_t q = 0; q < Q->n_seqs; ++q) (Q->len[q] > row_max() ? long_q : short_q).push_back(q);
+    for (uint64_t q = 0; q < Q->n_seqs; ++q) (Q->len[q] > R::kRowMax ? long_q : short_q).push_back(q);
     if (!short_q.empty() && (rc = run_short(short_q))) return rc;
     if (!long_q.empty() && (rc = run_long(long_q))) return rc;
     if (no_walk.any() && no_walk.key < fail.key) {   // the lowest failing pair's code is the call's
@@ -466,57 +415,20 @@ int sa_host::score_cross_check(const seqalign_seqset_t *queries, const seqalign_
   return SEQALIGN_OK;
 }
 
-int sa_host::score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
-                              const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a,
-                              uint32_t *out_end_b, uint64_t q_base) {
-  int rc = score_cross_check(queries, targets);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  StreamSyncOnExit sync(ctx->stream);
-  CrossCall call{ctx, queries, targets, scoring, is_sw, out_score, {out_end_a, out_end_b, nullptr, nullptr}, targets->n_seqs, FailPair()};
-  return call.run(q_base);
+template <class R>
+int sa_host::cross_call(const CrossArgs &a) {
+  CallScope scope(a.ctx);
+  if (!a.queries->n_seqs || !a.targets->n_seqs) return SEQALIGN_OK;
+  HIP_TRY(hipSetDevice(a.ctx->device));
+  StreamSyncOnExit sync(a.ctx->stream);
+  CrossCall<R> call{.ctx = a.ctx, .Q = a.queries, .T = a.targets, .scoring = a.scoring, .is_sw = a.is_sw,
+                    .out_score = a.out_score, .out_w = a.out_w, .nT = a.targets->n_seqs};
+  return call.run(a.q_base);
 }
-
-int sa_host::span_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
-                             const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
-                             uint32_t *out_len_a, uint32_t *out_len_b, uint64_t q_base) {
-  int rc = score_cross_check(queries, targets);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  StreamSyncOnExit sync(ctx->stream);
-  CrossCall call{ctx, queries, targets, scoring, true, out_score, {out_pos_a, out_pos_b, out_len_a, out_len_b}, targets->n_seqs,
-                 FailPair(), nullptr, true};
-  return call.run(q_base);
-}
-
-int sa_host::stats_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
-                              const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches,
-                              uint64_t q_base) {
-  int rc = score_cross_check(queries, targets);
-  if (rc) return rc;
-  CallScope scope(ctx);
-  if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  StreamSyncOnExit sync(ctx->stream);
-  CrossCall call{ctx, queries, targets, scoring, false, out_score, {out_matches, out_mismatches, nullptr, nullptr}, targets->n_seqs,
-                 FailPair(), nullptr, false, true};
-  return call.run(q_base);
-}
-
-int sa_host::sw_stats_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
-                                 const scoring_t *scoring, int32_t *out_score, uint32_t *const *out_w, uint64_t q_base) {
-  CallScope scope(ctx);
-  if (!queries->n_seqs || !targets->n_seqs) return SEQALIGN_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  StreamSyncOnExit sync(ctx->stream);
-  CrossCall call{ctx, queries, targets, scoring, true, out_score, {out_w[0], out_w[1], out_w[2], out_w[3], out_w[4], out_w[5]},
-                 targets->n_seqs, FailPair(), nullptr, false, false, FailPair(), true};
-  return call.run(q_base);
-}
+template int sa_host::cross_call<ScoreTraits>(const CrossArgs &);
+template int sa_host::cross_call<SpanTraits>(const CrossArgs &);
+template int sa_host::cross_call<StatsTraits>(const CrossArgs &);
+template int sa_host::cross_call<SwStatsTraits>(const CrossArgs &);
 
 int sa_host::score_search_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets, uint32_t k) {
   if (k == 0 || k > SEQALIGN_SEARCH_MAX_K) {
@@ -546,7 +458,8 @@ int sa_host::score_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *que
   HIP_TRY(hipSetDevice(ctx->device));
   StreamSyncOnExit sync(ctx->stream);
   const SearchOut out{k, min_score, hits, n_hits};
-  CrossCall call{ctx, queries, targets, scoring, is_sw, nullptr, {nullptr, nullptr, nullptr, nullptr}, targets->n_seqs, FailPair(), &out};
+  CrossCall<ScoreTraits> call{.ctx = ctx, .Q = queries, .T = targets, .scoring = scoring, .is_sw = is_sw,
+                              .out_score = nullptr, .out_w = nullptr, .nT = targets->n_seqs, .search = &out};
   return call.run(q_base);
 }
 
@@ -625,7 +538,8 @@ int sa_host::span_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *quer
   HIP_TRY(hipSetDevice(ctx->device));
   StreamSyncOnExit sync(ctx->stream);
   const SearchOut out{k, min_score, nullptr, n_hits, hits};
-  CrossCall call{ctx, queries, targets, scoring, true, nullptr, {nullptr, nullptr, nullptr, nullptr}, targets->n_seqs, FailPair(), &out};
+  CrossCall<ScoreTraits> call{.ctx = ctx, .Q = queries, .T = targets, .scoring = scoring, .is_sw = true,
+                              .out_score = nullptr, .out_w = nullptr, .nT = targets->n_seqs, .search = &out};
   if ((rc = call.run(q_base))) return rc;
   return span_of_hits(ctx, queries, targets, scoring, k, hits, n_hits, q_base);
 }
@@ -633,13 +547,20 @@ int sa_host::span_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *quer
 extern "C" int seqalign_nw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                                        const scoring_t *scoring, int32_t *out_score) {
   if (!ctx || !scoring || !out_score) return SEQALIGN_E_ARG;
-  return score_cross_call(ctx, queries, targets, scoring, false, out_score, nullptr, nullptr, 0);
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  return cross_call<ScoreTraits>({.ctx = ctx, .queries = queries, .targets = targets, .scoring = scoring,
+                                  .is_sw = false, .out_score = out_score, .out_w = nullptr, .q_base = 0});
 }
 
 extern "C" int seqalign_sw_score_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                                        const scoring_t *scoring, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b) {
   if (!ctx || !scoring || !out_score || !out_end_a || !out_end_b) return SEQALIGN_E_ARG;
-  return score_cross_call(ctx, queries, targets, scoring, true, out_score, out_end_a, out_end_b, 0);
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  uint32_t *const out_w[2] = {out_end_a, out_end_b};
+  return cross_call<ScoreTraits>({.ctx = ctx, .queries = queries, .targets = targets, .scoring = scoring,
+                                  .is_sw = true, .out_score = out_score, .out_w = out_w, .q_base = 0});
 }
 
 extern "C" int seqalign_nw_score_search(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
@@ -660,7 +581,11 @@ extern "C" int seqalign_sw_span_cross(seqalign_ctx_t *ctx, const seqalign_seqset
                                       const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
                                       uint32_t *out_len_a, uint32_t *out_len_b) {
   if (!ctx || !scoring || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b) return SEQALIGN_E_ARG;
-  return span_cross_call(ctx, queries, targets, scoring, out_score, out_pos_a, out_pos_b, out_len_a, out_len_b, 0);
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  uint32_t *const out_w[4] = {out_pos_a, out_pos_b, out_len_a, out_len_b};
+  return cross_call<SpanTraits>({.ctx = ctx, .queries = queries, .targets = targets, .scoring = scoring,
+                                 .is_sw = true, .out_score = out_score, .out_w = out_w, .q_base = 0});
 }
 
 extern "C" int seqalign_sw_span_search(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
@@ -673,7 +598,11 @@ extern "C" int seqalign_sw_span_search(seqalign_ctx_t *ctx, const seqalign_seqse
 extern "C" int seqalign_nw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                                        const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
   if (!ctx || !scoring || !out_score || !out_matches || !out_mismatches) return SEQALIGN_E_ARG;
-  return stats_cross_call(ctx, queries, targets, scoring, out_score, out_matches, out_mismatches, 0);
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  uint32_t *const out_w[2] = {out_matches, out_mismatches};
+  return cross_call<StatsTraits>({.ctx = ctx, .queries = queries, .targets = targets, .scoring = scoring,
+                                  .is_sw = false, .out_score = out_score, .out_w = out_w, .q_base = 0});
 }
 
 // seqalign_sw_stats_*'s length limit over a set (sa_host::sw_stats_check_batch): the lowest sequence over it is named
@@ -696,5 +625,6 @@ extern "C" int seqalign_sw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqse
   if (rc || (rc = sw_stats_check_set(queries, "query")) || (rc = sw_stats_check_set(targets, "target"))) return rc;
   if (!ctx) return SEQALIGN_E_ARG;   // (the limit is the arguments' own: found before the context is looked at)
   uint32_t *const out_w[6] = {out_pos_a, out_pos_b, out_len_a, out_len_b, out_matches, out_mismatches};
-  return sw_stats_cross_call(ctx, queries, targets, scoring, out_score, out_w, 0);
+  return cross_call<SwStatsTraits>({.ctx = ctx, .queries = queries, .targets = targets, .scoring = scoring,
+                                    .is_sw = true, .out_score = out_score, .out_w = out_w, .q_base = 0});
 }

@@ -419,38 +419,17 @@ void async_shutdown(seqalign_ctx *ctx);   // sa_async.hip: drain the submitted j
 SaFillParams score_fill_params(const seqalign_dev_scoring *s);
 int score_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw,
                      int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b, uint64_t *fail_pair = nullptr);
-// ... and seqalign_sw_span_batch without its entry checks (the span cross and span search calls' long queries and prefix pairs)
+// ... and seqalign_sw_span_batch without its entry checks (the span search call's prefix pairs)
 int span_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                     uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
                     uint64_t *fail_pair = nullptr);
-// ... and seqalign_nw_stats_batch without its entry checks (the stats cross call's long queries); SEQALIGN_E_TRACEBACK names its
-// pair through fail_pair too
-int stats_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
-                     uint32_t *out_matches, uint32_t *out_mismatches, uint64_t *fail_pair = nullptr);
-// ... and seqalign_sw_stats_batch without its entry checks (the SW stats cross call's long queries) -- out: pos_a, pos_b, len_a,
-// len_b, matches, mismatches -- and its length limit over a batch: SEQALIGN_E_TOO_LARGE with the lowest pair named, from the
-// descriptors alone
-int sw_stats_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
-                        uint32_t *const *out, uint64_t *fail_pair = nullptr);
+// seqalign_sw_stats_*'s length limit over a batch: SEQALIGN_E_TOO_LARGE with the lowest pair named, from the descriptors alone
 int sw_stats_check_batch(const seqalign_batch_t *batch);
-// sa_batch_score_cross.hip: the sets' checks (E_ARG; n_queries x n_targets must fit 64 bits), and one context's cross call
-// (its own CallScope) -- q_base: what the error message adds to a query index (the *_multi calls' ranges)
+// sa_batch_score_cross.hip: the sets' checks (E_ARG; n_queries x n_targets must fit 64 bits); one context's cross call is
+// cross_call<family> (sa_row_families.hpp)
 int score_cross_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets);
-int score_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
-                     const scoring_t *scoring, bool is_sw, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b,
-                     uint64_t q_base);
-// ... its span form (seqalign_sw_span_cross): five matrices
-int span_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
-                    const scoring_t *scoring, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b,
-                    uint32_t *out_len_a, uint32_t *out_len_b, uint64_t q_base);
-// ... its statistics form (seqalign_nw_stats_cross): three matrices
-int stats_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
-                     const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches, uint64_t q_base);
-// ... its SW statistics form (seqalign_sw_stats_cross): seven matrices, out_w in sw_stats_batch_impl's order
-int sw_stats_cross_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
-                        const scoring_t *scoring, int32_t *out_score, uint32_t *const *out_w, uint64_t q_base);
 // ... and the top-k search (seqalign_*_score_search) on the same tiles: its checks (E_ARG: k, the sets, n_targets), and
-// one context's call
+// one context's call (its own CallScope) -- q_base: what the error message adds to a query index (the *_multi calls' ranges)
 int score_search_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets, uint32_t k);
 int score_search_call(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                       const scoring_t *scoring, bool is_sw, uint32_t k, int32_t min_score, seqalign_search_hit_t *hits,

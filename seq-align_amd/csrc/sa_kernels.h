@@ -1,4 +1,5 @@
-/* sa_kernels.h -- launch interface between sa_device.hip and the kernels. */
+/* sa_kernels.h -- launch interface between sa_device.hip and the kernels.  HIP C++ only: every includer is a .hip file
+ * (SaCrossParams and sa_pair_params below are templates, the latter __host__ __device__). */
 #ifndef SA_KERNELS_H
 #define SA_KERNELS_H
 
@@ -466,33 +467,29 @@ static inline int sa_span_row_class(uint32_t len_a) {
   while (cpl[c] < need) ++c;
   return c;
 }
-/* score only over two sets (seqalign_*_score_cross): one launch per row class of the queries, one wave per (query, target).
- * f.off_a / f.len_a: the tile's queries, f.off_b / f.len_b: its targets, both into f.arena; f.n_pairs, f.status unused. */
-struct SaScoreCrossParams {
-  SaFillParams f;
-  const uint32_t *q_list;       /* [nq] the class's queries (indices into f.off_a / f.len_a)                           */
-  const uint32_t *t_order;      /* [n_t] every target of the tile, longest first (indices into f.off_b / f.len_b)       */
-  uint32_t nq, n_t;
-  uint32_t n_waves;             /* nq * n_t                                                                            */
-  int32_t *score;               /* [q * n_t + t] for every query q of the tile                                         */
-  uint32_t *end_a, *end_b;      /* (SW)                                                                                */
-  uint32_t *err_flag;           /* |= 1 when a pair has a cell without a score                                         */
-  unsigned long long *err_pair; /* min of q * n_t + t over those pairs; the caller set it to ~0                        */
-};
-/* every query of the class has len_a <= max_len_a <= SA_SCORE_ROW_MAX */
-hipError_t sa_launch_score_cross(const SaScoreCrossParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream);
-/* SW hit spans over two sets (seqalign_sw_span_cross): the span sweep of sa_span.hip's one-wave kernel with SaScoreCrossParams'
- * wave -> (query, target) mapping.  s.f as SaScoreCrossParams::f; s.score, s.pos_a, s.pos_b, s.len_a, s.len_b: [q * n_t + t] for
- * every query q of the tile; s.err_flag |= 1 when a pair has a cell without a score; the strips fields of s are unused. */
-struct SaSpanCrossParams {
-  SaSpanParams s;
-  const uint32_t *q_list;       /* [nq] the class's queries                                                            */
-  const uint32_t *t_order;      /* [n_t] every target of the tile, longest first                                       */
+/* Two sets instead of a pair list (the *_cross calls): one launch per row class of the queries, one wave per (query, target),
+ * for the one-wave kernel of every family -- P is its parameter block (SaScoreParams, SaSpanParams, SaStatsParams,
+ * SaSwStatsParams).  s.f.off_a / s.f.len_a: the tile's queries, s.f.off_b / s.f.len_b: its targets, both into s.f.arena;
+ * s.f.n_pairs, s.f.status and the strips fields of s are unused.  The result arrays of s: [q * n_t + t] for every query q of
+ * the tile; s.err_flag |= 1 when a pair has a cell without a score. */
+template <class P>
+struct SaCrossParams {
+  P s;
+  const uint32_t *q_list;       /* [nq] the class's queries (indices into s.f.off_a / s.f.len_a)                       */
+  const uint32_t *t_order;      /* [n_t] every target of the tile, longest first (indices into s.f.off_b / s.f.len_b)   */
   uint32_t nq, n_t;
   uint32_t n_waves;             /* nq * n_t                                                                            */
   unsigned long long *err_pair; /* min of q * n_t + t over the failing pairs; the caller set it to ~0                  */
 };
-/* every query of the class has len_a <= max_len_a <= SA_SPAN_ROW_MAX; recorded as "score_cross" (items: waves) */
+/* a family's parameter block inside either form */
+template <class P> __host__ __device__ inline const P &sa_pair_params(const P &p) { return p; }
+template <class P> __host__ __device__ inline const P &sa_pair_params(const SaCrossParams<P> &p) { return p.s; }
+using SaScoreCrossParams = SaCrossParams<SaScoreParams>;
+using SaSpanCrossParams = SaCrossParams<SaSpanParams>;
+/* every query of the class has len_a <= max_len_a <= SA_SCORE_ROW_MAX */
+hipError_t sa_launch_score_cross(const SaScoreCrossParams &p, uint32_t max_len_a, bool is_sw, hipStream_t stream);
+/* SW hit spans over two sets (seqalign_sw_span_cross): the CROSS form of sa_span.hip's one-wave kernel;
+ * every query of the class has len_a <= max_len_a <= SA_SPAN_ROW_MAX; recorded as "score_cross" (items: waves) */
 hipError_t sa_launch_span_cross(const SaSpanCrossParams &p, uint32_t max_len_a, hipStream_t stream);
 /* ---- NW alignment statistics (seqalign_nw_stats_batch / _cross, sa_nw_stats.hip): sa_score.hip's NW sweep with two counters
  * carried beside the three values of a cell.  Pair k of a launch: score[k] = SaScoreParams' NW score,
@@ -513,12 +510,7 @@ struct SaStatsParams {
   const uint64_t *handoff_off;      /* [n], in rows                                                                    */
   uint32_t strips_per_pair;
 };
-struct SaStatsCrossParams {         /* SaSpanCrossParams' wave -> (query, target) mapping                              */
-  SaStatsParams s;
-  const uint32_t *q_list, *t_order;
-  uint32_t nq, n_t, n_waves;
-  unsigned long long *err_pair;
-};
+using SaStatsCrossParams = SaCrossParams<SaStatsParams>;
 /* recorded as "score_rows" / "score_strips" / "score_cross"; the callers' duties are sa_launch_span_*'s */
 hipError_t sa_launch_stats_rows(const SaStatsParams &p, uint32_t max_len_a, hipStream_t stream);
 hipError_t sa_launch_stats_strips(const SaStatsParams &p, hipStream_t stream);
@@ -533,12 +525,7 @@ hipError_t sa_launch_stats_cross(const SaStatsCrossParams &p, uint32_t max_len_a
 struct SaSwStatsParams : SaSpanParams {
   uint32_t *matches, *mismatches;   /* [n]                                                                             */
 };
-struct SaSwStatsCrossParams {       /* SaSpanCrossParams' wave -> (query, target) mapping                              */
-  SaSwStatsParams s;
-  const uint32_t *q_list, *t_order;
-  uint32_t nq, n_t, n_waves;
-  unsigned long long *err_pair;
-};
+using SaSwStatsCrossParams = SaCrossParams<SaSwStatsParams>;
 /* recorded as "score_rows" / "score_strips" / "score_cross"; the callers' duties are sa_launch_span_*'s */
 hipError_t sa_launch_sw_stats_rows(const SaSwStatsParams &p, uint32_t max_len_a, hipStream_t stream);
 hipError_t sa_launch_sw_stats_strips(const SaSwStatsParams &p, hipStream_t stream);

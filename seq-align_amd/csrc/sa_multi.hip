@@ -1,5 +1,5 @@
 // sa_multi.hip -- the host-level calls over several contexts (GPUs) from one process.
-#include "sa_ctx.hpp"
+#include "sa_row_families.hpp"
 
 using namespace sa_host;
 
@@ -261,8 +261,9 @@ int score_cross_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const seqalign_seq
   const uint64_t nq = queries->n_seqs, nt = targets->n_seqs;
   if (!nq || !nt) return SEQALIGN_OK;
   return for_each_query_shard(queries, n_ctx, [&](int g, const seqalign_seqset_t *s, uint64_t first) {
-    return score_cross_call(ctxs[g], s, targets, scoring, is_sw, out_score + first * nt,
-                            is_sw ? out_end_a + first * nt : nullptr, is_sw ? out_end_b + first * nt : nullptr, first);
+    uint32_t *const out_w[2] = {is_sw ? out_end_a + first * nt : nullptr, is_sw ? out_end_b + first * nt : nullptr};
+    return cross_call<ScoreTraits>({.ctx = ctxs[g], .queries = s, .targets = targets, .scoring = scoring,
+                                    .is_sw = is_sw, .out_score = out_score + first * nt, .out_w = out_w, .q_base = first});
   });
 }
 }  // namespace
@@ -318,8 +319,9 @@ extern "C" int seqalign_sw_span_cross_multi(seqalign_ctx_t *const *ctxs, int n_c
   const uint64_t nt = targets->n_seqs;
   if (!queries->n_seqs || !nt) return SEQALIGN_OK;
   return for_each_query_shard(queries, n_ctx, [&](int g, const seqalign_seqset_t *s, uint64_t first) {
-    return span_cross_call(ctxs[g], s, targets, scoring, out_score + first * nt, out_pos_a + first * nt, out_pos_b + first * nt,
-                           out_len_a + first * nt, out_len_b + first * nt, first);
+    uint32_t *const out_w[4] = {out_pos_a + first * nt, out_pos_b + first * nt, out_len_a + first * nt, out_len_b + first * nt};
+    return cross_call<SpanTraits>({.ctx = ctxs[g], .queries = s, .targets = targets, .scoring = scoring,
+                                   .is_sw = true, .out_score = out_score + first * nt, .out_w = out_w, .q_base = first});
   });
 }
 

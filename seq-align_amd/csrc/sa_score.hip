@@ -30,7 +30,8 @@ constexpr uint32_t kScoreStripCols = kWave * kScoreStripCPL;
 // [q * n_t + t] of the tile; a failing pair leaves only its index, in one 64-bit atomicMin.
 template <int CPL, int SUBST, bool GENERAL, bool SW, bool CROSS = false>
 __global__ void __launch_bounds__(kWave *kWavesPerBlock)
-score_rows_kernel(const std::conditional_t<CROSS, SaScoreCrossParams, SaScoreParams> sp) {
+score_rows_kernel(const std::conditional_t<CROSS, SaScoreCrossParams, SaScoreParams> kp) {
+  const SaScoreParams &sp = sa_pair_params(kp);
   const SaFillParams &p = sp.f;
   extern __shared__ __attribute__((aligned(16))) int32_t lds_table[];
   const int32_t *table = stage_table<SUBST>(p, lds_table);
@@ -40,11 +41,11 @@ score_rows_kernel(const std::conditional_t<CROSS, SaScoreCrossParams, SaScorePar
   uint32_t qa = pair, tb = pair;   // descriptors of seq_a and seq_b
   uint64_t at = pair;              // where the result goes
   if constexpr (CROSS) {
-    if (pair >= sp.n_waves) return;   // wave-uniform, after the only barrier
-    const uint32_t ti = pair / sp.nq;
-    qa = sp.q_list[pair - ti * sp.nq];
-    tb = sp.t_order[ti];
-    at = (uint64_t)qa * sp.n_t + tb;
+    if (pair >= kp.n_waves) return;   // wave-uniform, after the only barrier
+    const uint32_t ti = pair / kp.nq;
+    qa = kp.q_list[pair - ti * kp.nq];
+    tb = kp.t_order[ti];
+    at = (uint64_t)qa * kp.n_t + tb;
   } else {
     if (pair >= p.n_pairs) return;   // wave-uniform, after the only barrier
   }
@@ -101,7 +102,7 @@ score_rows_kernel(const std::conditional_t<CROSS, SaScoreCrossParams, SaScorePar
   }
   if constexpr (CROSS) {
     if (lane == 0 && err != ~0ull) {
-      atomicMin(sp.err_pair, (unsigned long long)at);
+      atomicMin(kp.err_pair, (unsigned long long)at);
       atomicOr(sp.err_flag, 1u);
     }
   } else {
@@ -205,7 +206,7 @@ inline uint32_t one_wave_waves(const SaScoreCrossParams &p) { return p.n_waves; 
 template <int CPL, bool SW, bool CROSS, class P>
 static hipError_t launch_rows_cpl(const P &p, hipStream_t stream) {
   const dim3 grid((one_wave_waves(p) + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
-  launch_by_scoring(p.f, [&](auto subst, auto general, uint32_t table_ints) {
+  launch_by_scoring(sa_pair_params(p).f, [&](auto subst, auto general, uint32_t table_ints) {
     hipLaunchKernelGGL((score_rows_kernel<CPL, subst(), general(), SW, CROSS>), grid, block, table_ints * sizeof(int32_t), stream, p);
   });
   return hipGetLastError();

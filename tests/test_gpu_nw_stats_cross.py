@@ -3,6 +3,7 @@
 The three matrices equal nw_stats on the explicit Q x T batch (workloads.cross_batch), which test_gpu_nw_stats.py holds to the
 oracle; a sample of the pairs is checked against the oracle here as well."""
 import random
+import re
 
 import numpy as np
 import pytest
@@ -107,3 +108,31 @@ def test_unknown_pair_is_named_by_query_and_target(ctx):
         assert err.value.code == ref.value.code == S.E_UNKNOWN_PAIR
         assert named in str(err.value) and named in str(ref.value), (str(err.value), str(ref.value))
     got, _ = assert_equals_batch(ctx, W.seqset_from(queries), W.seqset_from(targets), hyb, "after the failures")
+
+
+def test_unknown_pair_across_tiles(ctx):
+    """test_gpu_sw_span_cross.py's sets: chunk_bytes = 1 MiB makes two target ranges.  X in query 8 fails (8, 0) in the first,
+    X in target 2 916 fails (3, 2 916) in the second: the lower pair, found in the later tile, is the one named -- as without
+    tiles."""
+    hyb = S.make_scoring({"preset": "DNA_hybridization"})
+    rng = W.Rng(75)
+    dna = lambda n: bytes(b"ACGT"[i] for i in rng.below(4, n))
+    queries = [b"", b"", b""] + [dna(40 + 13 * i) for i in range(12)]
+    queries[8] = queries[8][:3] + b"X" + queries[8][4:]
+    filler = W.random_set(3000, 76, 150, 250, b"ACGT")
+    targets = [dna(30 + 7 * j) for j in range(16)] + [filler.seq(j) for j in range(3000)]
+    targets[2916] = targets[2916][:100] + b"X" + targets[2916][101:]
+    q, t = W.seqset_from(queries), W.seqset_from(targets)
+
+    def named_pair(err):
+        m = re.search(r"query (\d+), target (\d+):", str(err.value))
+        assert err.value.code == S.E_UNKNOWN_PAIR and m, str(err.value)
+        return int(m.group(1)), int(m.group(2))
+
+    with pytest.raises(S.SeqAlignError) as err_one:
+        ctx.nw_stats_cross(q, t, hyb)
+    with ctx.options(chunk_bytes=MIB):
+        with pytest.raises(S.SeqAlignError) as err:
+            ctx.nw_stats_cross(q, t, hyb)
+        assert ctx.last_call()["score_cross"][0] >= 2
+    assert named_pair(err) == named_pair(err_one) == (3, 2916)

@@ -3,6 +3,7 @@
 The seven [n_queries][n_targets] matrices must be what sw_stats returns on the explicit Q x T batch (pos_a / len_a in the query),
 which tests/test_gpu_sw_stats.py holds to the oracle; the scores and spans are checked against the oracle here too."""
 import random
+import re
 
 import numpy as np
 import pytest
@@ -107,3 +108,57 @@ def test_empty_sets(ctx):
     some, none = W.seqset_from([b"ACGT", b"AC"]), W.seqset_from([])
     assert all(g.shape == (2, 0) for g in ctx.sw_stats_cross(some, none, sc))
     assert all(g.shape == (0, 2) for g in ctx.sw_stats_cross(none, some, sc))
+
+
+def named_pair(err):
+    m = re.search(r"query (\d+), target (\d+):", str(err.value))
+    assert err.value.code == S.E_UNKNOWN_PAIR and m, str(err.value)
+    return int(m.group(1)), int(m.group(2))
+
+
+def test_unknown_pair_is_named_by_query_and_target(ctx):
+    """DNA_hybridization scores no pair with 'X'.  The pair named is the lowest one that meets it, through the CROSS form (a
+    short query), through the strips on explicit pairs (the query of 600 letters) and for a target, and it is the pair
+    sw_span_cross names on the same sets."""
+    hyb = S.make_scoring({"preset": "DNA_hybridization"})
+    rng = random.Random(5)
+    queries = [rand_seq(rng, n, b"ACGT") for n in (80, 600, 120, 90)]
+    targets = [rand_seq(rng, 70, b"ACGT") for _ in range(20)]
+    for bad_q, bad_t, want in ((2, None, (2, 0)),      # a short query (the CROSS form): its first target
+                               (1, None, (1, 0)),      # a long one (the strips on explicit pairs)
+                               (None, 11, (0, 11)),    # a target: the first query meets it first
+                               (3, 11, (0, 11))):
+        qs, ts = list(queries), list(targets)
+        if bad_q is not None:
+            qs[bad_q] = qs[bad_q][:30] + b"X" + qs[bad_q][31:]
+        if bad_t is not None:
+            ts[bad_t] = ts[bad_t][:5] + b"X" + ts[bad_t][6:]
+        q, t = W.seqset_from(qs), W.seqset_from(ts)
+        with pytest.raises(S.SeqAlignError) as err:
+            ctx.sw_stats_cross(q, t, hyb)
+        with pytest.raises(S.SeqAlignError) as ref:
+            ctx.sw_span_cross(q, t, hyb)
+        assert named_pair(err) == named_pair(ref) == want, (str(err.value), str(ref.value))
+    check_cross(ctx, queries, targets, hyb, "after the failures")
+
+
+def test_unknown_pair_across_tiles(ctx):
+    """test_gpu_sw_span_cross.py's sets: chunk_bytes = 1 MiB makes two target ranges.  X in query 8 fails (8, 0) in the first,
+    X in target 2 916 fails (3, 2 916) in the second: the lower pair, found in the later tile, is the one named -- as without
+    tiles.  (Every sequence is far below SEQALIGN_SW_STATS_MAX_LEN.)"""
+    hyb = S.make_scoring({"preset": "DNA_hybridization"})
+    rng = W.Rng(75)
+    dna = lambda n: bytes(b"ACGT"[i] for i in rng.below(4, n))
+    queries = [b"", b"", b""] + [dna(40 + 13 * i) for i in range(12)]
+    queries[8] = queries[8][:3] + b"X" + queries[8][4:]
+    filler = W.random_set(3000, 76, 150, 250, b"ACGT")
+    targets = [dna(30 + 7 * j) for j in range(16)] + [filler.seq(j) for j in range(3000)]
+    targets[2916] = targets[2916][:100] + b"X" + targets[2916][101:]
+    q, t = W.seqset_from(queries), W.seqset_from(targets)
+    with pytest.raises(S.SeqAlignError) as err_one:
+        ctx.sw_stats_cross(q, t, hyb)
+    with ctx.options(chunk_bytes=MIB):
+        with pytest.raises(S.SeqAlignError) as err:
+            ctx.sw_stats_cross(q, t, hyb)
+        assert ctx.last_call()["score_cross"][0] >= 2
+    assert named_pair(err) == named_pair(err_one) == (3, 2916)
