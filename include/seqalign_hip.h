@@ -661,8 +661,8 @@ int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch
  * bytes, 28 bytes per pair and the error word come back.  Argument checks, scoring admission (SEQALIGN_E_DOMAIN) and
  * SEQALIGN_E_UNKNOWN_PAIR are seqalign_sw_span_batch's; SEQALIGN_E_TRACEBACK cannot occur.  The launches are recorded as
  * "score_rows" / "score_strips" (items: pairs).
- *   Not here: sequences over 65 535 letters (a four-word payload), a search form, banded forms, _cross_multi, _submit, the
- * command-line tools, gap-open counts. */
+ *   Not here: sequences over 65 535 letters (a four-word payload), a search form, _cross_multi, _submit, the
+ * command-line tools, gap-open counts.  The banded form is seqalign_sw_stats_banded below. */
 #define SEQALIGN_SW_STATS_MAX_LEN 65535u
 int seqalign_sw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                             uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
@@ -708,6 +708,42 @@ int seqalign_sw_span_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, 
  * one chunk, `repeats` launches between HIP events */
 int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                   const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
+/* ---- banded SW statistics: hit span and identity counts of the best local hit inside a band, no traceback ---- */
+/* seqalign_sw_stats_batch over the banded SW matrices: the seven integers of a BLAST-style tabular line per read at the cost
+ * of a banded sweep, nothing stored per cell and no walk.
+ *   Band and matrices are seqalign_sw_score_banded's ("banded SW" below), word for word: bounds anywhere in int32, clipped to
+ *   [-len_b, len_a]; every cell outside the band and every border cell holds 0 in all three matrices.
+ *   Per pair the fields of the hit seqalign_sw_align_banded(min_score = 1) delivers, and the counts of THAT hit's strings:
+ *   out_score, out_pos_a, out_pos_b, out_len_a, out_len_b   exactly seqalign_sw_span_banded's five;
+ *   out_matches, out_mismatches   counted as seqalign_sw_stats_batch counts them: the columns of the hit's strings that hold
+ *                      a letter of both sequences, split by whether the two letters are equal after the scoring's own case
+ *                      folding; substitution scores, wildcards and no_mismatches play no part.
+ *   All seven are 0 when no band cell is above 0, or when the band is empty after clipping.  With gap_extend > 0 the start may
+ *   lie one diagonal OUTSIDE the band, as seqalign_sw_span_banded's does: a cell outside the band is a stop that has counted
+ *   nothing.
+ * Refused before any device work, with a context that is never dereferenced, in this order:
+ *   1. SEQALIGN_E_ARG        a NULL argument (the timing hook: or repeats <= 0);
+ *   2. seqalign_sw_span_banded's checks of batch and band: SEQALIGN_E_ARG for an unreadable batch or diag_lo[p] > diag_hi[p]
+ *      (pair named); SEQALIGN_E_TOO_LARGE for a clipped width over SEQALIGN_SPAN_BAND_MAX_WIDTH (pair and width named) or
+ *      len_a + len_b >= 2^31 -- the lowest such pair;
+ *   3. SEQALIGN_E_TOO_LARGE  a sequence of more than SEQALIGN_SW_STATS_MAX_LEN letters, seqalign_sw_stats_batch's message
+ *      ("pair P: seq_a has N letters, SW statistics take at most 65535") -- the lowest such pair.
+ *   So a batch that is too wide in one pair and too long in another reports the width, whichever pair comes first.
+ * SEQALIGN_E_DOMAIN, SEQALIGN_E_UNKNOWN_PAIR (a character pair without a score INSIDE the band only) and the chunk rules are
+ * seqalign_sw_span_banded's; SEQALIGN_E_TRACEBACK cannot occur.  Device bytes per pair: len_a + len_b + 96 (the span call's 88
+ * and two result words); 28 bytes per pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band diagonals per
+ * lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted under band_score,
+ * one per width class of a chunk.
+ * Not in this call: banded NW statistics, widths over 512 and a _banded_wide form, cross, search, _multi, _submit, the
+ * command-line tools, gap-open counts. */
+int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                             const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
+                             uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
+                             uint32_t *out_matches, uint32_t *out_mismatches);
+/* Timing hook (tools/sw_stats_banded_bench.py), the sibling of seqalign_sw_span_band_time_ms for seqalign_sw_stats_banded:
+ * one chunk, `repeats` launches between HIP events; a batch that does not fit one chunk is SEQALIGN_E_ARG */
+int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                   const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
 /* ---- long pairs: alignments past the 2^31-cell cap --------------------------------- */
 /* The alignments of seqalign_nw_batch and of seqalign_sw_batch with max_hits = 1 -- same arguments, capacities and results,
  * byte for byte: score, both gapped strings and, SW, the hit's pos_a / pos_b / len_a / len_b / length -- for pairs of any

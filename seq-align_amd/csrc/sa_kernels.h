@@ -632,6 +632,18 @@ struct SaBandSpanParams {
 };
 /* every pair of the launch has width <= max_width <= SA_SPAN_BAND_MAX_WIDTH; max_width picks the columns per lane */
 hipError_t sa_launch_band_span(const SaBandSpanParams &p, uint32_t max_width, hipStream_t stream);
+/* ---- banded SW statistics (seqalign_sw_stats_banded, sa_band_stats.hip): the banded span sweep with SaSwStatsParams' payload,
+ * the stop cell in one word and matches | mismatches << 16 in the other.  Pair k of a launch has the band of SaBandSpanParams
+ * (1 <= width <= SA_SPAN_BAND_MAX_WIDTH) and at most SA_SW_STATS_MAX_LEN letters in either sequence (the caller's duty);
+ * b.score[k], pos_a[k], pos_b[k], len_a[k], len_b[k] are sa_launch_band_span's, matches[k] / mismatches[k] the columns of that
+ * hit's strings that hold two equal / two different letters (all 0 when no band cell is above 0); b.f.status / b.err_flag as
+ * above.  b.str_off, b.out_a, b.out_b and b.meta4 are unused. */
+struct SaBandSwStatsParams {
+  SaBandParams b;
+  uint32_t *pos_a, *pos_b, *len_a, *len_b, *matches, *mismatches;
+};
+/* recorded as "band_score"; max_width as sa_launch_band_span */
+hipError_t sa_launch_band_sw_stats(const SaBandSwStatsParams &p, uint32_t max_width, hipStream_t stream);
 /* ---- the wide banded calls (seqalign_*_banded_wide, sa_band_strips.hip): the same bands, matrices and layouts at any width,
  * one wave per (pair, strip of strip_cols columns) in the strips pipeline.  s (NW: s.b alone) is the narrow launch's record;
  * f.status must hold ~0 per pair before the launch (the strips atomicMin into it).  Pair k has max(1, ceil(len_a /

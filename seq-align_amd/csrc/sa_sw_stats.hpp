@@ -52,6 +52,8 @@ struct SwStatSweep {
   }
 
   // Row j.  f: the cell left of the strip on this row.  Leaves the last column's hand-off in `out` (lane 63's is the strip's).
+  // BAND (sa_band_stats.hip): ncol changes from row to row, so the running best takes a cell only while its column is in the band.
+  template <bool BAND = false>
   __device__ __forceinline__ void row(const SweepConsts &k, uint32_t j, uint32_t lb, uint32_t la, uint32_t W, int lane,
                                       uint32_t col0, int ncol, int code_b, const SpanFeed &f, SpanFeed &out) {
     int xd = wave_shr1(X[CPL - 1], boundX);
@@ -93,7 +95,7 @@ struct SwStatSweep {
       ac[c] = a > 0 ? (a_free ? Dc[c] : Vc[c]) : 0u;
       xd = X[c]; ds = Ds[c]; dc = Dc[c];
       mv[c] = m; av[c] = a;
-      const bool up = m > bs[c];   // strict: the first (lowest) row keeps a tie
+      const bool up = (!BAND || c < ncol) && m > bs[c];   // strict: the first (lowest) row keeps a tie
       bs[c] = up ? m : bs[c]; br[c] = up ? j : br[c]; bw0[c] = up ? ms[c] : bw0[c]; bw1[c] = up ? mc[c] : bw1[c];
     }
 

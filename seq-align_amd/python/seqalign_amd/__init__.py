@@ -778,6 +778,34 @@ class Context:
                                                    _ptr(ms)), "seqalign_sw_span_band_time_ms")
         return ms
 
+    # ---- banded SW statistics (seqalign_sw_stats_banded) -------------------------------
+    def sw_stats_banded(self, batch, scoring: Scoring, diag_lo, diag_hi):
+        """seqalign_sw_stats_banded: what sw_stats returns -- (score int32[n], pos_a, pos_b, len_a, len_b, matches, mismatches
+        uint32[n]) -- over the banded matrices of sw_score_banded: sw_span_banded's five and the counted columns of
+        sw_align_banded(min_score=1)'s strings.  Each bound an int or one per pair; clipped widths up to
+        SEQALIGN_SPAN_BAND_MAX_WIDTH (512), sequences up to SW_STATS_MAX_LEN letters (E_TOO_LARGE, the width first)."""
+        _score_args(batch, scoring)
+        lo, hi = _diag_args(batch, diag_lo, diag_hi)
+        n = batch.n_pairs
+        score = np.zeros(n, np.int32)
+        words = tuple(np.zeros(n, np.uint32) for _ in range(6))
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_stats_banded(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(score),
+                                              *(_ptr(w) for w in words)), "seqalign_sw_stats_banded")
+        return (score,) + words
+
+    def sw_stats_band_time_ms(self, batch, scoring: Scoring, diag_lo, diag_hi, repeats: int = 10) -> np.ndarray:
+        """seqalign_sw_stats_band_time_ms: kernel time (HIP events) of sw_stats_banded's launches, float32[repeats]."""
+        _score_args(batch, scoring)
+        lo, hi = _diag_args(batch, diag_lo, diag_hi)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "sw_stats_band_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_stats_band_time_ms(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), C.c_int(repeats),
+                                                    _ptr(ms)), "seqalign_sw_stats_band_time_ms")
+        return ms
+
     def sw_align_long(self, batch, scoring: Scoring, min_score):
         """seqalign_sw_align_long: what sw_batch(..., max_hits=1) returns -- per pair a list of at most one hit dict --
         for pairs of any size."""
@@ -1256,6 +1284,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_score_banded", "seqalign_nw_align_banded", "seqalign_band_score_time_ms", "seqalign_ctx_last_call_info_ext", "seqalign_kernel_kind_ext_name",
     "seqalign_sw_score_banded", "seqalign_sw_align_banded", "seqalign_sw_band_score_time_ms",
     "seqalign_sw_span_banded", "seqalign_sw_span_band_time_ms",
+    "seqalign_sw_stats_banded", "seqalign_sw_stats_band_time_ms",
     "seqalign_nw_score_banded_wide", "seqalign_nw_align_banded_wide", "seqalign_sw_score_banded_wide", "seqalign_sw_align_banded_wide",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",

@@ -2,7 +2,8 @@
 """Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, seqalign_sw_span_batch, *_score_cross,
 *_score_search, seqalign_sw_span_cross and seqalign_sw_span_search (against sw_span on the explicit batch), seqalign_nw_stats_batch
 (the columns of the oracle's strings) and seqalign_nw_stats_cross (against nw_stats on the explicit batch), seqalign_sw_stats_batch
-(the oracle's first hit and its counted strings) and seqalign_sw_stats_cross (against sw_stats on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+(the oracle's first hit and its counted strings) and seqalign_sw_stats_cross (against sw_stats on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded, seqalign_sw_stats_banded (the oracle's
+banded hit and its counted strings) and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -93,7 +94,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         import maglib as G      # only the scaled runs need it: the default run is what it was, imports included
     ctx = ctx or (None if dry else S.Context(0))
     t_end = time.time() + seconds
-    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0}
+    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0, "sw_stats_banded": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -334,6 +335,13 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
             if got != want:
                 fail("SW SPAN BANDED", spec, sub, lo, hi, got, want)
             n["span_banded"] += len(sub)
+            # ---- banded SW statistics on the same pairs and bounds: the oracle's banded hit and its counted strings
+            want = [tuple(w) + ST.count_columns(osc, h["a"].encode(), h["b"].encode()) if h else (0,) * 7 for w, h in zip(want, hits)]
+            res = ctx.sw_stats_banded(W.from_pairs(sub), sc, lo, hi)
+            got = [tuple(int(x[k]) for x in res) for k in range(len(sub))]
+            if got != want:
+                fail("SW STATS BANDED", spec, sub, lo, hi, got, want)
+            n["sw_stats_banded"] += len(sub)
 
         # ---- the wide banded calls: two small pairs (the narrow calls must agree) and one of 1 025 .. 1 624 columns whose band is
         # 700 .. 1 500 diagonals wide, under a random strip width
@@ -381,7 +389,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         print(f"fuzz_calls scale up to {scale}: {n['redraws']} factors redrawn in {n['redrawn_trials']} of {n['trials']} trials "
               f"({n['redrawn_trials'] / max(1, n['trials']):.1%} of the trials)", flush=True)
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
-          f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['stats']} NW and {n['sw_stats']} SW statistics, {n['stats_cross']} NW and {n['sw_stats_cross']} SW statistics cross cells, {n['long']} long alignments, {n['banded']} banded "
+          f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['sw_stats_banded']} banded SW statistics, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['stats']} NW and {n['sw_stats']} SW statistics, {n['stats_cross']} NW and {n['sw_stats_cross']} SW statistics cross cells, {n['long']} long alignments, {n['banded']} banded "
           f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results identical to the oracle "
           f"(seed {seed})", flush=True)
     return n
