@@ -629,8 +629,8 @@ int seqalign_sw_span_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
  * pair the missing score first).  Over whole matrices every pair keeps the alignment that puts all of seq_a and then all of
  * seq_b against gaps, whatever no_mismatches / no_gaps_in_a / no_gaps_in_b forbid, so within the admitted domain no pair
  * takes that path.  On an error the outputs are unspecified beyond the chunks already delivered.
- *   Not here: a search form, banded forms, _cross_multi, _submit, the command-line tools, gap-open counts.  SW statistics:
- * seqalign_sw_stats_batch below. */
+ *   Not here: a search form, a wide banded form, _cross_multi, _submit, the command-line tools, gap-open counts.  The banded
+ * form is seqalign_nw_stats_banded below.  SW statistics: seqalign_sw_stats_batch below. */
 int seqalign_nw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                             uint32_t *out_matches, uint32_t *out_mismatches);
 /* ... over several contexts (GPUs): contiguous ranges of nearly equal cells, results exactly the single-context call's */
@@ -734,7 +734,7 @@ int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  * and two result words); 28 bytes per pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band diagonals per
  * lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted under band_score,
  * one per width class of a chunk.
- * Not in this call: banded NW statistics, widths over 512 and a _banded_wide form, cross, search, _multi, _submit, the
+ * Not in this call (banded NW statistics: seqalign_nw_stats_banded below): widths over 512 and a _banded_wide form, cross, search, _multi, _submit, the
  * command-line tools, gap-open counts. */
 int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                              const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
@@ -744,6 +744,44 @@ int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
  * one chunk, `repeats` launches between HIP events; a batch that does not fit one chunk is SEQALIGN_E_ARG */
 int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                    const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
+/* ---- banded NW statistics: identity counts of the global alignment inside a band, no traceback ---- */
+/* seqalign_nw_stats_batch over the banded NW matrices: score, matches and mismatches of long similar pairs at the cost of a
+ * banded sweep, nothing stored per cell and no walk.
+ *   band[p] = w is seqalign_nw_score_banded's argument with the same geometry ("banded NW" below):
+ *       d_lo = max(-len_b, min(0, len_a - len_b) - w)      d_hi = min(len_a, max(0, len_a - len_b) + w)
+ *   and the matrices are its matrices: every cell outside the band holds the NW floor in all three.
+ *   out_score[p]   seqalign_nw_score_banded's value exactly.
+ *   A pair whose banded end value is at or above INT32_MIN / 2 has an alignment inside its band, the one
+ *   seqalign_nw_align_banded returns: out_matches[p] / out_mismatches[p] are the counts over THAT alignment's strings, split as
+ *   seqalign_nw_stats_batch splits them (letters compared after the scoring's own case folding; substitution scores and
+ *   wildcards play no part).  So when the unbanded alignment stays inside the band all three are seqalign_nw_stats_batch's.
+ *   A pair whose end value is below INT32_MIN / 2 has no alignment inside its band: SEQALIGN_E_TRACEBACK ("pair P: traceback
+ *   failed (no alignment inside the band)"), the lowest such pair named, ordered with SEQALIGN_E_UNKNOWN_PAIR as
+ *   seqalign_nw_stats_batch orders the two (the lowest failing pair's code).
+ *   This is decided by the VALUE, not by what seqalign_nw_align_banded does, and differs from it on one family of pairs: under
+ *   no_mismatches the align call's walker reads a blocked letter pair as score 0, floor + 0 == floor lets it step from a cell
+ *   at the floor to any other, cells outside the band included, and the walk can "succeed" with an end value at the floor.
+ *   Such strings are no alignment of the banded problem; this call returns SEQALIGN_E_TRACEBACK for those pairs.  The
+ *   reverse does not occur: no pair with an end value at or above INT32_MIN / 2 fails in the align call.
+ * Refused before any device work, with a context that is never dereferenced, in seqalign_nw_score_banded's order:
+ *   1. SEQALIGN_E_ARG        a NULL argument (the timing hook: or repeats <= 0);
+ *   2. SEQALIGN_E_ARG        an unreadable batch;
+ *   3. SEQALIGN_E_TOO_LARGE  len_a + len_b >= 2^31, or a width over SEQALIGN_SPAN_BAND_MAX_WIDTH = 512 diagonals ("pair P: a
+ *                            band of N diagonals, at most 512 are supported") -- the lowest such pair.
+ * No limit on the sequence lengths (the two counts are full words; SEQALIGN_SW_STATS_MAX_LEN plays no part) and no cell cap.
+ * SEQALIGN_E_DOMAIN and SEQALIGN_E_UNKNOWN_PAIR (a character pair without a score INSIDE the band only) are
+ * seqalign_nw_score_banded's.  Device bytes per pair: len_a + len_b + 72 (descriptors, status and three result words); chunks
+ * are cut within the option chunk_bytes; 12 bytes per pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band
+ * diagonals per lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted
+ * under band_score, one per width class of a chunk.
+ * Not in this call: widths over 512 and a _banded_wide form, cross, search, _multi, _submit, the command-line tools, gap-open
+ * counts. */
+int seqalign_nw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                             const uint32_t *band, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
+/* Timing hook (tools/nw_stats_banded_bench.py), the sibling of seqalign_band_score_time_ms for seqalign_nw_stats_banded:
+ * one chunk, `repeats` launches between HIP events; a batch that does not fit one chunk is SEQALIGN_E_ARG */
+int seqalign_nw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                   const uint32_t *band, int repeats, float *ms_each);
 /* ---- long pairs: alignments past the 2^31-cell cap --------------------------------- */
 /* The alignments of seqalign_nw_batch and of seqalign_sw_batch with max_hits = 1 -- same arguments, capacities and results,
  * byte for byte: score, both gapped strings and, SW, the hit's pos_a / pos_b / len_a / len_b / length -- for pairs of any

@@ -1,7 +1,8 @@
 // sa_batch_band.hip -- the banded calls over HOST batches: seqalign_nw_score_banded, seqalign_nw_align_banded and the timing
 // hook seqalign_band_score_time_ms; seqalign_sw_score_banded, seqalign_sw_align_banded and seqalign_sw_band_score_time_ms;
-// seqalign_sw_span_banded and seqalign_sw_span_band_time_ms; seqalign_sw_stats_banded and seqalign_sw_stats_band_time_ms (the
-// kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip; the contracts: include/seqalign_hip.h).
+// seqalign_sw_span_banded and seqalign_sw_span_band_time_ms; seqalign_sw_stats_banded and seqalign_sw_stats_band_time_ms;
+// seqalign_nw_stats_banded and seqalign_nw_stats_band_time_ms (the kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip,
+// sa_band_nw_stats.hip; the contracts: include/seqalign_hip.h).
 //
 // Everything that can be refused from lengths and bands alone is refused before any device work: the band of every pair is
 // clamped to its matrix and a width over SEQALIGN_BAND_MAX_WIDTH is SEQALIGN_E_TOO_LARGE.  Then, per chunk: the pairs are put
@@ -26,6 +27,11 @@
 // Banded SW statistics (seqalign_sw_stats_banded, seqalign_sw_stats_band_time_ms; kernel: sa_band_stats.hip) are the span
 // mode with two result words more (BandChunkRun::stats, finish_stats) and sw_stats' length limit checked after the band.
 //
+// Banded NW statistics (seqalign_nw_stats_banded, seqalign_nw_stats_band_time_ms; kernel: sa_band_nw_stats.hip) are the NW score
+// call's second mode (BandChunkRun::nw_stats): its band geometry with the span cap on the width, its chunk plan, width classes
+// and upload; three result words per pair instead of one, and a pair whose end value lies below INT32_MIN / 2 -- no alignment
+// inside its band -- is SEQALIGN_E_TRACEBACK (finish_nw_stats).
+//
 // The wide calls (seqalign_*_banded_wide; kernel: sa_band_strips.hip) run through the same plan with a strip width
 // (BandChunkRun::wide): no width check, the pipeline's scratch added to a pair's bytes, and per chunk ONE launch over all its
 // pairs instead of one per width class; the layouts, the walks and what comes home are the narrow calls'.
@@ -40,6 +46,7 @@ constexpr uint64_t kAlignPairBytes = 96;   // descriptors (48), status (8), the 
 constexpr uint64_t kSwScorePairBytes = 80;   // ... and end_a, end_b (8)
 constexpr uint64_t kSwSpanPairBytes = 88;    // ... and pos_a, pos_b, len_a, len_b in place of end_a, end_b (16)
 constexpr uint64_t kSwStatsPairBytes = 96;   // ... and matches, mismatches behind them (8)
+constexpr uint64_t kNwStatsPairBytes = 72;   // descriptors (48), status (8), score, matches, mismatches (12), slack
 constexpr uint64_t kSwAlignPairBytes = 128;  // descriptors (48), status (8), score and end cell (12), the walk's eight words (32), slack
 // a wide launch has (pairs rounded up to 8) x (the chunk's largest strip count) workgroups, most of which return at once when
 // one long pair sits among many short ones: a chunk is cut before that product passes this.  One pair alone stays below it
@@ -78,8 +85,9 @@ uint64_t wide_strips(uint32_t la, uint32_t cols) { return la ? ((uint64_t)la + c
 uint64_t wide_bytes(uint32_t la, uint32_t width, uint32_t cols) { return wide_strips(la, cols) * (8 * (uint64_t)width + 20) + 20; }
 
 uint64_t pair_bytes(uint32_t la, uint32_t lb, const Band &g, bool align, bool sw, uint32_t wide_cols, bool span = false,
-                    bool stats = false) {
+                    bool stats = false, bool nw_stats = false) {
   const uint64_t seq = (uint64_t)la + lb, cells = g.cells, wide = wide_cols ? wide_bytes(la, g.width, wide_cols) : 0;
+  if (nw_stats) return seq + kNwStatsPairBytes;
   if (stats) return seq + kSwStatsPairBytes;
   if (span) return seq + kSwSpanPairBytes;
   if (sw) return wide + (align ? 12 * cells + 3 * seq + kSwAlignPairBytes : seq + kSwScorePairBytes);
@@ -114,7 +122,8 @@ int too_long(uint64_t p) {
 }
 
 // argument checks and band geometry, before any device work
-int check_band_batch(const seqalign_batch_t *b, const uint32_t *band, std::vector<Band> &geom, bool wide = false) {
+int check_band_batch(const seqalign_batch_t *b, const uint32_t *band, std::vector<Band> &geom, bool wide = false,
+                     uint64_t max_width = SEQALIGN_BAND_MAX_WIDTH) {
   if (!batch_readable(b)) return SEQALIGN_E_ARG;
   geom.resize(b->n_pairs);
   for (uint64_t p = 0; p < b->n_pairs; ++p) {
@@ -122,7 +131,7 @@ int check_band_batch(const seqalign_batch_t *b, const uint32_t *band, std::vecto
     if ((uint64_t)la + lb >= ((uint64_t)1 << 31)) return too_long(p);
     uint64_t width = 0;
     geom[p] = band_of(la, lb, band[p], &width);
-    if (!wide && width > SEQALIGN_BAND_MAX_WIDTH) return too_wide(p, width);
+    if (!wide && width > max_width) return too_wide(p, width, max_width);
   }
   return SEQALIGN_OK;
 }
@@ -148,10 +157,10 @@ int check_sw_band_batch(const seqalign_batch_t *b, const int32_t *diag_lo, const
 
 // cut_chunks with the banded calls' bytes per pair, the band cells summed per chunk and the wide launch's grid capped
 int plan_band_chunks(const seqalign_batch_t *b, const std::vector<Band> &geom, bool align, bool sw, size_t budget, std::vector<ByteChunk> &out,
-                     uint32_t wide_cols = 0, bool span = false, bool stats = false) {
+                     uint32_t wide_cols = 0, bool span = false, bool stats = false, bool nw_stats = false) {
   return cut_chunks(b, budget, [&](uint64_t p) {
     const uint32_t la = b->len_a[p];
-    return PairNeed{pair_bytes(la, b->len_b[p], geom[p], align, sw, wide_cols, span, stats), geom[p].cells, wide_cols ? wide_strips(la, wide_cols) : 0};
+    return PairNeed{pair_bytes(la, b->len_b[p], geom[p], align, sw, wide_cols, span, stats, nw_stats), geom[p].cells, wide_cols ? wide_strips(la, wide_cols) : 0};
   }, out, true, kWideMaxBlocks);
 }
 
@@ -162,20 +171,21 @@ struct BandChunkRun {
   bool align = false, sw = false;
   bool span = false;                                    // banded SW hit spans: sw, not align, not wide
   bool stats = false;                                   // banded SW statistics: span, and two result words more
+  bool nw_stats = false;                                // banded NW statistics: not sw, not align, not wide
   // classes by band width; the descriptors behind the shared ones: mat_off, str_off (wide: slot_off, hand_off), width, d_lo
   ChunkStage<SA_SCORE_ROW_CLASSES> stage;
   uint64_t n = 0, seq_bytes = 0;
   uint32_t *d_res = nullptr;                            // [4] header (err_flag; wide: give-up word), then score[n]; SW: end_a[n], end_b[n] behind it
                                                         // (span: pos_a[n], pos_b[n], len_a[n], len_b[n]; stats: matches[n],
-                                                        // mismatches[n] behind those)
+                                                        // mismatches[n] behind those); nw_stats: matches[n], mismatches[n]
   uint64_t cells = 0;
   // the wide calls: columns per strip (0: the narrow calls), one launch per chunk over all its slots
   uint32_t wide = 0, strips_per_pair = 0;
   uint64_t slots = 0, hand_total = 0, busy_strips = 0;
 
   BandChunkRun(seqalign_ctx *c, const seqalign_dev_scoring *scoring, bool align_, bool sw_, uint32_t wide_cols, bool span_ = false,
-               bool stats_ = false)
-      : ctx(c), sc(scoring), align(align_), sw(sw_), span(span_), stats(stats_), wide(wide_cols) { stage.ctx = c; }
+               bool stats_ = false, bool nw_stats_ = false)
+      : ctx(c), sc(scoring), align(align_), sw(sw_), span(span_), stats(stats_), nw_stats(nw_stats_), wide(wide_cols) { stage.ctx = c; }
 
   // slot -> where its strings start in the chunk's string buffers: where its sequences do (a pair's strings are len_a + len_b
   // bytes at most); read from the pinned descriptors, which stay as laid out until the next chunk
@@ -199,7 +209,7 @@ struct BandChunkRun {
         busy_strips += wide_busy_strips(la, lb, geom[p], wide);
       }
     });
-    if (rc || (rc = ctx->best_score.reserve(16 + (stats ? 28 : span ? 20 : sw ? 12 : 4) * n))) return rc;
+    if (rc || (rc = ctx->best_score.reserve(16 + (stats ? 28 : span ? 20 : (sw || nw_stats) ? 12 : 4) * n))) return rc;
     if (align && ((rc = ctx->long_block.reserve(12 * cells + 64)) || (rc = ctx->t_out_a.reserve(seq_bytes + 16)) ||
                   (rc = ctx->t_out_b.reserve(seq_bytes + 16)) || (rc = ctx->t_meta.reserve((sw ? 32 : 16) * n))))
       return rc;
@@ -256,6 +266,14 @@ struct BandChunkRun {
     return p;
   }
 
+  // banded NW statistics: matches and mismatches behind the score
+  SaBandNwStatsParams nw_stats_params(uint64_t s0, uint64_t m) const {
+    SaBandNwStatsParams p;
+    p.b = params(s0, m);
+    p.matches = d_res + 4 + n + s0; p.mismatches = d_res + 4 + 2 * n + s0;
+    return p;
+  }
+
   // the wide calls: one launch over all slots of the chunk, strips_per_pair the chunk's maximum
   int launch_wide() {
     hipStream_t st = ctx->stream;
@@ -306,7 +324,9 @@ struct BandChunkRun {
       const uint64_t s0 = stage.cls_first[x], m = stage.class_size(x);
       if (!m) continue;
       hipError_t e;
-      if (stats) {
+      if (nw_stats) {
+        e = sa_launch_band_nw_stats(nw_stats_params(s0, m), stage.cls_max[x], st);
+      } else if (stats) {
         e = sa_launch_band_sw_stats(stats_params(s0, m), stage.cls_max[x], st);
       } else if (span) {
         e = sa_launch_band_span(span_params(s0, m), stage.cls_max[x], st);
@@ -367,6 +387,31 @@ struct BandChunkRun {
     HIP_TRY(stream_wait_spinning(ctx->stream));
     if (h[0]) return stage.fail_from_status();
     stage.scatter(h + 4, 7, out_score, out);
+    return SEQALIGN_OK;
+  }
+
+  // banded NW statistics: three fields per pair.  A pair whose end value lies below INT32_MIN / 2 has no alignment inside its
+  // band: SEQALIGN_E_TRACEBACK, decided by the value (include/seqalign_hip.h).  Between it and a pair without a score the
+  // lower pair's code is the call's, as in seqalign_nw_stats_batch
+  int finish_nw_stats(int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
+    int rc;
+    const size_t words = 4 + 3 * n;
+    if ((rc = ctx->h_misc.reserve(4 * words))) return rc;
+    uint32_t *h = ctx->h_misc.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(h, d_res, 4 * words, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(stream_wait_spinning(ctx->stream));
+    uint64_t unknown = ~0ull, no_walk = ~0ull;   // the chunk's lowest failing pairs, as batch indices
+    if (h[0] && (rc = stage.fail_from_status(&unknown)) != SEQALIGN_E_UNKNOWN_PAIR) return rc;
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
+    for (uint64_t s = 0; s < n; ++s)
+      if (hs[s] < INT32_MIN / 2) no_walk = std::min<uint64_t>(no_walk, stage.first + stage.order[s]);
+    if (no_walk < unknown) {
+      set_last_error("pair " + std::to_string(no_walk) + ": traceback failed (no alignment inside the band)");
+      return SEQALIGN_E_TRACEBACK;
+    }
+    if (h[0]) return SEQALIGN_E_UNKNOWN_PAIR;
+    uint32_t *const out[2] = {out_matches, out_mismatches};
+    stage.scatter(h + 4, 3, out_score, out);
     return SEQALIGN_OK;
   }
 
@@ -463,7 +508,7 @@ struct BandChunkRun {
 // A banded call behind its checks: every chunk prepared, launched and brought home by finish(run)
 template <class Finish>
 int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool align, bool sw,
-              bool wide, Finish finish, bool span = false, bool stats = false) {
+              bool wide, Finish finish, bool span = false, bool stats = false, bool nw_stats = false) {
   int rc;
   if (batch->n_pairs == 0) return SEQALIGN_OK;
   HIP_TRY(hipSetDevice(ctx->device));
@@ -472,18 +517,18 @@ int band_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   if ((rc = admit_batch(sc, batch, SA_FRAMES_BAND))) return rc;
   std::vector<ByteChunk> chunks;
   const uint32_t cols = wide ? wide_strip_cols(ctx, batch->n_pairs) : 0;
-  if ((rc = plan_band_chunks(batch, geom, align, sw, ctx->chunk_budget, chunks, cols, span, stats))) return rc;
+  if ((rc = plan_band_chunks(batch, geom, align, sw, ctx->chunk_budget, chunks, cols, span, stats, nw_stats))) return rc;
   StreamSyncOnExit sync(ctx->stream);
   for (const ByteChunk &c : chunks) {
-    BandChunkRun run(ctx, sc, align, sw, cols, span, stats);
+    BandChunkRun run(ctx, sc, align, sw, cols, span, stats, nw_stats);
     if ((rc = run.prepare(batch, geom, c)) || (rc = run.launch()) || (rc = finish(run))) return rc;
   }
   return SEQALIGN_OK;
 }
 
-// the score call's (span: the span call's, stats: the statistics call's) launches of one chunk, `repeats` times between HIP events
+// the score call's (span: the span call's, stats / nw_stats: the statistics calls') launches of one chunk, `repeats` times between HIP events
 int band_time(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const std::vector<Band> &geom, bool sw,
-              int repeats, float *ms_each, const char *name, bool span = false, bool stats = false) {
+              int repeats, float *ms_each, const char *name, bool span = false, bool stats = false, bool nw_stats = false) {
   int rc;
   if (batch->n_pairs == 0) return SEQALIGN_E_ARG;
   CallScope scope(ctx);
@@ -492,10 +537,10 @@ int band_time(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   if ((rc = cached_scoring(ctx, scoring, sw ? 1 : 0, &sc))) return rc;
   if ((rc = admit_batch(sc, batch, SA_FRAMES_BAND))) return rc;
   std::vector<ByteChunk> chunks;
-  if ((rc = plan_band_chunks(batch, geom, false, sw, ctx->chunk_budget, chunks, 0, span, stats))) return rc;
+  if ((rc = plan_band_chunks(batch, geom, false, sw, ctx->chunk_budget, chunks, 0, span, stats, nw_stats))) return rc;
   if (chunks.size() != 1) { set_last_error(std::string(name) + ": the batch does not fit one chunk"); return SEQALIGN_E_ARG; }
   StreamSyncOnExit sync(ctx->stream);
-  BandChunkRun run(ctx, sc, false, sw, 0, span, stats);
+  BandChunkRun run(ctx, sc, false, sw, 0, span, stats, nw_stats);
   if ((rc = run.prepare(batch, geom, chunks[0]))) return rc;
   return time_launches(ctx->stream, repeats, ms_each, [&] { return run.launch(); });
 }
@@ -655,6 +700,27 @@ extern "C" int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalig
   int rc = check_sw_stats_band_batch(batch, diag_lo, diag_hi, geom);
   if (rc) return rc;
   return band_time(ctx, batch, scoring, geom, true, repeats, ms_each, "seqalign_sw_stats_band_time_ms", true, true);
+}
+
+// banded NW statistics: seqalign_nw_score_banded's checks in its order, with the span cap on the width
+extern "C" int seqalign_nw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                        const uint32_t *band, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
+  if (!ctx || !batch || !scoring || !band || !out_score || !out_matches || !out_mismatches) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom, false, SEQALIGN_SPAN_BAND_MAX_WIDTH);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  return band_call(ctx, batch, scoring, geom, false, false, false,
+                   [&](BandChunkRun &run) { return run.finish_nw_stats(out_score, out_matches, out_mismatches); }, false, false, true);
+}
+
+extern "C" int seqalign_nw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                              const uint32_t *band, int repeats, float *ms_each) {
+  if (!ctx || !batch || !scoring || !band || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch(batch, band, geom, false, SEQALIGN_SPAN_BAND_MAX_WIDTH);
+  if (rc) return rc;
+  return band_time(ctx, batch, scoring, geom, false, repeats, ms_each, "seqalign_nw_stats_band_time_ms", false, false, true);
 }
 
 extern "C" int seqalign_sw_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,

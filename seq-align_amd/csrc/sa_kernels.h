@@ -644,6 +644,17 @@ struct SaBandSwStatsParams {
 };
 /* recorded as "band_score"; max_width as sa_launch_band_span */
 hipError_t sa_launch_band_sw_stats(const SaBandSwStatsParams &p, uint32_t max_width, hipStream_t stream);
+/* ---- banded NW statistics (seqalign_nw_stats_banded, sa_band_nw_stats.hip): SaStatsParams' payload through the NW band frame.
+ * Pair k of a launch has the band of sa_launch_band_score (d_lo <= 0 <= d_hi, 1 <= width <= SA_SPAN_BAND_MAX_WIDTH) and any
+ * length; b.score[k] is sa_launch_band_score's value, matches[k] / mismatches[k] the counts of the alignment inside the band
+ * that ends in the end pick's state, bit 31 of mismatches[k] (SA_STATS_NO_WALK) = that state has no walk; b.f.status /
+ * b.err_flag as above.  b.str_off, b.out_a, b.out_b and b.meta4 are unused. */
+struct SaBandNwStatsParams {
+  SaBandParams b;
+  uint32_t *matches, *mismatches;
+};
+/* every pair of the launch has width <= max_width <= SA_SPAN_BAND_MAX_WIDTH; max_width picks the columns per lane */
+hipError_t sa_launch_band_nw_stats(const SaBandNwStatsParams &p, uint32_t max_width, hipStream_t stream);
 /* ---- the wide banded calls (seqalign_*_banded_wide, sa_band_strips.hip): the same bands, matrices and layouts at any width,
  * one wave per (pair, strip of strip_cols columns) in the strips pipeline.  s (NW: s.b alone) is the narrow launch's record;
  * f.status must hold ~0 per pair before the launch (the strips atomicMin into it).  Pair k has max(1, ceil(len_a /

@@ -806,6 +806,33 @@ class Context:
                                                     _ptr(ms)), "seqalign_sw_stats_band_time_ms")
         return ms
 
+    # ---- banded NW statistics (seqalign_nw_stats_banded) -------------------------------
+    def nw_stats_banded(self, batch, scoring: Scoring, band):
+        """seqalign_nw_stats_banded: what nw_stats returns -- (score int32[n], matches uint32[n], mismatches uint32[n]) -- over
+        the banded matrices of nw_score_banded: its score and the counted columns of nw_align_banded's strings.  band: an int
+        or one per pair; widths up to SEQALIGN_SPAN_BAND_MAX_WIDTH (512), sequences of any length.  A pair whose banded end
+        value is below INT32_MIN / 2 has no alignment inside its band and raises SeqAlignError(E_TRACEBACK)."""
+        _score_args(batch, scoring)
+        bw = _band_arg(batch, band)
+        n = batch.n_pairs
+        score, matches, mismatches = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_stats_banded(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(score), _ptr(matches),
+                                              _ptr(mismatches)), "seqalign_nw_stats_banded")
+        return score, matches, mismatches
+
+    def nw_stats_band_time_ms(self, batch, scoring: Scoring, band, repeats: int = 10) -> np.ndarray:
+        """seqalign_nw_stats_band_time_ms: kernel time (HIP events) of nw_stats_banded's launches, float32[repeats]."""
+        _score_args(batch, scoring)
+        bw = _band_arg(batch, band)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "nw_stats_band_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_stats_band_time_ms(self._h, C.byref(d), C.byref(scoring), _ptr(bw), C.c_int(repeats), _ptr(ms)),
+               "seqalign_nw_stats_band_time_ms")
+        return ms
+
     def sw_align_long(self, batch, scoring: Scoring, min_score):
         """seqalign_sw_align_long: what sw_batch(..., max_hits=1) returns -- per pair a list of at most one hit dict --
         for pairs of any size."""
@@ -1285,6 +1312,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_sw_score_banded", "seqalign_sw_align_banded", "seqalign_sw_band_score_time_ms",
     "seqalign_sw_span_banded", "seqalign_sw_span_band_time_ms",
     "seqalign_sw_stats_banded", "seqalign_sw_stats_band_time_ms",
+    "seqalign_nw_stats_banded", "seqalign_nw_stats_band_time_ms",
     "seqalign_nw_score_banded_wide", "seqalign_nw_align_banded_wide", "seqalign_sw_score_banded_wide", "seqalign_sw_align_banded_wide",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
