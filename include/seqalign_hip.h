@@ -734,8 +734,8 @@ int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  * and two result words); 28 bytes per pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band diagonals per
  * lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted under band_score,
  * one per width class of a chunk.
- * Not in this call (banded NW statistics: seqalign_nw_stats_banded below): widths over 512 and a _banded_wide form, cross, search, _multi, _submit, the
- * command-line tools, gap-open counts. */
+ * Not in this call (banded NW statistics: seqalign_nw_stats_banded and seqalign_nw_stats_banded_wide below): widths over 512
+ * and a _banded_wide form, cross, search, _multi, _submit, the command-line tools, gap-open counts. */
 int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                              const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
                              uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
@@ -774,8 +774,8 @@ int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *
  * are cut within the option chunk_bytes; 12 bytes per pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band
  * diagonals per lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted
  * under band_score, one per width class of a chunk.
- * Not in this call: widths over 512 and a _banded_wide form, cross, search, _multi, _submit, the command-line tools, gap-open
- * counts. */
+ * Widths over 512: seqalign_nw_stats_banded_wide ("wide banded calls" below).
+ * Not in this call: cross, search, _multi, _submit, the command-line tools, gap-open counts. */
 int seqalign_nw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                              const uint32_t *band, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
 /* Timing hook (tools/nw_stats_banded_bench.py), the sibling of seqalign_band_score_time_ms for seqalign_nw_stats_banded:
@@ -882,7 +882,7 @@ int seqalign_sw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
 /* Timing hook (tools/align_banded_sw_bench.py), the sibling of seqalign_band_score_time_ms for seqalign_sw_score_banded */
 int seqalign_sw_band_score_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                    const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
-/* ---- wide banded calls: the four banded calls at any band width ---------------------- */
+/* ---- wide banded calls: banded calls at any band width ------------------------------ */
 /* The banded calls above hold a pair's whole band in one wave and stop at SEQALIGN_BAND_MAX_WIDTH diagonals.  These four take
  * the argument lists of their siblings unchanged and accept ANY width: a pair's band is cut into strips of columns, one
  * wave per strip, the waves of a pair working as a pipeline that hands a strip's last column on to the strip on its right
@@ -920,6 +920,21 @@ int seqalign_sw_score_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *b
 int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                   const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score, seqalign_sw_hit_t *hits,
                                   uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b, uint64_t str_cap);
+/* The wide form of seqalign_nw_stats_banded: its argument list and contract word for word -- the band, seqalign_nw_score_banded's
+ * score, the counts over the strings seqalign_nw_align_banded(_wide) returns, the case folding, SEQALIGN_E_TRACEBACK by the value
+ * rule and its order with SEQALIGN_E_UNKNOWN_PAIR, no limit on the lengths -- under the wide calls' width rule above: any width,
+ * SEQALIGN_E_TOO_LARGE for len_a + len_b >= 2^31 only, SEQALIGN_E_NOMEM and SEQALIGN_E_HIP as above, and for every batch the
+ * narrow call accepts the same bytes, the same status and the same pair named.  The refusals before the context is touched are
+ * seqalign_nw_score_banded_wide's, in its order.  A hand-off entry carries the two values, whose the first is and their two
+ * payloads, 32 bytes, so the device bytes per pair are
+ *     len_a + len_b + 72 + strips (32 width + 20) + 20,      strips = max(1, ceil(len_a / S)).
+ * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
+ * strip) waves.  Kernel: sa_band_nw_stats_strips.hip.  One pair of 100 000 letters at 511 diagonals runs on
+ * many waves here and on one in the narrow call; for many short pairs within 512 diagonals the narrow call is the faster one.
+ * No SW form (the best cell and its words across strips, and the 65 535 limit), no cross, search, _multi, _submit, timing-hook
+ * or command-line form. */
+int seqalign_nw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const uint32_t *band, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

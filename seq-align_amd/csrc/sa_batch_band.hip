@@ -1,6 +1,6 @@
-// sa_batch_band.hip -- the banded calls over HOST batches: the fifteen seqalign_*_banded, *_banded_wide and *_band_time_ms entry
+// sa_batch_band.hip -- the banded calls over HOST batches: the sixteen seqalign_*_banded, *_banded_wide and *_band_time_ms entry
 // points (the contracts: include/seqalign_hip.h; the kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip,
-// sa_band_nw_stats.hip, sa_band_strips.hip).  DESIGN.md 3.23b.
+// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip).  DESIGN.md 3.23b.
 //
 // One driver, seven modes.  A mode is a traits struct (below): NW or SW, score family or align, its result words and fixed
 // bytes per pair, its cap on the width, its kernels' parameter block and launches.  The driver is the same for all of them:
@@ -19,7 +19,7 @@
 //            reach min_score are delivered in pair order under seqalign_sw_align_long's capacity rule (finish_sw_align).
 // The cut, the staging of a chunk, the lowest failing pair and the timing loop are sa_chunks.hpp's.
 //
-// The wide calls (the first four modes) run through the same plan with a strip width (BandChunkRun::wide, a runtime value):
+// The wide calls (the first four modes and the last) run through the same plan with a strip width (BandChunkRun::wide, a runtime value):
 // no width check, the pipeline's scratch added to a pair's bytes, and per chunk ONE launch over all its pairs instead of one
 // per width class; the layouts, the walks and what comes home are the narrow calls'.
 #include "sa_chunks.hpp"
@@ -34,24 +34,48 @@ namespace {
 // Params with base() (its SaBandParams), set_results() (the arrays behind the score, res = the score's, n words each) and
 // launch() (one width class; recorded as band_score or band_fill).  The score family besides: kFloorIsNoWalk (a score below
 // INT32_MIN / 2 is SEQALIGN_E_TRACEBACK).  The align modes: the walk's record per pair in words, where its status sits, what
-// their message adds to "traceback failed", set_meta() and walk().  The modes with a wide form: strips(), their block as
-// sa_launch_band_strips takes it.
+// their message adds to "traceback failed", set_meta() and walk().  The modes with a wide form: kHandoffBytes (per entry of a
+// strip's hand-off column) and launch_strips() (one launch over a chunk's strips, laid out as StripsLayout says).
+
+// where a wide launch finds its pipeline's words (BandChunkRun::launch_wide): the fields of SaBandStripsParams behind s
+struct StripsLayout {
+  uint32_t strips_per_pair;
+  const uint64_t *slot_off, *hand_off;
+  uint32_t *progress, *ticket, *front, *strip_best, *give_up;
+  int32_t *handoff;
+};
+
+// the four score and align modes: band_strips_kernel (sa_band_strips.hip), 8 bytes per hand-off entry
+hipError_t launch_score_strips(const SaBandSwParams &s, const StripsLayout &l, uint32_t cols, bool fill, bool is_sw, uint64_t items, hipStream_t st) {
+  SaBandStripsParams w;
+  memset(&w, 0, sizeof(w));
+  w.s = s;
+  w.strips_per_pair = l.strips_per_pair;
+  w.slot_off = l.slot_off; w.hand_off = l.hand_off;
+  w.progress = l.progress; w.ticket = l.ticket; w.front = l.front; w.strip_best = l.strip_best; w.give_up = l.give_up;
+  w.handoff = l.handoff;
+  return sa_launch_band_strips(w, cols, fill, is_sw, items, st);
+}
+
 struct NwScoreBand {   // seqalign_nw_score_banded(_wide), seqalign_band_score_time_ms
   using Params = SaBandParams;
   static constexpr bool kSw = false, kAlign = false, kWideForm = true, kFloorIsNoWalk = false;
   static constexpr int kFields = 1;             // score
-  static constexpr uint64_t kPairBytes = 64, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH;
+  static constexpr uint64_t kPairBytes = 64, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8;
   static SaBandParams &base(Params &p) { return p; }
   static void set_results(Params &, uint32_t *, uint64_t) {}
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_score(p, max_width, st); }
-  static SaBandSwParams strips(const Params &p) { SaBandSwParams s{}; s.b = p; return s; }
+  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    SaBandSwParams s{}; s.b = p;
+    return launch_score_strips(s, l, cols, kAlign, kSw, items, st);
+  }
 };
 
 struct NwAlignBand {   // seqalign_nw_align_banded(_wide)
   using Params = SaBandParams;
   static constexpr bool kSw = false, kAlign = true, kWideForm = true;
   static constexpr int kFields = 1;
-  static constexpr uint64_t kPairBytes = 96, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH;   // the walk's four words (16)
+  static constexpr uint64_t kPairBytes = 96, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8;   // the walk's four words (16)
   static constexpr int kMetaWords = 4, kMetaStatus = 3;   // head, length, score, status
   static constexpr const char *kNoWalkText = " (no alignment inside the band)";
   static SaBandParams &base(Params &p) { return p; }
@@ -59,25 +83,30 @@ struct NwAlignBand {   // seqalign_nw_align_banded(_wide)
   static void set_meta(Params &p, uint32_t *meta, uint64_t s0) { p.meta4 = meta + 4 * s0; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_fill(p, max_width, st); }
   static hipError_t walk(const Params &p, hipStream_t st) { return sa_launch_band_walk(p, st); }
-  static SaBandSwParams strips(const Params &p) { SaBandSwParams s{}; s.b = p; return s; }
+  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    SaBandSwParams s{}; s.b = p;
+    return launch_score_strips(s, l, cols, kAlign, kSw, items, st);
+  }
 };
 
 struct SwScoreBand {   // seqalign_sw_score_banded(_wide), seqalign_sw_band_score_time_ms
   using Params = SaBandSwParams;
   static constexpr bool kSw = true, kAlign = false, kWideForm = true, kFloorIsNoWalk = false;
   static constexpr int kFields = 3;             // score, end_a, end_b
-  static constexpr uint64_t kPairBytes = 80, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH;
+  static constexpr uint64_t kPairBytes = 80, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8;
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) { p.end_a = res + n; p.end_b = res + 2 * n; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_score(p, max_width, st); }
-  static SaBandSwParams strips(const Params &p) { return p; }
+  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    return launch_score_strips(p, l, cols, kAlign, kSw, items, st);
+  }
 };
 
 struct SwAlignBand {   // seqalign_sw_align_banded(_wide)
   using Params = SaBandSwParams;
   static constexpr bool kSw = true, kAlign = true, kWideForm = true;
   static constexpr int kFields = 3;             // the fill's best cell: score, end_a, end_b
-  static constexpr uint64_t kPairBytes = 128, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH;   // the walk's eight words (32)
+  static constexpr uint64_t kPairBytes = 128, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8;   // the walk's eight words (32)
   static constexpr int kMetaWords = 8, kMetaStatus = 1;   // score, status, pos_a, pos_b, end_a, end_b, length, head
   static constexpr const char *kNoWalkText = "";
   static SaBandParams &base(Params &p) { return p.b; }
@@ -85,7 +114,9 @@ struct SwAlignBand {   // seqalign_sw_align_banded(_wide)
   static void set_meta(Params &p, uint32_t *meta, uint64_t s0) { p.meta8 = meta + 8 * s0; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_fill(p, max_width, st); }
   static hipError_t walk(const Params &p, hipStream_t st) { return sa_launch_band_sw_walk(p, st); }
-  static SaBandSwParams strips(const Params &p) { return p; }
+  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    return launch_score_strips(p, l, cols, kAlign, kSw, items, st);
+  }
 };
 
 struct SwSpanBand {   // seqalign_sw_span_banded, seqalign_sw_span_band_time_ms (sa_band_span.hip)
@@ -113,15 +144,26 @@ struct SwStatsBand {   // seqalign_sw_stats_banded, seqalign_sw_stats_band_time_
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_stats(p, max_width, st); }
 };
 
-struct NwStatsBand {   // seqalign_nw_stats_banded, seqalign_nw_stats_band_time_ms (sa_band_nw_stats.hip)
+struct NwStatsBand {   // seqalign_nw_stats_banded(_wide), seqalign_nw_stats_band_time_ms (sa_band_nw_stats.hip, sa_band_nw_stats_strips.hip)
   using Params = SaBandNwStatsParams;
-  static constexpr bool kSw = false, kAlign = false, kWideForm = false;
+  static constexpr bool kSw = false, kAlign = false, kWideForm = true;
   static constexpr bool kFloorIsNoWalk = true;  // no alignment inside the band, decided by the value (include/seqalign_hip.h)
   static constexpr int kFields = 3;             // score, matches, mismatches
   static constexpr uint64_t kPairBytes = 72, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
+  static constexpr uint64_t kHandoffBytes = SA_BAND_STATS_HANDOFF_BYTES;   // the two values, whose the first is, their payloads
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) { p.matches = res + n; p.mismatches = res + 2 * n; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_nw_stats(p, max_width, st); }
+  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    SaBandNwStatsStripsParams w;
+    memset(&w, 0, sizeof(w));
+    w.s = p;
+    w.strips_per_pair = l.strips_per_pair;
+    w.slot_off = l.slot_off; w.hand_off = l.hand_off;
+    w.progress = l.progress; w.ticket = l.ticket; w.front = l.front; w.give_up = l.give_up;
+    w.handoff = l.handoff;
+    return sa_launch_band_nw_stats_strips(w, cols, items, st);
+  }
 };
 
 // a wide launch has (pairs rounded up to 8) x (the chunk's largest strip count) workgroups, most of which return at once when
@@ -200,10 +242,12 @@ int check_sw_stats_band_batch(const seqalign_batch_t *batch, const int32_t *diag
 }
 
 // ---- the wide calls: a pair's strips of `cols` columns, and what they add to its bytes -- per strip a hand-off column of
-// `width` entries of 8 bytes, a progress word (4) and a best-cell entry (16), and per pair two more descriptors (16) and a
-// front word (4)
+// `width` entries of the mode's bytes (8; the statistics: 32), a progress word (4) and a best-cell entry (16), and per pair two
+// more descriptors (16) and a front word (4)
 uint64_t wide_strips(uint32_t la, uint32_t cols) { return la ? ((uint64_t)la + cols - 1) / cols : 1; }
-uint64_t wide_bytes(uint32_t la, uint32_t width, uint32_t cols) { return wide_strips(la, cols) * (8 * (uint64_t)width + 20) + 20; }
+uint64_t wide_bytes(uint32_t la, uint32_t width, uint32_t cols, uint64_t entry_bytes) {
+  return wide_strips(la, cols) * (entry_bytes * (uint64_t)width + 20) + 20;
+}
 
 // the (pair, strip) waves of a wide launch that sweep at least one row: the strips that hold one of the pair's columns with
 // an inner band cell, max(1, 1 + d_lo) .. min(len_a, len_b + d_hi)
@@ -224,9 +268,15 @@ uint32_t wide_strip_cols(const seqalign_ctx *ctx, uint64_t n_pairs) {
 // a pair's device bytes in mode M: the sequences (an align mode: the strings besides, and the band's cells), the mode's fixed
 // bytes, the strips' scratch of a wide call
 template <class M>
+constexpr uint64_t handoff_entry_bytes() {
+  if constexpr (M::kWideForm) return M::kHandoffBytes;
+  else return 0;
+}
+
+template <class M>
 uint64_t pair_bytes(uint32_t la, uint32_t lb, const Band &g, uint32_t wide_cols) {
   const uint64_t seq = (uint64_t)la + lb;
-  return (wide_cols ? wide_bytes(la, g.width, wide_cols) : 0) + (M::kAlign ? 12 * g.cells + 3 * seq : seq) + M::kPairBytes;
+  return (wide_cols ? wide_bytes(la, g.width, wide_cols, handoff_entry_bytes<M>()) : 0) + (M::kAlign ? 12 * g.cells + 3 * seq : seq) + M::kPairBytes;
 }
 
 // ---- One chunk of a call in mode M laid out and uploaded; launch() enqueues its kernels on ctx->stream
@@ -276,7 +326,7 @@ struct BandChunkRun {
         return rc;
     // wide: progress words, the ticket counter and the pairs' front words behind them, then (16-byte aligned) the best-cell
     // entries; the hand-off columns
-    if (wide && ((rc = ctx->strip_progress.reserve(4 * (slots + n + 8) + 16 * slots + 16)) || (rc = ctx->score_handoff.reserve(8 * hand_total + 16))))
+    if (wide && ((rc = ctx->strip_progress.reserve(4 * (slots + n + 8) + 16 * slots + 16)) || (rc = ctx->score_handoff.reserve(handoff_entry_bytes<M>() * hand_total + 16))))
       return rc;
     d_res = ctx->best_score.as<uint32_t>();
     return stage.upload();
@@ -306,9 +356,7 @@ struct BandChunkRun {
   int launch_wide() {
     if constexpr (M::kWideForm) {
       hipStream_t st = ctx->stream;
-      SaBandStripsParams w;
-      memset(&w, 0, sizeof(w));
-      w.s = M::strips(params(0, n));
+      StripsLayout w{};
       w.strips_per_pair = strips_per_pair;
       w.slot_off = stage.d_u64(2); w.hand_off = stage.d_u64(3);
       w.progress = ctx->strip_progress.as<uint32_t>();
@@ -319,7 +367,7 @@ struct BandChunkRun {
       w.handoff = ctx->score_handoff.as<int32_t>();
       HIP_TRY(hipMemsetAsync(w.progress, 0, 4 * (slots + 1 + n), st));
       HIP_TRY(hipMemsetAsync(ctx->status.p, 0xFF, 8 * n, st));
-      const hipError_t e = sa_launch_band_strips(w, wide, M::kAlign, M::kSw, busy_strips, st);
+      const hipError_t e = M::launch_strips(params(0, n), w, wide, busy_strips, st);
       if (e != hipSuccess) return fail_hip(e, "band strips kernel launch");
     }
     return SEQALIGN_OK;
@@ -679,16 +727,28 @@ extern "C" int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalig
   return band_time<SwStatsBand>(ctx, batch, scoring, geom, repeats, ms_each, "seqalign_sw_stats_band_time_ms");
 }
 
-// banded NW statistics: seqalign_nw_score_banded's checks in its order, with the span cap on the width
-extern "C" int seqalign_nw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
-                                        const uint32_t *band, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
+// banded NW statistics: seqalign_nw_score_banded's checks in its order, with the span cap on the width; the wide form: without
+// it (kernel: sa_band_nw_stats_strips.hip)
+static int nw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const uint32_t *band,
+                           int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches, bool wide) {
   if (!ctx || !batch || !scoring || !band || !out_score || !out_matches || !out_mismatches) return SEQALIGN_E_ARG;
   std::vector<Band> geom;
-  int rc = check_band_batch<NwStatsBand>(batch, NwBands{band}, geom);
+  int rc = check_band_batch<NwStatsBand>(batch, NwBands{band}, geom, wide);
   if (rc) return rc;
   CallScope scope(ctx);
   uint32_t *const out[2] = {out_matches, out_mismatches};
-  return band_call<NwStatsBand>(ctx, batch, scoring, geom, false, [&](auto &run) { return run.finish_words(out_score, out); });
+  return band_call<NwStatsBand>(ctx, batch, scoring, geom, wide, [&](auto &run) { return run.finish_words(out_score, out); });
+}
+
+extern "C" int seqalign_nw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                        const uint32_t *band, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches) {
+  return nw_stats_banded(ctx, batch, scoring, band, out_score, out_matches, out_mismatches, false);
+}
+
+extern "C" int seqalign_nw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const uint32_t *band, int32_t *out_score, uint32_t *out_matches,
+                                             uint32_t *out_mismatches) {
+  return nw_stats_banded(ctx, batch, scoring, band, out_score, out_matches, out_mismatches, true);
 }
 
 extern "C" int seqalign_nw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,

@@ -672,6 +672,21 @@ struct SaBandStripsParams {
 };
 /* strip_cols: 64 | 128 | 256 | 512; items: what the launch record counts (the (pair, strip) waves that sweep a row) */
 hipError_t sa_launch_band_strips(const SaBandStripsParams &p, uint32_t strip_cols, bool fill, bool is_sw, uint64_t items, hipStream_t stream);
+/* ---- wide banded NW statistics (seqalign_nw_stats_banded_wide, sa_band_nw_stats_strips.hip): sa_launch_band_nw_stats' results
+ * at any width through the strips pipeline of sa_launch_band_strips.  The fields behind s are SaBandStripsParams' and are
+ * prepared the same way (f.status ~0, progress / ticket / front / give_up zero), but for the hand-off: per strip `width` entries
+ * of SA_BAND_STATS_HANDOFF_BYTES -- {max(M, A), B, whether max(M, A) is an admitted A's, 0} {their payloads} of the strip's
+ * last column -- from entry hand_off[k] + t width of handoff (16-byte aligned).  There is no best cell.  Recorded as
+ * "band_score" with `items`. */
+#define SA_BAND_STATS_HANDOFF_BYTES 32u
+struct SaBandNwStatsStripsParams {
+  SaBandNwStatsParams s;
+  uint32_t strips_per_pair;
+  const uint64_t *slot_off, *hand_off;
+  uint32_t *progress, *ticket, *front, *give_up;
+  int32_t *handoff;
+};
+hipError_t sa_launch_band_nw_stats_strips(const SaBandNwStatsStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 /* the second launch record (seqalign_ctx_last_call_info_ext: SEQALIGN_KX_*) */
 void sa_record_launch_ext(int kind, uint64_t items);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */

@@ -48,8 +48,11 @@ struct StatSweep {
   }
 
   // Row j.  f: the cell left of the strip on this row.  Leaves the last column's hand-off in `out` (lane 63's is the strip's).
+  // PICK (sa_band_nw_stats_strips.hip, where the strip's last column moves through the frame): `out` is column `pick` of the
+  // lane instead of its last.
+  template <bool PICK = false>
   __device__ __forceinline__ void row(const SweepConsts &k, uint32_t j, uint32_t lb, uint32_t la, uint32_t W, int lane,
-                                      uint32_t col0, int ncol, int code_b, const StatFeed &f, StatFeed &out) {
+                                      uint32_t col0, int ncol, int code_b, const StatFeed &f, StatFeed &out, int pick = CPL - 1) {
     bool free_row = false, forced = false;   // wave-uniform: gap_b of this row costs nothing / is not admitted
     if constexpr (GENERAL) {
       const bool last_row = (j == lb);
@@ -156,10 +159,21 @@ struct StatSweep {
       if constexpr (GENERAL) Y[c] = mb;
       Ap[c] = av[c];
     }
-    const bool o_a = a_adm[CPL - 1] && av[CPL - 1] >= mv[CPL - 1];
-    out.z = max(mv[CPL - 1], av[CPL - 1]); out.b = bv[CPL - 1]; out.from_a = o_a;
-    out.zx = o_a ? am[CPL - 1] : mm_[CPL - 1]; out.zy = o_a ? an[CPL - 1] : mn[CPL - 1];
-    out.bx = bm[CPL - 1]; out.by = bn[CPL - 1];
+    if constexpr (!PICK) {
+      const bool o_a = a_adm[CPL - 1] && av[CPL - 1] >= mv[CPL - 1];
+      out.z = max(mv[CPL - 1], av[CPL - 1]); out.b = bv[CPL - 1]; out.from_a = o_a;
+      out.zx = o_a ? am[CPL - 1] : mm_[CPL - 1]; out.zy = o_a ? an[CPL - 1] : mn[CPL - 1];
+      out.bx = bm[CPL - 1]; out.by = bn[CPL - 1];
+    } else {
+#pragma unroll
+      for (int c = 0; c < CPL; ++c)
+        if (c == pick || CPL == 1) {
+          const bool o_a = a_adm[c] && av[c] >= mv[c];
+          out.z = max(mv[c], av[c]); out.b = bv[c]; out.from_a = o_a;
+          out.zx = o_a ? am[c] : mm_[c]; out.zy = o_a ? an[c] : mn[c];
+          out.bx = bm[c]; out.by = bn[c];
+        }
+    }
   }
 
   __device__ __forceinline__ unsigned long long reduce_err() {

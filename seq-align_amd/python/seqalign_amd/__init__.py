@@ -812,13 +812,19 @@ class Context:
         the banded matrices of nw_score_banded: its score and the counted columns of nw_align_banded's strings.  band: an int
         or one per pair; widths up to SEQALIGN_SPAN_BAND_MAX_WIDTH (512), sequences of any length.  A pair whose banded end
         value is below INT32_MIN / 2 has no alignment inside its band and raises SeqAlignError(E_TRACEBACK)."""
+        return self._nw_stats_banded("seqalign_nw_stats_banded", batch, scoring, band)
+
+    def nw_stats_banded_wide(self, batch, scoring: Scoring, band):
+        """seqalign_nw_stats_banded_wide: nw_stats_banded without the cap on the band's width."""
+        return self._nw_stats_banded("seqalign_nw_stats_banded_wide", batch, scoring, band)
+
+    def _nw_stats_banded(self, fn: str, batch, scoring: Scoring, band):
         _score_args(batch, scoring)
         bw = _band_arg(batch, band)
         n = batch.n_pairs
         score, matches, mismatches = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         d = batch_desc(batch)
-        _check(lib().seqalign_nw_stats_banded(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(score), _ptr(matches),
-                                              _ptr(mismatches)), "seqalign_nw_stats_banded")
+        _check(getattr(lib(), fn)(self._h, C.byref(d), C.byref(scoring), _ptr(bw), _ptr(score), _ptr(matches), _ptr(mismatches)), fn)
         return score, matches, mismatches
 
     def nw_stats_band_time_ms(self, batch, scoring: Scoring, band, repeats: int = 10) -> np.ndarray:
@@ -1314,6 +1320,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_sw_stats_banded", "seqalign_sw_stats_band_time_ms",
     "seqalign_nw_stats_banded", "seqalign_nw_stats_band_time_ms",
     "seqalign_nw_score_banded_wide", "seqalign_nw_align_banded_wide", "seqalign_sw_score_banded_wide", "seqalign_sw_align_banded_wide",
+    "seqalign_nw_stats_banded_wide",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",
