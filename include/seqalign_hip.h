@@ -734,8 +734,9 @@ int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  * and two result words); 28 bytes per pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band diagonals per
  * lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted under band_score,
  * one per width class of a chunk.
- * Not in this call (banded NW statistics: seqalign_nw_stats_banded and seqalign_nw_stats_banded_wide below): widths over 512
- * and a _banded_wide form, cross, search, _multi, _submit, the command-line tools, gap-open counts. */
+ * Widths over 512: seqalign_sw_stats_banded_wide ("wide banded calls" below).
+ * Not in this call (banded NW statistics: seqalign_nw_stats_banded and seqalign_nw_stats_banded_wide below): cross, search,
+ * _multi, _submit, the command-line tools, gap-open counts. */
 int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                              const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
                              uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
@@ -931,10 +932,29 @@ int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
  * strip) waves.  Kernel: sa_band_nw_stats_strips.hip.  One pair of 100 000 letters at 511 diagonals runs on
  * many waves here and on one in the narrow call; for many short pairs within 512 diagonals the narrow call is the faster one.
- * No SW form (the best cell and its words across strips, and the 65 535 limit), no cross, search, _multi, _submit, timing-hook
- * or command-line form. */
+ * The SW form is seqalign_sw_stats_banded_wide below.  No cross, search, _multi, _submit, timing-hook or command-line form. */
 int seqalign_nw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                   const uint32_t *band, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
+/* The wide form of seqalign_sw_stats_banded: its argument list and contract word for word -- the band and its clipping, the
+ * banded matrices, the best cell in hit order and the seven integers of its walk, seven zeros where no band cell is above 0 and
+ * for an empty band, a start one diagonal outside the band under gap_extend > 0, the case folding, SEQALIGN_E_UNKNOWN_PAIR for a
+ * character pair without a score inside the band only -- under the wide calls' width rule above: any clipped width is legal,
+ * SEQALIGN_E_NOMEM and SEQALIGN_E_HIP as above, and for every batch the narrow call accepts the same bytes, the same status
+ * and the same pair named.  Refused before the context is touched, in this order: a NULL argument (SEQALIGN_E_ARG); per pair,
+ * the lowest first, an unreadable batch or diag_lo[p] > diag_hi[p] (SEQALIGN_E_ARG) and len_a + len_b >= 2^31
+ * (SEQALIGN_E_TOO_LARGE); then a sequence of more than SEQALIGN_SW_STATS_MAX_LEN letters (SEQALIGN_E_TOO_LARGE, the narrow
+ * call's message, the lowest such pair) -- the narrow call's two passes without the width check.  A hand-off entry carries the
+ * two values, whose the first is and the two packed words of each, 32 bytes; a strip's best cell travels with its two words,
+ * 32 bytes; so the device bytes per pair are
+ *     len_a + len_b + 96 + strips (32 width + 36) + 20,      strips = max(1, ceil(len_a / S)).
+ * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
+ * strip) waves.  Kernel: sa_band_sw_stats_strips.hip.  For many short pairs within 512 diagonals the narrow
+ * call is the faster one.  No wide span call, no SW statistics past 65 535 letters, no cross, search, _multi, _submit,
+ * timing-hook or command-line form. */
+int seqalign_sw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
+                                  uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
+                                  uint32_t *out_matches, uint32_t *out_mismatches);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

@@ -1,6 +1,6 @@
-// sa_batch_band.hip -- the banded calls over HOST batches: the sixteen seqalign_*_banded, *_banded_wide and *_band_time_ms entry
+// sa_batch_band.hip -- the banded calls over HOST batches: the seventeen seqalign_*_banded, *_banded_wide and *_band_time_ms entry
 // points (the contracts: include/seqalign_hip.h; the kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip,
-// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip).  DESIGN.md 3.23b.
+// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip, sa_band_sw_stats_strips.hip).  DESIGN.md 3.23b.
 //
 // One driver, seven modes.  A mode is a traits struct (below): NW or SW, score family or align, its result words and fixed
 // bytes per pair, its cap on the width, its kernels' parameter block and launches.  The driver is the same for all of them:
@@ -19,7 +19,7 @@
 //            reach min_score are delivered in pair order under seqalign_sw_align_long's capacity rule (finish_sw_align).
 // The cut, the staging of a chunk, the lowest failing pair and the timing loop are sa_chunks.hpp's.
 //
-// The wide calls (the first four modes and the last) run through the same plan with a strip width (BandChunkRun::wide, a runtime value):
+// The wide calls (the first four modes and the last two) run through the same plan with a strip width (BandChunkRun::wide, a runtime value):
 // no width check, the pipeline's scratch added to a pair's bytes, and per chunk ONE launch over all its pairs instead of one
 // per width class; the layouts, the walks and what comes home are the narrow calls'.
 #include "sa_chunks.hpp"
@@ -35,7 +35,7 @@ namespace {
 // launch() (one width class; recorded as band_score or band_fill).  The score family besides: kFloorIsNoWalk (a score below
 // INT32_MIN / 2 is SEQALIGN_E_TRACEBACK).  The align modes: the walk's record per pair in words, where its status sits, what
 // their message adds to "traceback failed", set_meta() and walk().  The modes with a wide form: kHandoffBytes (per entry of a
-// strip's hand-off column) and launch_strips() (one launch over a chunk's strips, laid out as StripsLayout says).
+// strip's hand-off column), kBestBytes (per strip: its best-cell entry) and launch_strips() (one launch over a chunk's strips, laid out as StripsLayout says).
 
 // where a wide launch finds its pipeline's words (BandChunkRun::launch_wide): the fields of SaBandStripsParams behind s
 struct StripsLayout {
@@ -61,7 +61,7 @@ struct NwScoreBand {   // seqalign_nw_score_banded(_wide), seqalign_band_score_t
   using Params = SaBandParams;
   static constexpr bool kSw = false, kAlign = false, kWideForm = true, kFloorIsNoWalk = false;
   static constexpr int kFields = 1;             // score
-  static constexpr uint64_t kPairBytes = 64, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8;
+  static constexpr uint64_t kPairBytes = 64, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;
   static SaBandParams &base(Params &p) { return p; }
   static void set_results(Params &, uint32_t *, uint64_t) {}
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_score(p, max_width, st); }
@@ -75,7 +75,7 @@ struct NwAlignBand {   // seqalign_nw_align_banded(_wide)
   using Params = SaBandParams;
   static constexpr bool kSw = false, kAlign = true, kWideForm = true;
   static constexpr int kFields = 1;
-  static constexpr uint64_t kPairBytes = 96, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8;   // the walk's four words (16)
+  static constexpr uint64_t kPairBytes = 96, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;   // the walk's four words (16)
   static constexpr int kMetaWords = 4, kMetaStatus = 3;   // head, length, score, status
   static constexpr const char *kNoWalkText = " (no alignment inside the band)";
   static SaBandParams &base(Params &p) { return p; }
@@ -93,7 +93,7 @@ struct SwScoreBand {   // seqalign_sw_score_banded(_wide), seqalign_sw_band_scor
   using Params = SaBandSwParams;
   static constexpr bool kSw = true, kAlign = false, kWideForm = true, kFloorIsNoWalk = false;
   static constexpr int kFields = 3;             // score, end_a, end_b
-  static constexpr uint64_t kPairBytes = 80, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8;
+  static constexpr uint64_t kPairBytes = 80, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) { p.end_a = res + n; p.end_b = res + 2 * n; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_score(p, max_width, st); }
@@ -106,7 +106,7 @@ struct SwAlignBand {   // seqalign_sw_align_banded(_wide)
   using Params = SaBandSwParams;
   static constexpr bool kSw = true, kAlign = true, kWideForm = true;
   static constexpr int kFields = 3;             // the fill's best cell: score, end_a, end_b
-  static constexpr uint64_t kPairBytes = 128, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8;   // the walk's eight words (32)
+  static constexpr uint64_t kPairBytes = 128, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;   // the walk's eight words (32)
   static constexpr int kMetaWords = 8, kMetaStatus = 1;   // score, status, pos_a, pos_b, end_a, end_b, length, head
   static constexpr const char *kNoWalkText = "";
   static SaBandParams &base(Params &p) { return p.b; }
@@ -131,17 +131,29 @@ struct SwSpanBand {   // seqalign_sw_span_banded, seqalign_sw_span_band_time_ms 
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_span(p, max_width, st); }
 };
 
-struct SwStatsBand {   // seqalign_sw_stats_banded, seqalign_sw_stats_band_time_ms (sa_band_stats.hip)
+struct SwStatsBand {   // seqalign_sw_stats_banded(_wide), seqalign_sw_stats_band_time_ms (sa_band_stats.hip, sa_band_sw_stats_strips.hip)
   using Params = SaBandSwStatsParams;
-  static constexpr bool kSw = true, kAlign = false, kWideForm = false, kFloorIsNoWalk = false;
+  static constexpr bool kSw = true, kAlign = false, kWideForm = true, kFloorIsNoWalk = false;
   static constexpr int kFields = 7;             // the span mode's five, matches, mismatches
   static constexpr uint64_t kPairBytes = 96, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
+  // a hand-off entry as NwStatsBand's; the best cell travels with its two words (merge_left_best_span's entry)
+  static constexpr uint64_t kHandoffBytes = SA_BAND_STATS_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) {
     p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
     p.matches = res + 5 * n; p.mismatches = res + 6 * n;
   }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_stats(p, max_width, st); }
+  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    SaBandSwStatsStripsParams w;
+    memset(&w, 0, sizeof(w));
+    w.s = p;
+    w.strips_per_pair = l.strips_per_pair;
+    w.slot_off = l.slot_off; w.hand_off = l.hand_off;
+    w.progress = l.progress; w.ticket = l.ticket; w.front = l.front; w.strip_best = l.strip_best; w.give_up = l.give_up;
+    w.handoff = l.handoff;
+    return sa_launch_band_sw_stats_strips(w, cols, items, st);
+  }
 };
 
 struct NwStatsBand {   // seqalign_nw_stats_banded(_wide), seqalign_nw_stats_band_time_ms (sa_band_nw_stats.hip, sa_band_nw_stats_strips.hip)
@@ -151,6 +163,7 @@ struct NwStatsBand {   // seqalign_nw_stats_banded(_wide), seqalign_nw_stats_ban
   static constexpr int kFields = 3;             // score, matches, mismatches
   static constexpr uint64_t kPairBytes = 72, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
   static constexpr uint64_t kHandoffBytes = SA_BAND_STATS_HANDOFF_BYTES;   // the two values, whose the first is, their payloads
+  static constexpr uint64_t kBestBytes = 16;                               // (reserved as in the score modes, not used)
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) { p.matches = res + n; p.mismatches = res + 2 * n; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_nw_stats(p, max_width, st); }
@@ -235,18 +248,19 @@ int check_band_batch(const seqalign_batch_t *b, const Bands &bands, std::vector<
   return SEQALIGN_OK;
 }
 
-// the SW statistics calls' checks in the header's order: the band, then sw_stats' length limit
-int check_sw_stats_band_batch(const seqalign_batch_t *batch, const int32_t *diag_lo, const int32_t *diag_hi, std::vector<Band> &geom) {
-  const int rc = check_band_batch<SwStatsBand>(batch, SwBands{diag_lo, diag_hi}, geom);
+// the SW statistics calls' checks in the header's order: the band (a wide call: without the width), then sw_stats' length limit
+int check_sw_stats_band_batch(const seqalign_batch_t *batch, const int32_t *diag_lo, const int32_t *diag_hi, std::vector<Band> &geom,
+                              bool wide = false) {
+  const int rc = check_band_batch<SwStatsBand>(batch, SwBands{diag_lo, diag_hi}, geom, wide);
   return rc ? rc : sw_stats_check_batch(batch);
 }
 
 // ---- the wide calls: a pair's strips of `cols` columns, and what they add to its bytes -- per strip a hand-off column of
-// `width` entries of the mode's bytes (8; the statistics: 32), a progress word (4) and a best-cell entry (16), and per pair two
-// more descriptors (16) and a front word (4)
+// `width` entries of the mode's bytes (8; the statistics: 32), a progress word (4) and a best-cell entry of the mode's bytes (16;
+// SW statistics: 32), and per pair two more descriptors (16) and a front word (4)
 uint64_t wide_strips(uint32_t la, uint32_t cols) { return la ? ((uint64_t)la + cols - 1) / cols : 1; }
-uint64_t wide_bytes(uint32_t la, uint32_t width, uint32_t cols, uint64_t entry_bytes) {
-  return wide_strips(la, cols) * (entry_bytes * (uint64_t)width + 20) + 20;
+uint64_t wide_bytes(uint32_t la, uint32_t width, uint32_t cols, uint64_t entry_bytes, uint64_t best_bytes) {
+  return wide_strips(la, cols) * (entry_bytes * (uint64_t)width + 4 + best_bytes) + 20;
 }
 
 // the (pair, strip) waves of a wide launch that sweep at least one row: the strips that hold one of the pair's columns with
@@ -274,9 +288,15 @@ constexpr uint64_t handoff_entry_bytes() {
 }
 
 template <class M>
+constexpr uint64_t best_entry_bytes() {
+  if constexpr (M::kWideForm) return M::kBestBytes;
+  else return 0;
+}
+
+template <class M>
 uint64_t pair_bytes(uint32_t la, uint32_t lb, const Band &g, uint32_t wide_cols) {
   const uint64_t seq = (uint64_t)la + lb;
-  return (wide_cols ? wide_bytes(la, g.width, wide_cols, handoff_entry_bytes<M>()) : 0) + (M::kAlign ? 12 * g.cells + 3 * seq : seq) + M::kPairBytes;
+  return (wide_cols ? wide_bytes(la, g.width, wide_cols, handoff_entry_bytes<M>(), best_entry_bytes<M>()) : 0) + (M::kAlign ? 12 * g.cells + 3 * seq : seq) + M::kPairBytes;
 }
 
 // ---- One chunk of a call in mode M laid out and uploaded; launch() enqueues its kernels on ctx->stream
@@ -326,7 +346,7 @@ struct BandChunkRun {
         return rc;
     // wide: progress words, the ticket counter and the pairs' front words behind them, then (16-byte aligned) the best-cell
     // entries; the hand-off columns
-    if (wide && ((rc = ctx->strip_progress.reserve(4 * (slots + n + 8) + 16 * slots + 16)) || (rc = ctx->score_handoff.reserve(handoff_entry_bytes<M>() * hand_total + 16))))
+    if (wide && ((rc = ctx->strip_progress.reserve(4 * (slots + n + 8) + best_entry_bytes<M>() * slots + 16)) || (rc = ctx->score_handoff.reserve(handoff_entry_bytes<M>() * hand_total + 16))))
       return rc;
     d_res = ctx->best_score.as<uint32_t>();
     return stage.upload();
@@ -703,19 +723,36 @@ extern "C" int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign
   return band_time<SwSpanBand>(ctx, batch, scoring, geom, repeats, ms_each, "seqalign_sw_span_band_time_ms");
 }
 
-extern "C" int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
-                                        const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a,
-                                        uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b, uint32_t *out_matches,
-                                        uint32_t *out_mismatches) {
+// banded SW statistics: the two passes of checks in the header's order; the wide form: without the width check (kernel:
+// sa_band_sw_stats_strips.hip)
+static int sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const int32_t *diag_lo,
+                           const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a,
+                           uint32_t *out_len_b, uint32_t *out_matches, uint32_t *out_mismatches, bool wide) {
   if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b ||
       !out_matches || !out_mismatches)
     return SEQALIGN_E_ARG;
   std::vector<Band> geom;
-  int rc = check_sw_stats_band_batch(batch, diag_lo, diag_hi, geom);
+  int rc = check_sw_stats_band_batch(batch, diag_lo, diag_hi, geom, wide);
   if (rc) return rc;
   CallScope scope(ctx);
   uint32_t *const out[6] = {out_pos_a, out_pos_b, out_len_a, out_len_b, out_matches, out_mismatches};
-  return band_call<SwStatsBand>(ctx, batch, scoring, geom, false, [&](auto &run) { return run.finish_words(out_score, out); });
+  return band_call<SwStatsBand>(ctx, batch, scoring, geom, wide, [&](auto &run) { return run.finish_words(out_score, out); });
+}
+
+extern "C" int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                        const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a,
+                                        uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b, uint32_t *out_matches,
+                                        uint32_t *out_mismatches) {
+  return sw_stats_banded(ctx, batch, scoring, diag_lo, diag_hi, out_score, out_pos_a, out_pos_b, out_len_a, out_len_b, out_matches,
+                         out_mismatches, false);
+}
+
+extern "C" int seqalign_sw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a,
+                                             uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b, uint32_t *out_matches,
+                                             uint32_t *out_mismatches) {
+  return sw_stats_banded(ctx, batch, scoring, diag_lo, diag_hi, out_score, out_pos_a, out_pos_b, out_len_a, out_len_b, out_matches,
+                         out_mismatches, true);
 }
 
 extern "C" int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,

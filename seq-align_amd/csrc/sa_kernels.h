@@ -687,6 +687,21 @@ struct SaBandNwStatsStripsParams {
   int32_t *handoff;
 };
 hipError_t sa_launch_band_nw_stats_strips(const SaBandNwStatsStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
+/* ---- wide banded SW statistics (seqalign_sw_stats_banded_wide, sa_band_sw_stats_strips.hip): sa_launch_band_sw_stats' results
+ * at any width through the strips pipeline of sa_launch_band_strips.  The fields behind s are SaBandStripsParams' and are
+ * prepared the same way (f.status ~0, progress / ticket / front / give_up zero), but for two: the hand-off is per strip `width`
+ * entries of SA_BAND_STATS_HANDOFF_BYTES -- {max(M, A), B, whether max(M, A) is A's, 0} {word 0 and word 1 of each} of the strip's
+ * last column -- from entry hand_off[k] + t width of handoff (16-byte aligned), and strip t's best cell so far is the
+ * SA_SPAN_BEST_BYTES at strip_best + 8 (slot_off[k] + t) (16-byte aligned): {score, end_a, end_b, 0} {word 0, word 1, 0, 0}.
+ * Both sequences of every pair have at most SA_SW_STATS_MAX_LEN letters.  Recorded as "band_score" with `items`. */
+struct SaBandSwStatsStripsParams {
+  SaBandSwStatsParams s;
+  uint32_t strips_per_pair;
+  const uint64_t *slot_off, *hand_off;
+  uint32_t *progress, *ticket, *front, *strip_best, *give_up;
+  int32_t *handoff;
+};
+hipError_t sa_launch_band_sw_stats_strips(const SaBandSwStatsStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 /* the second launch record (seqalign_ctx_last_call_info_ext: SEQALIGN_KX_*) */
 void sa_record_launch_ext(int kind, uint64_t items);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */

@@ -784,14 +784,20 @@ class Context:
         uint32[n]) -- over the banded matrices of sw_score_banded: sw_span_banded's five and the counted columns of
         sw_align_banded(min_score=1)'s strings.  Each bound an int or one per pair; clipped widths up to
         SEQALIGN_SPAN_BAND_MAX_WIDTH (512), sequences up to SW_STATS_MAX_LEN letters (E_TOO_LARGE, the width first)."""
+        return self._sw_stats_banded("seqalign_sw_stats_banded", batch, scoring, diag_lo, diag_hi)
+
+    def sw_stats_banded_wide(self, batch, scoring: Scoring, diag_lo, diag_hi):
+        """seqalign_sw_stats_banded_wide: sw_stats_banded without the cap on the band's width."""
+        return self._sw_stats_banded("seqalign_sw_stats_banded_wide", batch, scoring, diag_lo, diag_hi)
+
+    def _sw_stats_banded(self, fn: str, batch, scoring: Scoring, diag_lo, diag_hi):
         _score_args(batch, scoring)
         lo, hi = _diag_args(batch, diag_lo, diag_hi)
         n = batch.n_pairs
         score = np.zeros(n, np.int32)
         words = tuple(np.zeros(n, np.uint32) for _ in range(6))
         d = batch_desc(batch)
-        _check(lib().seqalign_sw_stats_banded(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(score),
-                                              *(_ptr(w) for w in words)), "seqalign_sw_stats_banded")
+        _check(getattr(lib(), fn)(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(score), *(_ptr(w) for w in words)), fn)
         return (score,) + words
 
     def sw_stats_band_time_ms(self, batch, scoring: Scoring, diag_lo, diag_hi, repeats: int = 10) -> np.ndarray:
@@ -1320,7 +1326,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_sw_stats_banded", "seqalign_sw_stats_band_time_ms",
     "seqalign_nw_stats_banded", "seqalign_nw_stats_band_time_ms",
     "seqalign_nw_score_banded_wide", "seqalign_nw_align_banded_wide", "seqalign_sw_score_banded_wide", "seqalign_sw_align_banded_wide",
-    "seqalign_nw_stats_banded_wide",
+    "seqalign_nw_stats_banded_wide", "seqalign_sw_stats_banded_wide",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",
