@@ -696,8 +696,8 @@ int seqalign_sw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch
  * within the option chunk_bytes; 20 bytes per pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band
  * diagonals per lane.  seqalign_ctx_last_call_info_ext: the call adds no kind, its launches are counted under band_score, one
  * per width class of a chunk.
- * Not in this call: widths 513 .. 1 024 and a _banded_wide (strip pipeline) form -- the two-word span sweep does not fit the
- * registers at 12 and 16 columns per lane; they wait for the one-word span -- and no cross, search (the
+ * Not in this call: widths over 512 -- the two-word span sweep does not fit one wave's registers at 12 and 16 columns per lane
+ * (DESIGN.md 3.18); seqalign_sw_span_banded_wide ("wide banded calls" below) takes any width -- and no cross, search (the
  * unbanded call has both: seqalign_sw_span_cross, seqalign_sw_span_search), _multi,
  * _submit or command-line form, and no option steers it. */
 #define SEQALIGN_SPAN_BAND_MAX_WIDTH 512
@@ -949,12 +949,33 @@ int seqalign_nw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  *     len_a + len_b + 96 + strips (32 width + 36) + 20,      strips = max(1, ceil(len_a / S)).
  * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
  * strip) waves.  Kernel: sa_band_sw_stats_strips.hip.  For many short pairs within 512 diagonals the narrow
- * call is the faster one.  No wide span call, no SW statistics past 65 535 letters, no cross, search, _multi, _submit,
- * timing-hook or command-line form. */
+ * call is the faster one.  Past 65 535 letters the five span integers come from seqalign_sw_span_banded_wide below; no SW
+ * statistics past 65 535 letters, no cross, search, _multi, _submit, timing-hook or command-line form. */
 int seqalign_sw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                   const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
                                   uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
                                   uint32_t *out_matches, uint32_t *out_mismatches);
+/* The wide form of seqalign_sw_span_banded: its argument list and contract word for word -- the band and its clipping to
+ * [-len_b, len_a], the banded matrices, the best band cell in hit order and the five fields of the hit
+ * seqalign_sw_align_banded(_wide)(min_score = 1) delivers, five zeros where no band cell is above 0 and for an empty band, a start
+ * one diagonal outside the band under gap_extend > 0, SEQALIGN_E_UNKNOWN_PAIR for a character pair without a score inside the
+ * band only -- under the wide calls' width rule above: any clipped width is legal, SEQALIGN_E_NOMEM and SEQALIGN_E_HIP as above,
+ * and for every batch the narrow call accepts the same bytes, the same status and the same pair named.  There is NO limit on the
+ * lengths: the payload is two full words, the stop cell's x and y.  For every batch seqalign_sw_stats_banded_wide accepts the
+ * five equal its first five; score and pos + len equal seqalign_sw_score_banded_wide's three, always.  Refused before the context
+ * is touched, in this order: a NULL argument (SEQALIGN_E_ARG); per pair, the lowest first, an unreadable batch or diag_lo[p] >
+ * diag_hi[p] (SEQALIGN_E_ARG, the narrow call's message) and len_a + len_b >= 2^31 (SEQALIGN_E_TOO_LARGE).  A hand-off entry
+ * carries the two values, whose the first is and the span of each, 32 bytes; a strip's best cell travels with its span, 32
+ * bytes; so the device bytes per pair are
+ *     len_a + len_b + 88 + strips (32 width + 36) + 20,      strips = max(1, ceil(len_a / S)).
+ * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
+ * strip) waves.  Kernel: sa_band_span_strips.hip; all four strip widths run without scratch.  This is the
+ * cheap way to the start of a hit in long sequences with an indel-widened band: the align call stores 12 bytes per band cell,
+ * the wide score call gives the end only.  For many short pairs within 512 diagonals the narrow call is the faster one.
+ * No option, kind or constant of its own; no cross, search, _multi, _submit, timing-hook or command-line form. */
+int seqalign_sw_span_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                 const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
+                                 uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

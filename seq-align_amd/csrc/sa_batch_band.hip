@@ -1,6 +1,7 @@
-// sa_batch_band.hip -- the banded calls over HOST batches: the seventeen seqalign_*_banded, *_banded_wide and *_band_time_ms entry
+// sa_batch_band.hip -- the banded calls over HOST batches: the eighteen seqalign_*_banded, *_banded_wide and *_band_time_ms entry
 // points (the contracts: include/seqalign_hip.h; the kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip,
-// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip, sa_band_sw_stats_strips.hip).  DESIGN.md 3.23b.
+// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip, sa_band_sw_stats_strips.hip,
+// sa_band_span_strips.hip).  DESIGN.md 3.23b.
 //
 // One driver, seven modes.  A mode is a traits struct (below): NW or SW, score family or align, its result words and fixed
 // bytes per pair, its cap on the width, its kernels' parameter block and launches.  The driver is the same for all of them:
@@ -19,7 +20,7 @@
 //            reach min_score are delivered in pair order under seqalign_sw_align_long's capacity rule (finish_sw_align).
 // The cut, the staging of a chunk, the lowest failing pair and the timing loop are sa_chunks.hpp's.
 //
-// The wide calls (the first four modes and the last two) run through the same plan with a strip width (BandChunkRun::wide, a runtime value):
+// The wide calls (every mode has one) run through the same plan with a strip width (BandChunkRun::wide, a runtime value):
 // no width check, the pipeline's scratch added to a pair's bytes, and per chunk ONE launch over all its pairs instead of one
 // per width class; the layouts, the walks and what comes home are the narrow calls'.
 #include "sa_chunks.hpp"
@@ -30,11 +31,11 @@ namespace {
 
 // ---- the modes.  Of each: kSw (the SW recurrence and scoring), kAlign (fills M/A/B and walks), kFields (result words per pair
 // behind the header: the score first), kPairBytes (the fixed bytes per pair the chunk cut counts: descriptors (48), status (8),
-// the result words, kAlign: the walk's words; slack), kMaxWidth (the narrow call's cap), kWideForm (a *_banded_wide call exists),
+// the result words, kAlign: the walk's words; slack), kMaxWidth (the narrow call's cap),
 // Params with base() (its SaBandParams), set_results() (the arrays behind the score, res = the score's, n words each) and
 // launch() (one width class; recorded as band_score or band_fill).  The score family besides: kFloorIsNoWalk (a score below
 // INT32_MIN / 2 is SEQALIGN_E_TRACEBACK).  The align modes: the walk's record per pair in words, where its status sits, what
-// their message adds to "traceback failed", set_meta() and walk().  The modes with a wide form: kHandoffBytes (per entry of a
+// their message adds to "traceback failed", set_meta() and walk().  The wide form of each: kHandoffBytes (per entry of a
 // strip's hand-off column), kBestBytes (per strip: its best-cell entry) and launch_strips() (one launch over a chunk's strips, laid out as StripsLayout says).
 
 // where a wide launch finds its pipeline's words (BandChunkRun::launch_wide): the fields of SaBandStripsParams behind s
@@ -59,7 +60,7 @@ hipError_t launch_score_strips(const SaBandSwParams &s, const StripsLayout &l, u
 
 struct NwScoreBand {   // seqalign_nw_score_banded(_wide), seqalign_band_score_time_ms
   using Params = SaBandParams;
-  static constexpr bool kSw = false, kAlign = false, kWideForm = true, kFloorIsNoWalk = false;
+  static constexpr bool kSw = false, kAlign = false, kFloorIsNoWalk = false;
   static constexpr int kFields = 1;             // score
   static constexpr uint64_t kPairBytes = 64, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;
   static SaBandParams &base(Params &p) { return p; }
@@ -73,7 +74,7 @@ struct NwScoreBand {   // seqalign_nw_score_banded(_wide), seqalign_band_score_t
 
 struct NwAlignBand {   // seqalign_nw_align_banded(_wide)
   using Params = SaBandParams;
-  static constexpr bool kSw = false, kAlign = true, kWideForm = true;
+  static constexpr bool kSw = false, kAlign = true;
   static constexpr int kFields = 1;
   static constexpr uint64_t kPairBytes = 96, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;   // the walk's four words (16)
   static constexpr int kMetaWords = 4, kMetaStatus = 3;   // head, length, score, status
@@ -91,7 +92,7 @@ struct NwAlignBand {   // seqalign_nw_align_banded(_wide)
 
 struct SwScoreBand {   // seqalign_sw_score_banded(_wide), seqalign_sw_band_score_time_ms
   using Params = SaBandSwParams;
-  static constexpr bool kSw = true, kAlign = false, kWideForm = true, kFloorIsNoWalk = false;
+  static constexpr bool kSw = true, kAlign = false, kFloorIsNoWalk = false;
   static constexpr int kFields = 3;             // score, end_a, end_b
   static constexpr uint64_t kPairBytes = 80, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;
   static SaBandParams &base(Params &p) { return p.b; }
@@ -104,7 +105,7 @@ struct SwScoreBand {   // seqalign_sw_score_banded(_wide), seqalign_sw_band_scor
 
 struct SwAlignBand {   // seqalign_sw_align_banded(_wide)
   using Params = SaBandSwParams;
-  static constexpr bool kSw = true, kAlign = true, kWideForm = true;
+  static constexpr bool kSw = true, kAlign = true;
   static constexpr int kFields = 3;             // the fill's best cell: score, end_a, end_b
   static constexpr uint64_t kPairBytes = 128, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;   // the walk's eight words (32)
   static constexpr int kMetaWords = 8, kMetaStatus = 1;   // score, status, pos_a, pos_b, end_a, end_b, length, head
@@ -119,21 +120,33 @@ struct SwAlignBand {   // seqalign_sw_align_banded(_wide)
   }
 };
 
-struct SwSpanBand {   // seqalign_sw_span_banded, seqalign_sw_span_band_time_ms (sa_band_span.hip)
+struct SwSpanBand {   // seqalign_sw_span_banded(_wide), seqalign_sw_span_band_time_ms (sa_band_span.hip, sa_band_span_strips.hip)
   using Params = SaBandSpanParams;
-  static constexpr bool kSw = true, kAlign = false, kWideForm = false, kFloorIsNoWalk = false;
+  static constexpr bool kSw = true, kAlign = false, kFloorIsNoWalk = false;
   static constexpr int kFields = 5;             // score, pos_a, pos_b, len_a, len_b
   static constexpr uint64_t kPairBytes = 88, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
+  // a hand-off entry and a best entry as SwStatsBand's: the two payload words are the span's x and y
+  static constexpr uint64_t kHandoffBytes = SA_BAND_STATS_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) {
     p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
   }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_span(p, max_width, st); }
+  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    SaBandSpanStripsParams w;
+    memset(&w, 0, sizeof(w));
+    w.s = p;
+    w.strips_per_pair = l.strips_per_pair;
+    w.slot_off = l.slot_off; w.hand_off = l.hand_off;
+    w.progress = l.progress; w.ticket = l.ticket; w.front = l.front; w.strip_best = l.strip_best; w.give_up = l.give_up;
+    w.handoff = l.handoff;
+    return sa_launch_band_span_strips(w, cols, items, st);
+  }
 };
 
 struct SwStatsBand {   // seqalign_sw_stats_banded(_wide), seqalign_sw_stats_band_time_ms (sa_band_stats.hip, sa_band_sw_stats_strips.hip)
   using Params = SaBandSwStatsParams;
-  static constexpr bool kSw = true, kAlign = false, kWideForm = true, kFloorIsNoWalk = false;
+  static constexpr bool kSw = true, kAlign = false, kFloorIsNoWalk = false;
   static constexpr int kFields = 7;             // the span mode's five, matches, mismatches
   static constexpr uint64_t kPairBytes = 96, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
   // a hand-off entry as NwStatsBand's; the best cell travels with its two words (merge_left_best_span's entry)
@@ -158,7 +171,7 @@ struct SwStatsBand {   // seqalign_sw_stats_banded(_wide), seqalign_sw_stats_ban
 
 struct NwStatsBand {   // seqalign_nw_stats_banded(_wide), seqalign_nw_stats_band_time_ms (sa_band_nw_stats.hip, sa_band_nw_stats_strips.hip)
   using Params = SaBandNwStatsParams;
-  static constexpr bool kSw = false, kAlign = false, kWideForm = true;
+  static constexpr bool kSw = false, kAlign = false;
   static constexpr bool kFloorIsNoWalk = true;  // no alignment inside the band, decided by the value (include/seqalign_hip.h)
   static constexpr int kFields = 3;             // score, matches, mismatches
   static constexpr uint64_t kPairBytes = 72, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
@@ -282,21 +295,9 @@ uint32_t wide_strip_cols(const seqalign_ctx *ctx, uint64_t n_pairs) {
 // a pair's device bytes in mode M: the sequences (an align mode: the strings besides, and the band's cells), the mode's fixed
 // bytes, the strips' scratch of a wide call
 template <class M>
-constexpr uint64_t handoff_entry_bytes() {
-  if constexpr (M::kWideForm) return M::kHandoffBytes;
-  else return 0;
-}
-
-template <class M>
-constexpr uint64_t best_entry_bytes() {
-  if constexpr (M::kWideForm) return M::kBestBytes;
-  else return 0;
-}
-
-template <class M>
 uint64_t pair_bytes(uint32_t la, uint32_t lb, const Band &g, uint32_t wide_cols) {
   const uint64_t seq = (uint64_t)la + lb;
-  return (wide_cols ? wide_bytes(la, g.width, wide_cols, handoff_entry_bytes<M>(), best_entry_bytes<M>()) : 0) + (M::kAlign ? 12 * g.cells + 3 * seq : seq) + M::kPairBytes;
+  return (wide_cols ? wide_bytes(la, g.width, wide_cols, M::kHandoffBytes, M::kBestBytes) : 0) + (M::kAlign ? 12 * g.cells + 3 * seq : seq) + M::kPairBytes;
 }
 
 // ---- One chunk of a call in mode M laid out and uploaded; launch() enqueues its kernels on ctx->stream
@@ -346,7 +347,7 @@ struct BandChunkRun {
         return rc;
     // wide: progress words, the ticket counter and the pairs' front words behind them, then (16-byte aligned) the best-cell
     // entries; the hand-off columns
-    if (wide && ((rc = ctx->strip_progress.reserve(4 * (slots + n + 8) + best_entry_bytes<M>() * slots + 16)) || (rc = ctx->score_handoff.reserve(handoff_entry_bytes<M>() * hand_total + 16))))
+    if (wide && ((rc = ctx->strip_progress.reserve(4 * (slots + n + 8) + M::kBestBytes * slots + 16)) || (rc = ctx->score_handoff.reserve(M::kHandoffBytes * hand_total + 16))))
       return rc;
     d_res = ctx->best_score.as<uint32_t>();
     return stage.upload();
@@ -374,22 +375,20 @@ struct BandChunkRun {
 
   // the wide calls: one launch over all slots of the chunk, strips_per_pair the chunk's maximum
   int launch_wide() {
-    if constexpr (M::kWideForm) {
-      hipStream_t st = ctx->stream;
-      StripsLayout w{};
-      w.strips_per_pair = strips_per_pair;
-      w.slot_off = stage.d_u64(2); w.hand_off = stage.d_u64(3);
-      w.progress = ctx->strip_progress.as<uint32_t>();
-      w.ticket = w.progress + slots;
-      w.front = w.ticket + 1;
-      w.strip_best = w.progress + ((slots + n + 4) & ~(uint64_t)3);
-      w.give_up = d_res + 1;
-      w.handoff = ctx->score_handoff.as<int32_t>();
-      HIP_TRY(hipMemsetAsync(w.progress, 0, 4 * (slots + 1 + n), st));
-      HIP_TRY(hipMemsetAsync(ctx->status.p, 0xFF, 8 * n, st));
-      const hipError_t e = M::launch_strips(params(0, n), w, wide, busy_strips, st);
-      if (e != hipSuccess) return fail_hip(e, "band strips kernel launch");
-    }
+    hipStream_t st = ctx->stream;
+    StripsLayout w{};
+    w.strips_per_pair = strips_per_pair;
+    w.slot_off = stage.d_u64(2); w.hand_off = stage.d_u64(3);
+    w.progress = ctx->strip_progress.as<uint32_t>();
+    w.ticket = w.progress + slots;
+    w.front = w.ticket + 1;
+    w.strip_best = w.progress + ((slots + n + 4) & ~(uint64_t)3);
+    w.give_up = d_res + 1;
+    w.handoff = ctx->score_handoff.as<int32_t>();
+    HIP_TRY(hipMemsetAsync(w.progress, 0, 4 * (slots + 1 + n), st));
+    HIP_TRY(hipMemsetAsync(ctx->status.p, 0xFF, 8 * n, st));
+    const hipError_t e = M::launch_strips(params(0, n), w, wide, busy_strips, st);
+    if (e != hipSuccess) return fail_hip(e, "band strips kernel launch");
     return SEQALIGN_OK;
   }
 
@@ -542,7 +541,6 @@ struct BandPlan {
 
   int make(seqalign_ctx_t *ctx, const seqalign_batch_t *b, const scoring_t *scoring, const std::vector<Band> &geom, bool wide) {
     int rc;
-    if (wide && !M::kWideForm) { set_last_error("this banded call has no wide form"); return SEQALIGN_E_ARG; }
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = cached_scoring(ctx, scoring, M::kSw ? 1 : 0, &sc))) return rc;
     if ((rc = admit_batch(sc, b, SA_FRAMES_BAND))) return rc;
@@ -585,7 +583,7 @@ int band_time(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   return time_launches(ctx->stream, repeats, ms_each, [&] { return run.launch(); });
 }
 
-// ---- the four contracts with a wide form, each the body of its narrow call and of its wide one (any width; kernel:
+// ---- the contracts, each the body of its narrow call and of its wide one (any width; kernel:
 // sa_band_strips.hip)
 int nw_score_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const uint32_t *band, int32_t *out_score,
                     bool wide) {
@@ -702,16 +700,29 @@ extern "C" int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign
   return sw_align_banded(ctx, batch, scoring, diag_lo, diag_hi, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, true);
 }
 
-extern "C" int seqalign_sw_span_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
-                                       const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a,
-                                       uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b) {
+// banded SW hit spans: the narrow call, and the wide form without the width check (kernel: sa_band_span_strips.hip)
+static int sw_span_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const int32_t *diag_lo,
+                          const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a,
+                          uint32_t *out_len_b, bool wide) {
   if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !out_score || !out_pos_a || !out_pos_b || !out_len_a || !out_len_b) return SEQALIGN_E_ARG;
   std::vector<Band> geom;
-  int rc = check_band_batch<SwSpanBand>(batch, SwBands{diag_lo, diag_hi}, geom);
+  int rc = check_band_batch<SwSpanBand>(batch, SwBands{diag_lo, diag_hi}, geom, wide);
   if (rc) return rc;
   CallScope scope(ctx);
   uint32_t *const out[4] = {out_pos_a, out_pos_b, out_len_a, out_len_b};
-  return band_call<SwSpanBand>(ctx, batch, scoring, geom, false, [&](auto &run) { return run.finish_words(out_score, out); });
+  return band_call<SwSpanBand>(ctx, batch, scoring, geom, wide, [&](auto &run) { return run.finish_words(out_score, out); });
+}
+
+extern "C" int seqalign_sw_span_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                       const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a,
+                                       uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b) {
+  return sw_span_banded(ctx, batch, scoring, diag_lo, diag_hi, out_score, out_pos_a, out_pos_b, out_len_a, out_len_b, false);
+}
+
+extern "C" int seqalign_sw_span_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                            const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a,
+                                            uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b) {
+  return sw_span_banded(ctx, batch, scoring, diag_lo, diag_hi, out_score, out_pos_a, out_pos_b, out_len_a, out_len_b, true);
 }
 
 extern "C" int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,

@@ -702,6 +702,19 @@ struct SaBandSwStatsStripsParams {
   int32_t *handoff;
 };
 hipError_t sa_launch_band_sw_stats_strips(const SaBandSwStatsStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
+/* ---- wide banded SW hit spans (seqalign_sw_span_banded_wide, sa_band_span_strips.hip): sa_launch_band_span's results at any
+ * width and any length through the strips pipeline of sa_launch_band_strips.  The fields behind s are SaBandSwStatsStripsParams'
+ * and are prepared the same way; a hand-off entry is SA_BAND_STATS_HANDOFF_BYTES -- {max(M, A), B, whether max(M, A) is A's, 0}
+ * {the span of each: x, y, x, y} -- and a strip_best entry SA_SPAN_BEST_BYTES: {score, end_a, end_b, 0} {pos_a, pos_b, 0, 0}.
+ * Recorded as "band_score" with `items`. */
+struct SaBandSpanStripsParams {
+  SaBandSpanParams s;
+  uint32_t strips_per_pair;
+  const uint64_t *slot_off, *hand_off;
+  uint32_t *progress, *ticket, *front, *strip_best, *give_up;
+  int32_t *handoff;
+};
+hipError_t sa_launch_band_span_strips(const SaBandSpanStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 /* the second launch record (seqalign_ctx_last_call_info_ext: SEQALIGN_KX_*) */
 void sa_record_launch_ext(int kind, uint64_t items);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */

@@ -80,9 +80,11 @@ struct SpanSweep {
 
   // Row j.  f: the cell left of the strip on this row.  Leaves the last column's hand-off in `out` (lane 63's is the strip's).
   // BAND (sa_band_span.hip): ncol changes from row to row, so the running best takes a cell only while its column is in the band.
-  template <bool BAND = false>
+  // PICK (sa_band_span_strips.hip, where the strip's last column moves through the frame): `out` is column `pick` of the
+  // lane instead of its last.
+  template <bool BAND = false, bool PICK = false>
   __device__ __forceinline__ void row(const SweepConsts &k, uint32_t j, uint32_t lb, uint32_t la, uint32_t W, int lane,
-                                      uint32_t col0, int ncol, int code_b, const SpanFeed &f, SpanFeed &out) {
+                                      uint32_t col0, int ncol, int code_b, const SpanFeed &f, SpanFeed &out, int pick = CPL - 1) {
     int xd = wave_shr1(X[CPL - 1], boundX);
     uint32_t dx = (uint32_t)wave_shr1((int)Dx[CPL - 1], (int)boundDx), dy = (uint32_t)wave_shr1((int)Dy[CPL - 1], (int)boundDy);
     {   // the boundary cell of this row, for the next one: A > B > M over {max(M, A) and whose it is, B}
@@ -184,10 +186,21 @@ struct SpanSweep {
       if constexpr (GENERAL) Y[c] = mb;
       Ap[c] = av[c];
     }
-    const bool o_a = av[CPL - 1] >= mv[CPL - 1];
-    out.z = max(mv[CPL - 1], av[CPL - 1]); out.b = bv[CPL - 1]; out.from_a = o_a;
-    out.zx = o_a ? ax[CPL - 1] : mx[CPL - 1]; out.zy = o_a ? ay[CPL - 1] : my[CPL - 1];
-    out.bx = bxs[CPL - 1]; out.by = bys[CPL - 1];
+    if constexpr (!PICK) {
+      const bool o_a = av[CPL - 1] >= mv[CPL - 1];
+      out.z = max(mv[CPL - 1], av[CPL - 1]); out.b = bv[CPL - 1]; out.from_a = o_a;
+      out.zx = o_a ? ax[CPL - 1] : mx[CPL - 1]; out.zy = o_a ? ay[CPL - 1] : my[CPL - 1];
+      out.bx = bxs[CPL - 1]; out.by = bys[CPL - 1];
+    } else {
+#pragma unroll
+      for (int c = 0; c < CPL; ++c)
+        if (c == pick || CPL == 1) {
+          const bool o_a = av[c] >= mv[c];
+          out.z = max(mv[c], av[c]); out.b = bv[c]; out.from_a = o_a;
+          out.zx = o_a ? ax[c] : mx[c]; out.zy = o_a ? ay[c] : my[c];
+          out.bx = bxs[c]; out.by = bys[c];
+        }
+    }
   }
 
   __device__ __forceinline__ unsigned long long reduce_err() {

@@ -756,15 +756,21 @@ class Context:
         """seqalign_sw_span_banded: what sw_span returns -- (score int32[n], pos_a, pos_b, len_a, len_b uint32[n]) -- over the
         banded matrices of sw_score_banded: the fields of sw_align_banded(min_score=1)'s hit without its strings; pos + len is
         sw_score_banded's end.  Each bound an int or one per pair; clipped widths up to SEQALIGN_SPAN_BAND_MAX_WIDTH (512)."""
+        return self._sw_span_banded("seqalign_sw_span_banded", batch, scoring, diag_lo, diag_hi)
+
+    def sw_span_banded_wide(self, batch, scoring: Scoring, diag_lo, diag_hi):
+        """seqalign_sw_span_banded_wide: sw_span_banded without the cap on the band's width; sequences of any length."""
+        return self._sw_span_banded("seqalign_sw_span_banded_wide", batch, scoring, diag_lo, diag_hi)
+
+    def _sw_span_banded(self, fn: str, batch, scoring: Scoring, diag_lo, diag_hi):
         _score_args(batch, scoring)
         lo, hi = _diag_args(batch, diag_lo, diag_hi)
         n = batch.n_pairs
         score = np.zeros(n, np.int32)
-        pos_a, pos_b, len_a, len_b = (np.zeros(n, np.uint32) for _ in range(4))
+        words = tuple(np.zeros(n, np.uint32) for _ in range(4))
         d = batch_desc(batch)
-        _check(lib().seqalign_sw_span_banded(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(score), _ptr(pos_a),
-                                             _ptr(pos_b), _ptr(len_a), _ptr(len_b)), "seqalign_sw_span_banded")
-        return score, pos_a, pos_b, len_a, len_b
+        _check(getattr(lib(), fn)(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), _ptr(score), *(_ptr(w) for w in words)), fn)
+        return (score,) + words
 
     def sw_span_band_time_ms(self, batch, scoring: Scoring, diag_lo, diag_hi, repeats: int = 10) -> np.ndarray:
         """seqalign_sw_span_band_time_ms: kernel time (HIP events) of sw_span_banded's launches, float32[repeats]."""
@@ -1326,7 +1332,7 @@ EXPORTED_SYMBOLS = [
     "seqalign_sw_stats_banded", "seqalign_sw_stats_band_time_ms",
     "seqalign_nw_stats_banded", "seqalign_nw_stats_band_time_ms",
     "seqalign_nw_score_banded_wide", "seqalign_nw_align_banded_wide", "seqalign_sw_score_banded_wide", "seqalign_sw_align_banded_wide",
-    "seqalign_nw_stats_banded_wide", "seqalign_sw_stats_banded_wide",
+    "seqalign_nw_stats_banded_wide", "seqalign_sw_stats_banded_wide", "seqalign_sw_span_banded_wide",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",

@@ -3,7 +3,7 @@
 *_score_search, seqalign_sw_span_cross and seqalign_sw_span_search (against sw_span on the explicit batch), seqalign_nw_stats_batch
 (the columns of the oracle's strings) and seqalign_nw_stats_cross (against nw_stats on the explicit batch), seqalign_sw_stats_batch
 (the oracle's first hit and its counted strings) and seqalign_sw_stats_cross (against sw_stats on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded, seqalign_sw_stats_banded (the oracle's
-banded hit and its counted strings) and (on from the command line, --no-wide leaves them out) the four wide banded calls, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+banded hit and its counted strings) and (on from the command line, --no-wide leaves them out) the four wide banded score and align calls and seqalign_sw_span_banded_wide, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -94,7 +94,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         import maglib as G      # only the scaled runs need it: the default run is what it was, imports included
     ctx = ctx or (None if dry else S.Context(0))
     t_end = time.time() + seconds
-    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0, "sw_stats_banded": 0}
+    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span_banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0, "sw_stats_banded": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -383,6 +383,19 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                 if small and got[:len(small)] != ctx.sw_align_banded(W.from_pairs(sub[:len(small)]), sc, lo[:len(small)], hi[:len(small)], thr):
                     fail("WIDE / NARROW BAND SW ALIGN", spec, "cols", cols, sub, lo, hi)
                 n["banded_wide"] += len(sub)
+                # ---- wide banded SW hit spans on the same pairs and bounds: the fields of the oracle's banded hit at min_score = 1
+                # (the hit found above where it reached thr), and the narrow call's bytes on the small pairs
+                hits1 = [x[1] if x[1] else BS.expected(osc, a, b, lo[k], hi[k], 1)[1] for k, ((a, b), x) in enumerate(zip(sub, want))]
+                want5 = [(h["score"], h["pos_a"], h["pos_b"], h["len_a"], h["len_b"]) if h else (0, 0, 0, 0, 0) for h in hits1]
+                res = ctx.sw_span_banded_wide(wb, sc, lo, hi)
+                got5 = [tuple(int(x[k]) for x in res) for k in range(len(sub))]
+                if got5 != want5:
+                    fail("WIDE BAND SW SPAN", spec, "cols", cols, sub, lo, hi, got5, want5)
+                if small:
+                    narrow = ctx.sw_span_banded(W.from_pairs(sub[:len(small)]), sc, lo[:len(small)], hi[:len(small)])
+                    if any(x[:len(small)].tobytes() != y.tobytes() for x, y in zip(res, narrow)):
+                        fail("WIDE / NARROW BAND SW SPAN", spec, "cols", cols, sub, lo, hi)
+                n["span_banded_wide"] += len(sub)
         n["trials"] += 1
 
     if srng is not None:
@@ -390,7 +403,7 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
               f"({n['redrawn_trials'] / max(1, n['trials']):.1%} of the trials)", flush=True)
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
           f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['sw_stats_banded']} banded SW statistics, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['stats']} NW and {n['sw_stats']} SW statistics, {n['stats_cross']} NW and {n['sw_stats_cross']} SW statistics cross cells, {n['long']} long alignments, {n['banded']} banded "
-          f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results identical to the oracle "
+          f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results and {n['span_banded_wide']} wide banded hit spans identical to the oracle "
           f"(seed {seed})", flush=True)
     return n
 
