@@ -752,18 +752,22 @@ int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *
  *       d_lo = max(-len_b, min(0, len_a - len_b) - w)      d_hi = min(len_a, max(0, len_a - len_b) + w)
  *   and the matrices are its matrices: every cell outside the band holds the NW floor in all three.
  *   out_score[p]   seqalign_nw_score_banded's value exactly.
- *   A pair whose banded end value is at or above INT32_MIN / 2 has an alignment inside its band, the one
- *   seqalign_nw_align_banded returns: out_matches[p] / out_mismatches[p] are the counts over THAT alignment's strings, split as
- *   seqalign_nw_stats_batch splits them (letters compared after the scoring's own case folding; substitution scores and
- *   wildcards play no part).  So when the unbanded alignment stays inside the band all three are seqalign_nw_stats_batch's.
- *   A pair whose end value is below INT32_MIN / 2 has no alignment inside its band: SEQALIGN_E_TRACEBACK ("pair P: traceback
- *   failed (no alignment inside the band)"), the lowest such pair named, ordered with SEQALIGN_E_UNKNOWN_PAIR as
- *   seqalign_nw_stats_batch orders the two (the lowest failing pair's code).
- *   This is decided by the VALUE, not by what seqalign_nw_align_banded does, and differs from it on one family of pairs: under
- *   no_mismatches the align call's walker reads a blocked letter pair as score 0, floor + 0 == floor lets it step from a cell
- *   at the floor to any other, cells outside the band included, and the walk can "succeed" with an end value at the floor.
- *   Such strings are no alignment of the banded problem; this call returns SEQALIGN_E_TRACEBACK for those pairs.  The
- *   reverse does not occur: no pair with an end value at or above INT32_MIN / 2 fails in the align call.
+ *   A pair that has an alignment inside its band gets the one seqalign_nw_align_banded returns: out_matches[p] /
+ *   out_mismatches[p] are the counts over THAT alignment's strings, split as seqalign_nw_stats_batch splits them (letters
+ *   compared after the scoring's own case folding; substitution scores and wildcards play no part).  So when the unbanded
+ *   alignment stays inside the band all three are seqalign_nw_stats_batch's.
+ *   A pair that has no alignment inside its band: SEQALIGN_E_TRACEBACK ("pair P: traceback failed (no alignment inside the
+ *   band)"), the lowest such pair named, ordered with SEQALIGN_E_UNKNOWN_PAIR as seqalign_nw_stats_batch orders the two (the
+ *   lowest failing pair's code).
+ *   This is decided as seqalign_nw_stats_batch decides it, by the sticky mark the sweep carries beside the counts: the end
+ *   pick's state, or a state the walk from it would pass through, has every candidate below the NW floor (or none: a blocked
+ *   letter pair, a cell outside the band).  It is NOT decided by the end value: with a scoring of large numbers a real score
+ *   lies below INT32_MIN / 2, far above the floor, and such a pair has its alignment and gets its counts.
+ *   It differs from what seqalign_nw_align_banded does on one family of pairs: under no_mismatches the align call's walker
+ *   reads a blocked letter pair as score 0, floor + 0 == floor lets it step from a cell at the floor to any other, cells
+ *   outside the band included, and the walk can "succeed" with an end value at the floor.  Such strings are no alignment of
+ *   the banded problem (they hold a blocked letter pair or leave the band); this call returns SEQALIGN_E_TRACEBACK for those
+ *   pairs.  The reverse does not occur: no pair this call refuses has a walk that stays inside the band.
  * Refused before any device work, with a context that is never dereferenced, in seqalign_nw_score_banded's order:
  *   1. SEQALIGN_E_ARG        a NULL argument (the timing hook: or repeats <= 0);
  *   2. SEQALIGN_E_ARG        an unreadable batch;
@@ -816,7 +820,8 @@ int seqalign_sw_align_long(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, c
  * unbanded alignment of a pair stays inside its band, score and strings are seqalign_nw_batch's byte for byte; otherwise
  * the score is <= the unbanded one.  A scoring that forbids moves (no_mismatches, no_gaps_in_*) may leave NO alignment
  * inside a band: seqalign_nw_align_banded then returns SEQALIGN_E_TRACEBACK (lowest failing pair named in
- * seqalign_last_error); seqalign_nw_score_banded returns the end cell's value as it is, below INT32_MIN / 2 then.
+ * seqalign_last_error); seqalign_nw_score_banded returns the end cell's value as it is, below INT32_MIN / 2 then.  The value
+ * alone does not tell: with a scoring of large numbers a real score can lie below INT32_MIN / 2 as well.
  * Results, capacities and str_off exactly as seqalign_nw_score_batch / seqalign_nw_batch.  No 2^31-cell cap.
  *   SEQALIGN_E_ARG          NULL arguments, unreadable batch
  *   SEQALIGN_E_TOO_LARGE    a pair whose width exceeds SEQALIGN_BAND_MAX_WIDTH (found from lengths and bands alone, before
@@ -922,8 +927,8 @@ int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *b
                                   const int32_t *diag_lo, const int32_t *diag_hi, const int32_t *min_score, seqalign_sw_hit_t *hits,
                                   uint64_t hit_cap, uint64_t *n_hits, char *out_a, char *out_b, uint64_t str_cap);
 /* The wide form of seqalign_nw_stats_banded: its argument list and contract word for word -- the band, seqalign_nw_score_banded's
- * score, the counts over the strings seqalign_nw_align_banded(_wide) returns, the case folding, SEQALIGN_E_TRACEBACK by the value
- * rule and its order with SEQALIGN_E_UNKNOWN_PAIR, no limit on the lengths -- under the wide calls' width rule above: any width,
+ * score, the counts over the strings seqalign_nw_align_banded(_wide) returns, the case folding, SEQALIGN_E_TRACEBACK by the mark
+ * (not the end value) and its order with SEQALIGN_E_UNKNOWN_PAIR, no limit on the lengths -- under the wide calls' width rule above: any width,
  * SEQALIGN_E_TOO_LARGE for len_a + len_b >= 2^31 only, SEQALIGN_E_NOMEM and SEQALIGN_E_HIP as above, and for every batch the
  * narrow call accepts the same bytes, the same status and the same pair named.  The refusals before the context is touched are
  * seqalign_nw_score_banded_wide's, in its order.  A hand-off entry carries the two values, whose the first is and their two

@@ -33,8 +33,8 @@ namespace {
 // behind the header: the score first), kPairBytes (the fixed bytes per pair the chunk cut counts: descriptors (48), status (8),
 // the result words, kAlign: the walk's words; slack), kMaxWidth (the narrow call's cap),
 // Params with base() (its SaBandParams), set_results() (the arrays behind the score, res = the score's, n words each) and
-// launch() (one width class; recorded as band_score or band_fill).  The score family besides: kFloorIsNoWalk (a score below
-// INT32_MIN / 2 is SEQALIGN_E_TRACEBACK).  The align modes: the walk's record per pair in words, where its status sits, what
+// launch() (one width class; recorded as band_score or band_fill).  The score family besides: kMarkField (above 0: the result
+// array whose words carry SA_STATS_NO_WALK, SEQALIGN_E_TRACEBACK).  The align modes: the walk's record per pair in words, where its status sits, what
 // their message adds to "traceback failed", set_meta() and walk().  The wide form of each: kHandoffBytes (per entry of a
 // strip's hand-off column), kBestBytes (per strip: its best-cell entry) and launch_strips() (one launch over a chunk's strips, laid out as StripsLayout says).
 
@@ -60,8 +60,9 @@ hipError_t launch_score_strips(const SaBandSwParams &s, const StripsLayout &l, u
 
 struct NwScoreBand {   // seqalign_nw_score_banded(_wide), seqalign_band_score_time_ms
   using Params = SaBandParams;
-  static constexpr bool kSw = false, kAlign = false, kFloorIsNoWalk = false;
+  static constexpr bool kSw = false, kAlign = false;
   static constexpr int kFields = 1;             // score
+  static constexpr int kMarkField = 0;          // no result word carries a mark
   static constexpr uint64_t kPairBytes = 64, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;
   static SaBandParams &base(Params &p) { return p; }
   static void set_results(Params &, uint32_t *, uint64_t) {}
@@ -92,8 +93,9 @@ struct NwAlignBand {   // seqalign_nw_align_banded(_wide)
 
 struct SwScoreBand {   // seqalign_sw_score_banded(_wide), seqalign_sw_band_score_time_ms
   using Params = SaBandSwParams;
-  static constexpr bool kSw = true, kAlign = false, kFloorIsNoWalk = false;
+  static constexpr bool kSw = true, kAlign = false;
   static constexpr int kFields = 3;             // score, end_a, end_b
+  static constexpr int kMarkField = 0;
   static constexpr uint64_t kPairBytes = 80, kMaxWidth = SEQALIGN_BAND_MAX_WIDTH, kHandoffBytes = 8, kBestBytes = 16;
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) { p.end_a = res + n; p.end_b = res + 2 * n; }
@@ -122,8 +124,9 @@ struct SwAlignBand {   // seqalign_sw_align_banded(_wide)
 
 struct SwSpanBand {   // seqalign_sw_span_banded(_wide), seqalign_sw_span_band_time_ms (sa_band_span.hip, sa_band_span_strips.hip)
   using Params = SaBandSpanParams;
-  static constexpr bool kSw = true, kAlign = false, kFloorIsNoWalk = false;
+  static constexpr bool kSw = true, kAlign = false;
   static constexpr int kFields = 5;             // score, pos_a, pos_b, len_a, len_b
+  static constexpr int kMarkField = 0;
   static constexpr uint64_t kPairBytes = 88, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
   // a hand-off entry and a best entry as SwStatsBand's: the two payload words are the span's x and y
   static constexpr uint64_t kHandoffBytes = SA_BAND_STATS_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
@@ -146,8 +149,9 @@ struct SwSpanBand {   // seqalign_sw_span_banded(_wide), seqalign_sw_span_band_t
 
 struct SwStatsBand {   // seqalign_sw_stats_banded(_wide), seqalign_sw_stats_band_time_ms (sa_band_stats.hip, sa_band_sw_stats_strips.hip)
   using Params = SaBandSwStatsParams;
-  static constexpr bool kSw = true, kAlign = false, kFloorIsNoWalk = false;
+  static constexpr bool kSw = true, kAlign = false;
   static constexpr int kFields = 7;             // the span mode's five, matches, mismatches
+  static constexpr int kMarkField = 0;
   static constexpr uint64_t kPairBytes = 96, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
   // a hand-off entry as NwStatsBand's; the best cell travels with its two words (merge_left_best_span's entry)
   static constexpr uint64_t kHandoffBytes = SA_BAND_STATS_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
@@ -172,8 +176,10 @@ struct SwStatsBand {   // seqalign_sw_stats_banded(_wide), seqalign_sw_stats_ban
 struct NwStatsBand {   // seqalign_nw_stats_banded(_wide), seqalign_nw_stats_band_time_ms (sa_band_nw_stats.hip, sa_band_nw_stats_strips.hip)
   using Params = SaBandNwStatsParams;
   static constexpr bool kSw = false, kAlign = false;
-  static constexpr bool kFloorIsNoWalk = true;  // no alignment inside the band, decided by the value (include/seqalign_hip.h)
   static constexpr int kFields = 3;             // score, matches, mismatches
+  // no alignment inside the band: the end pick's state carries the sticky mark, SA_STATS_NO_WALK in the mismatch word, as in
+  // seqalign_nw_stats_batch (StatsTraits::kMarkField).  Not the end value: at large scales a real score lies below INT32_MIN / 2
+  static constexpr int kMarkField = 2;
   static constexpr uint64_t kPairBytes = 72, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
   static constexpr uint64_t kHandoffBytes = SA_BAND_STATS_HANDOFF_BYTES;   // the two values, whose the first is, their payloads
   static constexpr uint64_t kBestBytes = 16;                               // (reserved as in the score modes, not used)
@@ -421,8 +427,8 @@ struct BandChunkRun {
   }
 
   // the score family's way home: the header and M::kFields arrays of n words, array 0 to out_score, array f to out[f - 1].  The
-  // lowest pair of the chunk whose sweep met a band cell without a score is named; kFloorIsNoWalk: so is the lowest whose end
-  // value lies below INT32_MIN / 2, SEQALIGN_E_TRACEBACK, and between the two the lower pair's code is the call's, as in
+  // lowest pair of the chunk whose sweep met a band cell without a score is named; kMarkField: so is the lowest whose end
+  // pick carries the mark, SEQALIGN_E_TRACEBACK, and between the two the lower pair's code is the call's, as in
   // seqalign_nw_stats_batch
   int finish_words(int32_t *out_score, uint32_t *const *out) {
     int rc;
@@ -433,12 +439,12 @@ struct BandChunkRun {
     if ((rc = fail_if_gave_up(h))) return rc;
     uint64_t unknown = ~0ull;   // the chunk's lowest pair without a score, as a batch index
     if (h[0]) rc = stage.fail_from_status(&unknown);
-    if constexpr (M::kFloorIsNoWalk)
+    if constexpr (M::kMarkField > 0)
       if (!rc || rc == SEQALIGN_E_UNKNOWN_PAIR) {
         uint64_t no_walk = ~0ull;
-        const int32_t *hs = reinterpret_cast<const int32_t *>(h + 4);
+        const uint32_t *w = h + 4 + (uint64_t)M::kMarkField * n;
         for (uint64_t s = 0; s < n; ++s)
-          if (hs[s] < INT32_MIN / 2) no_walk = std::min<uint64_t>(no_walk, stage.first + stage.order[s]);
+          if (w[s] & SA_STATS_NO_WALK) no_walk = std::min<uint64_t>(no_walk, stage.first + stage.order[s]);
         if (no_walk < unknown) {
           set_last_error("pair " + std::to_string(no_walk) + ": traceback failed (no alignment inside the band)");
           return SEQALIGN_E_TRACEBACK;

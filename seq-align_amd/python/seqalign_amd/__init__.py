@@ -822,8 +822,8 @@ class Context:
     def nw_stats_banded(self, batch, scoring: Scoring, band):
         """seqalign_nw_stats_banded: what nw_stats returns -- (score int32[n], matches uint32[n], mismatches uint32[n]) -- over
         the banded matrices of nw_score_banded: its score and the counted columns of nw_align_banded's strings.  band: an int
-        or one per pair; widths up to SEQALIGN_SPAN_BAND_MAX_WIDTH (512), sequences of any length.  A pair whose banded end
-        value is below INT32_MIN / 2 has no alignment inside its band and raises SeqAlignError(E_TRACEBACK)."""
+        or one per pair; widths up to SEQALIGN_SPAN_BAND_MAX_WIDTH (512), sequences of any length.  A pair that has no
+        alignment inside its band (the sweep's "no walk" mark, not the end value) raises SeqAlignError(E_TRACEBACK)."""
         return self._nw_stats_banded("seqalign_nw_stats_banded", batch, scoring, band)
 
     def nw_stats_banded_wide(self, batch, scoring: Scoring, band):

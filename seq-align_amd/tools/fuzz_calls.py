@@ -2,14 +2,18 @@
 """Differential fuzz of the score-family calls against the oracle: seqalign_*_score_batch, seqalign_sw_span_batch, *_score_cross,
 *_score_search, seqalign_sw_span_cross and seqalign_sw_span_search (against sw_span on the explicit batch), seqalign_nw_stats_batch
 (the columns of the oracle's strings) and seqalign_nw_stats_cross (against nw_stats on the explicit batch), seqalign_sw_stats_batch
-(the oracle's first hit and its counted strings) and seqalign_sw_stats_cross (against sw_stats on the explicit batch), *_align_long, the banded NW calls, seqalign_sw_span_banded, seqalign_sw_stats_banded (the oracle's
-banded hit and its counted strings) and (on from the command line, --no-wide leaves them out) the four wide banded score and align calls and seqalign_sw_span_banded_wide, under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+(the oracle's first hit and its counted strings) and seqalign_sw_stats_cross (against sw_stats on the explicit batch), *_align_long, the banded NW calls,
+seqalign_nw_stats_banded (the counted strings of the oracle's walk over the banded matrices; the lowest pair without an alignment inside its
+band named), seqalign_sw_span_banded, seqalign_sw_stats_banded (the oracle's
+banded hit and its counted strings) and (on from the command line, --no-wide leaves them out) the four wide banded score and align calls,
+seqalign_sw_span_banded_wide, seqalign_nw_stats_banded_wide and seqalign_sw_stats_banded_wide (each with its narrow call's bytes on the small pairs), under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
 
-tests/test_gpu_soak_calls.py runs a seeded slice of it (run(seconds, seed, max_trials)) under the `gpu` marker; that slice
-leaves the wide banded calls out (their Python reference on bands past 1 024 diagonals takes most of a second a trial).
+tests/test_gpu_soak_calls.py runs seeded slices of it (run(seconds, seed, max_trials)) under the `gpu` marker; the long slices
+leave the wide banded calls out (their Python reference on bands past 1 024 diagonals takes most of a second a trial), a
+short one runs them.
 """
 import argparse
 import random
@@ -53,6 +57,18 @@ def top_k(score, end_a, end_b, k, min_score):
     return out
 
 
+def walked_along_the_floor(osc, a, b, w, ra, rb):
+    """Whether the strings of the oracle's walk over the banded NW matrices are no alignment of the banded problem: they leave
+    the band, or under no_mismatches they hold a column of two letters that the scoring does not call a match -- the align
+    walker stepping along cells at the floor (include/seqalign_hip.h, banded NW statistics).  seqalign_nw_stats_banded refuses
+    such a pair.  (tests/bandnwstatlib.py states the same rule for the tests; the tool keeps its own and takes from the test
+    helpers only bandlib's geometry and statlib's lookup.)"""
+    if not BL.in_band(ra, rb, len(a), len(b), w):
+        return True
+    look = ST.Lookup(osc)
+    return bool(osc.no_mismatches) and any(x != 45 and y != 45 and not look(x, y)[1] for x, y in zip(ra, rb))
+
+
 SCALE_LOW_BITS = 8      # the drawn factors start at 2^8
 
 
@@ -94,7 +110,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         import maglib as G      # only the scaled runs need it: the default run is what it was, imports included
     ctx = ctx or (None if dry else S.Context(0))
     t_end = time.time() + seconds
-    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span_banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0, "sw_stats_banded": 0}
+    n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span_banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0, "sw_stats_banded": 0,
+         "stats_banded": 0, "stats_banded_none": 0, "stats_banded_wide": 0, "sw_stats_banded_wide": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -102,6 +119,35 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
     def fail(what, spec, *details):
         print(f"{what} MISMATCH", spec, *details, flush=True)
         raise SystemExit(1)
+
+    def nw_stats_banded_check(what, call, narrow, spec, sub, bands, both, n_small):
+        """seqalign_nw_stats_banded(_wide) on pairs whose banded (end value, walk) `both` holds: the end value and the counted
+        columns of the walk's strings; the pairs the oracle does not walk inside their band (walked_along_the_floor
+        included) make the call fail with the lowest of them named, and the rest runs without them.  narrow: the call whose
+        bytes `call` must return on the first n_small pairs.  Returns (pairs equal to the oracle, pairs without an alignment)."""
+        want = [None if x[1] is None or walked_along_the_floor(osc, a, b, w, x[1][1], x[1][2]) else (x[0],) + ST.count_columns(osc, x[1][1], x[1][2])
+                for (a, b), w, x in zip(sub, bands, both)]
+        none = [k for k, x in enumerate(want) if x is None]
+        if none:
+            try:
+                call(W.from_pairs(sub), sc, bands)
+                fail(what + " NONE", spec, sub, bands, none, "no error")
+            except S.SeqAlignError as e:
+                if e.code != S.E_TRACEBACK or f"pair {none[0]}:" not in str(e):
+                    fail(what + " NONE", spec, sub, bands, none, str(e))
+        keep = [k for k in range(len(sub)) if k not in none]
+        if keep:
+            res = call(W.from_pairs([sub[k] for k in keep]), sc, [bands[k] for k in keep])
+            got = ST.got_stats(res)
+            if got != [want[k] for k in keep]:
+                fail(what, spec, [sub[k] for k in keep], [bands[k] for k in keep], got, [want[k] for k in keep])
+            small = [k for k in keep if k < n_small]
+            if narrow is not None and small:
+                wide_res = call(W.from_pairs([sub[k] for k in small]), sc, [bands[k] for k in small])
+                narrow_res = narrow(W.from_pairs([sub[k] for k in small]), sc, [bands[k] for k in small])
+                if any(x.tobytes() != y.tobytes() for x, y in zip(wide_res, narrow_res)):
+                    fail("WIDE / NARROW " + what, spec, [sub[k] for k in small], [bands[k] for k in small])
+        return len(keep), len(none)
 
     while time.time() < t_end and n["trials"] < max_trials:
         v = rng.below(1 << 20, 16).astype(int)
@@ -305,6 +351,10 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                 got = ctx.nw_score_banded(W.from_pairs(sub), sc, bands)
                 if [int(x) for x in got] != [x[0] for x in both]:
                     fail("BAND SCORE", spec, sub, bands, [int(x) for x in got], [x[0] for x in both])
+                # ---- banded NW statistics on the same pairs and bands
+                kept, lost = nw_stats_banded_check("BAND NW STATS", ctx.nw_stats_banded, None, spec, sub, bands, both, 0)
+                n["stats_banded"] += kept
+                n["stats_banded_none"] += lost
                 none = [k for k, x in enumerate(both) if x[1] is None]
                 if none:            # no alignment inside the band: the call says so and names the lowest such pair
                     try:
@@ -369,6 +419,9 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                         if got != [both[k][1] for k in keep]:
                             fail("WIDE BAND ALIGN", spec, "cols", cols, [sub[k] for k in keep], [bands[k] for k in keep], got)
                     n["banded_wide"] += len(keep)
+                    # ---- wide banded NW statistics on the same pairs and bands, and the narrow call's bytes on the small pairs
+                    n["stats_banded_wide"] += nw_stats_banded_check("WIDE BAND NW STATS", ctx.nw_stats_banded_wide, ctx.nw_stats_banded, spec, sub, bands,
+                                                                    both, len(small))[0]
                 shift = int(v[14] % 300) - 150
                 lo = [int(v[5] % 80) - 60] * len(small) + [shift - half]
                 hi = [lo[k] + int(v[6] % 90) for k in range(len(small))] + [shift + half]
@@ -396,6 +449,18 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                     if any(x[:len(small)].tobytes() != y.tobytes() for x, y in zip(res, narrow)):
                         fail("WIDE / NARROW BAND SW SPAN", spec, "cols", cols, sub, lo, hi)
                 n["span_banded_wide"] += len(sub)
+                # ---- wide banded SW statistics on the same pairs and bounds: that hit and its counted strings, and the narrow
+                # call's bytes on the small pairs
+                want7 = [w5 + (ST.count_columns(osc, h["a"].encode(), h["b"].encode()) if h else (0, 0)) for w5, h in zip(want5, hits1)]
+                res = ctx.sw_stats_banded_wide(wb, sc, lo, hi)
+                got7 = [tuple(int(x[k]) for x in res) for k in range(len(sub))]
+                if got7 != want7:
+                    fail("WIDE BAND SW STATS", spec, "cols", cols, sub, lo, hi, got7, want7)
+                if small:
+                    narrow = ctx.sw_stats_banded(W.from_pairs(sub[:len(small)]), sc, lo[:len(small)], hi[:len(small)])
+                    if any(x[:len(small)].tobytes() != y.tobytes() for x, y in zip(res, narrow)):
+                        fail("WIDE / NARROW BAND SW STATS", spec, "cols", cols, sub, lo, hi)
+                n["sw_stats_banded_wide"] += len(sub)
         n["trials"] += 1
 
     if srng is not None:
@@ -403,7 +468,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
               f"({n['redrawn_trials'] / max(1, n['trials']):.1%} of the trials)", flush=True)
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
           f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['sw_stats_banded']} banded SW statistics, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['stats']} NW and {n['sw_stats']} SW statistics, {n['stats_cross']} NW and {n['sw_stats_cross']} SW statistics cross cells, {n['long']} long alignments, {n['banded']} banded "
-          f"alignments (+ {n['banded_none']} with none in their band), {n['banded_wide']} wide banded results and {n['span_banded_wide']} wide banded hit spans identical to the oracle "
+          f"alignments (+ {n['banded_none']} with none in their band), {n['stats_banded']} banded NW statistics (+ {n['stats_banded_none']} with none), {n['banded_wide']} wide banded results, {n['span_banded_wide']} wide banded hit spans, "
+          f"{n['stats_banded_wide']} wide banded NW and {n['sw_stats_banded_wide']} wide banded SW statistics identical to the oracle "
           f"(seed {seed})", flush=True)
     return n
 

@@ -2,9 +2,14 @@
 
 want                what the call must return for one pair: (score, matches, mismatches) -- the banded end value
                     (bandlib.expected_both) and the counted columns (statlib.count_columns) of the oracle's walk over the banded
-                    matrices -- or None where the end value is below INT32_MIN / 2: no alignment inside the band, the call
-                    returns SEQALIGN_E_TRACEBACK.  The rule is the VALUE's; that the oracle's walk never fails at or above it is
-                    asserted here on every pair that passes through;
+                    matrices -- or None where that walk finds no alignment inside the band: the call returns
+                    SEQALIGN_E_TRACEBACK.  The rule is the WALK's: it fails, or (no_mismatches only, the documented family) it
+                    "succeeds" along the floor -- through a blocked letter pair or out of the band (walked_along_the_floor).
+                    The end value does not decide: at large
+                    scales a real score lies below INT32_MIN / 2 (tests/maglib.py, the deep families);
+below_half          the rule the call followed before -- the end value is below INT32_MIN / 2 -- kept for
+                    test_magnitude_argument_cpu.py, which holds the two rules together on every case list of the banded NW
+                    statistics tests that runs under a scoring that forbids moves;
 frame_model         the kernel's bookkeeping (sa_band_nw_stats.hip) in pure Python over payloads (matches,
                     mismatches, mark), values from bandlib.fill: frame positions, the three phases of the feed, the shift, the
                     reset of V AND D of the cell above the right edge, the end pick at position len_a - fc(len_b).  Modelled on
@@ -12,6 +17,8 @@ frame_model         the kernel's bookkeeping (sa_band_nw_stats.hip, DESIGN.md 3.
                     band cell that read one would show it;
 small_pairs         the CPU tier's pairs with a band each: len_a < len_b and len_a > len_b, widths 1 .. max_width;
 flag_pairs          the GPU tier's 40 mixed-case pairs per flag combination, at widths 69 / 70;
+row_flag_triples    the GPU tier's four pairs at width 385 for one flag that changes the row;
+bandless_pair       a sequence and its copy with one substitution: no alignment where mismatches and gaps are forbidden;
 counts_reversed_differ, tie_batch, tie_counts   the tie-dense batches of the GPU tier (statlib.tie_pairs) and, per batch and
                     band, how many pairs change their counts under the reversed priority M > B > A over the BANDED matrices
                     (statlib.walk(mats=...)).
@@ -29,18 +36,35 @@ Z, MARK = (0, 0, False), (0, 0, True)
 BORDER, STOPPED, MOVING = "border", "stopped", "moving"      # the three phases of the feed
 
 
+def below_half(osc, a: bytes, b: bytes, w: int) -> bool:
+    """The former rule: the banded end value is below INT32_MIN / 2."""
+    return BL.expected_both(osc, a, b, w)[0] < HALF
+
+
+def walked_along_the_floor(osc, a: bytes, b: bytes, w: int, ra: bytes, rb: bytes) -> bool:
+    """The documented family (include/seqalign_hip.h, banded NW statistics): under no_mismatches the align walker reads a
+    blocked letter pair as score 0, floor + 0 == floor lets it step from a cell at the floor to any other, cells outside the
+    band included, and the walk "succeeds".  Such strings are no alignment of the banded problem, and they show it: they hold
+    a column of two letters that the scoring does not call a match, or they leave the band (a walk that only follows real
+    candidates never does: outside the band every state holds the floor, which no candidate above the floor descends from)."""
+    if not BL.in_band(ra, rb, len(a), len(b), w):
+        return True
+    look = ST.Lookup(osc)
+    return bool(osc.no_mismatches) and any(x != 45 and y != 45 and not look(x, y)[1] for x, y in zip(ra, rb))
+
+
 def want_walked(osc, a: bytes, b: bytes, w: int):
-    """((score, matches, mismatches), (score, gapped a, gapped b) of the oracle's walk), or None: the end value is below
-    INT32_MIN / 2."""
+    """((score, matches, mismatches), (score, gapped a, gapped b) of the oracle's walk), or None: the oracle's walk over the
+    banded matrices fails, or runs along the floor (walked_along_the_floor)."""
     value, walked = BL.expected_both(osc, a, b, w)
-    if value < HALF:
+    if walked is None or walked_along_the_floor(osc, a, b, w, walked[1], walked[2]):
         return None
-    assert walked is not None and walked[0] == value, (a, b, w, value, walked)      # the value rule loses nothing
+    assert walked[0] == value, (a, b, w, value, walked)
     return (value,) + ST.count_columns(osc, walked[1], walked[2]), walked
 
 
 def want(osc, a: bytes, b: bytes, w: int):
-    """(score, matches, mismatches), or None: the end value is below INT32_MIN / 2."""
+    """(score, matches, mismatches), or None: no alignment inside the band."""
     both = want_walked(osc, a, b, w)
     return None if both is None else both[0]
 
@@ -207,6 +231,29 @@ def flag_pairs(idx: int, flags, alpha: bytes):
         assert BL.width_of(len(a), len(b), w) in (69, 70), (len(a), len(b), w)
         out.append((a, b, w))
     return out
+
+
+ROW_FLAGS = ("no_gaps_in_a", "no_gaps_in_b", "no_mismatches", "no_end")
+
+
+def row_flag_triples(flag: str):
+    """[(a, b, w)], four pairs of 275 .. 300 rows at width 385 (w = 192 on equal lengths, 191 two apart) for one of ROW_FLAGS.
+    len_a > d_hi, so the band's right edge meets the last column."""
+    rng = random.Random(385 + len(flag))
+    out = []
+    for d in (0, 2, -2, 0):                                  # len_b - len_a: even, so that 385 = |d| + 1 + 2 w
+        a = _rand_seq(rng, rng.randrange(275, 300), b"ACGT")
+        b = (BL.mutate(rng, a, 0.08) + _rand_seq(rng, len(a), b"ACGT"))[:len(a) + d]
+        out.append((a, b, 192 - abs(d) // 2))
+    assert all(BL.width_of(len(a), len(b), w) == 385 and len(a) > BL.band_of(len(a), len(b), w)[1] for a, b, w in out)
+    return out
+
+
+def bandless_pair(n: int, at: int):
+    """(s, t): n random letters and the same with the letter at `at` replaced -- under a scoring that forbids mismatches and both
+    kinds of gap the pair has no alignment inside any band."""
+    s = _rand_seq(random.Random(4), n, b"ACGT")
+    return s, s[:at] + bytes([b"ACGT"[(b"ACGT".index(s[at]) + 1) % 4]]) + s[at + 1:]
 
 
 def counts_reversed_differ(osc, a: bytes, b: bytes, w: int) -> bool:

@@ -9,7 +9,8 @@ strip_model         the kernel's schedule (sa_band_nw_stats_strips.hip, DESIGN.m
                     hand-off entry that is never written carry POISON, and the model asserts that no band cell reads one.
                     Modelled on bandnwstatlib.frame_model, whose cell arithmetic this repeats;
 walk_crosses_seam   whether the counted part of an alignment (its cells with x > 0 and y > 0) lies in more than one strip;
-long_pairs          pairs long enough for at least three strips at S = 7, len_a < len_b and len_a > len_b.
+long_pairs          pairs long enough for at least three strips at S = 7, len_a < len_b and len_a > len_b;
+definition_cases    the GPU tier's scorings and pairs of the 32 flag combinations.
 """
 from __future__ import annotations
 
@@ -205,4 +206,24 @@ def long_pairs(seed: int, n: int, alpha: bytes, lo: int = 15, hi: int = 40):
         if len(b) < lo or len(a) < lo or (len(a) < len(b)) != (len(out) % 2 == 0):
             continue
         out.append((a, b, rng.randrange(13)))
+    return out
+
+
+def definition_cases():
+    """[(the ten numbers of a scoring's init, [(a, b, w)])] of the GPU tier's definition test: the 32 flag combinations, eight
+    mixed-case pairs of up to 300 letters each -- seven in ten relatives with 20 % edits -- at w = 0 .. 40, or 150."""
+    import itertools
+    rng = random.Random(1501)
+    alpha = b"ACGTacgt"
+    seq = lambda n: bytes(rng.choice(alpha) for _ in range(n))
+    out = []
+    for idx, flags in enumerate(itertools.product([0, 1], repeat=5)):
+        both_no_gaps = flags[2] and flags[3]
+        init = [1, -6 if both_no_gaps else -2, -4, -1] if idx % 2 else [2, -7 if both_no_gaps else -3, 0, -2]
+        triples = []
+        for k in range(8):
+            a = seq(rng.randrange(0, 301))
+            b = BL.mutate(rng, a, 0.2, alpha)[:300] if rng.random() < 0.7 else seq(rng.randrange(0, 301))
+            triples.append((a, b, 150 if (idx + k) % 11 == 0 else rng.randrange(0, 41)))
+        out.append(([*init, *flags, 0], triples))
     return out

@@ -49,10 +49,24 @@ BASES = {
 FLOOR_BASES = ("floor_a", "floor_b", "floor_mm")
 POWERS = (15, 16, 23, 24, 27)
 TOP = "top"
-# (base, what the peak crosses): a power of two p -- the peak lands in [2^p, 2^(p + 1)) -- or TOP: in [2^30, 2^31)
+DEEP = "deep"
+DEEP_PEAK = 18 * 2 ** 30 // 10      # 1.8 * 2^30
+DEEP_BASES = ("dna", "flat", "mut", "floor_a")
+# (base, what the peak crosses): a power of two p -- the peak lands in [2^p, 2^(p + 1)) -- or TOP: in [2^30, 2^31) -- or DEEP:
+# the largest scale at which it stays at or below 1.8 * 2^30.  TOP takes the SMALLEST scale that reaches 2^30, and on these pairs
+# the peak is a positive cell or a border cell, so no real NW score lies below -2^30 there; under DEEP the long pairs' global
+# scores and banded end values stand in (-2^31, -2^30): real scores below INT32_MIN / 2, far above the floor (NW only; not
+# nomismatch / floor_mm, whose align walker steps along the floor and muddies what "has an alignment" means)
 FAMILIES = tuple(("dna", p) for p in POWERS) + (
     ("open0", 16), ("extpos", 23), ("nostart", 15), ("noend", 24), ("nogaps_a", 24), ("nogaps_b", 27), ("nomismatch", 16),
-    ("mut", 23), ("floor_a", 29), ("floor_b", 29), ("floor_mm", 29), ("steep", TOP), ("flat", TOP), ("extpos", TOP))
+    ("mut", 23), ("floor_a", 29), ("floor_b", 29), ("floor_mm", 29), ("steep", TOP), ("flat", TOP), ("extpos", TOP)) + tuple(
+    (base, DEEP) for base in DEEP_BASES)
+
+
+def nw_only(fam) -> bool:
+    """The families that run under NW alone: the floor families (under SW the floor is the score 0) and the deep ones (their
+    magnitude is a NW score's; SW has no negative cell)."""
+    return fam[0] in FLOOR_BASES or fam[1] == DEEP
 
 
 def family_id(fam) -> str:
@@ -357,9 +371,11 @@ def base_peak(base: str, shape: str, is_sw: int) -> int:
 
 def scale_for(fam, shape: str, is_sw: int) -> int:
     """The smallest scale (+ 1 for the powers: the low bits are populated too) at which the largest cell of the shape's pairs
-    reaches 2^p (TOP: 2^30)."""
+    reaches 2^p (TOP: 2^30); DEEP: the largest at which it stays at or below 1.8 * 2^30."""
     base, what = fam
     bp = base_peak(base, shape, is_sw)
+    if what == DEEP:
+        return DEEP_PEAK // bp
     return -(-2 ** 30 // bp) if what == TOP else -(-2 ** what // bp) + 1
 
 
@@ -367,11 +383,11 @@ _CASES = None
 
 
 def cases():
-    """Every case of the matrix.  The floor families are NW only: under SW the floor is the score 0."""
+    """Every case of the matrix.  The floor and the deep families are NW only (nw_only)."""
     global _CASES
     if _CASES is None:
         _CASES = [Case(fam, shape, kind, is_sw, scale_for(fam, shape, is_sw))
-                  for fam in FAMILIES for shape, _, _ in SHAPES for is_sw in (0, 1) if not (is_sw and fam[0] in FLOOR_BASES)
+                  for fam in FAMILIES for shape, _, _ in SHAPES for is_sw in (0, 1) if not (is_sw and nw_only(fam))
                   for kind in kinds_of(shape)]
     return _CASES
 

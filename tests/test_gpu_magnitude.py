@@ -10,16 +10,22 @@ The row sweeps de-trend gap_b (sa_rowsweep.hpp), which adds up to a frame's widt
 never forms.  The library refuses, before any launch and with SEQALIGN_E_DOMAIN, the scorings whose documented bound
 (include/seqalign_hip.h; maglib.admitted restates it independently) leaves int32 there; the tests assert the reference's
 result on one side of that bound and the refusal on the other, for every call.
+
+Sections G and H run the statistics calls, the span and statistics calls over sets and the banded statistics and span calls:
+their payload sweeps carry counts and spans beside the values and decide on the values which payload a cell inherits.  The deep
+families (NW only) put real scores into (-2^31, -2^30), below INT32_MIN / 2 and above the floor.
 """
 import numpy as np
 import pytest
 
 import bandlib as BL
+import bandnwstatlib as BN
 import bandspanlib as BSP
 import bandswlib as BS
 import denselib as D
 import maglib as G
 import orclib as O
+import statlib as ST
 import seqalign_amd as S
 from seqalign_amd import workloads as W
 
@@ -27,7 +33,7 @@ pytestmark = pytest.mark.gpu
 
 KERNELS = [S.KERNEL_WAVEFRONT, S.KERNEL_ROWSCAN, S.KERNEL_STREAM, S.KERNEL_STRIPS, S.KERNEL_WGSTREAM]
 FAMS = pytest.mark.parametrize("fam", G.FAMILIES, ids=G.family_id)
-FAMS_SW = pytest.mark.parametrize("fam", [f for f in G.FAMILIES if f[0] not in G.FLOOR_BASES], ids=G.family_id)      # the floor families are NW only
+FAMS_SW = pytest.mark.parametrize("fam", [f for f in G.FAMILIES if not G.nw_only(f)], ids=G.family_id)      # the floor and the deep families are NW only
 PACKED = ("fill_nw_dirs_x2", "fill_nw_dirs_x4", "fill_sw_dirs_x2", "fill_sw_best_x2", "fill_sw_best_x4", "sweep_dirs_x2")
 STRIP = 64
 LONG_ROWS = 8           # three blocks at len_b = 24, twelve at 96
@@ -73,6 +79,18 @@ def want(kind, c, *args):
         elif kind == "sw_band":
             cell, fields = BSP.want(osc, c.a, c.b, *args)
             v = (cell, fields, BS.expected(osc, c.a, c.b, *args, thr(c))[1])
+        elif kind == "nw_stats":                # the oracle's score and the counted columns of its strings
+            s, ra, rb = want("nw", c)
+            v = (s,) + ST.count_columns(osc, ra, rb)
+        elif kind == "sw_stats":                # the oracle's first hit at min_score = 1 and the counted columns of its strings
+            v = stats_of(osc, (want("sw", c, 1, 1) or [None])[0])
+        elif kind == "nw_band_stats":           # (the banded end value, its three statistics or None: no walk inside the band)
+            value, walked = want("nw_band", c, *args)
+            if walked is not None and BN.walked_along_the_floor(osc, c.a, c.b, *args, walked[1], walked[2]):
+                walked = None                   # the documented family under no_mismatches: no alignment of the banded problem
+            v = (value, None if walked is None else (walked[0],) + ST.count_columns(osc, walked[1], walked[2]))
+        elif kind == "sw_band_stats":           # the banded hit at min_score = 1 and its counted strings
+            v = stats_of(osc, BS.expected(osc, c.a, c.b, *args, 1)[1])
         _WANT[key] = v
     return _WANT[key]
 
@@ -82,13 +100,41 @@ def thr(c):
     return 4 * c.spec["init"][0]
 
 
+def stats_of(osc, hit):
+    """The seven words of the SW statistics calls for an oracle hit (or none): its five fields and its strings' counts."""
+    return BSP.fields(hit) + (ST.count_columns(osc, hit["a"].encode(), hit["b"].encode()) if hit else (0, 0))
+
+
+def want_set(cs, i, j, is_sw):
+    """The oracle's answer for seq_a of case i against seq_b of case j of one group, once for the whole file: NW (score,
+    matches, mismatches); SW the seven words of the first hit at min_score = 1."""
+    key = ("set", cs[i].id, cs[j].id, is_sw)
+    if key not in _WANT:
+        osc = cs[0].osc()
+        if is_sw:
+            rc, hits = O.oracle_sw(osc, cs[i].a, cs[j].b, 1, 1)
+            assert rc == 0
+            _WANT[key] = stats_of(osc, hits[0] if hits else None)
+        else:
+            rc, score, ra, rb = O.oracle_nw(osc, cs[i].a, cs[j].b)
+            assert rc == 0, key
+            _WANT[key] = (score,) + ST.count_columns(osc, ra, rb)
+    return _WANT[key]
+
+
+# per call name, over the whole file: [calls equal to the oracle, calls refused with E_DOMAIN], and the families that ran
+CALL_COUNTS, FAMILIES_RUN = {}, set()
+
+
 class Tally:
     """Collects what went wrong over a test's calls, so that one run names every call that differs."""
 
     def __init__(self):
         self.bad, self.exact, self.refused = [], 0, 0
 
-    def attempt(self, label, admitted, call, verify):
+    def attempt(self, label, admitted, call, verify, name=None):
+        """name: the call counted in CALL_COUNTS besides (results only: an expected SEQALIGN_E_TRACEBACK goes without)."""
+        per_call = CALL_COUNTS.setdefault(name, [0, 0]) if name else [0, 0]
         try:
             got = call()
         except S.SeqAlignError as e:
@@ -96,6 +142,7 @@ class Tally:
                 self.bad.append((label, f"raised {str(e)[:160]}"))
             else:
                 self.refused += 1
+                per_call[1] += 1
             return
         if not admitted:
             self.bad.append((label, "no SEQALIGN_E_DOMAIN for a scoring outside the documented bound"))
@@ -105,6 +152,7 @@ class Tally:
             self.bad.append((label, msg))
         else:
             self.exact += 1
+            per_call[0] += 1
 
     def done(self, what):
         print(f"{what}: {self.exact} calls equal to the oracle, {self.refused} refused with E_DOMAIN")
@@ -368,3 +416,180 @@ def test_banded_calls(ctx, fam):
                         ok, codes = same_status(calls[1][1], calls[0][1])
                         assert ok, (shape, k, codes)
     t.done(G.family_id(fam))
+
+
+# ------------------------------------------------------------------------- G. the statistics calls and the calls over sets ---
+NEW_CALLS = ("nw_stats", "nw_stats_cross", "sw_stats", "sw_stats_cross", "sw_span_cross", "sw_span_search", "nw_stats_banded",
+             "sw_stats_banded", "nw_stats_banded_wide", "sw_stats_banded_wide", "sw_span_banded_wide")
+
+
+def rows_of(res, n):
+    return [tuple(int(x[p]) for x in res) for p in range(n)]
+
+
+def form_of(ran, la):
+    """The payload sweeps (span, statistics) take a seq_a of up to 512 letters in one wave and strips beyond: the shapes of
+    1 001 and of 1 101 columns run as strips, and nothing else does."""
+    return None if set(ran) == ({"score_strips"} if la > 512 else {"score_rows"}) else f"wrong form: {ran}"
+
+
+@FAMS
+def test_stats_calls(ctx, fam):
+    """nw_stats: the oracle's score and the counted columns of its strings; sw_stats: the five fields of the oracle's first hit
+    at min_score = 1 and the counts of its strings.  One wave per pair up to 512 columns, strips beyond -- recorded as
+    score_strips on the shape of 1 101 columns (and of 1 001), as score_rows on the others."""
+    t = Tally()
+    for shape, is_sw, cs, batch, sc, la, lb in group_of(fam):
+        adm = G.admitted(cs[0].spec, la, lb, "score")
+        name = "sw_stats" if is_sw else "nw_stats"
+        wanted = [want(name, c) for c in cs]
+        fn = ctx.sw_stats if is_sw else ctx.nw_stats
+        t.attempt((shape, name), adm, lambda: (rows_of(fn(batch, sc), len(cs)), ctx.last_call()),
+                  lambda r: first_diff(r[0], wanted) or form_of(r[1], la), name)
+    FAMILIES_RUN.add(("stats", fam))
+    t.done(G.family_id(fam))
+
+
+def top_k(matrix, k, min_score):
+    """The search calls' contract on an expected matrix of tuples (score first): per query the targets with score >= min_score,
+    score descending then target ascending, the first k."""
+    out = []
+    for row in matrix:
+        order = sorted((j for j, x in enumerate(row) if x[0] >= min_score), key=lambda j: (-row[j][0], j))[:k]
+        out.append([(j,) + row[j][:5] for j in order])
+    return out
+
+
+@FAMS
+def test_stats_and_span_over_sets(ctx, fam):
+    """nw_stats_cross, sw_stats_cross and sw_span_cross: every seq_a of a group against every seq_b, from oracle fills and
+    walks.  sw_span_search with k = 3 at min_score = 1 and at four matches: sw_score_search's order (score descending, then
+    target ascending) over the expected matrix, spans taken from it."""
+    t = Tally()
+    for shape, is_sw, cs, batch, sc, la, lb in group_of(fam):
+        adm = G.admitted(cs[0].spec, la, lb, "score")      # the longest query and the longest target
+        n = len(cs)
+        q, tg = W.seqset_from([c.a for c in cs]), W.seqset_from([c.b for c in cs])
+        wanted = [[want_set(cs, i, j, is_sw) for j in range(n)] for i in range(n)]
+        grid = lambda res: [[tuple(int(x[i, j]) for x in res) for j in range(n)] for i in range(n)]
+        same = lambda w: lambda got: None if got == w else f"differs: got {got}, oracle {w}"
+        if not is_sw:
+            t.attempt((shape, "nw_stats_cross"), adm, lambda: grid(ctx.nw_stats_cross(q, tg, sc)), same(wanted), "nw_stats_cross")
+            continue
+        t.attempt((shape, "sw_stats_cross"), adm, lambda: grid(ctx.sw_stats_cross(q, tg, sc)), same(wanted), "sw_stats_cross")
+        t.attempt((shape, "sw_span_cross"), adm, lambda: grid(ctx.sw_span_cross(q, tg, sc)), same([[x[:5] for x in row] for row in wanted]),
+                  "sw_span_cross")
+        for min_score in (1, thr(cs[0])):
+            def search():
+                n_hits, hits = ctx.sw_span_search(q, tg, sc, 3, min_score=min_score)
+                assert hits.dtype == S.SPAN_HIT and hits.shape == (n, 3)
+                return [[tuple(int(h[f]) for f in ("target", "score", "pos_a", "pos_b", "len_a", "len_b")) for h in hits[i, :int(n_hits[i])]]
+                        for i in range(n)]
+            t.attempt((shape, "sw_span_search", min_score), adm, search, same(top_k(wanted, 3, min_score)), "sw_span_search")
+    FAMILIES_RUN.add(("sets", fam))
+    t.done(G.family_id(fam))
+
+
+# ------------------------------------------------------------------------------- H. the banded statistics and span calls ---
+SPAN_BAND_MAX_WIDTH = 512       # SEQALIGN_SPAN_BAND_MAX_WIDTH: the narrow statistics and span calls' cap
+
+
+def traceback_or(fn):
+    """fn's result, or the message of its SEQALIGN_E_TRACEBACK; any other error passes through."""
+    def call():
+        try:
+            return fn()
+        except S.SeqAlignError as e:
+            if e.code != S.E_TRACEBACK:
+                raise
+            return str(e)
+    return call
+
+
+def same_bytes(narrow, wide):
+    """Two calls' results array by array, byte for byte -- or both raise the same code."""
+    out = []
+    for fn in (narrow, wide):
+        try:
+            out.append(b"".join(x.tobytes() for x in fn()))
+        except S.SeqAlignError as e:
+            out.append(e.code)
+    return out[0] == out[1], [x if isinstance(x, int) else len(x) for x in out]
+
+
+@FAMS
+def test_banded_stats_and_span_calls(ctx, fam):
+    """nw_stats_banded, sw_stats_banded and the three wide forms at strips of 64 columns, under test_banded_calls' three bands
+    per pair.  NW: bandlib.expected_both's end value and the counted strings of the oracle's walk over the banded matrices;
+    where that walk fails the call returns SEQALIGN_E_TRACEBACK naming the lowest such pair, and the group runs again without
+    those pairs.  SW: the banded hit at min_score = 1 and its counted strings.  The narrow calls take at most 512 diagonals and
+    run where the group's widths allow; there narrow and wide agree on bytes and on status.
+    Under the deep families the banded end values of the long shapes stand below INT32_MIN / 2 and the oracle still walks
+    them: the value alone does not tell whether a pair has an alignment inside its band."""
+    t = Tally()
+    deep = 0
+    for shape, is_sw, cs, batch, sc, la, lb in group_of(fam):
+        adm = G.admitted(cs[0].spec, la, lb, "band")
+        for k in range(3):
+            if is_sw:
+                n = len(cs)
+                lo, hi = (np.array(v, np.int32) for v in zip(*[sw_band_of(c, k) for c in cs]))
+                w7 = [want("sw_band_stats", c, *sw_band_of(c, k)) for c in cs]
+                narrow = max(BS.width_of(len(c.a), len(c.b), *sw_band_of(c, k)) for c in cs) <= SPAN_BAND_MAX_WIDTH
+                with ctx.options(band_strip_cols=STRIP):
+                    t.attempt((shape, k, "sw_stats_banded_wide"), adm, lambda: rows_of(ctx.sw_stats_banded_wide(batch, sc, lo, hi), n),
+                              lambda g: first_diff(g, w7), "sw_stats_banded_wide")
+                    t.attempt((shape, k, "sw_span_banded_wide"), adm, lambda: rows_of(ctx.sw_span_banded_wide(batch, sc, lo, hi), n),
+                              lambda g: first_diff(g, [x[:5] for x in w7]), "sw_span_banded_wide")
+                    if narrow:
+                        t.attempt((shape, k, "sw_stats_banded"), adm, lambda: rows_of(ctx.sw_stats_banded(batch, sc, lo, hi), n),
+                                  lambda g: first_diff(g, w7), "sw_stats_banded")
+                        for a_, b_ in ((ctx.sw_stats_banded, ctx.sw_stats_banded_wide), (ctx.sw_span_banded, ctx.sw_span_banded_wide)):
+                            ok, what = same_bytes(lambda: a_(batch, sc, lo, hi), lambda: b_(batch, sc, lo, hi))
+                            assert ok, (shape, k, a_.__name__, what)
+                continue
+            bands = [nw_band_of(c, k) for c in cs]
+            both = [want("nw_band_stats", c, w) for c, w in zip(cs, bands)]
+            calls = [("nw_stats_banded_wide", ctx.nw_stats_banded_wide)]
+            if max(BL.width_of(len(c.a), len(c.b), w) for c, w in zip(cs, bands)) <= SPAN_BAND_MAX_WIDTH:
+                calls.append(("nw_stats_banded", ctx.nw_stats_banded))
+            none = [p for p, x in enumerate(both) if x[1] is None]
+            keep = [p for p in range(len(cs)) if p not in none]
+            kept = W.from_pairs([(cs[p].a, cs[p].b) for p in keep]) if none and keep else batch
+            bw, bw_kept = np.array(bands, np.uint32), np.array([bands[p] for p in keep], np.uint32)
+            wanted = [both[p][1] for p in keep]
+            with ctx.options(band_strip_cols=STRIP):
+                for name, fn in calls:
+                    if none:        # no alignment inside the band: the call says so and names the lowest such pair
+                        t.attempt((shape, k, name, "none"), adm, traceback_or(lambda: fn(batch, sc, bw)),
+                                  lambda g: None if isinstance(g, str) and f"pair {none[0]}:" in g else f"pairs {none} have no walk: got {g}")
+                    if keep:
+                        before = t.exact
+                        t.attempt((shape, k, name), adm, lambda: rows_of(fn(kept, sc, bw_kept), len(keep)),
+                                  lambda g: first_diff(g, wanted), name)
+                        deep += (t.exact > before) * sum(x[0] < -2 ** 30 for x in wanted)
+                if len(calls) == 2:
+                    ok, what = same_bytes(lambda: calls[1][1](batch, sc, bw), lambda: calls[0][1](batch, sc, bw))
+                    assert ok, (shape, k, what)
+                    if none and keep:
+                        ok, what = same_bytes(lambda: calls[1][1](kept, sc, bw_kept), lambda: calls[0][1](kept, sc, bw_kept))
+                        assert ok, (shape, k, what)
+    print(f"{G.family_id(fam)}: {deep} banded NW statistics below -2^30 equal to the oracle's walk")
+    FAMILIES_RUN.add(("banded", fam))
+    t.done(G.family_id(fam))
+    if fam[1] == G.DEEP:
+        assert deep > 0, "no banded statistics result below -2^30 from a deep family"
+
+
+def test_every_new_call_met_both_sides():
+    """Over the whole matrix each of the eleven calls of sections G and H returned the oracle's answer at least once and was
+    refused with SEQALIGN_E_DOMAIN at least once (tests/test_magnitude_argument_cpu.py argues on the CPU that the matrix holds
+    such groups).  Counted over the tests of sections G and H; where not all of them ran before this one in the same process
+    (a selection, another order, several workers) there is nothing to assert and the test skips."""
+    print({name: tuple(CALL_COUNTS.get(name, (0, 0))) for name in NEW_CALLS})
+    missing = {(sec, f) for sec in ("stats", "sets", "banded") for f in G.FAMILIES} - FAMILIES_RUN
+    if missing:
+        pytest.skip(f"{len(missing)} (section, family) tests of sections G and H did not run before this one in this process")
+    for name in NEW_CALLS:
+        exact, refused = CALL_COUNTS.get(name, (0, 0))
+        assert exact > 0 and refused > 0, (name, exact, refused)

@@ -1,8 +1,8 @@
 """GPU tier: banded NW statistics -- seqalign_nw_stats_banded (sa_band_nw_stats.hip, sa_batch_band.hip).
 
 Every result is checked three ways (check): bit for bit against the oracle -- the banded end value and the counted columns of
-its walk over the banded matrices (bandnwstatlib.want), or SEQALIGN_E_TRACEBACK naming the lowest pair whose end value is below
-INT32_MIN / 2; the score against ctx.nw_score_banded on the same batch; and all three values against ctx.nw_stats for every pair
+its walk over the banded matrices (bandnwstatlib.want), or SEQALIGN_E_TRACEBACK naming the lowest pair that has no
+alignment inside its band; the score against ctx.nw_score_banded on the same batch; and all three values against ctx.nw_stats for every pair
 whose band is the whole matrix.  Shapes are the smallest at which the frame can go wrong: len_b >= -d_lo + 70, so that the frame
 moves across a 64-row code fetch; every width at which the columns per lane step up, both sides of it; len_a above, below and
 beside len_b; the alignment along the band's left edge, its right edge and its middle."""
@@ -190,19 +190,13 @@ def test_all_flag_combinations_at_width_70(ctx, idx):
     assert lost <= BN.FLAG_N // 4 and (lost == 0 or flags[2] or flags[3] or flags[4]), (flags, lost)
 
 
-@pytest.mark.parametrize("flag", ["no_gaps_in_a", "no_gaps_in_b", "no_mismatches", "no_end"])
+@pytest.mark.parametrize("flag", BN.ROW_FLAGS)
 def test_flags_that_change_the_row_at_eight_columns_per_lane(ctx, flag):
     """Width 385 (w = 192 on equal lengths, 191 two apart), 275 .. 300 rows.  len_a > d_hi, so the band's right edge meets the
     last column (row len_a - d_hi): under no_end_gap_penalty gap_a of that cell reads the cell above -- outside the band --
     through D."""
     sc, osc = scoring(PLAIN, **{flag: 1})
-    rng = random.Random(385 + len(flag))
-    triples = []
-    for d in (0, 2, -2, 0):                                 # len_b - len_a: even, so that 385 = |d| + 1 + 2 w
-        a = rand_seq(rng, rng.randrange(275, 300))
-        b = (BL.mutate(rng, a, 0.08) + rand_seq(rng, len(a)))[:len(a) + d]
-        triples.append((a, b, 192 - abs(d) // 2))
-    assert all(BL.width_of(len(a), len(b), w) == 385 and len(a) > BL.band_of(len(a), len(b), w)[1] for a, b, w in triples)
+    triples = BN.row_flag_triples(flag)
     want = check(ctx, sc, osc, triples)
     assert sum(x is not None for x in want) >= 3, want
 
@@ -348,9 +342,8 @@ def test_the_lowest_failing_pair_decides_between_traceback_and_unknown_pair(ctx)
     sc = S.make_scoring({"preset": "DNA_hybridization",
                          "flags": {"no_mismatches": True, "no_gaps_in_a": True, "no_gaps_in_b": True}})
     osc = O.Scoring.from_buffer_copy(bytes(sc))
-    rng = random.Random(4)
-    a = rand_seq(rng, 120)
-    bandless = (a, a[:60] + bytes([b"ACGT"[(b"ACGT".index(a[60]) + 1) % 4]]) + a[61:])
+    bandless = BN.bandless_pair(120, 60)
+    a = bandless[0]
     unknown = (a[:50] + b"Z" + a[51:], a[:50] + b"Z" + a[51:])
     good = (a, a)
     assert BN.want(osc, *good, 8) == (BN.want(osc, *good, 8)[0], 120, 0) and BN.want(osc, *bandless, 8) is None

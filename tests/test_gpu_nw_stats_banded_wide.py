@@ -2,10 +2,9 @@
 
 The contract is seqalign_nw_stats_banded's at any width.  Results are checked bit for bit against the oracle (bandnwstatlib.want:
 the banded end value and the counted columns of its walk over the banded matrices, or SEQALIGN_E_TRACEBACK naming the lowest pair
-whose end value is below INT32_MIN / 2), the score against ctx.nw_score_banded_wide, and all three arrays against
+that has no alignment inside its band), the score against ctx.nw_score_banded_wide, and all three arrays against
 ctx.nw_stats_banded byte for byte wherever the narrow call accepts the batch.  Unless stated the strips are forced to 64 columns
 (option band_strip_cols), so that small pairs have several strips.  No call may return the hand-off time-out."""
-import itertools
 import json
 import random
 from pathlib import Path
@@ -15,6 +14,7 @@ import pytest
 
 import bandlib as BL
 import bandnwstatlib as BN
+import bandnwstatwidelib as BW
 import denselib as D
 import orclib as O
 import seqalign_amd as S
@@ -90,19 +90,14 @@ def check(ctx, sc, osc, triples, want=None):
 
 # ---------------------------------------------------------------- 1. the definition --
 def test_definition_all_flag_combinations(ctx):
-    rng = random.Random(1501)
+    """bandnwstatwidelib.definition_cases; which of its pairs have no alignment inside their band is held against the end
+    value on the oracle in test_magnitude_argument_cpu.py."""
     n_none = 0
+    cases = BW.definition_cases()
+    assert len(cases) == 32
     with ctx.options(band_strip_cols=64):
-        for idx, flags in enumerate(itertools.product([0, 1], repeat=5)):
-            both_no_gaps = flags[2] and flags[3]
-            init = [1, -6 if both_no_gaps else -2, -4, -1] if idx % 2 else [2, -7 if both_no_gaps else -3, 0, -2]
-            sc, osc = scoring([*init, *flags])
-            triples = []
-            for k in range(8):
-                la = rng.randrange(0, 301)
-                a = rand_seq(rng, la, b"ACGTacgt")
-                b = BL.mutate(rng, a, 0.2, b"ACGTacgt")[:300] if rng.random() < 0.7 else rand_seq(rng, rng.randrange(0, 301), b"ACGTacgt")
-                triples.append((a, b, 150 if (idx + k) % 11 == 0 else rng.randrange(0, 41)))
+        for init, triples in cases:
+            sc, osc = scoring(init)
             want = check(ctx, sc, osc, triples)
             n_none += sum(x is None for x in want)
     assert n_none > 0
@@ -320,9 +315,8 @@ def test_unknown_pair_no_walk_and_their_order(ctx):
         strict = S.make_scoring({"preset": "DNA_hybridization",
                                  "flags": {"no_mismatches": True, "no_gaps_in_a": True, "no_gaps_in_b": True}})
         ostrict = O.Scoring.from_buffer_copy(bytes(strict))
-        rng = random.Random(4)
-        c = rand_seq(rng, 200)
-        bandless = (c, c[:160] + bytes([b"ACGT"[(b"ACGT".index(c[160]) + 1) % 4]]) + c[161:])      # a substitution in strip 2
+        bandless = BN.bandless_pair(200, 160)      # a substitution in strip 2
+        c = bandless[0]
         unknown = (c[:150] + b"Z" + c[151:], c[:150] + b"Z" + c[151:])
         same = (c, c)
         assert BN.want(ostrict, *same, 8)[1:] == (200, 0) and BN.want(ostrict, *bandless, 8) is None

@@ -58,3 +58,27 @@ def test_fuzz_calls_slice_at_large_scores(ctx):
     assert 4 * r["redrawn_trials"] <= r["trials"], r
     for family in ("score", "cross", "search", "long", "banded", "nw_trials", "wide", "span", "span_banded"):
         assert r[family] > 0, (family, r)
+
+
+WIDE_TRIALS = 12
+
+
+def test_fuzz_calls_slice_with_the_wide_banded_calls(ctx):
+    """A short slice with wide_calls=True: the *_banded_wide calls -- the score, align and span forms and the NW and SW
+    statistics -- on two small pairs (where each must return its narrow call's bytes) and one pair of 1 025 .. 1 624 columns
+    whose band is 700 .. 1 500 diagonals wide, under a random strip width; the narrow banded NW statistics run in every slice.
+    12 trials.  Their Python and oracle reference side alone -- the draws of this recipe, the fills, walks and banded
+    definitions each block computes, no device: 1.7 s for the 12 trials (0.10 to 0.24 s a trial, of which the wide block
+    0.08 to 0.16 s)."""
+    spec = importlib.util.spec_from_file_location("soak_fuzz_calls", TOOLS / "fuzz_calls.py")
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    before = ctx.get_option("band_strip_cols"), ctx.get_option("long_block_rows")
+    try:
+        r = fz.run(seconds=40.0, seed=20261021, max_trials=WIDE_TRIALS, ctx=ctx, wide_calls=True)
+    except SystemExit as e:
+        pytest.fail(f"fuzz_calls mismatch with the wide calls; the failing case is in the captured output (exit {e.code})")
+    assert (ctx.get_option("band_strip_cols"), ctx.get_option("long_block_rows")) == before
+    assert r["trials"] == WIDE_TRIALS, r
+    for family in ("stats_banded", "stats_banded_wide", "sw_stats_banded_wide", "banded_wide", "span_banded_wide", "nw_trials"):
+        assert r[family] > 0, (family, r)

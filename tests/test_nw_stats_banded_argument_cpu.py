@@ -5,8 +5,9 @@
    gives the banded end value and the counted columns of the oracle's walk over the banded matrices (bandnwstatlib.want), under
    all 32 flag combinations, the three tie scorings and a gap that pays; no band cell reads a position that holds no band cell
    (the model carries POISON there and asserts); every phase of the feed is hit, with len_a < len_b and len_a > len_b.
-2. The mark agrees with the value: the model's end state carries the mark exactly where the end value is below INT32_MIN / 2.
-   The oracle agrees with the value: its walk never fails at or above INT32_MIN / 2 (asserted inside bandnwstatlib.want).
+2. The mark is the rule (bandnwstatlib.want: the oracle's walk, less the documented family).  On these scorings of small numbers
+   it agrees with the value: the model's end state carries the mark exactly where the end value is below INT32_MIN / 2, which is
+   what the call went by before (tests/test_magnitude_argument_cpu.py has the scorings of large numbers, where the two part).
 3. The documented family: pairs on which the oracle's walk "succeeds" although the end value is at the floor (no_mismatches:
    the walker reads a blocked letter pair as score 0).  The call returns SEQALIGN_E_TRACEBACK for them; they occur here.
 4. Conditions on the GPU tier's inputs, on the oracle alone: every tie batch and band holds a pair whose counts change under the
@@ -32,8 +33,8 @@ def osc_of(spec):
 
 
 def model_and_want(osc, a, b, w):
-    """(the model's three values or None by ITS mark, the wanted three or None by the VALUE); the mark must agree with the
-    value."""
+    """(the model's three values or None by ITS mark, the wanted three or None by the oracle's WALK); the mark must agree
+    with the walk, and here, at small numbers, with the value."""
     got, mark, phases = BN.frame_model(osc, a, b, w, 8)
     want = BN.want(osc, a, b, w)
     assert mark == (got[0] < BN.HALF) == (want is None), (a, b, w, got, mark, want)

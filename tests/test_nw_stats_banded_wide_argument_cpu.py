@@ -31,7 +31,7 @@ def pairs_of(seed, n_small, n_long, alpha):
 
 
 def models_and_want(osc, a, b, w, total):
-    """The wanted three (None by the VALUE) after checking that the model gives them at every strip width; adds the coverage of
+    """The wanted three (None by the oracle's WALK, which at these small numbers is also the value's rule) after checking that the model gives them at every strip width; adds the coverage of
     every run to `total`."""
     both = BN.want_walked(osc, a, b, w)
     want = None if both is None else both[0]
