@@ -953,7 +953,7 @@ int seqalign_nw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  * 32 bytes; so the device bytes per pair are
  *     len_a + len_b + 96 + strips (32 width + 36) + 20,      strips = max(1, ceil(len_a / S)).
  * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
- * strip) waves.  Kernel: sa_band_sw_stats_strips.hip.  For many short pairs within 512 diagonals the narrow
+ * strip) waves.  Kernel: sa_band_frame.hpp by sa_band_stats.hip.  For many short pairs within 512 diagonals the narrow
  * call is the faster one.  Past 65 535 letters the five span integers come from seqalign_sw_span_banded_wide below; no SW
  * statistics past 65 535 letters, no cross, search, _multi, _submit, timing-hook or command-line form. */
 int seqalign_sw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
@@ -974,7 +974,7 @@ int seqalign_sw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  * bytes; so the device bytes per pair are
  *     len_a + len_b + 88 + strips (32 width + 36) + 20,      strips = max(1, ceil(len_a / S)).
  * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
- * strip) waves.  Kernel: sa_band_span_strips.hip; all four strip widths run without scratch.  This is the
+ * strip) waves.  Kernel: sa_band_frame.hpp by sa_band_span.hip; all four strip widths run without scratch.  This is the
  * cheap way to the start of a hit in long sequences with an indel-widened band: the align call stores 12 bytes per band cell,
  * the wide score call gives the end only.  For many short pairs within 512 diagonals the narrow call is the faster one.
  * No option, kind or constant of its own; no cross, search, _multi, _submit, timing-hook or command-line form. */

@@ -48,67 +48,13 @@
 //   d_lo; no border cell is stored (BandSwAccess reads them, like the cells outside the band, as 0).  It reports the best
 //   cell itself, as the score form does.
 //   Walk: traceback_kernel's SW walk from the best cell until the score is 0, pos / len / length as it reports them.
-#include "sa_strips.hpp"   // wave_max_i32, wave_min_u64
+#include "sa_band_pipe.hpp"   // wave_shl1, frame_shift, BandBest
 #include "sa_trace_common.hpp"
 
 namespace sa {
 
-// Full-wave shift left by one lane: lane l receives src of lane l + 1, lane 63 receives lane63_value.  DPP ctrl 0x130 =
-// wave_shl:1, the mirror of wave_shr1 (sa_fill_common.hpp).
-__device__ __forceinline__ int wave_shl1(int src, int lane63_value) {
-  return __builtin_amdgcn_update_dpp(lane63_value, src, 0x130, 0xf, 0xf, false);
-}
-
-template <int N>
-__device__ __forceinline__ void frame_shift(int (&a)[N], int enters) {
-  const int first = a[0];
-#pragma unroll
-  for (int c = 0; c + 1 < N; ++c) a[c] = a[c + 1];
-  a[N - 1] = wave_shl1(first, enters);
-}
-
 __host__ __device__ __forceinline__ const SaBandParams &band_params(const SaBandParams &p) { return p; }
 __host__ __device__ __forceinline__ const SaBandParams &band_params(const SaBandSwParams &p) { return p.b; }
-
-// banded SW: the running best of match_scores per frame position, and of the columns that have left the frame
-template <int CPL>
-struct BandBest {
-  int s[CPL], r[CPL];                     // of the column each of my positions holds: best value, first row that reached it
-  int ret_s = 0, ret_col = 0, ret_row = 0;   // of the columns left of the frame (wave-uniform)
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) { s[c] = 0; r[c] = 0; }
-  }
-  // the frame moves off column `col`: it retires (a tie stays with the retired, lower columns), the others shift with the frame
-  __device__ __forceinline__ void retire(int col) {
-    const int s0 = read_lane(s[0], 0), r0 = read_lane(r[0], 0);
-    if (s0 > ret_s) { ret_s = s0; ret_col = col; ret_row = r0; }
-    frame_shift(s, 0);
-    frame_shift(r, 0);
-  }
-  __device__ __forceinline__ void row(const int (&mv)[CPL], uint32_t j, int ncol) {
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-      const bool up = c < ncol && mv[c] > s[c];   // strict: the first (lowest) row keeps a tie
-      s[c] = up ? mv[c] : s[c];
-      r[c] = up ? (int)j : r[c];
-    }
-  }
-  // the pair's best in hit order; my position c holds column col0 + c.  score 0: key ~0
-  __device__ __forceinline__ void reduce(int col0, int &score, unsigned long long &key) const {
-    int b = 0;
-    unsigned long long kb = ~0ull;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c)   // c ascending, strict >: the lowest column wins a tie
-      if (s[c] > b) { b = s[c]; kb = ((unsigned long long)(uint32_t)(col0 + c) << 32) | (uint32_t)r[c]; }
-    score = wave_max_i32(b);
-    key = wave_min_u64(b == score && score > 0 ? kb : ~0ull);
-    if (ret_s >= score && ret_s > 0) {   // a tie goes to the lower column: a retired one
-      score = ret_s;
-      key = ((unsigned long long)(uint32_t)ret_col << 32) | (uint32_t)ret_row;
-    }
-  }
-};
 
 // The sweep of both band families.  SW = false: banded NW.  SW = true: banded SW (header).
 template <int CPL, int SUBST, bool GENERAL, bool FILL, bool SW = false>

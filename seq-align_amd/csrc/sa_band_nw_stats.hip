@@ -7,7 +7,7 @@
 // band_nw_stats_rows_kernel<CPL, SUBST, GENERAL>: one wave per pair, 4 pairs per workgroup, a frame of F = 64 x CPL positions,
 // CPL from {1 .. 6, 8} by the launch's widest band.  Position g = lane * CPL + c holds column fc(j) + g on row j, fc(j) =
 // max(1, j + d_lo), d_lo <= 0 <= d_hi.  A sibling of band_payload_rows_kernel (sa_band_frame.hpp, the SW payload frame) that
-// shares span_frame_shift with it and nothing else; what differs from the SW frame:
+// shares frame_shift (sa_band_pipe.hpp) with it and nothing else; what differs from the SW frame:
 //   No best cell, no retire.  Both corners are in every NW band, so every row 1 .. len_b is swept and the result is the last
 //   row's position len_a - fc(len_b): its X and its diagonal feed Dm / Dn, the end pick's payload as in StatSweep::write.
 //   A cell outside the band is no stop.  It holds the floor in all three states, and a state at the floor with no candidate has
@@ -49,7 +49,7 @@
 // Every loop is bounded by the rows 1 .. len_b; no matrices, no hand-off, no waits but for the code fetches, no atomics but the
 // err_flag OR.  The launches are recorded as "band_score" (the second launch record's table is pinned).
 #include "sa_nw_stats.hpp"
-#include "sa_band_frame.hpp"   // span_frame_shift
+#include "sa_band_pipe.hpp"   // frame_shift
 
 namespace sa {
 
@@ -103,13 +103,13 @@ band_nw_stats_rows_kernel(const SaBandNwStatsParams kp) {
       sw.boundX = read_lane(sw.X[0], 0);
       sw.boundDm = (uint32_t)read_lane((int)sw.Dm[0], 0);
       sw.boundDn = (uint32_t)read_lane((int)sw.Dn[0], 0);
-      span_frame_shift(sw.X, k.floor_);
-      span_frame_shift(sw.Ap, k.floor_);
-      if constexpr (GENERAL) span_frame_shift(sw.Y, k.floor_);
-      span_frame_shift(sw.fa, cin & 0xff);
-      if constexpr (SUBST != SA_SUBST_SIMPLE) span_frame_shift(sw.arow, (cin >> 8) * k.K);
-      span_frame_shift(sw.Dm, 0u); span_frame_shift(sw.Dn, SA_STATS_NO_WALK);
-      span_frame_shift(sw.Vm, 0u); span_frame_shift(sw.Vn, SA_STATS_NO_WALK);
+      frame_shift(sw.X, k.floor_);
+      frame_shift(sw.Ap, k.floor_);
+      if constexpr (GENERAL) frame_shift(sw.Y, k.floor_);
+      frame_shift(sw.fa, cin & 0xff);
+      if constexpr (SUBST != SA_SUBST_SIMPLE) frame_shift(sw.arow, (cin >> 8) * k.K);
+      frame_shift(sw.Dm, 0u); frame_shift(sw.Dn, SA_STATS_NO_WALK);
+      frame_shift(sw.Vm, 0u); frame_shift(sw.Vn, SA_STATS_NO_WALK);
     }
     // the cell above the band's right edge is outside the band: the floor, and no walk starts in it (rule 2)
     const int ge = (int)j + d_hi - fc - g0;

@@ -1,7 +1,7 @@
 // sa_band_nw_stats_strips.hip -- wide banded NW statistics (seqalign_nw_stats_banded_wide): seqalign_nw_stats_banded's three
 // integers at any band width, one pair on many waves.  Two things that exist, crossed: the strip pipeline and moving frame of
 // band_strips_kernel<CPL, SUBST, GENERAL, FILL = false, SW = false> (sa_band_strips.hip's header: the strips, their rows, the
-// frame, the hand-off column, the tickets, the bounded wait and the give-up word) and the payload rules of
+// frame, the hand-off column and the tickets; the bounded wait and the give-up word: sa_band_pipe.hpp) and the payload rules of
 // band_nw_stats_rows_kernel (sa_band_nw_stats.hip's header: the mark, the four rules) around StatSweep::row.  DESIGN.md 3.26.
 //
 // band_nw_stats_strips_kernel<CPL, SUBST, GENERAL>: one workgroup = one wave = one (pair, strip), drawn by ticket.  Strip s owns
@@ -29,63 +29,13 @@
 // So a band cell reads what it reads in the narrow kernel (rule 4 there) and besides only the feed, which is a band cell of the
 // left strip or the floor and the mark.  Nothing waits on a strip to its right; every path out of the kernel publishes ~0.
 #include "sa_nw_stats.hpp"
+#include "sa_band_pipe.hpp"
 
 namespace sa {
-namespace wide_stats {
-
-constexpr unsigned long long kBandWaitTicks = 200000000ull;   // 2 s of the 100 MHz wall clock
-constexpr uint32_t kAllRows = 0xFFFFFFFFu;
-
-// copies of sa_band_strips.hip's helpers (that file's code objects do not change)
-__device__ __forceinline__ int wave_shl1(int src, int lane63_value) {
-  return __builtin_amdgcn_update_dpp(lane63_value, src, 0x130, 0xf, 0xf, false);   // wave_shl:1
-}
-
-template <int N>
-__device__ __forceinline__ void frame_shift(int (&a)[N], int enters) {
-  const int first = a[0];
-#pragma unroll
-  for (int c = 0; c + 1 < N; ++c) a[c] = a[c + 1];
-  a[N - 1] = wave_shl1(first, enters);
-}
-template <int N>
-__device__ __forceinline__ void frame_shift(uint32_t (&a)[N], uint32_t enters) {
-  const uint32_t first = a[0];
-#pragma unroll
-  for (int c = 0; c + 1 < N; ++c) a[c] = a[c + 1];
-  a[N - 1] = (uint32_t)wave_shl1((int)first, (int)enters);
-}
-
-__device__ __forceinline__ void band_publish(uint32_t *word, uint32_t *front, uint32_t value) {
-  strip_publish(word, value);
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(front, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ bool band_strip_wait(const uint32_t *word, const uint32_t *front, uint32_t need) {
-  uint32_t seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  if (seen < need) {
-    uint32_t at = __builtin_amdgcn_readfirstlane(__hip_atomic_load(front, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    unsigned long long t0 = wall_clock64();
-    for (;;) {
-      __builtin_amdgcn_s_sleep(8);
-      const uint32_t now = __builtin_amdgcn_readfirstlane(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      if (now >= need) break;
-      const unsigned long long t = wall_clock64();
-      if (now != seen) { seen = now; t0 = t; }   // it advanced: the budget restarts
-      else if (t - t0 > kBandWaitTicks) {         // has any strip of the pair published since the budget started?
-        const uint32_t f = __builtin_amdgcn_readfirstlane(__hip_atomic_load(front, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (f == at) return false;
-        at = f; t0 = t;
-      }
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  return true;
-}
 
 template <int CPL, int SUBST, bool GENERAL>
 __global__ void __launch_bounds__(kWave)
-band_nw_stats_strips_kernel(const SaBandNwStatsStripsParams wp) {
+band_nw_stats_strips_kernel(const SaBandWideParams<SaBandNwStatsParams> wp) {
   const SaBandNwStatsParams &kp = wp.s;
   const SaBandParams &bp = kp.b;
   const SaFillParams &p = bp.f;
@@ -95,14 +45,14 @@ band_nw_stats_strips_kernel(const SaBandNwStatsStripsParams wp) {
   constexpr int F = kWave * CPL;   // the strip's columns, and the frame's positions
   const int lane = threadIdx.x;
   uint32_t strip, pair;
-  strip_of_ticket(strip_ticket(wp.ticket), wp.strips_per_pair, strip, pair);
+  strip_of_ticket(strip_ticket(wp.w.ticket), wp.w.strips_per_pair, strip, pair);
   if (pair >= p.n_pairs) return;
 
   const uint32_t la = p.len_a[pair], lb = p.len_b[pair];
   const long long c0 = (long long)strip * F;
   if (c0 >= (long long)la && strip != 0) return;   // this pair has fewer strips: no progress word, nobody waits for it
-  uint32_t *word = wp.progress + wp.slot_off[pair] + strip;
-  uint32_t *front = wp.front + pair;   // publications by any strip of the pair
+  uint32_t *word = wp.w.progress + wp.w.slot_off[pair] + strip;
+  uint32_t *front = wp.w.front + pair;   // publications by any strip of the pair
 
   const int d_lo = __builtin_amdgcn_readfirstlane(bp.d_lo[pair]);
   const int width = __builtin_amdgcn_readfirstlane((int)bp.width[pair]);
@@ -123,9 +73,9 @@ band_nw_stats_strips_kernel(const SaBandNwStatsStripsParams wp) {
   const bool right_rows = lb >= 1 && c0 + F < (long long)la && c0 + F + 1 <= (long long)lb + d_hi;
 
   // entry e of a strip's hand-off column: two int4 at [2 e]
-  const uint64_t hbase = wp.hand_off[pair];
-  int4 *hand_out = reinterpret_cast<int4 *>(wp.handoff) + 2 * (hbase + (uint64_t)strip * (uint32_t)width);
-  const int4 *hand_in = reinterpret_cast<const int4 *>(wp.handoff) + 2 * (hbase + (uint64_t)(strip ? strip - 1 : 0) * (uint32_t)width);
+  const uint64_t hbase = wp.w.hand_off[pair];
+  int4 *hand_out = reinterpret_cast<int4 *>(wp.w.handoff) + 2 * (hbase + (uint64_t)strip * (uint32_t)width);
+  const int4 *hand_in = reinterpret_cast<const int4 *>(wp.w.handoff) + 2 * (hbase + (uint64_t)(strip ? strip - 1 : 0) * (uint32_t)width);
 
   StatSweep<CPL, SUBST, GENERAL> sw;
   const int g0 = lane * CPL;   // my first frame position
@@ -153,8 +103,7 @@ band_nw_stats_strips_kernel(const SaBandNwStatsStripsParams wp) {
       if (!left_done) {   // rows j .. j + 63 of the strip to my left, as far as it has rows
         const uint32_t need = (uint32_t)min((long long)j + kWave - 1, jl_left);
         if (!band_strip_wait(word - 1, front, need)) {
-          if (lane == 0) atomicCAS(wp.give_up, 0u, pair + 1u);
-          band_publish(word, front, kAllRows);
+          band_give_up(wp.w.give_up, pair, word, front);
           return;
         }
         left_done = (long long)need >= jl_left;
@@ -263,27 +212,17 @@ band_nw_stats_strips_kernel(const SaBandNwStatsStripsParams wp) {
   band_publish(word, front, kAllRows);
 }
 
-template <int CPL>
-static hipError_t launch_cpl(const SaBandNwStatsStripsParams &p, const dim3 grid, hipStream_t stream) {
-  launch_by_scoring(p.s.b.f, [&](auto subst, auto general, uint32_t table_ints) {
-    hipLaunchKernelGGL((band_nw_stats_strips_kernel<CPL, subst(), general()>), grid, dim3(kWave), table_ints * sizeof(int32_t), stream, p);
-  });
-  return hipGetLastError();
-}
-
-}  // namespace wide_stats
 }  // namespace sa
 
-hipError_t sa_launch_band_nw_stats_strips(const SaBandNwStatsStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream) {
+hipError_t sa_launch_band_nw_stats_strips(const SaBandWideParams<SaBandNwStatsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream) {
   if (p.s.b.f.n_pairs == 0) return hipSuccess;
-  const uint64_t blocks = (uint64_t)((p.s.b.f.n_pairs + 7) / 8) * 8 * p.strips_per_pair;
-  if (p.strips_per_pair == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)blocks);
-  switch (strip_cols) {
-    case 64: sa_record_launch_ext(SEQALIGN_KX_BAND_SCORE, items); return sa::wide_stats::launch_cpl<1>(p, grid, stream);
-    case 128: sa_record_launch_ext(SEQALIGN_KX_BAND_SCORE, items); return sa::wide_stats::launch_cpl<2>(p, grid, stream);
-    case 256: sa_record_launch_ext(SEQALIGN_KX_BAND_SCORE, items); return sa::wide_stats::launch_cpl<4>(p, grid, stream);
-    case 512: sa_record_launch_ext(SEQALIGN_KX_BAND_SCORE, items); return sa::wide_stats::launch_cpl<8>(p, grid, stream);
-  }
-  return hipErrorInvalidValue;
+  dim3 grid;
+  if (sa::band_strips_grid(p.s.b.f.n_pairs, p.w.strips_per_pair, grid) != hipSuccess) return hipErrorInvalidValue;
+  return sa::launch_by_strip_cols(strip_cols, [&](auto cpl) {
+    sa_record_launch_ext(SEQALIGN_KX_BAND_SCORE, items);
+    sa::launch_by_scoring(p.s.b.f, [&](auto subst, auto general, uint32_t table_ints) {
+      hipLaunchKernelGGL((sa::band_nw_stats_strips_kernel<cpl(), subst(), general()>), grid, dim3(sa::kWave), table_ints * sizeof(int32_t), stream, p);
+    });
+    return hipGetLastError();
+  });
 }

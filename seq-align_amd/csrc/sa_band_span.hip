@@ -28,6 +28,10 @@
 //      and before such a position's column enters the band it passes through g_e, where rule 2 resets it.
 // Every loop is bounded by the rows first .. min(len_b, len_a - d_lo); there are no matrices, no hand-off and no waits but
 // for the code fetches.  The launches are recorded as "band_score" (the second launch record's table is pinned).
+//
+// The wide form (seqalign_sw_span_banded_wide) is sa_band_frame.hpp's band_payload_strips_kernel<BandSpanFrame,
+// ..> over the same policy: the rules per strip are in that header.  The two payload words are full words, so there is no limit
+// on the lengths and nothing to overflow in a frame position that overhangs len_a.
 #include "sa_band_frame.hpp"
 
 namespace sa {
@@ -81,4 +85,7 @@ struct BandSpanFrame {
 
 hipError_t sa_launch_band_span(const SaBandSpanParams &p, uint32_t max_width, hipStream_t stream) {
   return sa::launch_band_payload<sa::BandSpanFrame>(p, max_width, stream);
+}
+hipError_t sa_launch_band_span_strips(const SaBandWideParams<SaBandSpanParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream) {
+  return sa::launch_band_payload_strips<sa::BandSpanFrame>(p, strip_cols, items, stream);
 }

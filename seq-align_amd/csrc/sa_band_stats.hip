@@ -45,6 +45,14 @@
 //
 // Every loop is bounded by the rows first .. min(len_b, len_a - d_lo); no matrices, no hand-off, no waits but for the code
 // fetches.  The launches are recorded as "band_score" (the second launch record's table is pinned).
+//
+// The wide form (seqalign_sw_stats_banded_wide) is sa_band_frame.hpp's band_payload_strips_kernel<
+// BandSwStatsFrame, ..> over the same policy.  The 16-bit argument, per strip: a frame position right of len_a or right of the
+// strip's end c0 + S can compute gx = fc(j) + g up to len_a + S - 1 > 65 535, and its word 0 is then garbage.  That header shows
+// cell by cell that a band cell of a strip reads only band cells (whose own word `x | j << 16` is exact, 1 <= x <= len_a), stops
+// in columns <= len_a and hand-off entries of band cells of the left strip, never such a position; so no mask is needed there
+// either, and tests/test_gpu_sw_stats_banded_wide.py runs both sequences at 65 535 letters over 1 024 strips with the last
+// frames overhanging len_a to catch a mistake in this.  Word 1 needs no argument, as above.
 #include "sa_sw_stats.hpp"
 #include "sa_band_frame.hpp"
 
@@ -102,4 +110,7 @@ struct BandSwStatsFrame {
 
 hipError_t sa_launch_band_sw_stats(const SaBandSwStatsParams &p, uint32_t max_width, hipStream_t stream) {
   return sa::launch_band_payload<sa::BandSwStatsFrame>(p, max_width, stream);
+}
+hipError_t sa_launch_band_sw_stats_strips(const SaBandWideParams<SaBandSwStatsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream) {
+  return sa::launch_band_payload_strips<sa::BandSwStatsFrame>(p, strip_cols, items, stream);
 }

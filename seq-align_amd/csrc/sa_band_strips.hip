@@ -29,105 +29,15 @@
 //   of the strips to its left (a tie stays left: lower columns) after waiting for that strip's ~0, and the last of the run
 //   writes the pair's result.  A pair none of whose strips has a row gets score 0 from strip 0.
 //   NW border cells of the fill form are written by strip 0, up front.
-//   The wait (band_strip_wait) is this kernel's own and is bounded.  Its budget, kBandWaitTicks of the 100 MHz wall clock,
-//   restarts whenever the awaited word advances; when it runs out the wave looks at the pair's FRONT word, which every strip
-//   of the pair bumps with each publication (a strip far right of the pipeline's front watches a word that stays 0 until
-//   the front arrives, but the front word moves all the while), and restarts the budget if that has moved since the budget
-//   started.  Only when no strip of the pair has published for a whole budget -- some running strip publishes every 64 row
-//   steps, so only preemption stretches that -- does it give up: it records its pair in the give-up
-//   word (the first to give up stays) and publishes ~0 itself so that the strips to its right fall through; the host then
-//   fails the call (SEQALIGN_E_HIP, "band strip hand-off timed out", that pair named).
-#include "sa_strips.hpp"
+//   The wait is sa_band_pipe.hpp's band_strip_wait, bounded, with its give-up path (that header: the budget and the front word);
+//   frame_shift, BandBest and band_publish are there too, shared with the other banded kernels.
+#include "sa_band_pipe.hpp"
 
 namespace sa {
-namespace wide {
-
-constexpr unsigned long long kBandWaitTicks = 200000000ull;   // 2 s of the 100 MHz wall clock
-constexpr uint32_t kAllRows = 0xFFFFFFFFu;
-
-// copies of sa_band.hip's helpers (that file's code objects do not change)
-__device__ __forceinline__ int wave_shl1(int src, int lane63_value) {
-  return __builtin_amdgcn_update_dpp(lane63_value, src, 0x130, 0xf, 0xf, false);   // wave_shl:1
-}
-
-template <int N>
-__device__ __forceinline__ void frame_shift(int (&a)[N], int enters) {
-  const int first = a[0];
-#pragma unroll
-  for (int c = 0; c + 1 < N; ++c) a[c] = a[c + 1];
-  a[N - 1] = wave_shl1(first, enters);
-}
-
-template <int CPL>
-struct BandBest {
-  int s[CPL], r[CPL];
-  int ret_s = 0, ret_col = 0, ret_row = 0;
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) { s[c] = 0; r[c] = 0; }
-  }
-  __device__ __forceinline__ void retire(int col) {
-    const int s0 = read_lane(s[0], 0), r0 = read_lane(r[0], 0);
-    if (s0 > ret_s) { ret_s = s0; ret_col = col; ret_row = r0; }
-    frame_shift(s, 0);
-    frame_shift(r, 0);
-  }
-  __device__ __forceinline__ void row(const int (&mv)[CPL], uint32_t j, int ncol) {
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-      const bool up = c < ncol && mv[c] > s[c];
-      s[c] = up ? mv[c] : s[c];
-      r[c] = up ? (int)j : r[c];
-    }
-  }
-  __device__ __forceinline__ void reduce(int col0, int &score, unsigned long long &key) const {
-    int b = 0;
-    unsigned long long kb = ~0ull;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c)
-      if (s[c] > b) { b = s[c]; kb = ((unsigned long long)(uint32_t)(col0 + c) << 32) | (uint32_t)r[c]; }
-    score = wave_max_i32(b);
-    key = wave_min_u64(b == score && score > 0 ? kb : ~0ull);
-    if (ret_s >= score && ret_s > 0) {
-      score = ret_s;
-      key = ((unsigned long long)(uint32_t)ret_col << 32) | (uint32_t)ret_row;
-    }
-  }
-};
-
-// strip_publish, and one more publication counted in the pair's front word
-__device__ __forceinline__ void band_publish(uint32_t *word, uint32_t *front, uint32_t value) {
-  strip_publish(word, value);
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(front, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// strip_wait with a way out: false when `word` stayed below `need` and the pair's front word -- the count of publications by
-// ANY of the pair's strips -- stood still for kBandWaitTicks (header)
-__device__ __forceinline__ bool band_strip_wait(const uint32_t *word, const uint32_t *front, uint32_t need) {
-  uint32_t seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  if (seen < need) {
-    uint32_t at = __builtin_amdgcn_readfirstlane(__hip_atomic_load(front, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    unsigned long long t0 = wall_clock64();
-    for (;;) {
-      __builtin_amdgcn_s_sleep(8);
-      const uint32_t now = __builtin_amdgcn_readfirstlane(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      if (now >= need) break;
-      const unsigned long long t = wall_clock64();
-      if (now != seen) { seen = now; t0 = t; }   // it advanced: the budget restarts
-      else if (t - t0 > kBandWaitTicks) {         // has any strip of the pair published since the budget started?
-        const uint32_t f = __builtin_amdgcn_readfirstlane(__hip_atomic_load(front, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (f == at) return false;
-        at = f; t0 = t;
-      }
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  return true;
-}
 
 template <int CPL, int SUBST, bool GENERAL, bool FILL, bool SW>
 __global__ void __launch_bounds__(kWave)
-band_strips_kernel(const SaBandStripsParams wp) {
+band_strips_kernel(const SaBandWideParams<SaBandSwParams> wp) {
   const SaBandSwParams &kp = wp.s;
   const SaBandParams &bp = kp.b;
   const SaFillParams &p = bp.f;
@@ -137,14 +47,14 @@ band_strips_kernel(const SaBandStripsParams wp) {
   constexpr int F = kWave * CPL;   // the strip's columns, and the frame's positions
   const int lane = threadIdx.x;
   uint32_t strip, pair;
-  strip_of_ticket(strip_ticket(wp.ticket), wp.strips_per_pair, strip, pair);
+  strip_of_ticket(strip_ticket(wp.w.ticket), wp.w.strips_per_pair, strip, pair);
   if (pair >= p.n_pairs) return;
 
   const uint32_t la = p.len_a[pair], lb = p.len_b[pair];
   const long long c0 = (long long)strip * F;
   if (c0 >= (long long)la && strip != 0) return;   // this pair has fewer strips: no progress word, nobody waits for it
-  uint32_t *word = wp.progress + wp.slot_off[pair] + strip;
-  uint32_t *front = wp.front + pair;   // publications by any strip of the pair
+  uint32_t *word = wp.w.progress + wp.w.slot_off[pair] + strip;
+  uint32_t *front = wp.w.front + pair;   // publications by any strip of the pair
 
   const int d_lo = __builtin_amdgcn_readfirstlane(bp.d_lo[pair]);
   const int width = __builtin_amdgcn_readfirstlane((int)bp.width[pair]);
@@ -164,9 +74,9 @@ band_strips_kernel(const SaBandStripsParams wp) {
   const bool left_rows = strip > 0 && jl_left >= 1;
   const bool right_rows = lb >= 1 && c0 + F < (long long)la && c0 + F + 1 <= (long long)lb + d_hi;
 
-  const uint64_t hbase = wp.hand_off[pair];
-  int2 *hand_out = reinterpret_cast<int2 *>(wp.handoff) + hbase + (uint64_t)strip * (uint32_t)width;
-  const int2 *hand_in = reinterpret_cast<const int2 *>(wp.handoff) + hbase + (uint64_t)(strip ? strip - 1 : 0) * (uint32_t)width;
+  const uint64_t hbase = wp.w.hand_off[pair];
+  int2 *hand_out = reinterpret_cast<int2 *>(wp.w.handoff) + hbase + (uint64_t)strip * (uint32_t)width;
+  const int2 *hand_in = reinterpret_cast<const int2 *>(wp.w.handoff) + hbase + (uint64_t)(strip ? strip - 1 : 0) * (uint32_t)width;
 
   int32_t *Mg = nullptr, *Ag = nullptr, *Bg = nullptr;   // cell (i, j) at [j (width - 1) + i]
   if constexpr (FILL && SW) {
@@ -233,8 +143,7 @@ band_strips_kernel(const SaBandStripsParams wp) {
       if (!left_done) {   // rows j .. j + 63 of the strip to my left, as far as it has rows
         const uint32_t need = (uint32_t)min((long long)j + kWave - 1, jl_left);
         if (!band_strip_wait(word - 1, front, need)) {
-          if (lane == 0) atomicCAS(wp.give_up, 0u, pair + 1u);
-          band_publish(word, front, kAllRows);
+          band_give_up(wp.w.give_up, pair, word, front);
           return;
         }
         left_done = (long long)need >= jl_left;
@@ -324,21 +233,20 @@ band_strips_kernel(const SaBandStripsParams wp) {
     int score;
     unsigned long long key;
     best.reduce((int)max(c0 + 1, jl + d_lo) + g0, score, key);   // the last row's frame
-    const uint64_t slot = wp.slot_off[pair] + strip;
+    const uint64_t slot = wp.w.slot_off[pair] + strip;
     if (left_rows) {   // the best of the strips to my left: written before that strip's last publication
       if (!band_strip_wait(word - 1, front, kAllRows)) {
-        if (lane == 0) atomicCAS(wp.give_up, 0u, pair + 1u);
-        band_publish(word, front, kAllRows);
+        band_give_up(wp.w.give_up, pair, word, front);
         return;
       }
-      merge_left_best(wp.strip_best + 4 * (slot - 1), score, key);
+      merge_left_best(wp.w.strip_best + 4 * (slot - 1), score, key);
     }
     const uint32_t ea = score > 0 ? (uint32_t)(key >> 32) : 0u, eb = score > 0 ? (uint32_t)key : 0u;
     if (lane == 0) {
       if (!right_rows) {
         bp.score[pair] = score; kp.end_a[pair] = ea; kp.end_b[pair] = eb;
       } else {
-        *reinterpret_cast<uint4 *>(wp.strip_best + 4 * slot) = make_uint4((uint32_t)score, ea, eb, 0u);
+        *reinterpret_cast<uint4 *>(wp.w.strip_best + 4 * slot) = make_uint4((uint32_t)score, ea, eb, 0u);
       }
     }
   }
@@ -355,34 +263,23 @@ band_strips_kernel(const SaBandStripsParams wp) {
   band_publish(word, front, kAllRows);
 }
 
-template <int CPL, bool FILL, bool SW>
-static hipError_t launch_cpl(const SaBandStripsParams &p, const dim3 grid, hipStream_t stream) {
-  launch_by_scoring(p.s.b.f, [&](auto subst, auto general, uint32_t table_ints) {
-    hipLaunchKernelGGL((band_strips_kernel<CPL, subst(), general(), FILL, SW>), grid, dim3(kWave), table_ints * sizeof(int32_t), stream, p);
-  });
-  return hipGetLastError();
-}
-
 template <bool FILL, bool SW>
-static hipError_t launch(const SaBandStripsParams &p, uint32_t strip_cols, const dim3 grid, hipStream_t stream) {
-  switch (strip_cols) {
-    case 64: return launch_cpl<1, FILL, SW>(p, grid, stream);
-    case 128: return launch_cpl<2, FILL, SW>(p, grid, stream);
-    case 256: return launch_cpl<4, FILL, SW>(p, grid, stream);
-    case 512: return launch_cpl<8, FILL, SW>(p, grid, stream);
-  }
-  return hipErrorInvalidValue;
+static hipError_t launch_band_strips(const SaBandWideParams<SaBandSwParams> &p, uint32_t strip_cols, const dim3 grid, hipStream_t stream) {
+  return launch_by_strip_cols(strip_cols, [&](auto cpl) {
+    launch_by_scoring(p.s.b.f, [&](auto subst, auto general, uint32_t table_ints) {
+      hipLaunchKernelGGL((band_strips_kernel<cpl(), subst(), general(), FILL, SW>), grid, dim3(kWave), table_ints * sizeof(int32_t), stream, p);
+    });
+    return hipGetLastError();
+  });
 }
 
-}  // namespace wide
 }  // namespace sa
 
-hipError_t sa_launch_band_strips(const SaBandStripsParams &p, uint32_t strip_cols, bool fill, bool is_sw, uint64_t items, hipStream_t stream) {
+hipError_t sa_launch_band_strips(const SaBandWideParams<SaBandSwParams> &p, uint32_t strip_cols, bool fill, bool is_sw, uint64_t items, hipStream_t stream) {
   if (p.s.b.f.n_pairs == 0) return hipSuccess;
-  const uint64_t blocks = (uint64_t)((p.s.b.f.n_pairs + 7) / 8) * 8 * p.strips_per_pair;
-  if (p.strips_per_pair == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  dim3 grid;
+  if (sa::band_strips_grid(p.s.b.f.n_pairs, p.w.strips_per_pair, grid) != hipSuccess) return hipErrorInvalidValue;
   sa_record_launch_ext(fill ? SEQALIGN_KX_BAND_FILL : SEQALIGN_KX_BAND_SCORE, items);
-  const dim3 grid((unsigned)blocks);
-  if (is_sw) return fill ? sa::wide::launch<true, true>(p, strip_cols, grid, stream) : sa::wide::launch<false, true>(p, strip_cols, grid, stream);
-  return fill ? sa::wide::launch<true, false>(p, strip_cols, grid, stream) : sa::wide::launch<false, false>(p, strip_cols, grid, stream);
+  if (is_sw) return fill ? sa::launch_band_strips<true, true>(p, strip_cols, grid, stream) : sa::launch_band_strips<false, true>(p, strip_cols, grid, stream);
+  return fill ? sa::launch_band_strips<true, false>(p, strip_cols, grid, stream) : sa::launch_band_strips<false, false>(p, strip_cols, grid, stream);
 }

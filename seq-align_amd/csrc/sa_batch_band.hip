@@ -1,7 +1,6 @@
 // sa_batch_band.hip -- the banded calls over HOST batches: the eighteen seqalign_*_banded, *_banded_wide and *_band_time_ms entry
 // points (the contracts: include/seqalign_hip.h; the kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip,
-// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip, sa_band_sw_stats_strips.hip,
-// sa_band_span_strips.hip).  DESIGN.md 3.23b.
+// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip).  DESIGN.md 3.23b.
 //
 // One driver, seven modes.  A mode is a traits struct (below): NW or SW, score family or align, its result words and fixed
 // bytes per pair, its cap on the width, its kernels' parameter block and launches.  The driver is the same for all of them:
@@ -36,26 +35,11 @@ namespace {
 // launch() (one width class; recorded as band_score or band_fill).  The score family besides: kMarkField (above 0: the result
 // array whose words carry SA_STATS_NO_WALK, SEQALIGN_E_TRACEBACK).  The align modes: the walk's record per pair in words, where its status sits, what
 // their message adds to "traceback failed", set_meta() and walk().  The wide form of each: kHandoffBytes (per entry of a
-// strip's hand-off column), kBestBytes (per strip: its best-cell entry) and launch_strips() (one launch over a chunk's strips, laid out as StripsLayout says).
-
-// where a wide launch finds its pipeline's words (BandChunkRun::launch_wide): the fields of SaBandStripsParams behind s
-struct StripsLayout {
-  uint32_t strips_per_pair;
-  const uint64_t *slot_off, *hand_off;
-  uint32_t *progress, *ticket, *front, *strip_best, *give_up;
-  int32_t *handoff;
-};
+// strip's hand-off column), kBestBytes (per strip: its best-cell entry) and launch_strips() (one launch over a chunk's strips, laid out as SaBandStripsLayout says: sa_kernels.h, where a wide launch finds its pipeline's words).
 
 // the four score and align modes: band_strips_kernel (sa_band_strips.hip), 8 bytes per hand-off entry
-hipError_t launch_score_strips(const SaBandSwParams &s, const StripsLayout &l, uint32_t cols, bool fill, bool is_sw, uint64_t items, hipStream_t st) {
-  SaBandStripsParams w;
-  memset(&w, 0, sizeof(w));
-  w.s = s;
-  w.strips_per_pair = l.strips_per_pair;
-  w.slot_off = l.slot_off; w.hand_off = l.hand_off;
-  w.progress = l.progress; w.ticket = l.ticket; w.front = l.front; w.strip_best = l.strip_best; w.give_up = l.give_up;
-  w.handoff = l.handoff;
-  return sa_launch_band_strips(w, cols, fill, is_sw, items, st);
+hipError_t launch_score_strips(const SaBandSwParams &s, const SaBandStripsLayout &l, uint32_t cols, bool fill, bool is_sw, uint64_t items, hipStream_t st) {
+  return sa_launch_band_strips({s, l}, cols, fill, is_sw, items, st);
 }
 
 struct NwScoreBand {   // seqalign_nw_score_banded(_wide), seqalign_band_score_time_ms
@@ -67,7 +51,7 @@ struct NwScoreBand {   // seqalign_nw_score_banded(_wide), seqalign_band_score_t
   static SaBandParams &base(Params &p) { return p; }
   static void set_results(Params &, uint32_t *, uint64_t) {}
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_score(p, max_width, st); }
-  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
     SaBandSwParams s{}; s.b = p;
     return launch_score_strips(s, l, cols, kAlign, kSw, items, st);
   }
@@ -85,7 +69,7 @@ struct NwAlignBand {   // seqalign_nw_align_banded(_wide)
   static void set_meta(Params &p, uint32_t *meta, uint64_t s0) { p.meta4 = meta + 4 * s0; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_fill(p, max_width, st); }
   static hipError_t walk(const Params &p, hipStream_t st) { return sa_launch_band_walk(p, st); }
-  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
     SaBandSwParams s{}; s.b = p;
     return launch_score_strips(s, l, cols, kAlign, kSw, items, st);
   }
@@ -100,7 +84,7 @@ struct SwScoreBand {   // seqalign_sw_score_banded(_wide), seqalign_sw_band_scor
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) { p.end_a = res + n; p.end_b = res + 2 * n; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_score(p, max_width, st); }
-  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
     return launch_score_strips(p, l, cols, kAlign, kSw, items, st);
   }
 };
@@ -117,12 +101,12 @@ struct SwAlignBand {   // seqalign_sw_align_banded(_wide)
   static void set_meta(Params &p, uint32_t *meta, uint64_t s0) { p.meta8 = meta + 8 * s0; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_fill(p, max_width, st); }
   static hipError_t walk(const Params &p, hipStream_t st) { return sa_launch_band_sw_walk(p, st); }
-  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
     return launch_score_strips(p, l, cols, kAlign, kSw, items, st);
   }
 };
 
-struct SwSpanBand {   // seqalign_sw_span_banded(_wide), seqalign_sw_span_band_time_ms (sa_band_span.hip, sa_band_span_strips.hip)
+struct SwSpanBand {   // seqalign_sw_span_banded(_wide), seqalign_sw_span_band_time_ms (sa_band_span.hip)
   using Params = SaBandSpanParams;
   static constexpr bool kSw = true, kAlign = false;
   static constexpr int kFields = 5;             // score, pos_a, pos_b, len_a, len_b
@@ -135,19 +119,12 @@ struct SwSpanBand {   // seqalign_sw_span_banded(_wide), seqalign_sw_span_band_t
     p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
   }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_span(p, max_width, st); }
-  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
-    SaBandSpanStripsParams w;
-    memset(&w, 0, sizeof(w));
-    w.s = p;
-    w.strips_per_pair = l.strips_per_pair;
-    w.slot_off = l.slot_off; w.hand_off = l.hand_off;
-    w.progress = l.progress; w.ticket = l.ticket; w.front = l.front; w.strip_best = l.strip_best; w.give_up = l.give_up;
-    w.handoff = l.handoff;
-    return sa_launch_band_span_strips(w, cols, items, st);
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    return sa_launch_band_span_strips({p, l}, cols, items, st);
   }
 };
 
-struct SwStatsBand {   // seqalign_sw_stats_banded(_wide), seqalign_sw_stats_band_time_ms (sa_band_stats.hip, sa_band_sw_stats_strips.hip)
+struct SwStatsBand {   // seqalign_sw_stats_banded(_wide), seqalign_sw_stats_band_time_ms (sa_band_stats.hip)
   using Params = SaBandSwStatsParams;
   static constexpr bool kSw = true, kAlign = false;
   static constexpr int kFields = 7;             // the span mode's five, matches, mismatches
@@ -161,15 +138,8 @@ struct SwStatsBand {   // seqalign_sw_stats_banded(_wide), seqalign_sw_stats_ban
     p.matches = res + 5 * n; p.mismatches = res + 6 * n;
   }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_stats(p, max_width, st); }
-  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
-    SaBandSwStatsStripsParams w;
-    memset(&w, 0, sizeof(w));
-    w.s = p;
-    w.strips_per_pair = l.strips_per_pair;
-    w.slot_off = l.slot_off; w.hand_off = l.hand_off;
-    w.progress = l.progress; w.ticket = l.ticket; w.front = l.front; w.strip_best = l.strip_best; w.give_up = l.give_up;
-    w.handoff = l.handoff;
-    return sa_launch_band_sw_stats_strips(w, cols, items, st);
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    return sa_launch_band_sw_stats_strips({p, l}, cols, items, st);
   }
 };
 
@@ -186,15 +156,8 @@ struct NwStatsBand {   // seqalign_nw_stats_banded(_wide), seqalign_nw_stats_ban
   static SaBandParams &base(Params &p) { return p.b; }
   static void set_results(Params &p, uint32_t *res, uint64_t n) { p.matches = res + n; p.mismatches = res + 2 * n; }
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_nw_stats(p, max_width, st); }
-  static hipError_t launch_strips(const Params &p, const StripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
-    SaBandNwStatsStripsParams w;
-    memset(&w, 0, sizeof(w));
-    w.s = p;
-    w.strips_per_pair = l.strips_per_pair;
-    w.slot_off = l.slot_off; w.hand_off = l.hand_off;
-    w.progress = l.progress; w.ticket = l.ticket; w.front = l.front; w.give_up = l.give_up;
-    w.handoff = l.handoff;
-    return sa_launch_band_nw_stats_strips(w, cols, items, st);
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    return sa_launch_band_nw_stats_strips({p, l}, cols, items, st);
   }
 };
 
@@ -382,7 +345,7 @@ struct BandChunkRun {
   // the wide calls: one launch over all slots of the chunk, strips_per_pair the chunk's maximum
   int launch_wide() {
     hipStream_t st = ctx->stream;
-    StripsLayout w{};
+    SaBandStripsLayout w{};
     w.strips_per_pair = strips_per_pair;
     w.slot_off = stage.d_u64(2); w.hand_off = stage.d_u64(3);
     w.progress = ctx->strip_progress.as<uint32_t>();
@@ -706,7 +669,7 @@ extern "C" int seqalign_sw_align_banded_wide(seqalign_ctx_t *ctx, const seqalign
   return sw_align_banded(ctx, batch, scoring, diag_lo, diag_hi, min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, true);
 }
 
-// banded SW hit spans: the narrow call, and the wide form without the width check (kernel: sa_band_span_strips.hip)
+// banded SW hit spans: the narrow call, and the wide form without the width check (kernel: band_payload_strips_kernel, sa_band_frame.hpp, by sa_band_span.hip)
 static int sw_span_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const int32_t *diag_lo,
                           const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a,
                           uint32_t *out_len_b, bool wide) {
@@ -741,7 +704,7 @@ extern "C" int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign
 }
 
 // banded SW statistics: the two passes of checks in the header's order; the wide form: without the width check (kernel:
-// sa_band_sw_stats_strips.hip)
+// band_payload_strips_kernel, sa_band_frame.hpp, by sa_band_stats.hip)
 static int sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const int32_t *diag_lo,
                            const int32_t *diag_hi, int32_t *out_score, uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a,
                            uint32_t *out_len_b, uint32_t *out_matches, uint32_t *out_mismatches, bool wide) {

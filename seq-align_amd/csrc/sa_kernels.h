@@ -655,66 +655,40 @@ struct SaBandNwStatsParams {
 };
 /* every pair of the launch has width <= max_width <= SA_SPAN_BAND_MAX_WIDTH; max_width picks the columns per lane */
 hipError_t sa_launch_band_nw_stats(const SaBandNwStatsParams &p, uint32_t max_width, hipStream_t stream);
-/* ---- the wide banded calls (seqalign_*_banded_wide, sa_band_strips.hip): the same bands, matrices and layouts at any width,
- * one wave per (pair, strip of strip_cols columns) in the strips pipeline.  s (NW: s.b alone) is the narrow launch's record;
- * f.status must hold ~0 per pair before the launch (the strips atomicMin into it).  Pair k has max(1, ceil(len_a /
- * strip_cols)) strips <= strips_per_pair; strip t of it owns progress word slot_off[k] + t (zero before the launch; ~0: all
- * its rows), strip_best entry 4 (slot_off[k] + t) (SW) and the `width` int2 of handoff from hand_off[k] + t width.  *ticket
- * (zero before the launch) deals the strips out; front[k] (zero before the launch) counts the publications of pair k's strips; *give_up (zero before the launch) becomes k + 1 for the first pair k of the launch
- * one of whose strips ran out of its wait budget: the results are void then.
- * The walks are sa_launch_band_walk / sa_launch_band_sw_walk over the fill form's cells. */
-struct SaBandStripsParams {
-  SaBandSwParams s;
+/* ---- the wide banded calls (seqalign_*_banded_wide): the same bands, matrices, results and layouts at any width, one wave
+ * per (pair, strip of strip_cols columns) in the strips pipeline (sa_band_pipe.hpp).  A launch's block is the narrow launch's
+ * record s and the pipeline's words w, the same for every family.  s.b.f.status (NW score and align: s.b alone is used) must hold
+ * ~0 per pair before the launch (the strips atomicMin into it).  Pair k has max(1, ceil(len_a / strip_cols)) strips <=
+ * strips_per_pair; strip t of it owns progress word slot_off[k] + t (zero before the launch; ~0: all its rows), the family's
+ * best entry at slot slot_off[k] + t of strip_best (16-byte aligned; the SW families) and the `width` hand-off entries from
+ * entry hand_off[k] + t width of handoff (16-byte aligned).  *ticket (zero before the launch) deals the strips out; front[k]
+ * (zero before the launch) counts the publications of pair k's strips; *give_up (zero before the launch) becomes k + 1 for the
+ * first pair k of the launch one of whose strips ran out of its wait budget: the results are void then.
+ * Every launch: strip_cols 64 | 128 | 256 | 512; items: what the launch record counts (the (pair, strip) waves that sweep a row). */
+struct SaBandStripsLayout {
   uint32_t strips_per_pair;
   const uint64_t *slot_off, *hand_off;
   uint32_t *progress, *ticket, *front, *strip_best, *give_up;
   int32_t *handoff;
 };
-/* strip_cols: 64 | 128 | 256 | 512; items: what the launch record counts (the (pair, strip) waves that sweep a row) */
-hipError_t sa_launch_band_strips(const SaBandStripsParams &p, uint32_t strip_cols, bool fill, bool is_sw, uint64_t items, hipStream_t stream);
-/* ---- wide banded NW statistics (seqalign_nw_stats_banded_wide, sa_band_nw_stats_strips.hip): sa_launch_band_nw_stats' results
- * at any width through the strips pipeline of sa_launch_band_strips.  The fields behind s are SaBandStripsParams' and are
- * prepared the same way (f.status ~0, progress / ticket / front / give_up zero), but for the hand-off: per strip `width` entries
- * of SA_BAND_STATS_HANDOFF_BYTES -- {max(M, A), B, whether max(M, A) is an admitted A's, 0} {their payloads} of the strip's
- * last column -- from entry hand_off[k] + t width of handoff (16-byte aligned).  There is no best cell.  Recorded as
- * "band_score" with `items`. */
+template <class S>
+struct SaBandWideParams {
+  S s;                          /* first: the offsets of the kernel's arguments behind it are the family's own */
+  SaBandStripsLayout w;
+};
+/* score and align, NW and SW (sa_band_strips.hip): a hand-off entry is the int2 {max(M, A), B} of the strip's last column, a best
+ * entry {score, end_a, end_b, 0}.  The walks are sa_launch_band_walk / sa_launch_band_sw_walk over the fill form's cells. */
+hipError_t sa_launch_band_strips(const SaBandWideParams<SaBandSwParams> &p, uint32_t strip_cols, bool fill, bool is_sw, uint64_t items, hipStream_t stream);
+/* the payload families: sa_launch_band_nw_stats' / sa_launch_band_sw_stats' / sa_launch_band_span's results, recorded as
+ * "band_score".  A hand-off entry is SA_BAND_STATS_HANDOFF_BYTES: {max(M, A), B, whether max(M, A) is an admitted A's, 0} {the
+ * two payload words of each}; a best entry SA_SPAN_BEST_BYTES: {score, end_a, end_b, 0} {its two payload words, 0, 0}.
+ * NW statistics (sa_band_nw_stats_strips.hip): the words are matches and mismatches; there is no best cell, strip_best is unused.
+ * SW statistics (sa_band_stats.hip): word 0 the stop cell x | y << 16, word 1 matches | mismatches << 16; both sequences of every
+ * pair have at most SA_SW_STATS_MAX_LEN letters.  SW hit spans (sa_band_span.hip): the stop cell's x and y, any length. */
 #define SA_BAND_STATS_HANDOFF_BYTES 32u
-struct SaBandNwStatsStripsParams {
-  SaBandNwStatsParams s;
-  uint32_t strips_per_pair;
-  const uint64_t *slot_off, *hand_off;
-  uint32_t *progress, *ticket, *front, *give_up;
-  int32_t *handoff;
-};
-hipError_t sa_launch_band_nw_stats_strips(const SaBandNwStatsStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
-/* ---- wide banded SW statistics (seqalign_sw_stats_banded_wide, sa_band_sw_stats_strips.hip): sa_launch_band_sw_stats' results
- * at any width through the strips pipeline of sa_launch_band_strips.  The fields behind s are SaBandStripsParams' and are
- * prepared the same way (f.status ~0, progress / ticket / front / give_up zero), but for two: the hand-off is per strip `width`
- * entries of SA_BAND_STATS_HANDOFF_BYTES -- {max(M, A), B, whether max(M, A) is A's, 0} {word 0 and word 1 of each} of the strip's
- * last column -- from entry hand_off[k] + t width of handoff (16-byte aligned), and strip t's best cell so far is the
- * SA_SPAN_BEST_BYTES at strip_best + 8 (slot_off[k] + t) (16-byte aligned): {score, end_a, end_b, 0} {word 0, word 1, 0, 0}.
- * Both sequences of every pair have at most SA_SW_STATS_MAX_LEN letters.  Recorded as "band_score" with `items`. */
-struct SaBandSwStatsStripsParams {
-  SaBandSwStatsParams s;
-  uint32_t strips_per_pair;
-  const uint64_t *slot_off, *hand_off;
-  uint32_t *progress, *ticket, *front, *strip_best, *give_up;
-  int32_t *handoff;
-};
-hipError_t sa_launch_band_sw_stats_strips(const SaBandSwStatsStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
-/* ---- wide banded SW hit spans (seqalign_sw_span_banded_wide, sa_band_span_strips.hip): sa_launch_band_span's results at any
- * width and any length through the strips pipeline of sa_launch_band_strips.  The fields behind s are SaBandSwStatsStripsParams'
- * and are prepared the same way; a hand-off entry is SA_BAND_STATS_HANDOFF_BYTES -- {max(M, A), B, whether max(M, A) is A's, 0}
- * {the span of each: x, y, x, y} -- and a strip_best entry SA_SPAN_BEST_BYTES: {score, end_a, end_b, 0} {pos_a, pos_b, 0, 0}.
- * Recorded as "band_score" with `items`. */
-struct SaBandSpanStripsParams {
-  SaBandSpanParams s;
-  uint32_t strips_per_pair;
-  const uint64_t *slot_off, *hand_off;
-  uint32_t *progress, *ticket, *front, *strip_best, *give_up;
-  int32_t *handoff;
-};
-hipError_t sa_launch_band_span_strips(const SaBandSpanStripsParams &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
+hipError_t sa_launch_band_nw_stats_strips(const SaBandWideParams<SaBandNwStatsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
+hipError_t sa_launch_band_sw_stats_strips(const SaBandWideParams<SaBandSwStatsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
+hipError_t sa_launch_band_span_strips(const SaBandWideParams<SaBandSpanParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 /* the second launch record (seqalign_ctx_last_call_info_ext: SEQALIGN_KX_*) */
 void sa_record_launch_ext(int kind, uint64_t items);
 /* long rows (1024..4095 columns), fast-path scorings: one workgroup per pair, shared LDS ring */

@@ -80,7 +80,7 @@ struct SpanSweep {
 
   // Row j.  f: the cell left of the strip on this row.  Leaves the last column's hand-off in `out` (lane 63's is the strip's).
   // BAND (sa_band_span.hip): ncol changes from row to row, so the running best takes a cell only while its column is in the band.
-  // PICK (sa_band_span_strips.hip, where the strip's last column moves through the frame): `out` is column `pick` of the
+  // PICK (band_payload_strips_kernel, sa_band_frame.hpp, where the strip's last column moves through the frame): `out` is column `pick` of the
   // lane instead of its last.
   template <bool BAND = false, bool PICK = false>
   __device__ __forceinline__ void row(const SweepConsts &k, uint32_t j, uint32_t lb, uint32_t la, uint32_t W, int lane,

@@ -1,6 +1,6 @@
 """Helpers of the wide banded SW statistics tests (seqalign_sw_stats_banded_wide).  Not a test module.
 
-strip_model         the kernel's schedule (sa_band_sw_stats_strips.hip) in pure Python over payloads IN PACKED
+strip_model         the kernel's schedule (sa_band_frame.hpp) in pure Python over payloads IN PACKED
                     FORM (cell word, counts word; masked to 32 bits), values from bandswlib.fill: the strips of S columns and
                     their rows, the standing and the moving frame, the stop feed and the left strip's hand-off entry, the up-left
                     of a strip's first row, the reset of V above the right edge, the hand-off entries and which rows have one,
@@ -48,7 +48,7 @@ def outside_left_of_seam(seven, la: int, lb: int, lo: int, hi: int, S: int) -> b
 
 
 def strip_model(osc, a: bytes, b: bytes, lo: int, hi: int, S: int, mats=None):
-    """((score, pos_a, pos_b, len_a, len_b, matches, mismatches), coverage) the way band_sw_stats_strips_kernel finds them with
+    """((score, pos_a, pos_b, len_a, len_b, matches, mismatches), coverage) the way band_payload_strips_kernel finds them with
     strips of S columns.  coverage: strips, busy (strips with rows), late_start (strips with jf > 1), both_phases (strips that
     stand and then move), entries (hand-off entries written), stop_feeds (rows fed by a stop), tie_left (merges in which the
     left strip's best equals mine), tie_retired (end picks in which the retired best equals the live one)."""

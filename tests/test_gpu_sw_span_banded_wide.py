@@ -1,4 +1,4 @@
-"""GPU tier: wide banded SW hit spans -- seqalign_sw_span_banded_wide (sa_band_span_strips.hip, sa_batch_band.hip).
+"""GPU tier: wide banded SW hit spans -- seqalign_sw_span_banded_wide (sa_band_frame.hpp by sa_band_span.hip, sa_batch_band.hip).
 
 The contract is seqalign_sw_span_banded's at any clipped width and any length.  Every result is checked bit for bit against the
 oracle (bandspanlib.want: the five fields of the banded hit, zeros without one), the first three (score, pos + len) against

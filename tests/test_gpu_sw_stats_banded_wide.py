@@ -1,4 +1,4 @@
-"""GPU tier: wide banded SW statistics -- seqalign_sw_stats_banded_wide (sa_band_sw_stats_strips.hip, sa_batch_band.hip).
+"""GPU tier: wide banded SW statistics -- seqalign_sw_stats_banded_wide (sa_band_frame.hpp by sa_band_stats.hip, sa_batch_band.hip).
 
 The contract is seqalign_sw_stats_banded's at any clipped width.  Every result is checked bit for bit against the oracle
 (bandstatlib.want: the seven values of the banded hit and the counted columns of its strings, zeros without one), the first three
