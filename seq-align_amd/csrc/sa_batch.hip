@@ -633,18 +633,14 @@ static int nw_chunk_pipelined(seqalign_ctx *ctx, const seqalign_batch_t *batch, 
       if (g1 > g0) {
         const uint64_t c0 = h_slot[g0], c1 = h_slot[g1];
         const seqalign_dev_batch_t d = dev_range(g0, g1);
-        SaTraceParams t;
-        memset(&t, 0, sizeof(t));
-        t.arena = d.arena; t.off_a = d.off_a; t.len_a = d.len_a; t.off_b = d.off_b; t.len_b = d.len_b; t.mat_off = d.mat_off;
-        t.M = d.match_scores; t.A = d.gap_a_scores; t.B = d.gap_b_scores; t.code = sc->d_code; t.table = sc->d_table;
+        SaTraceParams t = trace_params(ctx, sc, d);
+        t.M = d.match_scores; t.A = d.gap_a_scores; t.B = d.gap_b_scores;
         t.str_off = dv_slot + g0;
         t.out_a = d_chars + 2 * c0 - c0;                  // + slot offset: a-strings at [2 c0, 2 c0 + (c1 - c0))
         t.out_b = d_chars + 2 * c0 + (c1 - c0) - c0;      //                b-strings right behind them
         t.out_meta4 = d_meta + 4 * g0; t.fill_status = d.status;
         if (use_dirs) { t.dirs = ctx->dirs.as<uint8_t>(); t.dirs_blocked = blocked; t.nw_score = ctx->best_score.as<int32_t>() + g0; t.nw_state = ctx->best_index.as<uint64_t>() + g0; }
-        t.n_pairs = (uint32_t)(g1 - g0); t.K = sc->flat.n_classes; t.open1 = sc->flat.open1; t.ext = sc->flat.ext;
-        t.gen_eq = sc->flat.gen_eq; t.gen_ne = sc->flat.gen_ne; t.flags = sc->flat.flags;
-        t.tune_walker = ctx->opt.trace_kernel; t.tune_group = ctx->opt.walk_group;
+        t.n_pairs = (uint32_t)(g1 - g0);
         // the last group's walk has no fill to run beside: it stays in the fills' stream, right behind the last fill (on
         // its own stream it waited for the previous group's download -- streams share hardware queues; rocprofv3
         // timeline of C5's share: 0.6 ms)
@@ -1009,19 +1005,14 @@ static int nw_chunk_moves(seqalign_ctx *ctx, const seqalign_batch_t *batch, cons
       const uint64_t g0 = pair_at(bcut[gcut[g]]), g1 = k1;
       if (g1 > g0) {
         const seqalign_dev_batch_t d = dev_range(g0, g1);
-        SaTraceParams t;
-        memset(&t, 0, sizeof(t));
-        t.arena = d.arena; t.off_a = d.off_a; t.len_a = d.len_a; t.off_b = d.off_b; t.len_b = d.len_b; t.mat_off = d.mat_off;
-        t.code = sc->d_code; t.table = sc->d_table;
+        SaTraceParams t = trace_params(ctx, sc, d);
         t.str_off = dv_slot + g0;
         t.stage_words = (c.max_a + c.max_b + 31u) >> 5;
         t.moves = dv_moves + 2 * g0;        // walk w of the launch is pair g0 + w: words 2 ((slot >> 5) + g0 + w)
         t.out_meta2 = dv_meta + 2 * g0;
         t.fill_status = d.status;
         t.dirs = ctx->dirs.as<uint8_t>(); t.dirs_blocked = blocked; t.dirs_local = local; t.tune_stage = ctx->opt.walk_stage; t.tune_tile = ctx->opt.walk_tile; t.nw_score = ctx->best_score.as<int32_t>() + g0; t.nw_state = ctx->best_index.as<uint64_t>() + g0;
-        t.n_pairs = (uint32_t)(g1 - g0); t.K = sc->flat.n_classes; t.open1 = sc->flat.open1; t.ext = sc->flat.ext;
-        t.gen_eq = sc->flat.gen_eq; t.gen_ne = sc->flat.gen_ne; t.flags = sc->flat.flags;
-        t.tune_walker = ctx->opt.trace_kernel; t.tune_group = ctx->opt.walk_group;
+        t.n_pairs = (uint32_t)(g1 - g0);
         // the last group's walk has no fill to run beside: it stays in the fills' stream, right behind the last fill
         hipStream_t sg = g + 1 < n_grp ? sw : sf;
         if (sg != sf) {

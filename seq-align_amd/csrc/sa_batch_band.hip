@@ -449,8 +449,7 @@ struct BandChunkRun {
 
   // banded SW: the chunk's hits in pair order, under seqalign_sw_align_long's capacity rule.  A pair's own error comes before
   // SEQALIGN_E_NOMEM and nothing of the chunk is delivered then.
-  int finish_sw_align(const int32_t *min_score, seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits,
-                      char *out_a, char *out_b, uint64_t str_cap, uint64_t *used_str) {
+  int finish_sw_align(const int32_t *min_score, HitSink &sink, uint64_t *n_hits) {
     const int rc = fetch_walks();
     if (rc) return rc;
     const uint64_t first = stage.first;
@@ -464,14 +463,9 @@ struct BandChunkRun {
       const int32_t score = (int32_t)m[0];
       if (score <= 0 || score < min_score[p]) continue;   // no hit
       const uint32_t len = m[6], head = m[7];
-      const uint64_t took = *n_hits >= hit_cap ? 0 : put_alignment(ctx, ha + str_at(s) + head, hb + str_at(s) + head, len, out_a, out_b, *used_str,
-                                                                    str_cap > *used_str ? str_cap - *used_str : 0);
-      if (!took) return SEQALIGN_E_NOMEM;
-      seqalign_sw_hit_t &h = hits[(*n_hits)++];
-      h.pair = p; h.score = score;
-      h.pos_a = m[2]; h.pos_b = m[3]; h.len_a = m[4] - m[2]; h.len_b = m[5] - m[3];   // smith_waterman.c:251-255
-      h.length = len; h.str_off = *used_str;
-      *used_str += took;
+      const seqalign_sw_hit_t h{p, score, m[2], m[3], m[4] - m[2], m[5] - m[3], len, 0};   // smith_waterman.c:251-255
+      if (!sink.put(ctx, h, ha + str_at(s) + head, hb + str_at(s) + head)) return SEQALIGN_E_NOMEM;
+      *n_hits = sink.found;
     }
     return SEQALIGN_OK;
   }
@@ -595,10 +589,8 @@ int sw_align_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const sc
   int rc = check_band_batch<SwAlignBand>(batch, SwBands{diag_lo, diag_hi}, geom, wide);
   if (rc) return rc;
   CallScope scope(ctx);
-  uint64_t used_str = 0;
-  return band_call<SwAlignBand>(ctx, batch, scoring, geom, wide, [&](auto &run) {
-    return run.finish_sw_align(min_score, hits, hit_cap, n_hits, out_a, out_b, str_cap, &used_str);
-  });
+  HitSink sink{hits, hit_cap, out_a, out_b, str_cap};
+  return band_call<SwAlignBand>(ctx, batch, scoring, geom, wide, [&](auto &run) { return run.finish_sw_align(min_score, sink, n_hits); });
 }
 
 }  // namespace

@@ -228,7 +228,7 @@ int long_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
   if ((rc = cached_scoring(ctx, scoring, is_sw ? 1 : 0, &sc))) return rc;
   if ((rc = admit_batch(sc, batch, SA_FRAMES_ROWS))) return rc;
   LongPair run{ctx, sc, is_sw};
-  uint64_t found = 0, used_str = 0;
+  HitSink sink{hits, hit_cap, out_a, out_b, str_cap};
   for (uint64_t p = 0; p < batch->n_pairs; ++p) {
     bool has = false;
     uint32_t len = 0;
@@ -243,14 +243,10 @@ int long_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_
       continue;
     }
     if (!has) continue;
-    const uint64_t took = found >= hit_cap ? 0 : put_alignment(ctx, sa, sb, len, out_a, out_b, used_str, str_cap > used_str ? str_cap - used_str : 0);
-    if (!took) { *n_hits = found; return SEQALIGN_E_NOMEM; }
-    seqalign_sw_hit_t &h = hits[found++];
-    h.pair = p; h.score = m.walk.end_score;
-    h.pos_a = m.walk.x; h.pos_b = m.walk.y; h.len_a = m.walk.end_x - m.walk.x; h.len_b = m.walk.end_y - m.walk.y;   // smith_waterman.c:251-255
-    h.length = len; h.str_off = used_str;
-    used_str += took;
-    *n_hits = found;
+    const seqalign_sw_hit_t h{p, m.walk.end_score, m.walk.x, m.walk.y, m.walk.end_x - m.walk.x, m.walk.end_y - m.walk.y, len, 0};   // smith_waterman.c:251-255
+    const bool fitted = sink.put(ctx, h, sa, sb);
+    *n_hits = sink.found;
+    if (!fitted) return SEQALIGN_E_NOMEM;
   }
   return SEQALIGN_OK;
 }

@@ -120,417 +120,159 @@ static SaKeyLayout key_layout(const seqalign_dev_scoring *sc, uint32_t max_a, ui
 // a key is at most 64 bits wide, all ones excluded
 static bool key_layout_fits(const SaKeyLayout &l) { return l.row_bits + l.col_bits + l.score_bits <= 63; }
 
-// SW hits of one chunk, enumerated on the device:
-//   fill (reports the candidates' count, box and columns per row) -> reverse sweep (sa_sw_sweep.hip: every hit's
-//   key, in order)
-//   -> one traceback per wanted hit -> strings packed -> D2H.
-// Host round trips: the hit counts (they size the traceback), the hits' lengths (they size the packing), the strings.
-// Appends to the caller's hit array / string buffers.
-static int sw_chunk_device_enumerate(seqalign_ctx *ctx, const seqalign_batch_t *batch, const Chunk &c,
-                                     const seqalign_dev_scoring *sc, const int32_t *min_score, uint32_t max_hits,
-                                     seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *found,
-                                     char *out_a, char *out_b, uint64_t str_cap, uint64_t *used_str) {
+// ------------------------------------------------- what the chunk functions share ---
+namespace {
+
+// The packed two-pairs-per-wave fills' layout of a chunk (sa_fill_dirs_x2.hip), decided once for both SW paths.  stride: 0 -- the
+// chunk is not packed; every pair of the chunk the same shape (reads against windows of one length) -- one stride for all, a
+// multiple of 256, so that every pair's cells start on one; ragged -- kBucketShapes: run_chunk pairs up the pairs of equal shape,
+// every pair on a multiple of 256.  dir_bytes: the direction bytes that layout holds for the chunk (`blocked`: rows in
+// the best-hit fill's blocked layout, sa_kernels.h).  min_pairs: from how many same-shape pairs packing pays on this path.
+struct PackedShape { uint64_t stride = 0, dir_bytes = 0; };
+static PackedShape packed_fill_shape(const seqalign_ctx *ctx, const seqalign_batch_t *batch, const Chunk &c, const seqalign_dev_scoring *sc,
+                                     bool (*applicable)(const seqalign_ctx_t *, const seqalign_dev_scoring_t *, uint32_t, uint32_t),
+                                     uint64_t min_pairs, bool blocked) {
   const uint64_t n = c.count;
-  hipStream_t st = ctx->stream;
-  int rc;
-  DevBuf &d_min = ctx->e[0], &d_keys = ctx->e[1], &d_box = ctx->e[3], &d_rows = ctx->e[4],
-         &d_rowoff = ctx->e[5], &d_walk = ctx->e[6], &d_hits = ctx->e[7], &d_meta = ctx->e[8],
-         &d_gath_a = ctx->e[9], &d_dst = ctx->e[11];
-  // sources of asynchronous H2D copies: declared BEFORE the guard below, so that they are destroyed after its
-  // hipStreamSynchronize on every exit path
-  std::vector<uint64_t> hit_off(n + 1, 0), row_off, walk_str, dst_off;
-  std::vector<uint32_t> walk_pair, walk_rank;
-  StreamSyncOnExit sync_on_exit(st);
-  StageTimer tm(ctx->opt.timing);
-  const SaKeyLayout layout = key_layout(sc, c.max_a, c.max_b);
-  if (!key_layout_fits(layout)) return SEQALIGN_E_TOO_LARGE;   // (seqalign_sw_batch checks the whole batch first)
-
-  // ---- fill + candidates' count and box
-  // every pair's part of the scratch arena (its rows' candidate columns, then its hits' keys)
-  {
-    const int64_t best = best_move(sc);
-    uint32_t pa = ~0u, pb = ~0u; int32_t pm = 0; uint64_t pe = 0;   // (reads of one length: the division once per run of equal pairs)
-    for (uint64_t k = 0; k < n; ++k) {
-      const uint32_t xa = batch->len_a[c.first + k], xb = batch->len_b[c.first + k];
-      const int32_t xm = min_score[c.first + k];
-      if (xa != pa || xb != pb || xm != pm) { pa = xa; pb = xb; pm = xm; pe = hit_arena_elements(xa, xb, xm, best); }
-      hit_off[k + 1] = hit_off[k] + pe;
-    }
-  }
-  DevBuf &d_hitoff = ctx->e[13];
-  if ((rc = d_min.reserve(n * 4)) || (rc = ctx->cand_count.reserve(n * 4)) || (rc = d_box.reserve(n * 16)) ||
-      (rc = d_keys.reserve(hit_off[n] * 8 + 16)) || (rc = d_meta.reserve(n * 16 + 16)) || (rc = d_hitoff.reserve((n + 1) * 8)))
-    return rc;
-  // (from pinned staging: a copy from the caller's pageable array is staged by the runtime and waited for)
-  if ((rc = ctx->h_tb.reserve((n + 1) * 8 + n * 4 + 16))) return rc;
-  { uint64_t *hs_off = ctx->h_tb.as<uint64_t>();
-    int32_t *hs_min = reinterpret_cast<int32_t *>(hs_off + n + 1);
-    memcpy(hs_off, hit_off.data(), (n + 1) * 8); memcpy(hs_min, min_score + c.first, n * 4);
-    HIP_TRY(hipMemcpyAsync(d_hitoff.p, hs_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_min.p, hs_min, n * 4, hipMemcpyHostToDevice, st)); }
-  SaCandBox cand{};
-  cand.cand_count = ctx->cand_count.as<uint32_t>(); cand.cand_box = d_box.as<uint32_t>(); cand.cand_min = d_min.as<int32_t>();
-  cand.cand_rows = d_keys.as<uint32_t>(); cand.hit_off = d_hitoff.as<uint64_t>();
-  // plain scorings, rows up to 1 024 columns (513 and up: see wide_ok below): the fill writes match_scores + one byte of directions per cell instead of the
-  // three matrices (sa_fill_dirs.hip); the directions go where gap_a_scores would have gone
-  bool dirs_used = false;
-  // every pair of the chunk the same shape (reads against windows of one length), match / mismatch scoring: the packed
-  // two-pairs-per-wave fill (sa_fill_dirs_x2.hip); every pair's cells then start on a multiple of 256
-  uint64_t stride = 0;
-  {
-    bool same_shape = true;
-    for (uint64_t k = 1; k < n && same_shape; ++k)
-      same_shape = batch->len_a[c.first + k] == batch->len_a[c.first] && batch->len_b[c.first + k] == batch->len_b[c.first];
-    if (same_shape && (n >= kPackedFillMinPairs || ctx->opt.pack16 == 2) && sw_dirs_x2_applicable(ctx, sc, c.max_a, c.max_b))
-      stride = (((uint64_t)(c.max_a + 1ull) * (c.max_b + 1ull)) + 255u) & ~(uint64_t)255u;
-    else if (!same_shape && (n >= kBucketedFillMinPairs || ctx->opt.pack16 == 2) && ((uint64_t)c.max_a + 1) * ((uint64_t)c.max_b + 1) <= kShapeTableMax &&
-             sw_dirs_x2_applicable(ctx, sc, c.max_a, c.max_b))
-      stride = kBucketShapes;   // ragged: run_chunk pairs up the pairs of equal shape, every pair on a multiple of 256 cells
-  }
-  uint64_t cells256 = 0;
-  if (stride == kBucketShapes)
-    for (uint64_t k = 0; k < n; ++k) cells256 += (((uint64_t)batch->len_a[c.first + k] + 1) * ((uint64_t)batch->len_b[c.first + k] + 1) + 255u) & ~(uint64_t)255u;
-  // (only when the sweep will run in its rows-in-registers form: not with the strip / LDS forms forced by an option)
-  // and rows of 513 .. 1 024 columns only where the sweep's one-word form takes them (sa_launch_sw_sweep) and a wave per pair fills
-  // the chip (few wide pairs: strips, below, as before)
-  const bool wide_row = c.max_a + 1 > 512;
-  const bool wide_ok = ctx->opt.sweep_ev && layout.row_bits + layout.col_bits + layout.score_bits <= 62 &&
-                       (n >= (c.max_a + 1 > 768 ? 640u : 128u) || ctx->opt.sweep_mode == 1);
-  // (tools/sw_wide_few.py, 700 x 1000 -- 12 columns per lane: 128 pairs 4.04 -> 3.69 ms, 64: 3.51 -> 3.67; 900 x 1000 -- 16 per lane:
-  //  512 pairs 5.8 on strips / 6.3 here, 1 024 pairs 8.1 / 6.2)
-  const bool allow_dirs = ctx->opt.sweep_mode != 2 && ctx->opt.sweep_cpl == 0 && (!wide_row || wide_ok);
-  // (the packed direction-byte fill is bound by instruction issue: its arenas need no placement walk)
-  if ((rc = reserve_arenas(ctx, (stride == kBucketShapes ? cells256 : stride ? n * stride : c.cells) * 4, !(allow_dirs && stride != 0)))) return rc;
-  cand.dirs = allow_dirs ? ctx->A.as<uint8_t>() : nullptr; cand.dirs_used = &dirs_used;
-  if (!allow_dirs) stride = 0;
-  cand.uniform_stride = stride == kBucketShapes ? 256 : stride;
-  // ---- ONE trip for everything, when the call is the common kind: direction bytes, one wave per pair in the sweep, a few
-  // hits per pair wanted.  The hit walks are launched BEFORE anybody has seen the sweep's counts -- max_hits walks per pair,
-  // walk w = hit w % max_hits of pair w / max_hits, those beyond a pair's hits return at once (sa_traceback.hip) -- and send
-  // home two bits per column into fixed slots of pinned memory (host/sa_moves.c), so nothing has to be sized, gathered or
-  // copied by a second and third launch + wait: counts, per-walk words and moves are all there after one synchronisation,
-  // and the host threads expand the hits straight into the caller's buffers.  (Round 3: counts -> walker lists -> walks ->
-  // lengths -> gather -> strings, three waits.)  Sweep and walks follow the chunk's last fill, in the fills' stream.
-  // (Measured, profiles/r04/r04_sw_pipeline.txt: on a second stream, with equal slices so that a slice's sweep runs beside
-  // the next slice's fill -- both issue vector instructions 50-70 % of the time, neither is bound by memory -- the two
-  // kernels simply share the SIMDs: C3's sweep of 4 096 pairs 0.62 -> 1.97 ms beside a fill, the call 4.6 -> 5.4 ms; and a
-  // sweep on the second, high-priority stream alone behind an event starts 80 us late and runs 0.93 instead of 0.80 ms on C4.)
-  // A pair that needs the host between sweep and walks -- more than 64 hits (keys unsorted), an error to weigh against
-  // max_hits -- sends the whole chunk down the three-trip path below, which starts from the same counts.
-  const bool trace = ctx->opt.sweep_trace;   // development aid: per-pair counters on stderr
-  DevBuf &d_trace = ctx->e[12];
-  const bool may_one_trip = allow_dirs && ctx->opt.sweep_mode == 0 && !trace && ctx->opt.nw_moves && max_hits <= 8 &&
-                            n * max_hits <= ((uint64_t)4 << 20) && c.max_a + 1 <= 1024;
-  SaSweepParams q;
-  memset(&q, 0, sizeof(q));
-  auto sweep_params = [&](const seqalign_dev_batch_t &dd, uint64_t k0, uint64_t k1, bool dirs) {
-    SaSweepParams r;
-    memset(&r, 0, sizeof(r));
-    r.arena = dd.arena; r.off_a = dd.off_a; r.len_a = dd.len_a; r.off_b = dd.off_b; r.len_b = dd.len_b;
-    r.mat_off = dd.mat_off; r.M = dd.match_scores; r.A = dd.gap_a_scores; r.B = dd.gap_b_scores;
-    r.code = sc->d_code; r.table = sc->d_table; r.cand_count = cand.cand_count + k0; r.cand_box = cand.cand_box + 4 * k0;
-    r.min_score = d_min.as<int32_t>() + k0; r.hit_keys = d_keys.as<unsigned long long>(); r.hit_off = d_hitoff.as<uint64_t>() + k0;
-    r.err_key = d_meta.as<unsigned long long>() + k0;
-    r.hit_count = reinterpret_cast<uint32_t *>(d_meta.as<unsigned long long>() + n) + k0; r.status = r.hit_count + n;
-    r.n_pairs = (uint32_t)(k1 - k0); r.K = sc->flat.n_classes; r.open1 = sc->flat.open1; r.ext = sc->flat.ext;
-    r.gen_eq = sc->flat.gen_eq; r.gen_ne = sc->flat.gen_ne; r.flags = sc->flat.flags;
-    r.max_len_a = c.max_a; r.max_len_b = c.max_b; r.layout = layout; r.tune_cpl = ctx->opt.sweep_cpl; r.tune_ev = ctx->opt.sweep_ev;
-    r.dirs = dirs ? cand.dirs : nullptr;
-    return r;
+  auto bytes256 = [&](uint32_t xa, uint32_t xb) -> uint64_t {
+    return ((blocked ? sa_dirs_blocked_bytes(xa, xb) : ((uint64_t)xa + 1) * ((uint64_t)xb + 1)) + 255u) & ~(uint64_t)255u;
   };
-  hipError_t e;
-  bool piped = may_one_trip, piped_any = false;
-  const uint64_t nwalk = n * max_hits;
-  if (may_one_trip) {
-    const uint64_t move_words = 2ull * max_hits * ((c.seq_bytes >> 5) + n) + 2;
-    if ((rc = ctx->h_ta.reserve(move_words * 4)) || (rc = ctx->h_B.reserve(nwalk * 16 + 16)) || (rc = ctx->h_tmeta.reserve(n * 16 + 64)))   // (h_misc is fetch_status')
-      return rc;
+  bool same_shape = true;
+  for (uint64_t k = 1; k < n && same_shape; ++k)
+    same_shape = batch->len_a[c.first + k] == batch->len_a[c.first] && batch->len_b[c.first + k] == batch->len_b[c.first];
+  PackedShape s;
+  if (same_shape && (n >= min_pairs || ctx->opt.pack16 == 2) && applicable(ctx, sc, c.max_a, c.max_b)) {
+    s.stride = bytes256(c.max_a, c.max_b);
+    s.dir_bytes = n * s.stride;
+  } else if (!same_shape && (n >= kBucketedFillMinPairs || ctx->opt.pack16 == 2) && ((uint64_t)c.max_a + 1) * ((uint64_t)c.max_b + 1) <= kShapeTableMax &&
+             applicable(ctx, sc, c.max_a, c.max_b)) {
+    s.stride = kBucketShapes;
+    for (uint64_t k = 0; k < n; ++k) s.dir_bytes += bytes256(batch->len_a[c.first + k], batch->len_b[c.first + k]);
   }
-  auto after_fill = [&](uint64_t k0, uint64_t k1, const seqalign_dev_batch_t &dd, bool dirs, bool cand_reported) -> int {
-    if (!piped || !dirs || !cand_reported) { piped = false; return SEQALIGN_OK; }   // not the common kind: everything below, for the whole chunk
-    hipError_t he;
-    const SaSweepParams r = sweep_params(dd, k0, k1, true);
-    if ((he = sa_launch_sw_sweep(r, st)) != hipSuccess) return fail_hip(he, "sw sweep");
-    SaTraceParams t;
-    memset(&t, 0, sizeof(t));
-    t.arena = dd.arena; t.off_a = dd.off_a; t.len_a = dd.len_a; t.off_b = dd.off_b; t.len_b = dd.len_b; t.mat_off = dd.mat_off;
-    t.M = dd.match_scores; t.code = sc->d_code; t.table = sc->d_table;
-    t.str_off = dd.off_a;                       // (run_chunk packs a, b, a, b, ...: off_a IS the prefix of len_a + len_b)
-    // walk w of the launch is hit w % max_hits of the slice's pair w / max_hits = the chunk's pair k0 + that: its slot is
-    // 2 max_hits ((off_a >> 5) + chunk pair) + ..., so the bases move by the slice's first pair
-    t.stage_words = (c.max_a + c.max_b + 31u) >> 5;
-    t.moves = ctx->h_ta.dev_as<uint32_t>() + 2ull * max_hits * k0; t.out_meta4 = ctx->h_B.dev_as<uint32_t>() + 4ull * max_hits * k0;
-    t.walks_per_pair = max_hits; t.hit_count = r.hit_count; t.sweep_status = r.status;
-    t.hit_keys = r.hit_keys; t.hit_off = r.hit_off; t.layout = layout; t.fill_status = dd.status;
-    t.n_pairs = (uint32_t)((k1 - k0) * max_hits); t.K = r.K; t.open1 = r.open1; t.ext = r.ext; t.gen_eq = r.gen_eq; t.gen_ne = r.gen_ne;
-    t.flags = r.flags; t.tune_walker = ctx->opt.trace_kernel; t.tune_group = ctx->opt.walk_group; t.dirs = r.dirs;
-    if ((he = sa_launch_nw_traceback(t, st)) != hipSuccess) return fail_hip(he, "sw hit traceback");
-    piped_any = true;
-    return SEQALIGN_OK;
+  return s;
+}
+
+// Hits that came home as MOVES -- two bit planes per walk in fixed slots of pinned memory (host/sa_moves.c) and four words per
+// walk: score, walked columns (or SA_MOVES_ERR | code), end cell x, y -- into the caller's room, for both paths whose walks send
+// moves (the packed best-hit call: one walk per pair; the one-trip multi-hit call: max_hits walk slots per pair).
+//   h_w, h_moves   the per-walk words and the planes; walk j of pair k is walk k * wpp + j, its planes start at word
+//                  2 wpp ((slot[k] >> 5) + k) + 2 j nwd of h_moves (nwd: words per plane of the pair)
+//   slot           the prefix of len_a + len_b over the chunk's pairs (run_chunk's packed offsets)
+//   walks(k)       how many of pair k's walk slots hold a walk that ran
+//   take(k, j)     whether that walk is a hit the caller wants
+// Where every hit goes in the caller's buffers: hits and string bytes per block of pairs (parallel -- round 4 counted in one
+// serial pass over words the GPU had just written, every line of them a miss: 0.1 ms of C4's 0.89 ms call), a prefix over
+// the blocks, then every block places and expands its own hits.  What fits: whole blocks while they do, the first that does not
+// hit by hit; SEQALIGN_E_NOMEM is returned AFTER what fits is delivered (as the strings delivery does).  A walk that ran and
+// failed is the call's error, the lowest such walk's code (the lowest failing pair's: what the header promises), and nothing
+// is delivered then.
+template <class Walks, class Take>
+static int deliver_moves(seqalign_ctx *ctx, const seqalign_batch_t *batch, const Chunk &c, const uint32_t *h_w, const uint32_t *h_moves,
+                         const uint64_t *slot, uint32_t wpp, Walks walks, Take take, HitSink &sink, StageTimer &tm) {
+  const uint64_t n = c.count, first = c.first;
+  constexpr uint64_t kBlk = 64;    // (pairs per task: C3's 10 000 pairs are 157 tasks for 16-32 threads; 256 left some threads a third more than others)
+  const uint64_t nblk = (n + kBlk - 1) / kBlk;
+  std::vector<uint64_t> blk_hits_v(nblk + 1, 0), blk_bytes_v(nblk + 1, 0);
+  uint64_t *const blk_hits = blk_hits_v.data(), *const blk_bytes = blk_bytes_v.data();
+  std::atomic<uint64_t> first_err{~0ull};   // walk << 8 | code of the LOWEST failing walk
+  // The tasks capture what they read per hit BY VALUE, so that the closure's copy on the heap holds it.  Measured (C3, up to 4
+  // hits, the placement pass over 10 000 pairs, profiles/r30): 0.19-0.21 ms with everything captured by reference, 0.10-0.13 by
+  // value, the parent's copy 0.11-0.12.  The cause is supposed, not shown: after every call into host/sa_moves.c a task reads its
+  // constants again, and by reference they lie in this frame, whose lines the calling thread writes next to while it runs tasks.
+  auto planes_of = [=](uint64_t k, uint32_t j, uint32_t nwd) { return h_moves + 2ull * wpp * ((slot[k] >> 5) + k) + 2ull * j * nwd; };
+  // what hit j of pair k takes in the caller's string buffer: its columns + NUL, or in CIGAR mode (seqalign_sw_batch_cigar) its
+  // CIGAR's length + NUL, counted from the planes (host/sa_moves.c)
+  auto out_bytes = [=](uint64_t k, uint32_t j, uint32_t len) -> uint64_t {
+    if (!ctx->cigar_format) return (uint64_t)len + 1;
+    const uint64_t p = first + k, w = k * wpp + j;
+    const uint32_t nwd = (batch->len_a[p] + batch->len_b[p] + 31u) >> 5;
+    const uint32_t *pa = planes_of(k, j, nwd);
+    uint32_t pos[4], clen = 0;
+    if (sa_cigar_sw_moves(batch->arena + batch->off_a[p], batch->arena + batch->off_b[p], h_w[4 * w + 2], h_w[4 * w + 3], pa, pa + nwd, nwd, len,
+                          ctx->cigar_format, ctx->cigar_fold, nullptr, 0, pos, &clen))
+      return 1;   // (the placement pass meets the same error and reports it)
+    return (uint64_t)clen + 1;
   };
-  seqalign_dev_batch_t d;
-  bool reported = false;
-  if ((rc = run_chunk(ctx, batch, c, sc, &d, nullptr, &cand, &reported, stride))) return rc;
-  // (behind ALL the fills: per slice -- a small first slice's sweep and walks, then the rest's -- C3 took 5.2 instead of 4.7 ms)
-  if (may_one_trip && (rc = after_fill(0, n, d, dirs_used, reported))) return rc;
-  const bool strips_needed = !dirs_used && c.max_a + 1 > 512 && (c.max_a + 1 > SA_SWEEP_LDS_COLUMNS || n < 1024);
-  bool strips = false;
-  if (piped && piped_any) {
-    // everything is enqueued on the one stream: one wait for all of it
-    q = sweep_params(d, 0, n, true);
-    tm.lap("sw: fills, sweeps, walks enqueued");
-  } else {
-  if (!reported) {   // a fill kernel that cannot report them itself: one pass over match_scores
-    SaReduceParams r;
-    memset(&r, 0, sizeof(r));
-    r.len_a = d.len_a; r.len_b = d.len_b; r.mat_off = d.mat_off; r.M = d.match_scores; r.n_pairs = (uint32_t)n;
-    if ((e = sa_launch_sw_box(r, cand, c.max_b, st)) != hipSuccess) return fail_hip(e, "sw candidate box");
-  }
-
-  // ---- the sweep: every hit of every pair
-  q = sweep_params(d, 0, n, dirs_used);
-  // How the pairs are laid over waves (sa_sw_sweep.hip): one wave per pair -- rows in registers (up to 512 columns on three matrices, up to 1 024 on direction bytes),
-  // wider ones in segments with the winners of two rows in LDS -- or, for FEW wide pairs (a wave per pair would leave
-  // the chip empty) and for rows too wide for LDS, one wave per 256-column strip.  The option sweep_mode = strips | pair
-  // forces one (tests, experiments).
-  const int mode_opt = ctx->opt.sweep_mode;   // 0 auto, 1 pair, 2 strips
-  const uint32_t w_max = c.max_a + 1;
-  strips = strips_needed;
-  if (mode_opt == 2) strips = true;
-  if (mode_opt == 1 && w_max <= SA_SWEEP_LDS_COLUMNS) strips = false;
-  if (w_max <= SA_SWEEP_LDS_COLUMNS) q.lds_columns = (c.max_a + 2u) & ~1u;
-  DevBuf &d_prog = ctx->e[2];
-  if (strips) {
-    // strip width by how many waves that makes: 128-column strips (and progress published every 16 rows instead of
-    // 64) when the pairs are so few that 256-column strips would leave most of the chip idle (2 x 10 000^2: 42.7 ->
-    // 32.8 ms; 64-column strips gain nothing more: a row's dependent passes cost ~2 us whatever its width)
-    uint32_t cols = sa_sweep_strip_blocks((uint32_t)n, c.max_a, 256) < 1024 ? 128 : 256;
-    if (const uint32_t v = ctx->opt.sweep_strip; v == 64 || v == 128 || v == 256) cols = v;
-    q.strip_columns = cols; q.strip_interval = cols == 256 ? 64 : 16;
-    const uint32_t spp = sa_sweep_strips_per_pair(c.max_a, cols);
-    const uint64_t blocks = sa_sweep_strip_blocks((uint32_t)n, c.max_a, cols);
-    row_off.resize(n);
-    uint64_t rows_total = 0;
-    for (uint64_t k = 0; k < n; ++k) { row_off[k] = rows_total; rows_total += (uint64_t)batch->len_b[c.first + k] + 1; }
-    if ((rc = d_prog.reserve((2 * blocks + 1) * 4 + 16)) || (rc = d_rows.reserve(rows_total * spp * 16 + 16)) ||
-        (rc = d_rowoff.reserve(n * 8)))
-      return rc;
-    HIP_TRY(hipMemsetAsync(d_prog.p, 0, (2 * blocks + 1) * 4, st));
-    HIP_TRY(hipMemsetAsync(q.err_key, 0xff, n * 8, st));     // the strips of a pair report into the same words
-    HIP_TRY(hipMemsetAsync(q.hit_count, 0, n * 8, st));      // hit_count | status
-    HIP_TRY(hipMemcpyAsync(d_rowoff.p, row_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    q.strip_progress = d_prog.as<uint32_t>(); q.strips_per_pair = spp;
-    q.bnd = d_rows.as<unsigned long long>(); q.row_off = d_rowoff.as<uint64_t>();
-  }
-  if (trace) {
-    if ((rc = d_trace.reserve(n * 64))) return rc;
-    HIP_TRY(hipMemsetAsync(d_trace.p, 0, n * 64, st));
-    q.trace = d_trace.as<unsigned long long>();
-  }
-  if ((e = sa_launch_sw_sweep(q, st)) != hipSuccess) return fail_hip(e, "sw sweep");
-  tm.lap("sw: enqueue fill + sweep");
-  }
-
-  const bool one_trip = piped && piped_any;
-  if (one_trip) {
-    unsigned long long *h_err = ctx->h_tmeta.as<unsigned long long>();
-    const uint32_t *h_cnt = reinterpret_cast<const uint32_t *>(h_err + n), *h_st = h_cnt + n;
-    HIP_TRY(hipMemcpyAsync(h_err, d_meta.p, n * 16, hipMemcpyDeviceToHost, st));
-    if ((rc = fetch_status(ctx, c, nullptr))) return rc;   // the fill's status words; synchronises the stream
-    tm.lap("sw one trip: wait (fill, sweep, walks)");
-    bool clean = true;
-    for (uint64_t k = 0; k < n && clean; ++k) clean = h_st[k] == 0;
-    tm.lap("sw one trip: statuses checked");
-    if (clean) {
-      const uint32_t *h_w = ctx->h_B.as<uint32_t>(), *h_moves = ctx->h_ta.as<uint32_t>();
-      // where every hit goes in the caller's buffers: hits and string bytes per block of pairs (parallel), a prefix over the
-      // blocks, then every block places and expands its own hits
-      constexpr uint64_t kBlk = 64;    // (pairs per task: C3's 10 000 pairs are 157 tasks for 16-32 threads; 256 left some threads a third more than others)
-      const uint64_t nblk = (n + kBlk - 1) / kBlk;
-      std::vector<uint64_t> blk_hits(nblk + 1, 0), blk_bytes(nblk + 1, 0);
-      std::atomic<int> bad{SEQALIGN_OK};
-      // where hit j of pair k lies: its planes, and what it takes in the caller's string buffer -- its columns + NUL, or in CIGAR
-      // mode (seqalign_sw_batch_cigar) its CIGAR's length + NUL, counted from the planes (host/sa_moves.c)
-      auto planes_of = [&](uint64_t k, uint32_t j, uint32_t *nwd_out) {
-        const uint64_t pp = c.first + k;
-        const uint32_t nwd = (batch->len_a[pp] + batch->len_b[pp] + 31u) >> 5;
-        *nwd_out = nwd;
-        return h_moves + 2ull * max_hits * ((ctx->h_desc.as<uint64_t>()[k] >> 5) + k) + 2ull * j * nwd;
-      };
-      auto out_bytes = [&](uint64_t k, uint32_t j, uint32_t len) -> uint64_t {
-        if (!ctx->cigar_format) return (uint64_t)len + 1;
-        const uint64_t pp = c.first + k, w = k * max_hits + j;
-        uint32_t nwd, pos[4], clen = 0;
-        const uint32_t *pa = planes_of(k, j, &nwd);
-        if (sa_cigar_sw_moves(batch->arena + batch->off_a[pp], batch->arena + batch->off_b[pp], h_w[4 * w + 2], h_w[4 * w + 3], pa, pa + nwd,
-                              nwd, len, ctx->cigar_format, ctx->cigar_fold, nullptr, 0, pos, &clen))
-          return 1;   // (the placement pass meets the same error and reports it)
-        return (uint64_t)clen + 1;
-      };
-      parallel_for(nblk, [&](uint64_t bi) {
-        uint64_t hs = 0, bytes = 0;
-        for (uint64_t k = bi * kBlk, e2 = std::min(n, (bi + 1) * kBlk); k < e2; ++k) {
-          const uint32_t take = std::min(h_cnt[k], max_hits);
-          for (uint32_t j = 0; j < take; ++j) {
-            const uint32_t len = h_w[4 * (k * max_hits + j) + 1];
-            if (len >= SA_MOVES_ERR) { int expected = SEQALIGN_OK; bad.compare_exchange_strong(expected, (int)(len & 15u)); continue; }
-            ++hs; bytes += out_bytes(k, j, len);
-          }
+  parallel_for(nblk, [=, &first_err](uint64_t bi) {
+    uint64_t hs = 0, bytes = 0;
+    for (uint64_t k = bi * kBlk, e = std::min(n, (bi + 1) * kBlk); k < e; ++k) {
+      for (uint32_t j = 0, nj = walks(k); j < nj; ++j) {
+        const uint64_t w = k * wpp + j;
+        const uint32_t len = h_w[4 * w + 1];
+        if (len >= SA_MOVES_ERR) {
+          uint64_t seen = first_err.load(std::memory_order_relaxed);
+          const uint64_t mine = w << 8 | (len & 15u);
+          while (mine < seen && !first_err.compare_exchange_weak(seen, mine, std::memory_order_relaxed)) {}
+          continue;
         }
-        blk_hits[bi + 1] = hs; blk_bytes[bi + 1] = bytes;
-      });
-      if (bad.load()) return bad.load();
-      tm.lap("sw one trip: hits counted");
-      for (uint64_t bi = 0; bi < nblk; ++bi) { blk_hits[bi + 1] += blk_hits[bi]; blk_bytes[bi + 1] += blk_bytes[bi]; }
-      // what fits the caller's buffers: whole blocks while they fit, the first one that does not hit by hit (reported after
-      // what fits is delivered, as the three-trip path does)
-      const uint64_t hit_room = hit_cap > *found ? hit_cap - *found : 0, str_room = str_cap > *used_str ? str_cap - *used_str : 0;
-      bool no_room = blk_hits[nblk] > hit_room || blk_bytes[nblk] > str_room;
-      const uint64_t first_hit = *found, first_str = *used_str;
-      std::atomic<uint64_t> delivered_hits{0}, delivered_bytes{0};
-      parallel_for(nblk, [&](uint64_t bi) {
-        uint64_t hi = blk_hits[bi], at = blk_bytes[bi], done_h = 0, done_b = 0;
-        bool stop = false;
-        for (uint64_t k = bi * kBlk, e2 = std::min(n, (bi + 1) * kBlk); k < e2 && !stop; ++k) {
-          const uint64_t pp = c.first + k;
-          const uint32_t take = std::min(h_cnt[k], max_hits), la = batch->len_a[pp], lb = batch->len_b[pp], nwd = (la + lb + 31u) >> 5;
-          // (run_chunk's packed offsets: the prefix of len_a + len_b over the chunk's pairs, in the pinned descriptor block)
-          const uint64_t slot = ctx->h_desc.as<uint64_t>()[k];
-          if (k + 6 < e2) {   // the GPU wrote these lines: every first touch is a miss -- have the pair six ahead on its way
-            const uint64_t kn = k + 6, sn = ctx->h_desc.as<uint64_t>()[kn];
-            const uint32_t nwn = (batch->len_a[c.first + kn] + batch->len_b[c.first + kn] + 31u) >> 5;
-            const uint32_t *pn = h_moves + 2ull * max_hits * ((sn >> 5) + kn);
-            __builtin_prefetch(h_w + 4 * kn * max_hits); __builtin_prefetch(pn + nwn - 1); __builtin_prefetch(pn + 2 * nwn - 1);
-            __builtin_prefetch(batch->arena + batch->off_a[c.first + kn]);
-          }
-          for (uint32_t j = 0; j < take; ++j, ++hi) {
-            const uint64_t w = k * max_hits + j;
-            const uint32_t len = h_w[4 * w + 1];
-            const uint64_t need = out_bytes(k, j, len);
-            if (hi >= hit_room || at + need > str_room) { stop = true; break; }   // (no_room is set: the call reports it)
-            const uint32_t *pa = h_moves + 2ull * max_hits * ((slot >> 5) + k) + 2ull * j * nwd;
-            seqalign_sw_hit_t &h = hits[first_hit + hi];
-            uint32_t pos[4], clen = 0;
-            const int prc = ctx->cigar_format
-              ? sa_cigar_sw_moves(batch->arena + batch->off_a[pp], batch->arena + batch->off_b[pp], h_w[4 * w + 2], h_w[4 * w + 3], pa, pa + nwd,
-                                  nwd, len, ctx->cigar_format, ctx->cigar_fold, out_a + first_str + at, need, pos, &clen)
-              : sa_expand_sw_moves(batch->arena + batch->off_a[pp], batch->arena + batch->off_b[pp], h_w[4 * w + 2], h_w[4 * w + 3],
-                                   pa, pa + nwd, nwd, len, out_a + first_str + at, out_b + first_str + at, pos);
-            if (prc) { int expected = SEQALIGN_OK; bad.compare_exchange_strong(expected, prc); stop = true; break; }
-            h.pair = pp; h.score = (int32_t)h_w[4 * w]; h.pos_a = pos[0]; h.pos_b = pos[1]; h.len_a = pos[2]; h.len_b = pos[3];
-            h.length = len; h.str_off = first_str + at;
-            at += need; ++done_h; done_b += need;
-          }
-        }
-        delivered_hits.fetch_add(done_h); delivered_bytes.fetch_add(done_b);
-      });
-      const uint64_t n_out = no_room ? std::min<uint64_t>(delivered_hits.load(), hit_room) : blk_hits[nblk];
-      *used_str += no_room ? delivered_bytes.load() : blk_bytes[nblk];
-      if (bad.load()) return bad.load();
-      *found += n_out;
-      tm.lap("sw one trip: hits expanded");
-      return no_room ? SEQALIGN_E_NOMEM : SEQALIGN_OK;
-    }
-  }
-
-  // ---- round trip 1: hit counts and status
-  if ((rc = ctx->h_tmeta.reserve(n * 16 + 64))) return rc;
-  unsigned long long *h_err_key = ctx->h_tmeta.as<unsigned long long>();
-  const uint32_t *h_count = reinterpret_cast<const uint32_t *>(h_err_key + n), *h_status = h_count + n;
-  HIP_TRY(hipMemcpyAsync(h_err_key, d_meta.p, n * 16, hipMemcpyDeviceToHost, st));
-  if ((rc = fetch_status(ctx, c, nullptr))) return rc;   // fill status; synchronises the stream
-  tm.lap("sw: wait (fill + sweep), counts");
-  if (trace) {
-    std::vector<unsigned long long> t(8 * n);
-    HIP_TRY(hipMemcpyAsync(t.data(), d_trace.p, n * 64, hipMemcpyDeviceToHost, st));
-    HIP_TRY(stream_wait_spinning(st));
-    double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hits_total = 0;
-    for (uint64_t k = 0; k < n; ++k) {
-      for (int j = 0; j < 8; ++j) sum[j] += (double)t[8 * k + j];
-      hits_total += h_count[k];
-    }
-    fprintf(stderr, "[seqalign sweep trace] pairs %llu  per pair: %.0f cycles (s_memtime), %.1f rows, %.1f active row segments, "
-                    "%.1f passes, %.0f cycles in active segments, %.2f hits; wide pairs, per row: prefetch issue %.0f, segments %.0f, fence + rotate %.0f cycles\n",
-            (unsigned long long)n, sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n, hits_total / n, sum[5] / n, sum[6] / n, sum[7] / n);
-  }
-
-  uint64_t str_total = 0;
-  bool overflow = false;
-  std::vector<unsigned long long> big;
-  for (uint64_t k = 0; k < n && !overflow; ++k) {
-    const uint32_t cnt = h_count[k], take = std::min(cnt, max_hits);
-    unsigned long long *dev_keys = d_keys.as<unsigned long long>() + hit_off[k] + batch->len_b[c.first + k] + 1;
-    if (h_status[k] & SA_SWEEP_UNSORTED) {   // more than 64 hits in one pair: ordered here (rare; that pair's keys only)
-      // (on the context's stream, waited for both ways: the kernels that wrote the keys and the walkers that read them
-      // run on that stream, and it is a non-blocking one -- a null-stream hipMemcpy would not be ordered with it)
-      big.resize(cnt);
-      HIP_TRY(hipMemcpyAsync(big.data(), dev_keys, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(stream_wait_spinning(st));
-      std::sort(big.begin(), big.end());
-      HIP_TRY(hipMemcpyAsync(dev_keys, big.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(stream_wait_spinning(st));
-    }
-    if (h_status[k] & SA_SWEEP_OVERFLOW) {
-      set_last_error("seqalign_sw_batch: internal error: pair " + std::to_string(c.first + k) + " has more hits than its share of the scratch arena");
-      return SEQALIGN_E_HIP;
-    }
-    if (const uint32_t err = h_status[k] & ~SA_SWEEP_UNSORTED) {
-      // a walk met an error.  The reference would have met it too unless it had stopped before: max_hits hits
-      // found among the walks in front of this one
-      bool moot = false;
-      if (cnt >= max_hits) {
-        unsigned long long last;
-        HIP_TRY(hipMemcpyAsync(&last, dev_keys + (max_hits - 1), 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(stream_wait_spinning(st));
-        moot = last < h_err_key[k];
+        if (take(k, j)) { ++hs; bytes += out_bytes(k, j, len); }
       }
-      if (!moot) return (int)err;
     }
-    const uint64_t slot = (uint64_t)batch->len_a[c.first + k] + batch->len_b[c.first + k];
-    for (uint32_t j = 0; j < take; ++j) {
-      if (*found + walk_pair.size() >= hit_cap) { overflow = true; break; }   // reported after what fits is delivered
-      walk_pair.push_back((uint32_t)k); walk_rank.push_back(j); walk_str.push_back(str_total);
-      str_total += slot;
+    blk_hits[bi + 1] = hs; blk_bytes[bi + 1] = bytes;
+  });
+  if (first_err.load() != ~0ull) return (int)(first_err.load() & 255u);
+  tm.lap("sw moves: hits counted");
+  for (uint64_t bi = 0; bi < nblk; ++bi) { blk_hits[bi + 1] += blk_hits[bi]; blk_bytes[bi + 1] += blk_bytes[bi]; }
+  const uint64_t hit_room = sink.hit_room(), str_room = sink.str_room();
+  const bool out_of_room = blk_hits[nblk] > hit_room || blk_bytes[nblk] > str_room;
+  const uint64_t first_hit = sink.found, first_str = sink.used;
+  std::atomic<uint64_t> delivered_hits{0}, delivered_bytes{0};
+  std::atomic<int> bad{SEQALIGN_OK};
+  parallel_for(nblk, [=, &sink, &bad, &delivered_hits, &delivered_bytes](uint64_t bi) {
+    uint64_t hi = blk_hits[bi], at = blk_bytes[bi], done_h = 0, done_b = 0;
+    if (hi >= hit_room || at >= str_room) return;   // (everything from here on is beyond the caller's room)
+    bool stop = false;
+    for (uint64_t k = bi * kBlk, e = std::min(n, (bi + 1) * kBlk); k < e && !stop; ++k) {
+      if (k + 6 < e) {   // the GPU wrote these lines: every first touch is a miss -- have the pair six ahead on its way
+        const uint64_t kn = k + 6;
+        const uint32_t nwn = (batch->len_a[first + kn] + batch->len_b[first + kn] + 31u) >> 5;
+        const uint32_t *pn = planes_of(kn, 0, nwn);
+        __builtin_prefetch(h_w + 4 * kn * wpp); __builtin_prefetch(pn + nwn - 1); __builtin_prefetch(pn + 2 * nwn - 1);
+        __builtin_prefetch(batch->arena + batch->off_a[first + kn]);
+      }
+      const uint64_t p = first + k;
+      const uint32_t nwd = (batch->len_a[p] + batch->len_b[p] + 31u) >> 5;
+      for (uint32_t j = 0, nj = walks(k); j < nj; ++j) {
+        if (!take(k, j)) continue;
+        const uint64_t w = k * wpp + j;
+        const uint32_t len = h_w[4 * w + 1];
+        const uint64_t need = out_bytes(k, j, len);
+        if (hi >= hit_room || at + need > str_room) { stop = true; break; }   // (out_of_room is set: the call reports it)
+        const uint32_t *pa = planes_of(k, j, nwd);
+        uint32_t pos[4], clen = 0;
+        const int prc = ctx->cigar_format
+          ? sa_cigar_sw_moves(batch->arena + batch->off_a[p], batch->arena + batch->off_b[p], h_w[4 * w + 2], h_w[4 * w + 3], pa, pa + nwd, nwd, len,
+                              ctx->cigar_format, ctx->cigar_fold, sink.out_a + first_str + at, need, pos, &clen)
+          : sa_expand_sw_moves(batch->arena + batch->off_a[p], batch->arena + batch->off_b[p], h_w[4 * w + 2], h_w[4 * w + 3],
+                               pa, pa + nwd, nwd, len, sink.out_a + first_str + at, sink.out_b + first_str + at, pos);
+        if (prc) { int expected = SEQALIGN_OK; bad.compare_exchange_strong(expected, prc); stop = true; break; }
+        sink.record(first_hit + hi, seqalign_sw_hit_t{p, (int32_t)h_w[4 * w], pos[0], pos[1], pos[2], pos[3], len, 0}, first_str + at);
+        ++hi; at += need; ++done_h; done_b += need;
+      }
     }
-  }
-  const uint64_t nw = walk_pair.size();
-  if (nw > 0xffffffffull) return SEQALIGN_E_TOO_LARGE;
+    delivered_hits.fetch_add(done_h, std::memory_order_relaxed); delivered_bytes.fetch_add(done_b, std::memory_order_relaxed);
+  });
+  sink.used += delivered_bytes.load();
+  tm.lap("sw moves: hits expanded");
+  if (bad.load()) return bad.load();
+  sink.found += delivered_hits.load();
+  return out_of_room ? SEQALIGN_E_NOMEM : SEQALIGN_OK;
+}
 
-  // ---- one traceback per hit (smith_waterman.c:217-255; the traceback kernels of sa_traceback.hip, one walk per hit)
-  // per walk: head | len | score | status | pos[4]
-  if ((rc = d_walk.reserve(nw * 16 + 16)) || (rc = d_hits.reserve(nw * 32 + 16)) ||
-      (rc = ctx->t_out_a.reserve(str_total + 16)) || (rc = ctx->t_out_b.reserve(str_total + 16)) ||
-      (rc = ctx->h_misc.reserve(nw * 32 + 16)) || (rc = d_dst.reserve(nw * 8 + 16)))
-    return rc;
-  uint64_t *dv_walk_str = d_walk.as<uint64_t>();
-  uint32_t *dv_walk_pair = reinterpret_cast<uint32_t *>(dv_walk_str + nw), *dv_walk_rank = dv_walk_pair + nw;
-  uint32_t *dv_meta = d_hits.as<uint32_t>();
-  const uint32_t *h_meta = ctx->h_misc.as<uint32_t>();
-  if (nw) {
-    // the three lists as the one block they are on the device, from pinned memory: one copy instead of three staged ones
-    if ((rc = ctx->h_desc.reserve(nw * 16 + 16))) return rc;
-    { uint64_t *hw_str = ctx->h_desc.as<uint64_t>();
-      uint32_t *hw_pair = reinterpret_cast<uint32_t *>(hw_str + nw), *hw_rank = hw_pair + nw;
-      memcpy(hw_str, walk_str.data(), nw * 8); memcpy(hw_pair, walk_pair.data(), nw * 4); memcpy(hw_rank, walk_rank.data(), nw * 4);
-      HIP_TRY(hipMemcpyAsync(dv_walk_str, hw_str, nw * 16, hipMemcpyHostToDevice, st)); }
-    SaTraceParams t;
-    memset(&t, 0, sizeof(t));
-    t.arena = d.arena; t.off_a = d.off_a; t.len_a = d.len_a; t.off_b = d.off_b; t.len_b = d.len_b;
-    t.mat_off = d.mat_off; t.M = d.match_scores; t.A = d.gap_a_scores; t.B = d.gap_b_scores;
-    t.code = sc->d_code; t.table = sc->d_table; t.str_off = dv_walk_str;
-    t.out_a = ctx->t_out_a.as<char>(); t.out_b = ctx->t_out_b.as<char>();
-    t.out_head = dv_meta; t.out_len = dv_meta + nw; t.out_score = reinterpret_cast<int32_t *>(dv_meta + 2 * nw);
-    t.trace_status = dv_meta + 3 * nw; t.out_pos = dv_meta + 4 * nw;
-    t.walker_pair = dv_walk_pair; t.walker_rank = dv_walk_rank; t.hit_keys = q.hit_keys; t.hit_off = q.hit_off; t.layout = layout;
-    t.n_pairs = (uint32_t)nw; t.K = q.K; t.open1 = q.open1; t.ext = q.ext; t.gen_eq = q.gen_eq; t.gen_ne = q.gen_ne;
-    t.flags = q.flags; t.tune_walker = ctx->opt.trace_kernel; t.tune_group = ctx->opt.walk_group; t.dirs = q.dirs;
-    if ((e = sa_launch_nw_traceback(t, st)) != hipSuccess) return fail_hip(e, "sw hit traceback");
-    // ---- round trip 2: the hits (their lengths size the packing)
-    HIP_TRY(hipMemcpyAsync(ctx->h_misc.p, dv_meta, nw * 32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(stream_wait_spinning(st));
-  }
-  tm.lap("sw: hit tracebacks");
-  dst_off.resize(nw);
+// Hits that came home as STRINGS (walkers that write the two gapped strings into slots of len_a + len_b characters on the
+// device), for both paths that have them (the best-hit call off the moves form, the three-trip multi-hit call).  Given nw walks
+// with their words at home in h_meta and on the device in dv_meta -- head | len | score | status | pos[4], nw of each -- and
+// their string slots' offsets on the device (dv_str_off):
+//   a hit is much shorter than its slot of len_a + len_b characters: pack the strings on the device, bring back
+//   what was written (C3: 2 x 1.7 MB instead of 2 x 11.5 MB over PCIe),
+// then where every wanted hit (take(w, score)) goes in the caller's buffers -- a prefix over the lengths while there is room --
+// and the copies and records on the thread pool.  The lowest walk with a status is the call's error; SEQALIGN_E_NOMEM is returned
+// after what fits is delivered.  pair_of(w): the batch's pair of walk w.
+template <class PairOf, class Take>
+static int deliver_strings(seqalign_ctx *ctx, hipStream_t st, uint64_t nw, const uint32_t *h_meta, const uint32_t *dv_meta,
+                           const uint64_t *dv_str_off, PairOf pair_of, Take take, HitSink &sink, StageTimer &tm) {
+  int rc;
+  DevBuf &d_dst = ctx->e[11], &d_gath_a = ctx->e[9];
+  std::vector<uint64_t> dst_off(nw);
   uint64_t gathered = 0;
   for (uint64_t w = 0; w < nw; ++w) {
     if (h_meta[3 * nw + w]) return (int)h_meta[3 * nw + w];
@@ -539,65 +281,400 @@ static int sw_chunk_device_enumerate(seqalign_ctx *ctx, const seqalign_batch_t *
   }
   const uint64_t gath_b_at = (gathered + 15) & ~(uint64_t)15;   // a-strings, then b-strings: one buffer, one copy home
   if (nw) {
-    if ((rc = d_gath_a.reserve(gath_b_at + gathered + 16)) || (rc = ctx->h_ta.reserve(gath_b_at + gathered + 16)) ||
-        (rc = ctx->h_desc.reserve(nw * 16 + 16)))
+    if ((rc = d_dst.reserve(nw * 8 + 16)) || (rc = d_gath_a.reserve(gath_b_at + gathered + 16)) ||
+        (rc = ctx->h_ta.reserve(gath_b_at + gathered + 16)) || (rc = ctx->h_desc.reserve(nw * 8 + 16)))
       return rc;
-    memcpy(ctx->h_desc.p, dst_off.data(), nw * 8);   // (pinned; the walker lists it held are on the device by now: the stream was waited for)
+    memcpy(ctx->h_desc.p, dst_off.data(), nw * 8);   // (pinned; whatever it held -- run_chunk's descriptors, the walker lists -- is on the device by now: the stream was waited for)
     HIP_TRY(hipMemcpyAsync(d_dst.p, ctx->h_desc.p, nw * 8, hipMemcpyHostToDevice, st));
-    if ((e = sa_launch_gather_hits(ctx->t_out_a.as<char>(), ctx->t_out_b.as<char>(), dv_walk_str, dv_meta, dv_meta + nw,
-                                   d_dst.as<uint64_t>(), d_gath_a.as<char>(), d_gath_a.as<char>() + gath_b_at, (uint32_t)nw, st)) != hipSuccess)
-      return fail_hip(e, "gather hits");
+    const hipError_t e = sa_launch_gather_hits(ctx->t_out_a.as<char>(), ctx->t_out_b.as<char>(), dv_str_off, dv_meta, dv_meta + nw,
+                                               d_dst.as<uint64_t>(), d_gath_a.as<char>(), d_gath_a.as<char>() + gath_b_at, (uint32_t)nw, st);
+    if (e != hipSuccess) return fail_hip(e, "gather hits");
     HIP_TRY(hipMemcpyAsync(ctx->h_ta.p, d_gath_a.p, gath_b_at + gathered, hipMemcpyDeviceToHost, st));
     HIP_TRY(stream_wait_spinning(st));
   }
-  tm.lap("sw: gather + strings D2H");
+  tm.lap("sw strings: gather + strings D2H");
   const char *ha = ctx->h_ta.as<char>(), *hb = ha + gath_b_at;
-  // where every hit goes in the caller's buffers (a prefix over the lengths), then the copies on the thread pool
-  uint64_t n_out = 0;
+  auto hit_of = [=](uint64_t w) {
+    const uint32_t *pos = h_meta + 4 * nw + 4 * w;
+    return seqalign_sw_hit_t{pair_of(w), reinterpret_cast<const int32_t *>(h_meta)[2 * nw + w], pos[0], pos[1], pos[2], pos[3], h_meta[nw + w], 0};
+  };
+  struct Placed { uint64_t walk, str_off; };
+  std::vector<Placed> placed;
+  const uint64_t first_hit = sink.found;
   bool no_room = false;
-  std::vector<uint64_t> out_off(nw);
   for (uint64_t w = 0; w < nw; ++w) {
     const uint32_t len = h_meta[nw + w];
-    if (*found + n_out >= hit_cap) { no_room = true; break; }
+    if (!take(w, reinterpret_cast<const int32_t *>(h_meta)[2 * nw + w])) continue;
     if (ctx->cigar_format) {   // CIGAR mode on a path whose walkers write strings: encode them, one after the other (not the common kind)
-      const uint64_t took = put_alignment(ctx, ha + dst_off[w], hb + dst_off[w], len, out_a, out_b, *used_str, str_cap > *used_str ? str_cap - *used_str : 0);
-      if (!took) { no_room = true; break; }
-      out_off[w] = *used_str;
-      *used_str += took;
-      ++n_out;
+      if (!sink.put(ctx, hit_of(w), ha + dst_off[w], hb + dst_off[w])) { no_room = true; break; }
       continue;
     }
-    if (*used_str + len + 1 > str_cap) { no_room = true; break; }
-    out_off[w] = *used_str;
-    *used_str += len + 1;
-    ++n_out;
+    if (!sink.hit_room() || (uint64_t)len + 1 > sink.str_room()) { no_room = true; break; }
+    placed.push_back(Placed{w, sink.used});
+    ++sink.found; sink.used += (uint64_t)len + 1;
   }
-  const uint64_t first_hit = *found;
   constexpr uint64_t kPack = 1024;
-  parallel_for((n_out + kPack - 1) / kPack, [&](uint64_t blk) {
-    for (uint64_t w = blk * kPack, e2 = std::min(n_out, (blk + 1) * kPack); w < e2; ++w) {
-      const uint32_t len = h_meta[nw + w], *pos = h_meta + 4 * nw + 4 * w;
-      if (!ctx->cigar_format) {
-        memcpy(out_a + out_off[w], ha + dst_off[w], len);
-        memcpy(out_b + out_off[w], hb + dst_off[w], len);
-        out_a[out_off[w] + len] = out_b[out_off[w] + len] = '\0';
-      }
-      seqalign_sw_hit_t &h = hits[first_hit + w];
-      h.pair = c.first + walk_pair[w]; h.score = reinterpret_cast<const int32_t *>(h_meta)[2 * nw + w];
-      h.pos_a = pos[0]; h.pos_b = pos[1]; h.len_a = pos[2]; h.len_b = pos[3]; h.length = len; h.str_off = out_off[w];
+  const Placed *const pl = placed.data();
+  const uint64_t n_placed = placed.size(), *const src_off = dst_off.data();
+  parallel_for((n_placed + kPack - 1) / kPack, [=, &sink](uint64_t blk) {   // (by value: see deliver_moves)
+    for (uint64_t i = blk * kPack, e = std::min(n_placed, (blk + 1) * kPack); i < e; ++i) {
+      const uint64_t w = pl[i].walk, at = pl[i].str_off;
+      const uint32_t len = h_meta[nw + w];
+      memcpy(sink.out_a + at, ha + src_off[w], len);
+      memcpy(sink.out_b + at, hb + src_off[w], len);
+      sink.out_a[at + len] = sink.out_b[at + len] = '\0';
+      sink.record(first_hit + i, hit_of(w), at);
     }
   });
-  *found += n_out;
-  if (no_room) return SEQALIGN_E_NOMEM;
-  tm.lap("sw: unpack hits");
-  return overflow ? SEQALIGN_E_NOMEM : SEQALIGN_OK;
+  tm.lap("sw strings: unpack hits");
+  return no_room ? SEQALIGN_E_NOMEM : SEQALIGN_OK;
 }
 
-// best hit of every pair of one chunk: fill (+ best cell) -> device traceback -> strings back
+// SW hits of one chunk, enumerated on the device:
+//   fill (reports the candidates' count, box and columns per row) -> reverse sweep (sa_sw_sweep.hip: every hit's
+//   key, in order)
+//   -> one traceback per wanted hit -> strings packed -> D2H.
+// Host round trips: the hit counts (they size the traceback), the hits' lengths (they size the packing), the strings -- or ONE
+// trip for everything when the call is the common kind (enqueue).  Appends to the caller's hit array / string buffers.
+// plan (sizes, scratch, which fill) -> enqueue (fill, sweep, with luck the walks) -> finish_one_trip | finish_three_trip.
+struct SwEnumChunk {
+  seqalign_ctx *ctx;
+  const seqalign_batch_t *batch;
+  const Chunk &c;
+  const seqalign_dev_scoring *sc;
+  const int32_t *min_score;
+  const uint32_t max_hits;
+  HitSink &sink;
+  const uint64_t n;
+  hipStream_t st;
+  DevBuf &d_min, &d_keys, &d_box, &d_rows, &d_rowoff, &d_walk, &d_hits, &d_meta, &d_hitoff, &d_trace;
+  // sources of asynchronous H2D copies: declared BEFORE the guard below, so that they are destroyed after its
+  // hipStreamSynchronize on every exit path
+  std::vector<uint64_t> hit_off, row_off, walk_str;
+  std::vector<uint32_t> walk_pair, walk_rank;
+  StreamSyncOnExit sync_on_exit;
+  StageTimer tm;
+  const SaKeyLayout layout;
+  const bool trace;   // development aid: per-pair counters on stderr
+  SaCandBox cand{};
+  SaSweepParams q;
+  seqalign_dev_batch_t d;
+  bool dirs_used = false, allow_dirs = false, may_one_trip = false, one_trip = false;
+  uint64_t stride = 0;
+
+  SwEnumChunk(seqalign_ctx *ctx_, const seqalign_batch_t *batch_, const Chunk &c_, const seqalign_dev_scoring *sc_, const int32_t *min_score_,
+              uint32_t max_hits_, HitSink &sink_)
+      : ctx(ctx_), batch(batch_), c(c_), sc(sc_), min_score(min_score_), max_hits(max_hits_), sink(sink_), n(c_.count), st(ctx_->stream),
+        d_min(ctx_->e[0]), d_keys(ctx_->e[1]), d_box(ctx_->e[3]), d_rows(ctx_->e[4]), d_rowoff(ctx_->e[5]), d_walk(ctx_->e[6]),
+        d_hits(ctx_->e[7]), d_meta(ctx_->e[8]), d_hitoff(ctx_->e[13]), d_trace(ctx_->e[12]), hit_off(c_.count + 1, 0), sync_on_exit(ctx_->stream),
+        tm(ctx_->opt.timing), layout(key_layout(sc_, c_.max_a, c_.max_b)), trace(ctx_->opt.sweep_trace) {
+    memset(&q, 0, sizeof(q));
+  }
+  SwEnumChunk(const SwEnumChunk &) = delete;   // (cand points into it)
+
+  SaSweepParams sweep_params(bool dirs) const {
+    SaSweepParams r;
+    memset(&r, 0, sizeof(r));
+    r.arena = d.arena; r.off_a = d.off_a; r.len_a = d.len_a; r.off_b = d.off_b; r.len_b = d.len_b;
+    r.mat_off = d.mat_off; r.M = d.match_scores; r.A = d.gap_a_scores; r.B = d.gap_b_scores;
+    r.code = sc->d_code; r.table = sc->d_table; r.cand_count = cand.cand_count; r.cand_box = cand.cand_box;
+    r.min_score = d_min.as<int32_t>(); r.hit_keys = d_keys.as<unsigned long long>(); r.hit_off = d_hitoff.as<uint64_t>();
+    r.err_key = d_meta.as<unsigned long long>();
+    r.hit_count = reinterpret_cast<uint32_t *>(d_meta.as<unsigned long long>() + n); r.status = r.hit_count + n;
+    r.n_pairs = (uint32_t)n; r.K = sc->flat.n_classes; r.open1 = sc->flat.open1; r.ext = sc->flat.ext;
+    r.gen_eq = sc->flat.gen_eq; r.gen_ne = sc->flat.gen_ne; r.flags = sc->flat.flags;
+    r.max_len_a = c.max_a; r.max_len_b = c.max_b; r.layout = layout; r.tune_cpl = ctx->opt.sweep_cpl; r.tune_ev = ctx->opt.sweep_ev;
+    r.dirs = dirs ? cand.dirs : nullptr;
+    return r;
+  }
+
+  // ---- sizes and scratch; which fill, and whether everything may go in one trip
+  int plan() {
+    int rc;
+    if (!key_layout_fits(layout)) return SEQALIGN_E_TOO_LARGE;   // (seqalign_sw_batch checks the whole batch first)
+    // every pair's part of the scratch arena (its rows' candidate columns, then its hits' keys)
+    {
+      const int64_t best = best_move(sc);
+      uint32_t pa = ~0u, pb = ~0u; int32_t pm = 0; uint64_t pe = 0;   // (reads of one length: the division once per run of equal pairs)
+      for (uint64_t k = 0; k < n; ++k) {
+        const uint32_t xa = batch->len_a[c.first + k], xb = batch->len_b[c.first + k];
+        const int32_t xm = min_score[c.first + k];
+        if (xa != pa || xb != pb || xm != pm) { pa = xa; pb = xb; pm = xm; pe = hit_arena_elements(xa, xb, xm, best); }
+        hit_off[k + 1] = hit_off[k] + pe;
+      }
+    }
+    if ((rc = d_min.reserve(n * 4)) || (rc = ctx->cand_count.reserve(n * 4)) || (rc = d_box.reserve(n * 16)) ||
+        (rc = d_keys.reserve(hit_off[n] * 8 + 16)) || (rc = d_meta.reserve(n * 16 + 16)) || (rc = d_hitoff.reserve((n + 1) * 8)))
+      return rc;
+    // (from pinned staging: a copy from the caller's pageable array is staged by the runtime and waited for)
+    if ((rc = ctx->h_tb.reserve((n + 1) * 8 + n * 4 + 16))) return rc;
+    { uint64_t *hs_off = ctx->h_tb.as<uint64_t>();
+      int32_t *hs_min = reinterpret_cast<int32_t *>(hs_off + n + 1);
+      memcpy(hs_off, hit_off.data(), (n + 1) * 8); memcpy(hs_min, min_score + c.first, n * 4);
+      HIP_TRY(hipMemcpyAsync(d_hitoff.p, hs_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_min.p, hs_min, n * 4, hipMemcpyHostToDevice, st)); }
+    cand.cand_count = ctx->cand_count.as<uint32_t>(); cand.cand_box = d_box.as<uint32_t>(); cand.cand_min = d_min.as<int32_t>();
+    cand.cand_rows = d_keys.as<uint32_t>(); cand.hit_off = d_hitoff.as<uint64_t>();
+    // plain scorings, rows up to 1 024 columns (513 and up: see wide_ok below): the fill writes match_scores + one byte of directions per cell instead of the
+    // three matrices (sa_fill_dirs.hip); the directions go where gap_a_scores would have gone
+    // every pair of the chunk the same shape (reads against windows of one length), match / mismatch scoring: the packed
+    // two-pairs-per-wave fill (sa_fill_dirs_x2.hip); every pair's cells then start on a multiple of 256
+    const PackedShape shape = packed_fill_shape(ctx, batch, c, sc, sw_dirs_x2_applicable, kPackedFillMinPairs, false);
+    stride = shape.stride;
+    // (only when the sweep will run in its rows-in-registers form: not with the strip / LDS forms forced by an option)
+    // and rows of 513 .. 1 024 columns only where the sweep's one-word form takes them (sa_launch_sw_sweep) and a wave per pair fills
+    // the chip (few wide pairs: strips, below, as before)
+    const bool wide_row = c.max_a + 1 > 512;
+    const bool wide_ok = ctx->opt.sweep_ev && layout.row_bits + layout.col_bits + layout.score_bits <= 62 &&
+                         (n >= (c.max_a + 1 > 768 ? 640u : 128u) || ctx->opt.sweep_mode == 1);
+    // (tools/sw_wide_few.py, 700 x 1000 -- 12 columns per lane: 128 pairs 4.04 -> 3.69 ms, 64: 3.51 -> 3.67; 900 x 1000 -- 16 per lane:
+    //  512 pairs 5.8 on strips / 6.3 here, 1 024 pairs 8.1 / 6.2)
+    allow_dirs = ctx->opt.sweep_mode != 2 && ctx->opt.sweep_cpl == 0 && (!wide_row || wide_ok);
+    // (the packed direction-byte fill is bound by instruction issue: its arenas need no placement walk)
+    if ((rc = reserve_arenas(ctx, (stride ? shape.dir_bytes : c.cells) * 4, !(allow_dirs && stride != 0)))) return rc;
+    cand.dirs = allow_dirs ? ctx->A.as<uint8_t>() : nullptr; cand.dirs_used = &dirs_used;
+    if (!allow_dirs) stride = 0;
+    cand.uniform_stride = stride == kBucketShapes ? 256 : stride;
+    may_one_trip = allow_dirs && ctx->opt.sweep_mode == 0 && !trace && ctx->opt.nw_moves && max_hits <= 8 &&
+                   n * max_hits <= ((uint64_t)4 << 20) && c.max_a + 1 <= 1024;
+    if (may_one_trip) {
+      const uint64_t move_words = 2ull * max_hits * ((c.seq_bytes >> 5) + n) + 2;
+      if ((rc = ctx->h_ta.reserve(move_words * 4)) || (rc = ctx->h_B.reserve(n * max_hits * 16 + 16)) || (rc = ctx->h_tmeta.reserve(n * 16 + 64)))   // (h_misc is fetch_status')
+        return rc;
+    }
+    return SEQALIGN_OK;
+  }
+
+  // ---- the fill, the sweep -- every hit of every pair -- and, when the call is the common kind, the walks
+  int enqueue() {
+    int rc;
+    hipError_t e;
+    bool reported = false;
+    if ((rc = run_chunk(ctx, batch, c, sc, &d, nullptr, &cand, &reported, stride))) return rc;
+    // ---- ONE trip for everything, when the call is the common kind: direction bytes, one wave per pair in the sweep, a few
+    // hits per pair wanted.  The hit walks are launched BEFORE anybody has seen the sweep's counts -- max_hits walks per pair,
+    // walk w = hit w % max_hits of pair w / max_hits, those beyond a pair's hits return at once (sa_traceback.hip) -- and send
+    // home two bits per column into fixed slots of pinned memory (host/sa_moves.c), so nothing has to be sized, gathered or
+    // copied by a second and third launch + wait: counts, per-walk words and moves are all there after one synchronisation,
+    // and the host threads expand the hits straight into the caller's buffers.  (Round 3: counts -> walker lists -> walks ->
+    // lengths -> gather -> strings, three waits.)  Sweep and walks follow the chunk's last fill, in the fills' stream.
+    // (Measured, profiles/r04/r04_sw_pipeline.txt: on a second stream, with equal slices so that a slice's sweep runs beside
+    // the next slice's fill -- both issue vector instructions 50-70 % of the time, neither is bound by memory -- the two
+    // kernels simply share the SIMDs: C3's sweep of 4 096 pairs 0.62 -> 1.97 ms beside a fill, the call 4.6 -> 5.4 ms; and a
+    // sweep on the second, high-priority stream alone behind an event starts 80 us late and runs 0.93 instead of 0.80 ms on C4.)
+    // A pair that needs the host between sweep and walks -- more than 64 hits (keys unsorted), an error to weigh against
+    // max_hits -- sends the whole chunk down the three-trip path, which starts from the same counts.
+    // (behind ALL the fills: per slice -- a small first slice's sweep and walks, then the rest's -- C3 took 5.2 instead of 4.7 ms)
+    one_trip = may_one_trip && dirs_used && reported;   // (else not the common kind: the three-trip path, for the whole chunk)
+    if (one_trip) {
+      q = sweep_params(true);
+      if ((e = sa_launch_sw_sweep(q, st)) != hipSuccess) return fail_hip(e, "sw sweep");
+      SaTraceParams t = trace_params(ctx, sc, d);
+      t.M = d.match_scores;
+      t.str_off = d.off_a;                       // (run_chunk packs a, b, a, b, ...: off_a IS the prefix of len_a + len_b)
+      // walk w of the launch is hit w % max_hits of pair w / max_hits: its slot is 2 max_hits ((off_a >> 5) + pair) + ...
+      t.stage_words = (c.max_a + c.max_b + 31u) >> 5;
+      t.moves = ctx->h_ta.dev_as<uint32_t>(); t.out_meta4 = ctx->h_B.dev_as<uint32_t>();
+      t.walks_per_pair = max_hits; t.hit_count = q.hit_count; t.sweep_status = q.status;
+      t.hit_keys = q.hit_keys; t.hit_off = q.hit_off; t.layout = layout; t.fill_status = d.status;
+      t.n_pairs = (uint32_t)(n * max_hits); t.dirs = q.dirs;
+      if ((e = sa_launch_nw_traceback(t, st)) != hipSuccess) return fail_hip(e, "sw hit traceback");
+      // everything is enqueued on the one stream: one wait for all of it
+      tm.lap("sw: fills, sweeps, walks enqueued");
+      return SEQALIGN_OK;
+    }
+    if (!reported) {   // a fill kernel that cannot report them itself: one pass over match_scores
+      SaReduceParams r;
+      memset(&r, 0, sizeof(r));
+      r.len_a = d.len_a; r.len_b = d.len_b; r.mat_off = d.mat_off; r.M = d.match_scores; r.n_pairs = (uint32_t)n;
+      if ((e = sa_launch_sw_box(r, cand, c.max_b, st)) != hipSuccess) return fail_hip(e, "sw candidate box");
+    }
+    q = sweep_params(dirs_used);
+    // How the pairs are laid over waves (sa_sw_sweep.hip): one wave per pair -- rows in registers (up to 512 columns on three matrices, up to 1 024 on direction bytes),
+    // wider ones in segments with the winners of two rows in LDS -- or, for FEW wide pairs (a wave per pair would leave
+    // the chip empty) and for rows too wide for LDS, one wave per 256-column strip.  The option sweep_mode = strips | pair
+    // forces one (tests, experiments).
+    const int mode_opt = ctx->opt.sweep_mode;   // 0 auto, 1 pair, 2 strips
+    const uint32_t w_max = c.max_a + 1;
+    bool strips = !dirs_used && c.max_a + 1 > 512 && (c.max_a + 1 > SA_SWEEP_LDS_COLUMNS || n < 1024);
+    if (mode_opt == 2) strips = true;
+    if (mode_opt == 1 && w_max <= SA_SWEEP_LDS_COLUMNS) strips = false;
+    if (w_max <= SA_SWEEP_LDS_COLUMNS) q.lds_columns = (c.max_a + 2u) & ~1u;
+    DevBuf &d_prog = ctx->e[2];
+    if (strips) {
+      // strip width by how many waves that makes: 128-column strips (and progress published every 16 rows instead of
+      // 64) when the pairs are so few that 256-column strips would leave most of the chip idle (2 x 10 000^2: 42.7 ->
+      // 32.8 ms; 64-column strips gain nothing more: a row's dependent passes cost ~2 us whatever its width)
+      uint32_t cols = sa_sweep_strip_blocks((uint32_t)n, c.max_a, 256) < 1024 ? 128 : 256;
+      if (const uint32_t v = ctx->opt.sweep_strip; v == 64 || v == 128 || v == 256) cols = v;
+      q.strip_columns = cols; q.strip_interval = cols == 256 ? 64 : 16;
+      const uint32_t spp = sa_sweep_strips_per_pair(c.max_a, cols);
+      const uint64_t blocks = sa_sweep_strip_blocks((uint32_t)n, c.max_a, cols);
+      row_off.resize(n);
+      uint64_t rows_total = 0;
+      for (uint64_t k = 0; k < n; ++k) { row_off[k] = rows_total; rows_total += (uint64_t)batch->len_b[c.first + k] + 1; }
+      if ((rc = d_prog.reserve((2 * blocks + 1) * 4 + 16)) || (rc = d_rows.reserve(rows_total * spp * 16 + 16)) ||
+          (rc = d_rowoff.reserve(n * 8)))
+        return rc;
+      HIP_TRY(hipMemsetAsync(d_prog.p, 0, (2 * blocks + 1) * 4, st));
+      HIP_TRY(hipMemsetAsync(q.err_key, 0xff, n * 8, st));     // the strips of a pair report into the same words
+      HIP_TRY(hipMemsetAsync(q.hit_count, 0, n * 8, st));      // hit_count | status
+      HIP_TRY(hipMemcpyAsync(d_rowoff.p, row_off.data(), n * 8, hipMemcpyHostToDevice, st));
+      q.strip_progress = d_prog.as<uint32_t>(); q.strips_per_pair = spp;
+      q.bnd = d_rows.as<unsigned long long>(); q.row_off = d_rowoff.as<uint64_t>();
+    }
+    if (trace) {
+      if ((rc = d_trace.reserve(n * 64))) return rc;
+      HIP_TRY(hipMemsetAsync(d_trace.p, 0, n * 64, st));
+      q.trace = d_trace.as<unsigned long long>();
+    }
+    if ((e = sa_launch_sw_sweep(q, st)) != hipSuccess) return fail_hip(e, "sw sweep");
+    tm.lap("sw: enqueue fill + sweep");
+    return SEQALIGN_OK;
+  }
+
+  // ---- the one trip's end: counts, per-walk words and moves are at home after one wait.  *clean = false: a pair needs the
+  // host between sweep and walks, the chunk goes the three-trip way (nothing was delivered)
+  int finish_one_trip(bool *clean) {
+    int rc;
+    unsigned long long *h_err = ctx->h_tmeta.as<unsigned long long>();
+    const uint32_t *h_cnt = reinterpret_cast<const uint32_t *>(h_err + n), *h_st = h_cnt + n;
+    HIP_TRY(hipMemcpyAsync(h_err, d_meta.p, n * 16, hipMemcpyDeviceToHost, st));
+    if ((rc = fetch_status(ctx, c, nullptr))) return rc;   // the fill's status words; synchronises the stream
+    tm.lap("sw one trip: wait (fill, sweep, walks)");
+    *clean = true;
+    for (uint64_t k = 0; k < n && *clean; ++k) *clean = h_st[k] == 0;
+    tm.lap("sw one trip: statuses checked");
+    if (!*clean) return SEQALIGN_OK;
+    // (run_chunk's packed offsets: the prefix of len_a + len_b over the chunk's pairs, in the pinned descriptor block)
+    const uint32_t wpp = max_hits;
+    return deliver_moves(ctx, batch, c, ctx->h_B.as<uint32_t>(), ctx->h_ta.as<uint32_t>(), ctx->h_desc.as<uint64_t>(), wpp,
+                         [=](uint64_t k) { return std::min(h_cnt[k], wpp); }, [](uint64_t, uint32_t) { return true; }, sink, tm);
+  }
+
+  // ---- three trips: the hit counts (with the rare cases the host settles: a pair's unsorted keys, an error that max_hits
+  // makes moot), one traceback per wanted hit and its lengths, the strings
+  int finish_three_trip() {
+    int rc;
+    // ---- round trip 1: hit counts and status
+    if ((rc = ctx->h_tmeta.reserve(n * 16 + 64))) return rc;
+    unsigned long long *h_err_key = ctx->h_tmeta.as<unsigned long long>();
+    const uint32_t *h_count = reinterpret_cast<const uint32_t *>(h_err_key + n), *h_status = h_count + n;
+    HIP_TRY(hipMemcpyAsync(h_err_key, d_meta.p, n * 16, hipMemcpyDeviceToHost, st));
+    if ((rc = fetch_status(ctx, c, nullptr))) return rc;   // fill status; synchronises the stream
+    tm.lap("sw: wait (fill + sweep), counts");
+    if (trace) {
+      std::vector<unsigned long long> t(8 * n);
+      HIP_TRY(hipMemcpyAsync(t.data(), d_trace.p, n * 64, hipMemcpyDeviceToHost, st));
+      HIP_TRY(stream_wait_spinning(st));
+      double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hits_total = 0;
+      for (uint64_t k = 0; k < n; ++k) {
+        for (int j = 0; j < 8; ++j) sum[j] += (double)t[8 * k + j];
+        hits_total += h_count[k];
+      }
+      fprintf(stderr, "[seqalign sweep trace] pairs %llu  per pair: %.0f cycles (s_memtime), %.1f rows, %.1f active row segments, "
+                      "%.1f passes, %.0f cycles in active segments, %.2f hits; wide pairs, per row: prefetch issue %.0f, segments %.0f, fence + rotate %.0f cycles\n",
+              (unsigned long long)n, sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n, hits_total / n, sum[5] / n, sum[6] / n, sum[7] / n);
+    }
+
+    uint64_t str_total = 0;
+    bool overflow = false;
+    std::vector<unsigned long long> big;
+    for (uint64_t k = 0; k < n && !overflow; ++k) {
+      const uint32_t cnt = h_count[k], take = std::min(cnt, max_hits);
+      unsigned long long *dev_keys = d_keys.as<unsigned long long>() + hit_off[k] + batch->len_b[c.first + k] + 1;
+      if (h_status[k] & SA_SWEEP_UNSORTED) {   // more than 64 hits in one pair: ordered here (rare; that pair's keys only)
+        // (on the context's stream, waited for both ways: the kernels that wrote the keys and the walkers that read them
+        // run on that stream, and it is a non-blocking one -- a null-stream hipMemcpy would not be ordered with it)
+        big.resize(cnt);
+        HIP_TRY(hipMemcpyAsync(big.data(), dev_keys, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(stream_wait_spinning(st));
+        std::sort(big.begin(), big.end());
+        HIP_TRY(hipMemcpyAsync(dev_keys, big.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(stream_wait_spinning(st));
+      }
+      if (h_status[k] & SA_SWEEP_OVERFLOW) {
+        set_last_error("seqalign_sw_batch: internal error: pair " + std::to_string(c.first + k) + " has more hits than its share of the scratch arena");
+        return SEQALIGN_E_HIP;
+      }
+      if (const uint32_t err = h_status[k] & ~SA_SWEEP_UNSORTED) {
+        // a walk met an error.  The reference would have met it too unless it had stopped before: max_hits hits
+        // found among the walks in front of this one
+        bool moot = false;
+        if (cnt >= max_hits) {
+          unsigned long long last;
+          HIP_TRY(hipMemcpyAsync(&last, dev_keys + (max_hits - 1), 8, hipMemcpyDeviceToHost, st));
+          HIP_TRY(stream_wait_spinning(st));
+          moot = last < h_err_key[k];
+        }
+        if (!moot) return (int)err;
+      }
+      const uint64_t slot = (uint64_t)batch->len_a[c.first + k] + batch->len_b[c.first + k];
+      for (uint32_t j = 0; j < take; ++j) {
+        if (sink.found + walk_pair.size() >= sink.hit_cap) { overflow = true; break; }   // reported after what fits is delivered
+        walk_pair.push_back((uint32_t)k); walk_rank.push_back(j); walk_str.push_back(str_total);
+        str_total += slot;
+      }
+    }
+    const uint64_t nw = walk_pair.size();
+    if (nw > 0xffffffffull) return SEQALIGN_E_TOO_LARGE;
+
+    // ---- one traceback per hit (smith_waterman.c:217-255; the traceback kernels of sa_traceback.hip, one walk per hit)
+    // per walk: head | len | score | status | pos[4]
+    if ((rc = d_walk.reserve(nw * 16 + 16)) || (rc = d_hits.reserve(nw * 32 + 16)) ||
+        (rc = ctx->t_out_a.reserve(str_total + 16)) || (rc = ctx->t_out_b.reserve(str_total + 16)) ||
+        (rc = ctx->h_misc.reserve(nw * 32 + 16)))
+      return rc;
+    uint64_t *dv_walk_str = d_walk.as<uint64_t>();
+    uint32_t *dv_walk_pair = reinterpret_cast<uint32_t *>(dv_walk_str + nw), *dv_walk_rank = dv_walk_pair + nw;
+    uint32_t *dv_meta = d_hits.as<uint32_t>();
+    if (nw) {
+      // the three lists as the one block they are on the device, from pinned memory: one copy instead of three staged ones
+      if ((rc = ctx->h_desc.reserve(nw * 16 + 16))) return rc;
+      { uint64_t *hw_str = ctx->h_desc.as<uint64_t>();
+        uint32_t *hw_pair = reinterpret_cast<uint32_t *>(hw_str + nw), *hw_rank = hw_pair + nw;
+        memcpy(hw_str, walk_str.data(), nw * 8); memcpy(hw_pair, walk_pair.data(), nw * 4); memcpy(hw_rank, walk_rank.data(), nw * 4);
+        HIP_TRY(hipMemcpyAsync(dv_walk_str, hw_str, nw * 16, hipMemcpyHostToDevice, st)); }
+      SaTraceParams t = trace_params(ctx, sc, d);
+      t.M = d.match_scores; t.A = d.gap_a_scores; t.B = d.gap_b_scores;
+      t.str_off = dv_walk_str;
+      t.out_a = ctx->t_out_a.as<char>(); t.out_b = ctx->t_out_b.as<char>();
+      t.out_head = dv_meta; t.out_len = dv_meta + nw; t.out_score = reinterpret_cast<int32_t *>(dv_meta + 2 * nw);
+      t.trace_status = dv_meta + 3 * nw; t.out_pos = dv_meta + 4 * nw;
+      t.walker_pair = dv_walk_pair; t.walker_rank = dv_walk_rank; t.hit_keys = q.hit_keys; t.hit_off = q.hit_off; t.layout = layout;
+      t.n_pairs = (uint32_t)nw; t.dirs = q.dirs;
+      const hipError_t e = sa_launch_nw_traceback(t, st);
+      if (e != hipSuccess) return fail_hip(e, "sw hit traceback");
+      // ---- round trip 2: the hits (their lengths size the packing)
+      HIP_TRY(hipMemcpyAsync(ctx->h_misc.p, dv_meta, nw * 32, hipMemcpyDeviceToHost, st));
+      HIP_TRY(stream_wait_spinning(st));
+    }
+    tm.lap("sw: hit tracebacks");
+    // ---- round trip 3: the strings
+    const uint64_t first = c.first;
+    const uint32_t *pair_in_chunk = walk_pair.data();
+    if ((rc = deliver_strings(ctx, st, nw, ctx->h_misc.as<uint32_t>(), dv_meta, dv_walk_str,
+                              [=](uint64_t w) { return first + pair_in_chunk[w]; }, [](uint64_t, int32_t) { return true; }, sink, tm)))
+      return rc;
+    return overflow ? SEQALIGN_E_NOMEM : SEQALIGN_OK;
+  }
+};
+
+static int sw_chunk_device_enumerate(seqalign_ctx *ctx, const seqalign_batch_t *batch, const Chunk &c, const seqalign_dev_scoring *sc,
+                                     const int32_t *min_score, uint32_t max_hits, HitSink &sink) {
+  SwEnumChunk s(ctx, batch, c, sc, min_score, max_hits, sink);
+  int rc;
+  if ((rc = s.plan()) || (rc = s.enqueue())) return rc;
+  if (s.one_trip) {
+    bool clean = false;
+    if ((rc = s.finish_one_trip(&clean)) || clean) return rc;
+  }
+  return s.finish_three_trip();
+}
+
+// best hit of every pair of one chunk: fill (+ best cell) -> device traceback -> the hits home as moves or as strings
 static int sw_chunk_best_hit(seqalign_ctx *ctx, const seqalign_batch_t *batch, const Chunk &c,
-                             const seqalign_dev_scoring *sc, const int32_t *min_score, seqalign_sw_hit_t *hits,
-                             uint64_t hit_cap, uint64_t *n_hits, uint64_t &found, char *out_a, char *out_b,
-                             uint64_t str_cap, uint64_t &used_str) {
+                             const seqalign_dev_scoring *sc, const int32_t *min_score, HitSink &sink) {
   int rc;
   seqalign_dev_batch_t d;
   bool have_best = false;   // the stream kernel reports the best cell itself
@@ -607,41 +684,24 @@ static int sw_chunk_best_hit(seqalign_ctx *ctx, const seqalign_batch_t *batch, c
   // directions per cell and finds the best cell itself, two pairs per wave (sa_fill_dirs_x2.hip: fill_sw_best_x2_kernel);
   // the walk follows the bytes.  No match_scores, no gap matrices: they are not even allocated.
   bool dirs_used = false;
-  uint64_t stride = 0;
   // (the walks below as tile walks sending home moves: the fill writes the direction byte's LOCAL form, sa_kernels.h)
   // (whatever the chunk's size: 26 000-40 000 pairs of configs[2]'s / [3]'s shape are 0-9 % faster with tile walks on the local form than with
   //  lane walks on the older one: profiles/r06/r06_local_dirs.txt)
   const bool local = ctx->opt.dirs_local && ctx->opt.nw_moves && (ctx->opt.trace_kernel ? ctx->opt.trace_kernel == 2 : true);
-  {
-    bool same_shape = true;
-    for (uint64_t k = 1; k < n && same_shape; ++k)
-      same_shape = batch->len_a[c.first + k] == batch->len_a[c.first] && batch->len_b[c.first + k] == batch->len_b[c.first];
-    // From how many pairs: what this fill competes with below that is not a one-pair direction fill (the NW / multi-hit paths'
-    // kPackedFillMinPairs) but three matrices and their walker.  tools/sw_best_few.py, same process, packed against not:
-    // BLOSUM62 300 x 300 -- ahead at every size (128 pairs 0.52 -> 0.46 ms, 2 047 pairs 0.92 -> 0.58); match / mismatch, 150 x 1 000 --
-    // level at ~1 400 pairs (1 024: 0.68 -> 0.76, 2 047: 0.99 -> 0.83); 700 x 1 000 -- at ~700 (512: 1.63 -> 1.94, 1 024: 2.25 -> 2.00,
-    // 2 047: 4.10 -> 2.11): a wave's row costs more with two pairs in it, which is what a launch too small to fill the chip pays.
-    const uint64_t best_min_pairs = sc->flat.n_classes > 1 ? 128 : c.max_a + 1 > 512 ? 1024 : 1536;
-    if (same_shape && (n >= best_min_pairs || ctx->opt.pack16 == 2) && sw_best_x2_applicable(ctx, sc, c.max_a, c.max_b))
-      stride = ((sa_dirs_blocked_shape(c.max_a) ? sa_dirs_blocked_bytes(c.max_a, c.max_b) : (uint64_t)(c.max_a + 1ull) * (c.max_b + 1ull)) + 255u) & ~(uint64_t)255u;
-    else if (!same_shape && (n >= kBucketedFillMinPairs || ctx->opt.pack16 == 2) && ((uint64_t)c.max_a + 1) * ((uint64_t)c.max_b + 1) <= kShapeTableMax &&
-             sw_best_x2_applicable(ctx, sc, c.max_a, c.max_b))
-      stride = kBucketShapes;   // ragged: run_chunk pairs up the pairs of equal shape
-  }
-  if (stride) {
-    uint64_t dir_bytes = n * stride;
-    if (stride == kBucketShapes) {
-      dir_bytes = 0;
-      for (uint64_t k = 0; k < n; ++k) {
-        const uint32_t xa = batch->len_a[c.first + k], xb = batch->len_b[c.first + k];
-        dir_bytes += ((sa_dirs_blocked_shape(c.max_a) ? sa_dirs_blocked_bytes(xa, xb) : ((uint64_t)xa + 1) * ((uint64_t)xb + 1)) + 255u) & ~(uint64_t)255u;
-      }
-    }
-    if ((rc = ctx->dirs.reserve(dir_bytes + 4096))) return rc;
+  // From how many pairs: what this fill competes with below that is not a one-pair direction fill (the NW / multi-hit paths'
+  // kPackedFillMinPairs) but three matrices and their walker.  tools/sw_best_few.py, same process, packed against not:
+  // BLOSUM62 300 x 300 -- ahead at every size (128 pairs 0.52 -> 0.46 ms, 2 047 pairs 0.92 -> 0.58); match / mismatch, 150 x 1 000 --
+  // level at ~1 400 pairs (1 024: 0.68 -> 0.76, 2 047: 0.99 -> 0.83); 700 x 1 000 -- at ~700 (512: 1.63 -> 1.94, 1 024: 2.25 -> 2.00,
+  // 2 047: 4.10 -> 2.11): a wave's row costs more with two pairs in it, which is what a launch too small to fill the chip pays.
+  const uint64_t best_min_pairs = sc->flat.n_classes > 1 ? 128 : c.max_a + 1 > 512 ? 1024 : 1536;
+  const PackedShape shape = packed_fill_shape(ctx, batch, c, sc, sw_best_x2_applicable, best_min_pairs, sa_dirs_blocked_shape(c.max_a));
+  if (shape.stride) {
+    if ((rc = ctx->dirs.reserve(shape.dir_bytes + 4096))) return rc;
     SaCandBox bc;
     memset(&bc, 0, sizeof(bc));
-    bc.dirs = ctx->dirs.as<uint8_t>(); bc.dirs_used = &dirs_used; bc.best_only = true; bc.dirs_local = local; bc.uniform_stride = stride == kBucketShapes ? 256 : stride;
-    if ((rc = run_chunk(ctx, batch, c, sc, &d, &have_best, &bc, nullptr, stride))) return rc;
+    bc.dirs = ctx->dirs.as<uint8_t>(); bc.dirs_used = &dirs_used; bc.best_only = true; bc.dirs_local = local;
+    bc.uniform_stride = shape.stride == kBucketShapes ? 256 : shape.stride;
+    if ((rc = run_chunk(ctx, batch, c, sc, &d, &have_best, &bc, nullptr, shape.stride))) return rc;
     if (!dirs_used || !have_best) { set_last_error("seqalign_sw_batch: internal error: the best-hit direction fill did not run"); return SEQALIGN_E_HIP; }
   } else if ((rc = run_chunk(ctx, batch, c, sc, &d, &have_best))) {
     return rc;
@@ -669,30 +729,21 @@ static int sw_chunk_best_hit(seqalign_ctx *ctx, const seqalign_batch_t *batch, c
       (rc = ctx->t_out_b.reserve(total + 16)) || (rc = ctx->t_meta.reserve(n * 32)))
     return rc;
   hipStream_t st = ctx->stream;
-  std::vector<uint64_t> dst_off(n);    // (source of an asynchronous copy: declared before the guard, destroyed after its sync)
   StreamSyncOnExit sync_on_exit(st);
   HIP_TRY(hipMemcpyAsync(ctx->t_str_off.p, h_off, n * 8, hipMemcpyHostToDevice, st));
-  uint32_t *d_meta = ctx->t_meta.as<uint32_t>();   // head | len | score | status | pos[4]
-  seqalign_trace_t t;
-  memset(&t, 0, sizeof(t));
-  t.str_off = ctx->t_str_off.as<uint64_t>(); t.out_a = ctx->t_out_a.as<char>(); t.out_b = ctx->t_out_b.as<char>();
-  t.out_head = d_meta; t.out_len = d_meta + n; t.out_score = reinterpret_cast<int32_t *>(d_meta + 2 * n);
-  t.status = d_meta + 3 * n; t.out_pos = d_meta + 4 * n; t.start_index = ctx->best_index.as<uint64_t>();
+  const uint64_t first = c.first;
   if (dirs_used && ctx->opt.nw_moves) {
     // the walk sends home two bits per column into the pair's slot of pinned memory, the host expands (as seqalign_nw_batch):
     // one launch, one wait -- no lengths to fetch before a gather, no gather, no strings over PCIe
     const uint64_t move_words = 2ull * ((total >> 5) + n) + 2;
     if ((rc = ctx->h_ta.reserve(move_words * 4)) || (rc = ctx->h_B.reserve(n * 16 + 16))) return rc;   // (h_misc is fetch_status')
-    SaTraceParams tp;
-    memset(&tp, 0, sizeof(tp));
-    tp.arena = d.arena; tp.off_a = d.off_a; tp.len_a = d.len_a; tp.off_b = d.off_b; tp.len_b = d.len_b; tp.mat_off = d.mat_off;
-    tp.code = sc->d_code; tp.table = sc->d_table; tp.str_off = d.off_a;
+    SaTraceParams tp = trace_params(ctx, sc, d);
+    tp.str_off = d.off_a;
     tp.stage_words = (c.max_a + c.max_b + 31u) >> 5;
     tp.moves = ctx->h_ta.dev_as<uint32_t>(); tp.out_meta4 = ctx->h_B.dev_as<uint32_t>();
     tp.start_index = ctx->best_index.as<uint64_t>(); tp.start_score = ctx->best_score.as<int32_t>();
     tp.dirs = ctx->dirs.as<uint8_t>(); tp.dirs_blocked = sa_dirs_blocked_shape(c.max_a); tp.dirs_local = local; tp.tune_stage = ctx->opt.walk_stage; tp.tune_tile = ctx->opt.walk_tile; tp.fill_status = d.status;
-    tp.n_pairs = (uint32_t)n; tp.K = sc->flat.n_classes; tp.open1 = sc->flat.open1; tp.ext = sc->flat.ext;
-    tp.gen_eq = sc->flat.gen_eq; tp.gen_ne = sc->flat.gen_ne; tp.flags = sc->flat.flags; tp.tune_walker = ctx->opt.trace_kernel; tp.tune_group = ctx->opt.walk_group;
+    tp.n_pairs = (uint32_t)n;
     hipError_t e2 = sa_launch_nw_traceback(tp, st);
     if (e2 != hipSuccess) return fail_hip(e2, "sw best-hit traceback");
     tm.lap("sw best hit: fill + walk enqueued");
@@ -700,140 +751,33 @@ static int sw_chunk_best_hit(seqalign_ctx *ctx, const seqalign_batch_t *batch, c
     // walks carry a pair's fill status home in their own word anyway -- the copy and its scan were 20 us of nothing)
     HIP_TRY(stream_wait_spinning(st));
     tm.lap("sw best hit: wait (upload, fill, walk)");
-    const uint32_t *h_w = ctx->h_B.as<uint32_t>(), *h_moves = ctx->h_ta.as<uint32_t>();
-    // Where every hit goes in the caller's buffers: hits and string bytes per block of pairs (parallel -- round 4 counted in one
-    // serial pass over words the GPU had just written, every line of them a miss: 0.1 ms of C4's 0.89 ms call), a prefix over
-    // the blocks, then every block places and expands its own hits.
-    constexpr uint64_t kBlk = 64;
-    const uint64_t nblk = (n + kBlk - 1) / kBlk;
-    std::vector<uint64_t> blk_hits(nblk + 1, 0), blk_bytes(nblk + 1, 0);
-    std::atomic<uint64_t> first_err{~0ull};   // pair << 8 | code of the LOWEST failing pair
-    auto is_hit = [&](uint64_t k) { const int32_t sc_ = (int32_t)h_w[4 * k]; return sc_ > 0 && sc_ >= min_score[c.first + k]; };
-    // what pair k's hit takes in the caller's string buffer: its columns + NUL, or (seqalign_sw_batch_cigar) its CIGAR + NUL, counted from the planes
-    auto out_bytes = [&](uint64_t k, uint32_t len) -> uint64_t {
-      if (!ctx->cigar_format) return (uint64_t)len + 1;
-      const uint64_t p = c.first + k;
-      const uint32_t nwd = (batch->len_a[p] + batch->len_b[p] + 31u) >> 5;
-      const uint32_t *pa = h_moves + 2ull * ((h_off[k] >> 5) + k);
-      uint32_t pos[4], clen = 0;
-      if (sa_cigar_sw_moves(batch->arena + batch->off_a[p], batch->arena + batch->off_b[p], h_w[4 * k + 2], h_w[4 * k + 3], pa, pa + nwd, nwd, len,
-                            ctx->cigar_format, ctx->cigar_fold, nullptr, 0, pos, &clen))
-        return 1;   // (the placement pass meets the same error and reports it)
-      return (uint64_t)clen + 1;
-    };
-    parallel_for(nblk, [&](uint64_t bi) {
-      uint64_t hs = 0, bytes = 0;
-      for (uint64_t k = bi * kBlk, e3 = std::min(n, (bi + 1) * kBlk); k < e3; ++k) {
-        const uint32_t len = h_w[4 * k + 1];
-        if (len >= SA_MOVES_ERR) {
-          uint64_t seen = first_err.load(std::memory_order_relaxed);
-          const uint64_t mine = k << 8 | (len & 15u);
-          while (mine < seen && !first_err.compare_exchange_weak(seen, mine, std::memory_order_relaxed)) {}
-          continue;
-        }
-        if (is_hit(k)) { ++hs; bytes += out_bytes(k, len); }
-      }
-      blk_hits[bi + 1] = hs; blk_bytes[bi + 1] = bytes;
-    });
-    if (first_err.load() != ~0ull) return (int)(first_err.load() & 255u);
-    for (uint64_t bi = 0; bi < nblk; ++bi) { blk_hits[bi + 1] += blk_hits[bi]; blk_bytes[bi + 1] += blk_bytes[bi]; }
-    // what fits: whole blocks while they do, the first that does not pair by pair; the call reports SEQALIGN_E_NOMEM AFTER
-    // delivering what fits (as the string path below and the one-trip multi-hit path do)
-    const uint64_t hit_room = hit_cap > found ? hit_cap - found : 0, str_room = str_cap > used_str ? str_cap - used_str : 0;
-    const bool out_of_room = blk_hits[nblk] > hit_room || blk_bytes[nblk] > str_room;
-    const uint64_t first_hit = found, first_str = used_str;
-    std::atomic<uint64_t> delivered_hits{0}, delivered_bytes{0};
-    std::atomic<int> bad{SEQALIGN_OK};
-    parallel_for(nblk, [&](uint64_t bi) {
-      uint64_t hi = blk_hits[bi], at = blk_bytes[bi], done_h = 0, done_b = 0;
-      if (hi >= hit_room || at >= str_room) return;   // (everything from here on is beyond the caller's room)
-      for (uint64_t k = bi * kBlk, e3 = std::min(n, (bi + 1) * kBlk); k < e3; ++k) {
-        if (k + 6 < e3) {   // the GPU wrote these lines: every first touch is a miss -- have the pair six ahead on its way
-          const uint64_t kn = k + 6;
-          const uint32_t nwn = (batch->len_a[c.first + kn] + batch->len_b[c.first + kn] + 31u) >> 5;
-          const uint32_t *pn = h_moves + 2ull * ((h_off[kn] >> 5) + kn);
-          __builtin_prefetch(h_w + 4 * kn); __builtin_prefetch(pn + nwn - 1); __builtin_prefetch(pn + 2 * nwn - 1);
-          __builtin_prefetch(batch->arena + batch->off_a[c.first + kn]);
-        }
-        if (!is_hit(k)) continue;
-        const uint64_t p = c.first + k;
-        const uint32_t len = h_w[4 * k + 1];
-        const uint64_t need = out_bytes(k, len);
-        if (hi >= hit_room || at + need > str_room) break;   // (out_of_room is set: the call reports it)
-        const uint32_t la = batch->len_a[p], lb = batch->len_b[p], nwd = (la + lb + 31u) >> 5;
-        const uint32_t *pa = h_moves + 2ull * ((h_off[k] >> 5) + k);
-        uint32_t pos[4], clen = 0;
-        const int prc = ctx->cigar_format
-          ? sa_cigar_sw_moves(batch->arena + batch->off_a[p], batch->arena + batch->off_b[p], h_w[4 * k + 2], h_w[4 * k + 3], pa, pa + nwd, nwd, len,
-                              ctx->cigar_format, ctx->cigar_fold, out_a + first_str + at, need, pos, &clen)
-          : sa_expand_sw_moves(batch->arena + batch->off_a[p], batch->arena + batch->off_b[p], h_w[4 * k + 2], h_w[4 * k + 3],
-                               pa, pa + nwd, nwd, len, out_a + first_str + at, out_b + first_str + at, pos);
-        if (prc) { int expected = SEQALIGN_OK; bad.compare_exchange_strong(expected, prc); break; }
-        seqalign_sw_hit_t &h = hits[first_hit + hi];
-        h.pair = p; h.score = (int32_t)h_w[4 * k]; h.pos_a = pos[0]; h.pos_b = pos[1]; h.len_a = pos[2]; h.len_b = pos[3];
-        h.length = len; h.str_off = first_str + at;
-        ++hi; at += need; ++done_h; done_b += need;
-      }
-      delivered_hits.fetch_add(done_h, std::memory_order_relaxed); delivered_bytes.fetch_add(done_b, std::memory_order_relaxed);
-    });
-    const uint64_t n_out = delivered_hits.load();
-    used_str += delivered_bytes.load();
-    tm.lap("sw best hit: hits collected + expanded");
-    if (bad.load()) return bad.load();
-    found += n_out;
-    if (out_of_room) { *n_hits = found; return SEQALIGN_E_NOMEM; }
-    return SEQALIGN_OK;
+    const uint32_t *h_w = ctx->h_B.as<uint32_t>();
+    return deliver_moves(ctx, batch, c, h_w, ctx->h_ta.as<uint32_t>(), h_off, 1, [](uint64_t) { return 1u; },
+                         [=](uint64_t k, uint32_t) { const int32_t s = (int32_t)h_w[4 * k]; return s > 0 && s >= min_score[first + k]; }, sink, tm);
   }
+  uint32_t *d_meta = ctx->t_meta.as<uint32_t>();   // head | len | score | status | pos[4]
+  seqalign_trace_t t;
+  memset(&t, 0, sizeof(t));
+  t.str_off = ctx->t_str_off.as<uint64_t>(); t.out_a = ctx->t_out_a.as<char>(); t.out_b = ctx->t_out_b.as<char>();
+  t.out_head = d_meta; t.out_len = d_meta + n; t.out_score = reinterpret_cast<int32_t *>(d_meta + 2 * n);
+  t.status = d_meta + 3 * n; t.out_pos = d_meta + 4 * n; t.start_index = ctx->best_index.as<uint64_t>();
   if (dirs_used) rc = sw_traceback_dirs(ctx, sc, &d, &t, ctx->dirs.as<uint8_t>(), ctx->best_score.as<int32_t>(), st);
   else rc = seqalign_sw_traceback_device(ctx, sc, &d, &t, st);
   if (rc) return rc;
   uint32_t *h_meta = reinterpret_cast<uint32_t *>(h_off + n);
   HIP_TRY(hipMemcpyAsync(h_meta, d_meta, n * 32, hipMemcpyDeviceToHost, st));
   if ((rc = fetch_status(ctx, c, nullptr))) return rc;   // syncs
-  // a hit is much shorter than its slot of len_a + len_b characters: pack the strings on the device, bring back
-  // what was written (C3: 2 x 1.7 MB instead of 2 x 11.5 MB over PCIe)
-  DevBuf &d_dst = ctx->e[11], &d_gath_a = ctx->e[9];
-  uint64_t gathered = 0;
-  for (uint64_t k = 0; k < n; ++k) {
-    if (h_meta[3 * n + k]) return (int)h_meta[3 * n + k];
-    dst_off[k] = gathered;
-    gathered += h_meta[n + k];
-  }
-  const uint64_t gath_b_at = (gathered + 15) & ~(uint64_t)15;   // a-strings, then b-strings: one buffer, one copy home
-  if ((rc = d_dst.reserve(n * 8 + 16)) || (rc = d_gath_a.reserve(gath_b_at + gathered + 16)) ||
-      (rc = ctx->h_ta.reserve(gath_b_at + gathered + 16)) || (rc = ctx->h_desc.reserve(n * 8 + 16)))
-    return rc;
-  memcpy(ctx->h_desc.p, dst_off.data(), n * 8);   // (pinned; run_chunk's descriptors left it with the stream's last wait)
-  HIP_TRY(hipMemcpyAsync(d_dst.p, ctx->h_desc.p, n * 8, hipMemcpyHostToDevice, st));
-  hipError_t e = sa_launch_gather_hits(ctx->t_out_a.as<char>(), ctx->t_out_b.as<char>(), ctx->t_str_off.as<uint64_t>(), d_meta,
-                                       d_meta + n, d_dst.as<uint64_t>(), d_gath_a.as<char>(), d_gath_a.as<char>() + gath_b_at, (uint32_t)n, st);
-  if (e != hipSuccess) return fail_hip(e, "gather hits");
-  HIP_TRY(hipMemcpyAsync(ctx->h_ta.p, d_gath_a.p, gath_b_at + gathered, hipMemcpyDeviceToHost, st));
-  HIP_TRY(stream_wait_spinning(st));
-  const char *ha = ctx->h_ta.as<char>(), *hb = ha + gath_b_at;
-  for (uint64_t k = 0; k < n; ++k) {
-    const uint64_t p = c.first + k;
-    const uint32_t len = h_meta[n + k];
-    const int32_t score = reinterpret_cast<const int32_t *>(h_meta)[2 * n + k];
-    if (score <= 0 || score < min_score[p]) continue;
-    const uint64_t took = found >= hit_cap ? 0 : put_alignment(ctx, ha + dst_off[k], hb + dst_off[k], len, out_a, out_b, used_str, str_cap > used_str ? str_cap - used_str : 0);
-    if (!took) { *n_hits = found; return SEQALIGN_E_NOMEM; }
-    seqalign_sw_hit_t &h = hits[found++];
-    const uint32_t *pos = h_meta + 4 * n + 4 * k;
-    h.pair = p; h.score = score; h.pos_a = pos[0]; h.pos_b = pos[1]; h.len_a = pos[2]; h.len_b = pos[3];
-    h.length = len; h.str_off = used_str;
-    used_str += took;
-  }
-  return SEQALIGN_OK;
+  return deliver_strings(ctx, st, n, h_meta, d_meta, ctx->t_str_off.as<uint64_t>(), [=](uint64_t w) { return first + w; },
+                         [=](uint64_t w, int32_t score) { return score > 0 && score >= min_score[first + w]; }, sink, tm);
 }
+
+}  // namespace
 
 // every pair through the host: matrices and compacted candidates copied back, hits enumerated by host threads
 static int sw_batch_host_enumeration(seqalign_ctx *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                      const seqalign_dev_scoring *sc, const int32_t *min_score, uint32_t max_hits,
-                                     seqalign_sw_hit_t *hits, uint64_t hit_cap, uint64_t *n_hits, char *out_a,
-                                     char *out_b, uint64_t str_cap) {
+                                     HitSink &sink, uint64_t *n_hits) {
   int rc = SEQALIGN_OK;
-  uint64_t used_str = 0, found = 0;
   const size_t budget = std::min<size_t>(ctx->chunk_budget, (size_t)6 << 30);
 
   // the reduction kernel takes one threshold per launch: group by threshold
@@ -920,20 +864,15 @@ static int sw_batch_host_enumeration(seqalign_ctx *ctx, const seqalign_batch_t *
     for (uint64_t k = 0; k < n && rc == SEQALIGN_OK; ++k) {
       const PairHits &ph = per_pair[k];
       for (size_t i = 0; i < ph.hits.size(); ++i) {
-        const seqalign_sw_hit_t &src = ph.hits[i];
-        const uint64_t took = found >= hit_cap ? 0 : put_alignment(ctx, ph.str_a.data() + src.str_off, ph.str_b.data() + src.str_off, src.length, out_a, out_b,
-                                                                   used_str, str_cap > used_str ? str_cap - used_str : 0);
-        if (!took) { rc = SEQALIGN_E_NOMEM; break; }
-        seqalign_sw_hit_t &h = hits[found++];
-        h = src;
+        seqalign_sw_hit_t h = ph.hits[i];
+        const uint64_t at = h.str_off;
         h.pair = c.first + k;
-        h.str_off = used_str;
-        used_str += took;
+        if (!sink.put(ctx, h, ph.str_a.data() + at, ph.str_b.data() + at)) { rc = SEQALIGN_E_NOMEM; break; }
       }
     }
     if (rc) break;
   }
-  *n_hits = found;
+  *n_hits = sink.found;
   return rc;
 }
 
@@ -948,14 +887,15 @@ static int sw_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, con
   seqalign_dev_scoring *sc = nullptr;
   if ((rc = cached_scoring(ctx, scoring, 1, &sc))) return rc;
   if ((rc = admit_batch(sc, batch, SA_FRAMES_FILL))) return rc;
-  uint64_t used_str = 0, found = 0;
+  HitSink sink{hits, hit_cap, out_a, out_b, str_cap};
   if (max_hits == 0) return SEQALIGN_OK;
   if (max_hits == 1 && !traceback_on_host(ctx)) {   // best hit only: nothing but the strings crosses PCIe
     for (const Chunk &c : plan_chunks(batch, ctx->chunk_budget))
-      if ((rc = sw_chunk_best_hit(ctx, batch, c, sc, min_score, hits, hit_cap, n_hits, found, out_a, out_b, str_cap,
-                                  used_str)))
+      if ((rc = sw_chunk_best_hit(ctx, batch, c, sc, min_score, sink))) {
+        if (rc == SEQALIGN_E_NOMEM) *n_hits = sink.found;   // (out of the caller's room: what fitted is delivered; any other error: nothing is)
         return rc;
-    *n_hits = found;
+      }
+    *n_hits = sink.found;
     return SEQALIGN_OK;
   }
   uint32_t max_a = 0, max_b = 0;
@@ -970,15 +910,12 @@ static int sw_batch_impl(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, con
         extra[p] = 8 * hit_arena_elements(batch->len_a[p], batch->len_b[p], min_score[p], best) + 64;
     }
     for (const Chunk &c : plan_chunks(batch, ctx->chunk_budget, 12, extra.data())) {
-      if ((rc = sw_chunk_device_enumerate(ctx, batch, c, sc, min_score, max_hits, hits, hit_cap, &found, out_a, out_b,
-                                          str_cap, &used_str)))
-        break;
+      if ((rc = sw_chunk_device_enumerate(ctx, batch, c, sc, min_score, max_hits, sink))) break;
     }
-    *n_hits = found;
+    *n_hits = sink.found;
     return rc;
   }
-  return sw_batch_host_enumeration(ctx, batch, scoring, sc, min_score, max_hits, hits, hit_cap, n_hits, out_a, out_b,
-                                   str_cap);
+  return sw_batch_host_enumeration(ctx, batch, scoring, sc, min_score, max_hits, sink, n_hits);
 }
 
 extern "C" int seqalign_sw_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,

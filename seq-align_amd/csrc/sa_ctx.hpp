@@ -452,6 +452,45 @@ struct CigarScope {   // RAII: the call's output format, put back on every way o
 // used with the NUL, or 0 when `room` bytes do not hold it.
 uint64_t put_alignment(const seqalign_ctx *ctx, const char *sa, const char *sb, uint32_t len, char *out_a, char *out_b, uint64_t at, uint64_t room);
 
+// Where a call's local hits go: the caller's records and string room, and how much of both is taken.  Built once per call
+// (seqalign_sw_batch, seqalign_sw_align_long, seqalign_sw_align_banded) and handed to whatever writes hits; no hits[] record is
+// filled anywhere else.  When *n_hits is written, and what comes before SEQALIGN_E_NOMEM, is each call's own rule.
+struct HitSink {
+  seqalign_sw_hit_t *hits;
+  uint64_t hit_cap;
+  char *out_a, *out_b;
+  uint64_t str_cap;
+  uint64_t found = 0, used = 0;   // records written, string bytes taken
+  uint64_t hit_room() const { return hit_cap > found ? hit_cap - found : 0; }
+  uint64_t str_room() const { return str_cap > used ? str_cap - used : 0; }
+  // record `slot` = h with its text at str_off (the writers that place many hits at once, at offsets they worked out from
+  // hit_room() / str_room(), and advance found / used themselves afterwards)
+  void record(uint64_t slot, seqalign_sw_hit_t h, uint64_t str_off) { h.str_off = str_off; hits[slot] = h; }
+  // the whole of "this alignment (h.length columns of sa / sb), as strings or in CIGAR mode as text, into the room": false
+  // when a record or the text does not fit, and nothing is taken then
+  bool put(const seqalign_ctx *ctx, const seqalign_sw_hit_t &h, const char *sa, const char *sb) {
+    const uint64_t took = hit_room() ? put_alignment(ctx, sa, sb, h.length, out_a, out_b, used, str_room()) : 0;
+    if (!took) return false;
+    record(found++, h, used);
+    used += took;
+    return true;
+  }
+};
+
+// The traceback launch's parameters as every launch site starts them: zeroed, then the batch's descriptors, the scoring's
+// constants and the two walker options every walk takes.  Matrices, direction bytes, outputs, walk numbering, n_pairs,
+// fill_status, tune_stage / tune_tile (the local tile walks' sites only: they feed the walker choice) stay with the site.
+inline SaTraceParams trace_params(const seqalign_ctx *ctx, const seqalign_dev_scoring *sc, const seqalign_dev_batch_t &d) {
+  SaTraceParams t;
+  memset(&t, 0, sizeof(t));
+  t.arena = d.arena; t.off_a = d.off_a; t.len_a = d.len_a; t.off_b = d.off_b; t.len_b = d.len_b; t.mat_off = d.mat_off;
+  t.code = sc->d_code; t.table = sc->d_table;
+  t.K = sc->flat.n_classes; t.open1 = sc->flat.open1; t.ext = sc->flat.ext;
+  t.gen_eq = sc->flat.gen_eq; t.gen_ne = sc->flat.gen_ne; t.flags = sc->flat.flags;
+  t.tune_walker = ctx->opt.trace_kernel; t.tune_group = ctx->opt.walk_group;
+  return t;
+}
+
 // grow the context's three matrix arenas together (spread placement, sa_placement.hip)
 int reserve_arenas(seqalign_ctx *ctx, size_t bytes, bool placed = true);
 

@@ -678,17 +678,13 @@ int sa_host::sw_traceback_dirs(seqalign_ctx_t *ctx, const seqalign_dev_scoring_t
   if (!ctx || !sc || !b || !t || !dirs || !start_score || !t->start_index || !t->out_pos) return SEQALIGN_E_ARG;
   if (b->n_pairs == 0) return SEQALIGN_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  SaTraceParams p;
-  memset(&p, 0, sizeof(p));
-  p.arena = b->arena; p.off_a = b->off_a; p.len_a = b->len_a; p.off_b = b->off_b; p.len_b = b->len_b;
-  p.mat_off = b->mat_off; p.dirs = dirs; p.start_score = start_score; p.fill_status = nullptr;
+  SaTraceParams p = trace_params(ctx, sc, *b);
+  p.dirs = dirs; p.start_score = start_score; p.fill_status = nullptr;
   p.dirs_blocked = sa_dirs_blocked_shape(b->max_len_a);   // (the best-hit fill's layout for this chunk: sa_kernels.h)
-  p.code = sc->d_code; p.table = sc->d_table; p.str_off = t->str_off; p.out_a = t->out_a; p.out_b = t->out_b;
+  p.str_off = t->str_off; p.out_a = t->out_a; p.out_b = t->out_b;
   p.out_head = t->out_head; p.out_len = t->out_len; p.out_score = t->out_score; p.trace_status = t->status;
   p.start_index = t->start_index; p.out_pos = t->out_pos;
-  p.n_pairs = (uint32_t)b->n_pairs; p.K = sc->flat.n_classes; p.open1 = sc->flat.open1; p.ext = sc->flat.ext;
-  p.gen_eq = sc->flat.gen_eq; p.gen_ne = sc->flat.gen_ne; p.flags = sc->flat.flags;
-  p.tune_walker = ctx->opt.trace_kernel; p.tune_group = ctx->opt.walk_group;
+  p.n_pairs = (uint32_t)b->n_pairs;
   hipError_t e = sa_launch_nw_traceback(p, st);
   if (e != hipSuccess) return fail_hip(e, "traceback launch");
   return SEQALIGN_OK;
@@ -720,16 +716,12 @@ static int launch_traceback(seqalign_ctx_t *ctx, const seqalign_dev_scoring_t *s
   if (sw && (!t->start_index || !t->out_pos)) return SEQALIGN_E_ARG;
   if (b->n_pairs == 0) return SEQALIGN_OK;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  SaTraceParams p;
-  memset(&p, 0, sizeof(p));
-  p.arena = b->arena; p.off_a = b->off_a; p.len_a = b->len_a; p.off_b = b->off_b; p.len_b = b->len_b;
-  p.mat_off = b->mat_off; p.M = b->match_scores; p.A = b->gap_a_scores; p.B = b->gap_b_scores;
-  p.code = sc->d_code; p.table = sc->d_table; p.str_off = t->str_off; p.out_a = t->out_a; p.out_b = t->out_b;
+  SaTraceParams p = trace_params(ctx, sc, *b);
+  p.M = b->match_scores; p.A = b->gap_a_scores; p.B = b->gap_b_scores;
+  p.str_off = t->str_off; p.out_a = t->out_a; p.out_b = t->out_b;
   p.out_head = t->out_head; p.out_len = t->out_len; p.out_score = t->out_score; p.trace_status = t->status;
   p.start_index = sw ? t->start_index : nullptr; p.out_pos = sw ? t->out_pos : nullptr;
-  p.n_pairs = (uint32_t)b->n_pairs; p.K = sc->flat.n_classes; p.open1 = sc->flat.open1; p.ext = sc->flat.ext;
-  p.gen_eq = sc->flat.gen_eq; p.gen_ne = sc->flat.gen_ne; p.flags = sc->flat.flags;
-  p.tune_walker = ctx->opt.trace_kernel; p.tune_group = ctx->opt.walk_group;
+  p.n_pairs = (uint32_t)b->n_pairs;
   hipError_t e = sa_launch_nw_traceback(p, st);
   if (e != hipSuccess) return fail_hip(e, "traceback launch");
   return SEQALIGN_OK;

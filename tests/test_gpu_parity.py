@@ -1186,6 +1186,106 @@ def test_sw_batch_out_of_room_delivers_what_fits(ctx, nw_moves):
             assert h.pair == p and got == want, (k, p)
 
 
+# ---- seqalign_sw_batch's four ways home under a capacity: 130 pairs of one shape are three delivery blocks of 64, 64 and 2 pairs
+# (path name, max_hits, extra options, whether the walks send home moves)
+SW_ROOM_PATHS = [("best hit on moves", 1, {}, True), ("best hit on strings", 1, {"nw_moves": 0}, False),
+                 ("one-trip", 4, {}, True), ("three-trip", 9, {}, False)]   # (the one-trip form stops at 8 hits per pair)
+SW_ROOM_THRESHOLD = 20   # (more than 65 of the 130 pairs have a hit at 20: asserted below)
+SW_ROOM_SENTINEL = 0xEE
+
+
+@pytest.fixture(scope="module")
+def sw_room_batch():
+    return W.dna_sw_read_vs_ref(130, seed=7, read_len=60, ref_len=200)
+
+
+def _sw_room_call(c, batch, sc, max_hits, hit_cap, str_cap, cigar):
+    """One raw seqalign_sw_batch (or _cigar, format M) call into sentinel-filled buffers: (rc, the delivered hits as
+    (record fields without str_off, text a, text b), bytes used per hit, the output arrays, the hit array)."""
+    hits = (S.SwHit * (hit_cap + 1))()
+    C.memset(hits, SW_ROOM_SENTINEL, C.sizeof(hits))
+    out_a, out_b = np.full(str_cap + 1, SW_ROOM_SENTINEL, np.uint8), np.full(str_cap + 1, SW_ROOM_SENTINEL, np.uint8)
+    n_hits = C.c_uint64(0)
+    ms = np.full(batch.n_pairs, SW_ROOM_THRESHOLD, np.int32)
+    d = S.batch_desc(batch)
+    if cigar:
+        rc = S.lib().seqalign_sw_batch_cigar(c._h, C.byref(d), C.byref(sc), S._ptr(ms), C.c_uint32(max_hits), C.c_int(1), hits,
+                                             C.c_uint64(hit_cap), C.byref(n_hits), S._ptr(out_a), C.c_uint64(str_cap))
+    else:
+        rc = S.lib().seqalign_sw_batch(c._h, C.byref(d), C.byref(sc), S._ptr(ms), C.c_uint32(max_hits), hits, C.c_uint64(hit_cap),
+                                       C.byref(n_hits), S._ptr(out_a), S._ptr(out_b), C.c_uint64(str_cap))
+    got, used = [], 0
+    for k in range(n_hits.value):
+        h = hits[k]
+        assert h.str_off == used, (k, h.str_off, used)   # the hits lie back to back
+        if cigar:
+            end = int(h.str_off)
+            while out_a[end]:
+                end += 1
+            text = (out_a[h.str_off:end].tobytes(), b"")
+            used = end + 1
+        else:
+            text = (out_a[h.str_off:h.str_off + h.length].tobytes(), out_b[h.str_off:h.str_off + h.length].tobytes())
+            assert out_a[h.str_off + h.length] == 0 and out_b[h.str_off + h.length] == 0, k
+            used += h.length + 1
+        got.append(((h.pair, h.score, h.pos_a, h.pos_b, h.len_a, h.len_b, h.length), text, used - int(h.str_off)))
+    # nothing behind the used part was touched, in the strings and in the records
+    assert (out_a[used:] == SW_ROOM_SENTINEL).all() and (cigar or (out_b[used:] == SW_ROOM_SENTINEL).all()), (hit_cap, str_cap, used)
+    assert bytes(hits[hit_cap]) == bytes([SW_ROOM_SENTINEL]) * C.sizeof(S.SwHit), (hit_cap, str_cap)
+    return rc, got
+
+
+def _sw_room_check(c, batch, sc, max_hits, moves, cigar, caps_of):
+    ample_hits, ample_str = 130 * max_hits, 130 * max_hits * (60 + 200 + 2)
+    rc, full = _sw_room_call(c, batch, sc, max_hits, ample_hits, ample_str, cigar)
+    ran = c.last_call()
+    assert any(k.startswith("walk_moves_") for k in ran) == moves, ran
+    assert rc == 0 and len(full) > 65, (rc, len(full))
+    assert [f[0][0] for f in full] == sorted(f[0][0] for f in full)          # pair order
+    H, need = len(full), np.cumsum([0] + [f[2] for f in full])               # need[h]: the bytes of the first h hits
+    for hit_cap, str_cap in caps_of(H, need, ample_hits, ample_str):
+        fits = max(h for h in range(H + 1) if h <= hit_cap and need[h] <= str_cap)
+        rc, got = _sw_room_call(c, batch, sc, max_hits, hit_cap, str_cap, cigar)
+        assert any(k.startswith("walk_moves_") for k in c.last_call()) == moves, c.last_call()
+        assert rc == (0 if fits == H else 4), (hit_cap, str_cap, rc)          # SEQALIGN_E_NOMEM after what fits
+        assert len(got) == fits, (hit_cap, str_cap, len(got), fits)
+        assert got == full[:fits], (hit_cap, str_cap)
+
+
+@pytest.mark.parametrize("path", SW_ROOM_PATHS, ids=[p[0].replace(" ", "-") for p in SW_ROOM_PATHS])
+def test_sw_batch_room_prefix_on_every_path(sw_room_batch, path):
+    """Every way seqalign_sw_batch brings hits home -- best hit on moves, best hit on strings, the one-trip and the three-trip
+    multi-hit forms -- delivers, under any hit_cap / str_cap, exactly the longest prefix of the uncapped call's hits (pair order)
+    whose count and bytes (length + 1 per hit) fit: record for record, string for string, nothing written behind the used part,
+    then SEQALIGN_E_NOMEM; with room for everything the call returns 0 and the uncapped result.  The caps sit on the edges of
+    the delivery blocks of 64 pairs."""
+    name, max_hits, options, moves = path
+    sc = S.make_scoring({"init": [2, -2, -2, -1, 0, 0, 0, 0, 0, 0]})
+    with S.Context(0) as c:
+        c.set_option("pack16", 2)   # the packed fills, and with them the moves forms, at this size
+        for k, v in options.items():
+            c.set_option(k, v)
+
+        def caps_of(H, need, ample_hits, ample_str):
+            caps = [(hc, ample_str) for hc in (0, 1, 63, 64, 65, H - 1)]
+            for h in (1, 64, 65):
+                caps += [(ample_hits, int(need[h])), (ample_hits, int(need[h]) - 1)]
+            return caps + [(H, int(need[H]))]
+        _sw_room_check(c, sw_room_batch, sc, max_hits, moves, False, caps_of)
+
+
+@pytest.mark.parametrize("path", [SW_ROOM_PATHS[0], SW_ROOM_PATHS[2]], ids=["best-hit-on-moves", "one-trip"])
+def test_sw_batch_cigar_room_prefix_on_moves_paths(sw_room_batch, path):
+    """... and seqalign_sw_batch_cigar (format M) on the two moves forms, where a hit's bytes are its CIGAR's length + 1 counted
+    from the planes: hit_cap 65, and the bytes of 65 hits minus one."""
+    name, max_hits, options, moves = path
+    sc = S.make_scoring({"init": [2, -2, -2, -1, 0, 0, 0, 0, 0, 0]})
+    with S.Context(0) as c:
+        c.set_option("pack16", 2)
+        _sw_room_check(c, sw_room_batch, sc, max_hits, moves, True,
+                       lambda H, need, ample_hits, ample_str: [(65, ample_str), (ample_hits, int(need[65]) - 1)])
+
+
 def test_sw_batch_multi_hit_in_several_chunks(ctx):
     """seqalign_sw_batch(max_hits > 1) on a batch that does not fit one chunk (tiny chunk budget): the per-chunk
     scratch (hit keys, walker lists, string slots) is reused chunk after chunk; hits equal the one-chunk call's."""
