@@ -133,20 +133,17 @@ static PackedShape packed_fill_shape(const seqalign_ctx *ctx, const seqalign_bat
                                      bool (*applicable)(const seqalign_ctx_t *, const seqalign_dev_scoring_t *, uint32_t, uint32_t),
                                      uint64_t min_pairs, bool blocked) {
   const uint64_t n = c.count;
-  auto bytes256 = [&](uint32_t xa, uint32_t xb) -> uint64_t {
-    return ((blocked ? sa_dirs_blocked_bytes(xa, xb) : ((uint64_t)xa + 1) * ((uint64_t)xb + 1)) + 255u) & ~(uint64_t)255u;
-  };
   bool same_shape = true;
   for (uint64_t k = 1; k < n && same_shape; ++k)
     same_shape = batch->len_a[c.first + k] == batch->len_a[c.first] && batch->len_b[c.first + k] == batch->len_b[c.first];
   PackedShape s;
   if (same_shape && (n >= min_pairs || ctx->opt.pack16 == 2) && applicable(ctx, sc, c.max_a, c.max_b)) {
-    s.stride = bytes256(c.max_a, c.max_b);
+    s.stride = dirs_bytes256(blocked, c.max_a, c.max_b);
     s.dir_bytes = n * s.stride;
   } else if (!same_shape && (n >= kBucketedFillMinPairs || ctx->opt.pack16 == 2) && ((uint64_t)c.max_a + 1) * ((uint64_t)c.max_b + 1) <= kShapeTableMax &&
              applicable(ctx, sc, c.max_a, c.max_b)) {
     s.stride = kBucketShapes;
-    for (uint64_t k = 0; k < n; ++k) s.dir_bytes += bytes256(batch->len_a[c.first + k], batch->len_b[c.first + k]);
+    for (uint64_t k = 0; k < n; ++k) s.dir_bytes += dirs_bytes256(blocked, batch->len_a[c.first + k], batch->len_b[c.first + k]);
   }
   return s;
 }
@@ -173,7 +170,7 @@ static int deliver_moves(seqalign_ctx *ctx, const seqalign_batch_t *batch, const
   const uint64_t nblk = (n + kBlk - 1) / kBlk;
   std::vector<uint64_t> blk_hits_v(nblk + 1, 0), blk_bytes_v(nblk + 1, 0);
   uint64_t *const blk_hits = blk_hits_v.data(), *const blk_bytes = blk_bytes_v.data();
-  std::atomic<uint64_t> first_err{~0ull};   // walk << 8 | code of the LOWEST failing walk
+  LowestFailure first_err;   // (of the LOWEST failing walk)
   // The tasks capture what they read per hit BY VALUE, so that the closure's copy on the heap holds it.  Measured (C3, up to 4
   // hits, the placement pass over 10 000 pairs, profiles/r30): 0.19-0.21 ms with everything captured by reference, 0.10-0.13 by
   // value, the parent's copy 0.11-0.12.  The cause is supposed, not shown: after every call into host/sa_moves.c a task reads its
@@ -198,18 +195,13 @@ static int deliver_moves(seqalign_ctx *ctx, const seqalign_batch_t *batch, const
       for (uint32_t j = 0, nj = walks(k); j < nj; ++j) {
         const uint64_t w = k * wpp + j;
         const uint32_t len = h_w[4 * w + 1];
-        if (len >= SA_MOVES_ERR) {
-          uint64_t seen = first_err.load(std::memory_order_relaxed);
-          const uint64_t mine = w << 8 | (len & 15u);
-          while (mine < seen && !first_err.compare_exchange_weak(seen, mine, std::memory_order_relaxed)) {}
-          continue;
-        }
+        if (len >= SA_MOVES_ERR) { first_err.note(w, (int)(len & 15u)); continue; }
         if (take(k, j)) { ++hs; bytes += out_bytes(k, j, len); }
       }
     }
     blk_hits[bi + 1] = hs; blk_bytes[bi + 1] = bytes;
   });
-  if (first_err.load() != ~0ull) return (int)(first_err.load() & 255u);
+  if (first_err.code()) return first_err.code();
   tm.lap("sw moves: hits counted");
   for (uint64_t bi = 0; bi < nblk; ++bi) { blk_hits[bi + 1] += blk_hits[bi]; blk_bytes[bi + 1] += blk_bytes[bi]; }
   const uint64_t hit_room = sink.hit_room(), str_room = sink.str_room();

@@ -368,7 +368,7 @@ struct seqalign_ctx {
   size_t chunk_budget = 0;   // bytes of device memory one host-level chunk may use
   size_t chunk_budget_default = 0;
   // device scratch for the host-level entry points
-  sa_host::DevBuf arena, off_a, pair_list, status;   // (off_a holds all five descriptor arrays; pair_list: nw_chunk_pipelined's mixed chunks)
+  sa_host::DevBuf arena, off_a, pair_list, status;   // (off_a holds all five descriptor arrays; pair_list: seqalign_nw_batch's ragged chunks for the packed fill)
   sa_host::DevBuf M, A, B;           // views of arena_set (sa_host::reserve_arenas); never reserved / released on their own
   SaArenaSet *arena_set = nullptr;   // the three matrix arenas, placed (sa_placement.hip)
   bool arena_placed = false;         // the set in arena_set went through the placement walk (reserve_arenas(.., placed = true))
@@ -532,6 +532,53 @@ int ensure_copy_streams(seqalign_ctx *ctx, int count);
 constexpr uint64_t kBucketShapes = ~(uint64_t)0;
 constexpr uint64_t kShapeTableMax = (uint64_t)1 << 20;   // (len_a + 1) x (len_b + 1) entries of the pairing table: 4 MiB per host thread at most
 int fetch_status(seqalign_ctx *ctx, const Chunk &c, uint64_t *status_out);
+
+// One pair's direction bytes rounded up to 256: one byte per cell, or (`blocked`) in blocks of 8 x 16 cells (sa_kernels.h).  What a
+// pair takes in every layout of the packed fills, NW and SW.
+inline uint64_t dirs_bytes256(bool blocked, uint32_t la, uint32_t lb) {
+  return ((blocked ? sa_dirs_blocked_bytes(la, lb) : ((uint64_t)la + 1) * ((uint64_t)lb + 1)) + 255u) & ~(uint64_t)255u;
+}
+
+// The descriptor block of a chunk of n pairs as the host-level calls of sa_batch.hip keep it, pinned (ctx->h_desc) and on the device
+// (ctx->off_a, or the pinned block's device address), one view for both copies:
+//   off_a[n] | off_b[n] | mat_off[n] | (slot[n + 1]) | len_a[n] | len_b[n] | (list[2 n])
+// slot: where a pair's string slot of len_a + len_b characters starts (seqalign_nw_batch; the same prefix as off_a, with the end);
+// list: the pair list of a ragged chunk for the packed fills (run_chunk).
+struct DescBlock {
+  uint64_t *off_a, *off_b, *mat_off, *slot;
+  uint32_t *len_a, *len_b, *list;
+  static size_t bytes(uint64_t n, bool slots, bool with_list = false) {
+    return (3 * n + (slots ? n + 1 : 0)) * sizeof(uint64_t) + (2 * n + (with_list ? 2 * n : 0)) * sizeof(uint32_t);
+  }
+  DescBlock(const void *base, uint64_t n, bool slots) {
+    off_a = static_cast<uint64_t *>(const_cast<void *>(base)); off_b = off_a + n; mat_off = off_b + n; slot = slots ? mat_off + n : nullptr;
+    len_a = reinterpret_cast<uint32_t *>(slots ? slot + n + 1 : mat_off + n); len_b = len_a + n; list = len_b + n;
+  }
+  // pairs [k0, k1) of the chunk as a device batch (of the device copy's view)
+  seqalign_dev_batch_t range(uint64_t k0, uint64_t k1, const uint8_t *arena, int32_t *M, int32_t *A, int32_t *B, uint64_t *status,
+                             uint32_t max_a, uint32_t max_b) const {
+    seqalign_dev_batch_t d;
+    d.n_pairs = k1 - k0; d.arena = arena;
+    d.off_a = off_a + k0; d.len_a = len_a + k0; d.off_b = off_b + k0; d.len_b = len_b + k0; d.mat_off = mat_off + k0;
+    d.match_scores = M; d.gap_a_scores = A; d.gap_b_scores = B;
+    d.status = status + k0; d.max_len_a = max_a; d.max_len_b = max_b;
+    return d;
+  }
+  // where pair k's two planes of moves start, in words (sa_traceback.hip: move_slot)
+  uint64_t move_word(uint64_t k) const { return 2 * ((slot[k] >> 5) + k); }
+};
+
+// A call's error is the LOWEST failing item's (pair, walk), whichever worker meets one first; items without an error have been
+// written by then (outputs are unspecified after a failed call).  One word, item << 8 | code, lowered by compare-and-swap.
+struct LowestFailure {
+  std::atomic<uint64_t> first{~0ull};
+  void note(uint64_t item, int code) {
+    uint64_t seen = first.load(std::memory_order_relaxed);
+    const uint64_t mine = item << 8 | ((uint64_t)code & 255u);
+    while (mine < seen && !first.compare_exchange_weak(seen, mine, std::memory_order_relaxed)) {}
+  }
+  int code() const { const uint64_t v = first.load(); return v == ~0ull ? SEQALIGN_OK : (int)(v & 255u); }
+};
 int nw_dirs_fill(seqalign_ctx_t *ctx, const seqalign_dev_scoring_t *scoring, const seqalign_dev_batch_t *batch, uint8_t *dirs,
                  int32_t *end_score, uint64_t *end_state, void *stream, bool *used, uint64_t uniform_stride = 0,
                  const uint32_t *pair_list = nullptr, uint32_t list_count = 0, bool local = false);

@@ -626,7 +626,8 @@ int sa_host::nw_dirs_fill(seqalign_ctx_t *ctx, const seqalign_dev_scoring_t *sco
   *used = true;
   return SEQALIGN_OK;
 }
-// the same for a chunk whose pairs are mostly of one shape (modal_a x modal_b): pairs list[0 .. n_modal) two per wave, pairs
+// the same for a ragged chunk: pairs list[0 .. n_modal) two per wave -- list entries 2u, 2u + 1 have one shape, none larger than
+// modal_a x modal_b (the majority shape's pairs, or pairs paired up by shape: sa_batch.hip) -- and pairs
 // list[n_modal .. n_modal + n_rest) one per wave, in one grid (sa_fill_dirs_x2.hip: fill_nw_dirs_mixed_kernel).  `batch`: the whole
 // chunk's arrays (the list holds indices into them); every pair's bytes start on a multiple of 256.
 int sa_host::nw_dirs_fill_mixed(seqalign_ctx_t *ctx, const seqalign_dev_scoring_t *scoring, const seqalign_dev_batch_t *batch,

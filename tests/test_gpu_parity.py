@@ -386,7 +386,7 @@ def test_nw_batch_strings_match_oracle_and_golden(ctx, where, opts):
 @pytest.mark.parametrize("n_sub", [2, 5, 16])
 def test_nw_batch_pipelined_subbatches(ctx, opts, n_sub, dirs):
     """seqalign_nw_batch with a chunk cut into sub-batches that overlap fill / traceback / copies on two streams
-    (sa_batch.hip: nw_chunk_pipelined; by default only for large chunks, forced here): same strings and scores as
+    (sa_batch.hip: nw_chunk; by default only for large chunks, forced here): same strings and scores as
     the reference's needleman_wunsch_align (src/needleman_wunsch.c:53-145) -- golden C2 pairs, a ragged batch with
     empty sequences and sub-batch cuts inside runs of tiny pairs -- and an unknown character pair inside one
     sub-batch is still reported (alignment_scoring.c:178-181)."""
@@ -518,9 +518,10 @@ def test_nw_batch_two_pairs_per_wave(ctx, opts, shape):
 
 @pytest.mark.parametrize("n_sub", [0, 3])
 def test_nw_batch_mostly_one_shape(ctx, opts, n_sub):
-    """A chunk whose pairs are MOSTLY of one shape (reads of one length, some trimmed): the pairs of that shape go through the
-    packed kernel and the others through the one-pair kernel, each launch with the list of its pairs (sa_batch.hip:
-    nw_chunk_pipelined, SaFillParams::pair_list).  Strings and scores equal the oracle's and the one-pair path's, with the
+    """A chunk whose pairs are MOSTLY of one shape (reads of one length, some trimmed), on the default route (moves come home):
+    the pairs that find a partner of their shape go through the packed kernel two per wave and the others through the one-pair
+    kernel, side by side in one grid per sub-batch with the list of its pairs (sa_batch.hip: nw_chunk, pair_up_shapes;
+    SaFillParams::pair_list).  Strings and scores equal the oracle's and the one-pair path's, with the
     odd ones (other lengths, empty sequences) scattered through the batch, for one and for several sub-batches, at a
     size where the packed kernel is chosen by itself (2 600 pairs) and forced on a small batch."""
     rng = W.Rng(4242 + n_sub)
@@ -1562,3 +1563,207 @@ def test_randomised_scorings_differential(ctx):
             assert_pairs_match_oracle(db, batch, osc, is_sw, range(batch.n_pairs), tag=f"trial {trial} {spec}")
             checked += batch.n_pairs
     assert checked > 1500
+
+
+# ---- seqalign_nw_batch's pipeline (sa_batch.hip): sub-batches, groups, streams, staging or in place, per result form ------------
+
+import nwbatchlib as NB  # noqa: E402
+
+NW_ROUTES = {"default": {}, "zero_copy=0": {"zero_copy": 0}, "zero_copy=1": {"zero_copy": 1}, "zero_copy=2": {"zero_copy": 2},
+             "zero_copy=3": {"zero_copy": 3}, "zero_copy=auto": {"zero_copy": "auto"}, "nw_moves=0": {"nw_moves": 0}, "nw_dirs=0": {"nw_dirs": 0}}
+NW_PIPELINE_SHAPES = list(itertools.product((0, 2, 5), (0, 1), (1, 4), (0, 2)))   # subbatches x walk_overlap x upload_slices x pack16
+
+
+@pytest.fixture(scope="module")
+def small_ragged(ctx):
+    """The 1 300-pair batch (packed and unpacked host blocks), the default route's results and the oracle's: computed once."""
+    batch, pairs = NB.half_packed_ragged()
+    sc = S.make_scoring({"preset": "default"})
+    osc = oracle_scoring_of(sc)
+    want = []
+    for a, b in pairs:
+        rc, s_, ra, rb = O.oracle_nw(osc, a, b)
+        assert rc == 0
+        want.append((s_, ra, rb))
+    base = ctx.nw_batch(batch, sc)
+    assert set(ctx.last_call()) == {"fill_nw_dirs", "walk_moves_tile"}, ctx.last_call()
+    bad = [p for p in range(len(pairs)) if base[p] != want[p]]
+    assert not bad, (len(bad), bad[:5], base[bad[0]], want[bad[0]])
+    return batch, sc, want
+
+
+def cigar_of_strings(ra: bytes, rb: bytes, extended: int, fold: int) -> bytes:
+    lib = S.lib()
+    lib.seqalign_cigar.restype = C.c_size_t
+    out = C.create_string_buffer(2 * len(ra) + 8)
+    n = lib.seqalign_cigar(ra, rb, C.c_size_t(len(ra)), C.c_int(extended), C.c_int(fold), out, C.c_size_t(len(out)))
+    assert n != C.c_size_t(-1).value
+    return out.value
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", list(NW_ROUTES))
+def test_nw_batch_pipeline_shapes_small_ragged(ctx, opts, small_ragged, route):
+    """Every way through the chunk pipeline that a small batch can be made to take: the result forms (moves home staged or in
+    place, strings home, three matrices) crossed with 1 / 2 / 5 sub-batches, walk_overlap on or off (one group here: the walks
+    run beside fills in test_nw_batch_more_than_one_group), 1 / 4 upload
+    slices asked for (one runs at this size; more: test_nw_batch_upload_slices), packed fills forced or off -- on 1 300 pairs of lengths 0 .. 40 (empty sequences, runs of one tiny shape) in more than
+    two host blocks, half of them `packed` in the caller's arena and half not.  Every result equals the default route's, which
+    equals the oracle's for every pair; the CIGAR call (both formats) equals seqalign_cigar of the oracle's strings."""
+    batch, sc, want = small_ragged
+    for n_sub, overlap, slices, pk in NW_PIPELINE_SHAPES:
+        opts(subbatches=n_sub, walk_overlap=overlap, upload_slices=slices, pack16=pk, **NW_ROUTES[route])
+        got = ctx.nw_batch(batch, sc)
+        ran = ctx.last_call()
+        assert any(k.startswith("fill_nw_dirs") for k in ran) == (route != "nw_dirs=0"), (route, ran)
+        assert any(k.startswith("walk_moves_") for k in ran) == (route not in ("nw_dirs=0", "nw_moves=0")), (route, ran)
+        bad = [p for p in range(batch.n_pairs) if got[p] != want[p]]
+        assert not bad, (route, n_sub, overlap, slices, pk, len(bad), bad[:5], got[bad[0]], want[bad[0]])
+    if route in ("default", "nw_dirs=0"):
+        fold = int(not sc.case_sensitive)
+        for fmt in (1, 2):   # SEQALIGN_CIGAR_M, SEQALIGN_CIGAR_EQX
+            for n_sub, overlap, slices, pk in ((0, 0, 1, 0), (5, 1, 4, 2)):
+                opts(subbatches=n_sub, walk_overlap=overlap, upload_slices=slices, pack16=pk)
+                got = ctx.nw_batch_cigar(batch, sc, fmt=fmt)
+                bad = [p for p in range(batch.n_pairs) if got[p] != (want[p][0], cigar_of_strings(want[p][1], want[p][2], int(fmt == 2), fold))]
+                assert not bad, (route, fmt, n_sub, len(bad), bad[:5], got[bad[0]], want[bad[0]])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["default", "zero_copy=0", "zero_copy=2"])
+def test_nw_batch_upload_slices(ctx, opts, route):
+    """The moves form's sliced upload (option upload_slices: a sub-batch's sequences are packed and sent slice by slice, at most one
+    slice per two host blocks): 4 200 pairs of lengths 0 .. 40 are 9 host blocks of 512 in one sub-batch (2 and 4 slices) and 17 blocks
+    of 256 in two (4 slices each), the first half of the pairs `packed` in the caller's arena, the second half not, one block both.
+    Every result equals the oracle's and the unsliced call's."""
+    batch, pairs = NB.half_packed_ragged(n=4200, seed=4242)
+    sc = S.make_scoring({"preset": "default"})
+    osc = oracle_scoring_of(sc)
+    want = []
+    for a, b in pairs:
+        rc, s_, ra, rb = O.oracle_nw(osc, a, b)
+        assert rc == 0
+        want.append((s_, ra, rb))
+    opts(**NW_ROUTES[route])
+    assert ctx.nw_batch(batch, sc) == want
+    for n_sub, slices in ((0, 2), (0, 4), (0, 16), (2, 4)):
+        opts(subbatches=n_sub, upload_slices=slices)
+        got = ctx.nw_batch(batch, sc)
+        bad = [p for p in range(batch.n_pairs) if got[p] != want[p]]
+        assert not bad, (route, n_sub, slices, len(bad), bad[:5], got[bad[0]], want[bad[0]])
+
+
+def nw_raw_copy(ctx, batch, sc):
+    str_off, out_a, out_b, out_len, out_score = ctx.nw_batch(batch, sc, raw=True)
+    return str_off, out_a.copy(), out_b.copy(), out_len.copy(), out_score.copy()
+
+
+def nw_raw_pair(raw, p):
+    str_off, out_a, out_b, out_len, out_score = raw
+    o, ln = int(str_off[p]), int(out_len[p])
+    return int(out_score[p]), out_a[o:o + ln].tobytes(), out_b[o:o + ln].tobytes()
+
+
+# what a call launches on 65 536 pairs in four sub-batches: {kernel kind: (launches, pairs)} per (batch, nw_moves), the same with
+# the walks beside the fills and behind them (read off the library before the two pipelines became one driver: 4 fills, 2 walks).
+# The ragged batch's mixed grids count under both kinds, one launch each per sub-batch; with strings home it has no majority shape
+# and nothing is packed.
+NW_GROUP_LAUNCHES = {
+    ("one_shape", 1): {"fill_nw_dirs_x4": (4, 65536), "walk_moves_tile": (2, 65536)},
+    ("one_shape", 0): {"fill_nw_dirs_x4": (4, 65536), "walk_dirs_lane": (2, 65536)},
+    ("ragged", 1): {"fill_nw_dirs": (4, 350), "fill_nw_dirs_x2": (4, 65186), "walk_moves_tile": (2, 65536)},
+    ("ragged", 0): {"fill_nw_dirs": (4, 65536), "walk_dirs_lane": (2, 65536)},
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["one_shape", "ragged"])
+def test_nw_batch_more_than_one_group(ctx, opts, kind):
+    """A pipeline of more than one GROUP (>= 32 768 pairs per group: sa_batch.hip): 65 536 pairs of 12 x 10 in four sub-batches of
+    whole rounds (cuts at 16 384, 32 768, 49 152: two groups), and a ragged twin of lengths 4 .. 16 cut at equal cells; moves home
+    and strings home, the first group's walk beside the second group's fills and behind them.  The four settings agree, every
+    257th pair equals the oracle's, and the fills' and walks' launch and pair counts are the recorded ones."""
+    n = 65536
+    if kind == "one_shape":
+        rng = W.Rng(31)
+        a = W.DNA[rng.below(4, n * 12).astype(np.int64)].reshape(n, 12)
+        b = W.DNA[rng.below(4, n * 10).astype(np.int64)].reshape(n, 10)
+        b[:, :8] = np.where(rng.unit(n * 8).reshape(n, 8) < 0.8, a[:, 2:10], b[:, :8])
+        batch = W._fixed_batch(a, b)
+    else:
+        batch = NB.ragged_related(n, 4, 16, seed=32)
+    sc = S.make_scoring({"preset": "default"})
+    osc = oracle_scoring_of(sc)
+    first, launched = None, {}
+    for moves, overlap in ((1, 1), (1, 0), (0, 1), (0, 0)):
+        opts(subbatches=4, nw_moves=moves, walk_overlap=overlap)
+        raw = nw_raw_copy(ctx, batch, sc)
+        ran = ctx.last_call()
+        print(f"launches {kind} nw_moves={moves} walk_overlap={overlap}: {ran}")
+        if first is None:
+            first = raw
+            for p in range(0, n, 257):
+                rc, s_, ra, rb = O.oracle_nw(osc, batch.seq_a(p), batch.seq_b(p))
+                assert rc == 0 and nw_raw_pair(raw, p) == (s_, ra, rb), (kind, p)
+        else:
+            assert all(np.array_equal(x, y) for x, y in zip(raw[3:], first[3:])), (kind, moves, overlap)
+            ends = raw[0] + raw[3].astype(np.uint64)
+            for x, y in zip(raw[1:3], first[1:3]):   # (bytes behind a string's NUL are unspecified: compare the strings)
+                diff = np.nonzero(x != y)[0]
+                if diff.size:
+                    owner = np.searchsorted(raw[0], diff, side="right") - 1
+                    assert np.all(diff.astype(np.uint64) > ends[owner]), (kind, moves, overlap, int(diff[0]))
+        launched[moves, overlap] = ran
+    for (moves, overlap), ran in launched.items():
+        fills = {k: v for k, v in ran.items() if k.startswith("fill_")}
+        assert all(v[0] == 4 for v in fills.values()) and sum(v[1] for v in fills.values()) == n, (kind, moves, overlap, ran)
+        assert ran == NW_GROUP_LAUNCHES[kind, moves], (kind, moves, overlap, ran)
+
+
+def mostly_one_shape_pairs(rng, n):
+    def rand(m):
+        return bytes(b"ACGT"[i] for i in rng.below(4, m)) if m else b""
+    pairs = []
+    for k in range(n):
+        la, lb = (int(rng.below(160, 1)[0]), int(rng.below(160, 1)[0])) if k % 7 == 3 else (100, 100)
+        a = rand(la)
+        pairs.append((a, (a[:lb] + rand(max(0, lb - la))) if k % 2 else rand(lb)))
+    return pairs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["mostly_one_shape", "mostly_one_shape_forced", "every_length", "table_too_large"])
+def test_nw_batch_strings_form_on_ragged_packable_chunks(ctx, opts, case):
+    """nw_moves = 0 (strings come home) on ragged chunks the packed fill may take: which pairs go two per wave is the chunk
+    layout's choice (this form's: the majority shape's pairs, sa_batch.hip: majority_vote_layout) and never shows in the results --
+    equal to pack16 = 0 and to the oracle on every 23rd pair.  mostly one shape: test_nw_batch_mostly_one_shape's batch, 2 600 pairs at pack16 = 1 and 90 forced;
+    every length 100 .. 150: no majority shape; table too large: a majority of 100 x 100 that the packed fill takes beside one
+    pair of 1 023 x 10 and one of 10 x 1 100, whose (max_a + 1) (max_b + 1) is beyond the moves form's pairing table.  (No launch counts:
+    the mix of waves is the layout rule's business.)"""
+    rng = W.Rng(777)
+    n, pk = 2600, 1
+    if case == "mostly_one_shape":
+        batch = W.from_pairs(mostly_one_shape_pairs(rng, n))
+    elif case == "mostly_one_shape_forced":
+        n, pk = 90, 2
+        batch = W.from_pairs(mostly_one_shape_pairs(rng, n))
+    elif case == "every_length":
+        batch = NB.ragged_related(n, 100, 150, seed=778)
+    else:
+        pairs = mostly_one_shape_pairs(rng, n)
+        pairs[23] = (pairs[23][0] * 11)[:1023], pairs[23][1][:10]
+        pairs[46] = pairs[46][0][:10], (pairs[46][1] * 12)[:1100]
+        assert len(pairs[23][0]) == 1023 and len(pairs[46][1]) == 1100
+        batch = W.from_pairs(pairs)
+    sc = S.make_scoring({"preset": "default"})
+    osc = oracle_scoring_of(sc)
+    for n_sub in (0, 3):
+        opts(nw_moves=0, pack16=pk, subbatches=n_sub)
+        got = ctx.nw_batch(batch, sc)
+        ran = ctx.last_call()
+        assert any(k.startswith("fill_nw_dirs") for k in ran) and not any(k.startswith("walk_moves_") for k in ran), ran
+        opts(nw_moves=0, pack16=0, subbatches=n_sub)
+        assert got == ctx.nw_batch(batch, sc), (case, n_sub)
+        for p in range(0, n, 1 if n < 200 else 23):
+            rc, s_, ra, rb = O.oracle_nw(osc, batch.seq_a(p), batch.seq_b(p))
+            assert rc == 0 and got[p] == (s_, ra, rb), (case, n_sub, p)
