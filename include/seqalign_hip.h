@@ -661,8 +661,9 @@ int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch
  * bytes, 28 bytes per pair and the error word come back.  Argument checks, scoring admission (SEQALIGN_E_DOMAIN) and
  * SEQALIGN_E_UNKNOWN_PAIR are seqalign_sw_span_batch's; SEQALIGN_E_TRACEBACK cannot occur.  The launches are recorded as
  * "score_rows" / "score_strips" (items: pairs).
- *   Not here: sequences over 65 535 letters (a four-word payload), a search form, _cross_multi, _submit, the
- * command-line tools, gap-open counts.  The banded form is seqalign_sw_stats_banded below. */
+ *   Not here: a search form, _cross_multi, _submit, the command-line tools, gap-open counts.  Sequences over 65 535 letters:
+ * seqalign_sw_counts_batch below returns score, end and the two counts at any length, seqalign_sw_span_batch start and length
+ * (a four-word payload does not fit: DESIGN.md 3.22, 3.32).  The banded form is seqalign_sw_stats_banded below. */
 #define SEQALIGN_SW_STATS_MAX_LEN 65535u
 int seqalign_sw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                             uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
@@ -675,6 +676,32 @@ int seqalign_sw_stats_batch_multi(seqalign_ctx_t *const *ctxs, int n_ctx, const 
 /* Kernel time of seqalign_sw_stats_batch (seq-align_amd/tools/sw_stats_bench.py), the sibling of seqalign_sw_span_time_ms */
 int seqalign_sw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
                               float *ms_each);
+/* ---- SW identity counts at any length: score, end and identity counts of the best local hit, no traceback ---- */
+/* seqalign_sw_stats_batch without its length limit and without the start of the hit.  For every pair, over the first hit of
+ * seqalign_sw_batch(min_score = 1, max_hits = 1):
+ *   out_score, out_end_a, out_end_b   byte for byte seqalign_sw_score_batch's three: the best match_scores cell in hit order,
+ *                      1-based; 0, 0, 0 when no cell is above 0;
+ *   out_matches[p], out_mismatches[p]   the two counts of seqalign_sw_stats_batch: the letter columns of that hit's strings,
+ *                      split by whether the two letters are equal after the scoring's own case folding; substitution scores,
+ *                      wildcards and no_mismatches play no part; both 0 where there is no hit.
+ * For every batch seqalign_sw_stats_batch accepts, the counts equal its sixth and seventh outputs and end_a / end_b its
+ * pos + len.  There is NO limit on the sequence lengths: the two payload words of the sweep are the two counts, a full 32-bit
+ * word each, and a walk has at most min(len_a, len_b) letter columns, so neither can wrap.  The counts do not
+ * depend on where the walk stops, so seqalign_sw_span_batch on the same batch supplies pos and len for any pair.  The recipe:
+ * up to 65 535 letters one seqalign_sw_stats_batch sweep gives all seven integers; past that, two sweeps -- this call and
+ * seqalign_sw_span_batch.
+ *   Argument checks and their order, scoring admission (SEQALIGN_E_DOMAIN), SEQALIGN_E_UNKNOWN_PAIR and the chunk rules are
+ * seqalign_sw_span_batch's; SEQALIGN_E_TRACEBACK cannot occur.  Device bytes per pair are the span call's: len_a + len_b + 72,
+ * and for rows over 512 columns 32 x (strips - 1) x (len_b + 1) of hand-off plus 36 per strip, strips = ceil(len_a / 512);
+ * batches are chunked by these bytes (option chunk_bytes), 20 bytes per pair and the error word come back.  The launches are
+ * recorded as "score_rows" / "score_strips" (items: pairs); the call adds no kernel kind.
+ *   Not here: cross, search, _multi, _submit and command-line forms; one call that returns all seven integers at any length;
+ * gap-open counts.  Banded: seqalign_sw_counts_banded and seqalign_sw_counts_banded_wide below. */
+int seqalign_sw_counts_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                             uint32_t *out_end_a, uint32_t *out_end_b, uint32_t *out_matches, uint32_t *out_mismatches);
+/* Kernel time of seqalign_sw_counts_batch (seq-align_amd/tools/sw_counts_bench.py), as seqalign_sw_stats_time_ms */
+int seqalign_sw_counts_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                               float *ms_each);
 /* ---- banded SW hit spans: start and end of the best local hit inside a band, no traceback ---- */
 /* seqalign_sw_span_batch over the banded SW matrices: the five integers a mapper reports per read at the cost of a banded
  * sweep, nothing stored per cell and no walk.
@@ -745,6 +772,32 @@ int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch,
  * one chunk, `repeats` launches between HIP events; a batch that does not fit one chunk is SEQALIGN_E_ARG */
 int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                    const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
+/* ---- banded SW identity counts at any length: score, end and identity counts of the best hit inside a band ---- */
+/* seqalign_sw_counts_batch over the banded SW matrices: percent identity of a long read against its window at the cost of a
+ * banded sweep, nothing stored per cell and no walk.
+ *   Band and matrices are seqalign_sw_score_banded's ("banded SW" below), word for word.
+ *   out_score, out_end_a, out_end_b   byte for byte seqalign_sw_score_banded's three;
+ *   out_matches, out_mismatches       the two counts of seqalign_sw_stats_banded: the letter columns of the strings of the hit
+ *                      seqalign_sw_align_banded(min_score = 1) delivers, split by whether the two letters are equal after the
+ *                      scoring's own case folding.
+ *   All five are 0 when no band cell is above 0, or when the band is empty after clipping.  For every batch
+ *   seqalign_sw_stats_banded accepts the counts equal its sixth and seventh outputs and the ends its pos + len.
+ * NO limit on the sequence lengths (two full count words); seqalign_sw_span_banded on the same arguments
+ * supplies pos and len for any pair.
+ * Band geometry, clipping, argument checks, their order and every error are seqalign_sw_span_banded's, with a context that is
+ * never dereferenced before them: SEQALIGN_E_ARG (a NULL argument, an unreadable batch, diag_lo[p] > diag_hi[p]);
+ * SEQALIGN_E_TOO_LARGE (a clipped width over SEQALIGN_SPAN_BAND_MAX_WIDTH = 512, or len_a + len_b >= 2^31; the lowest such
+ * pair); SEQALIGN_E_DOMAIN by the same bound; SEQALIGN_E_UNKNOWN_PAIR for a character pair without a score INSIDE the band
+ * only; SEQALIGN_E_NOMEM with the bytes named.  Device bytes per pair: len_a + len_b + 88 (the span call's); 20 bytes per
+ * pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band diagonals per lane.  The launches are counted
+ * under band_score, one per width class of a chunk.  Widths over 512: seqalign_sw_counts_banded_wide below.
+ * Not here: cross, search, _multi, _submit, the command-line tools, gap-open counts. */
+int seqalign_sw_counts_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                              const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                              uint32_t *out_end_b, uint32_t *out_matches, uint32_t *out_mismatches);
+/* Timing hook (tools/sw_counts_bench.py), as seqalign_sw_stats_band_time_ms for seqalign_sw_counts_banded */
+int seqalign_sw_counts_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                    const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
 /* ---- banded NW statistics: identity counts of the global alignment inside a band, no traceback ---- */
 /* seqalign_nw_stats_batch over the banded NW matrices: score, matches and mismatches of long similar pairs at the cost of a
  * banded sweep, nothing stored per cell and no walk.
@@ -954,8 +1007,9 @@ int seqalign_nw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  *     len_a + len_b + 96 + strips (32 width + 36) + 20,      strips = max(1, ceil(len_a / S)).
  * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
  * strip) waves.  Kernel: sa_band_frame.hpp by sa_band_stats.hip.  For many short pairs within 512 diagonals the narrow
- * call is the faster one.  Past 65 535 letters the five span integers come from seqalign_sw_span_banded_wide below; no SW
- * statistics past 65 535 letters, no cross, search, _multi, _submit, timing-hook or command-line form. */
+ * call is the faster one.  Past 65 535 letters the five span integers come from seqalign_sw_span_banded_wide and the two
+ * counts from seqalign_sw_counts_banded_wide, both below; no cross, search, _multi, _submit, timing-hook or command-line
+ * form. */
 int seqalign_sw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                   const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
                                   uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
@@ -981,6 +1035,22 @@ int seqalign_sw_stats_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *b
 int seqalign_sw_span_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                  const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
                                  uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b);
+/* The wide form of seqalign_sw_counts_banded: its argument list and contract word for word -- score and end byte for byte
+ * seqalign_sw_score_banded_wide's, the two counts seqalign_sw_stats_banded_wide's wherever that call accepts the batch, five
+ * zeros where no band cell is above 0 and for an empty band -- under the wide calls' width rule above: any clipped width is
+ * legal, SEQALIGN_E_NOMEM and SEQALIGN_E_HIP (the hand-off timeout) as above, and for every batch the narrow call accepts the
+ * same bytes, the same status and the same pair named.  There is NO limit on the lengths.  Checks, their order and every
+ * error are seqalign_sw_span_banded_wide's: a NULL argument (SEQALIGN_E_ARG); per pair, the lowest first, an unreadable batch
+ * or diag_lo[p] > diag_hi[p] (SEQALIGN_E_ARG) and len_a + len_b >= 2^31 (SEQALIGN_E_TOO_LARGE).  Hand-off and best entries
+ * are the span call's, 32 bytes each, with the two counts where its span is; so the device bytes per pair are the span call's:
+ *     len_a + len_b + 88 + strips (32 width + 36) + 20,      strips = max(1, ceil(len_a / S)).
+ * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
+ * strip) waves.  Kernel: sa_band_frame.hpp by sa_band_counts.hip.  With seqalign_sw_span_banded_wide on the
+ * same arguments this gives the seven integers of a tabular line for a 200 kb read in its band: two sweeps, nothing stored per
+ * cell.  No cross, search, _multi, _submit, timing-hook or command-line form. */
+int seqalign_sw_counts_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                   const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                                   uint32_t *out_end_b, uint32_t *out_matches, uint32_t *out_mismatches);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

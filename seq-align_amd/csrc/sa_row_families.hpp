@@ -88,8 +88,28 @@ struct SwStatsTraits {   // sa_sw_stats.hip: the span kernels' classes, strips, 
   static hipError_t launch_cross(const CrossParams &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_sw_stats_cross(p, max_a, st); }
 };
 
+struct SwCountsTraits {   // sa_sw_counts.hip: the span kernels' classes, strips, hand-off, best-cell bytes and five result words
+  using Params = SaSwCountsParams;
+  static constexpr int kRowClasses = SA_SPAN_ROW_CLASSES;
+  static constexpr uint32_t kRowMax = SA_SPAN_ROW_MAX;
+  static constexpr uint64_t kPairBytes = 72;   // descriptors (32), results (20), status (8), slack
+  static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
+  static constexpr const char *kLaunch = "sw counts kernel launch";
+  static constexpr int kMarkField = 0;
+  static int fields(bool) { return 5; }   // score, end_a, end_b, matches, mismatches
+  static int row_class(uint32_t la) { return sa_span_row_class(la); }
+  static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
+  static void set_results(Params &p, uint32_t *res, uint64_t n) {   // the span block's arrays by their new names (sa_kernels.h)
+    p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
+  }
+  static void set_strip_best(Params &p, uint32_t *best) { p.strip_best = best; }
+  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_sw_counts_rows(p, max_a, st); }
+  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_sw_counts_strips(p, st); }
+  // no cross form: nothing for the cross driver to instantiate
+};
+
 // A family's batch call behind its entry checks: every chunk prepared, launched, brought home (sa_batch_score.hip, which
-// instantiates it for the four families).  out: the arrays behind the score, T::fields(is_sw) - 1 of them; fail_pair
+// instantiates it for the five families).  out: the arrays behind the score, T::fields(is_sw) - 1 of them; fail_pair
 // (optional): the failing pair it names, for SEQALIGN_E_TRACEBACK too.
 template <class T>
 int row_batch_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw, int32_t *out_score,

@@ -6,7 +6,8 @@
 seqalign_nw_stats_banded (the counted strings of the oracle's walk over the banded matrices; the lowest pair without an alignment inside its
 band named), seqalign_sw_span_banded, seqalign_sw_stats_banded (the oracle's
 banded hit and its counted strings) and (on from the command line, --no-wide leaves them out) the four wide banded score and align calls,
-seqalign_sw_span_banded_wide, seqalign_nw_stats_banded_wide and seqalign_sw_stats_banded_wide (each with its narrow call's bytes on the small pairs), under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+seqalign_sw_span_banded_wide, seqalign_nw_stats_banded_wide and seqalign_sw_stats_banded_wide (each with its narrow call's bytes on the small pairs),
+and seqalign_sw_counts_batch / _banded / _banded_wide (each against the sw_stats and the sw_score call of the same geometry on the same batch), under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -72,6 +73,12 @@ def walked_along_the_floor(osc, a, b, w, ra, rb):
 SCALE_LOW_BITS = 8      # the drawn factors start at 2^8
 
 
+def counts_view(seven):
+    """(score, end_a, end_b, matches, mismatches) arrays of a sw_stats call's seven: what the sw_counts call of the same geometry
+    must return byte for byte."""
+    return [seven[0], seven[1] + seven[3], seven[2] + seven[4], seven[5], seven[6]]
+
+
 def scaled_spec(spec, f):
     """Every number of the scoring times f: match, mismatch, the gap penalties, wildcard and mutation scores."""
     out = dict(spec, init=[x * f for x in spec["init"][:4]] + list(spec["init"][4:]),
@@ -111,7 +118,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
     ctx = ctx or (None if dry else S.Context(0))
     t_end = time.time() + seconds
     n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span_banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0, "sw_stats_banded": 0,
-         "stats_banded": 0, "stats_banded_none": 0, "stats_banded_wide": 0, "sw_stats_banded_wide": 0}
+         "stats_banded": 0, "stats_banded_none": 0, "stats_banded_wide": 0, "sw_stats_banded_wide": 0,
+         "sw_counts": 0, "sw_counts_banded": 0, "sw_counts_banded_wide": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -251,6 +259,11 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                 fail("SW STATS", spec, p, pairs[p], tuple(int(x[p]) for x in got7), want7)
         n["span"] += 12
         n["sw_stats"] += len(pairs)
+        # ---- SW identity counts on the same batch: sw_score's three byte for byte, sw_stats' two counts and its pos + len
+        got5 = ctx.sw_counts(batch, sc)
+        if any(x.tobytes() != y.tobytes() for x, y in zip(got5, counts_view(got7))) or any(x.tobytes() != y.tobytes() for x, y in zip(got5[:3], (s, ea, eb))):
+            fail("SW COUNTS", spec, pairs, [tuple(int(x[p]) for x in got5) for p in range(len(pairs))])
+        n["sw_counts"] += len(pairs)
 
         # ---- NW statistics: the columns of the oracle's strings, counted on the host
         if nw_ok:
@@ -392,6 +405,12 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
             if got != want:
                 fail("SW STATS BANDED", spec, sub, lo, hi, got, want)
             n["sw_stats_banded"] += len(sub)
+            # ---- banded SW identity counts on the same pairs and bounds: sw_score_banded's three, sw_stats_banded's counts
+            res5 = ctx.sw_counts_banded(W.from_pairs(sub), sc, lo, hi)
+            if any(x.tobytes() != y.tobytes() for x, y in zip(res5, counts_view(res))) or \
+                    any(x.tobytes() != y.tobytes() for x, y in zip(res5[:3], ctx.sw_score_banded(W.from_pairs(sub), sc, lo, hi))):
+                fail("SW COUNTS BANDED", spec, sub, lo, hi, [tuple(int(x[k]) for x in res5) for k in range(len(sub))], want)
+            n["sw_counts_banded"] += len(sub)
 
         # ---- the wide banded calls: two small pairs (the narrow calls must agree) and one of 1 025 .. 1 624 columns whose band is
         # 700 .. 1 500 diagonals wide, under a random strip width
@@ -461,6 +480,16 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                     if any(x[:len(small)].tobytes() != y.tobytes() for x, y in zip(res, narrow)):
                         fail("WIDE / NARROW BAND SW STATS", spec, "cols", cols, sub, lo, hi)
                 n["sw_stats_banded_wide"] += len(sub)
+                # ---- wide banded SW identity counts on the same pairs and bounds: sw_score_banded_wide's three (checked against
+                # the oracle above), sw_stats_banded_wide's counts, and the narrow call's bytes on the small pairs
+                res5 = ctx.sw_counts_banded_wide(wb, sc, lo, hi)
+                if any(x.tobytes() != y.tobytes() for x, y in zip(res5, counts_view(res))) or any(x.tobytes() != y.tobytes() for x, y in zip(res5[:3], (s, ea, eb))):
+                    fail("WIDE BAND SW COUNTS", spec, "cols", cols, sub, lo, hi, [tuple(int(x[k]) for x in res5) for k in range(len(sub))], want7)
+                if small:
+                    narrow = ctx.sw_counts_banded(W.from_pairs(sub[:len(small)]), sc, lo[:len(small)], hi[:len(small)])
+                    if any(x[:len(small)].tobytes() != y.tobytes() for x, y in zip(res5, narrow)):
+                        fail("WIDE / NARROW BAND SW COUNTS", spec, "cols", cols, sub, lo, hi)
+                n["sw_counts_banded_wide"] += len(sub)
         n["trials"] += 1
 
     if srng is not None:
@@ -469,7 +498,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
     print(f"fuzz_calls ok: {n['trials']} random scorings x batches ({n['nw_trials']} in NW's domain, {n['wide']} pairs over 1 024 columns); "
           f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['sw_stats_banded']} banded SW statistics, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['stats']} NW and {n['sw_stats']} SW statistics, {n['stats_cross']} NW and {n['sw_stats_cross']} SW statistics cross cells, {n['long']} long alignments, {n['banded']} banded "
           f"alignments (+ {n['banded_none']} with none in their band), {n['stats_banded']} banded NW statistics (+ {n['stats_banded_none']} with none), {n['banded_wide']} wide banded results, {n['span_banded_wide']} wide banded hit spans, "
-          f"{n['stats_banded_wide']} wide banded NW and {n['sw_stats_banded_wide']} wide banded SW statistics identical to the oracle "
+          f"{n['stats_banded_wide']} wide banded NW and {n['sw_stats_banded_wide']} wide banded SW statistics identical to the oracle; "
+          f"{n['sw_counts']} SW identity counts, {n['sw_counts_banded']} banded and {n['sw_counts_banded_wide']} wide banded identical to sw_stats* and sw_score* "
           f"(seed {seed})", flush=True)
     return n
 
