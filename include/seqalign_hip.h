@@ -661,7 +661,8 @@ int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch
  * bytes, 28 bytes per pair and the error word come back.  Argument checks, scoring admission (SEQALIGN_E_DOMAIN) and
  * SEQALIGN_E_UNKNOWN_PAIR are seqalign_sw_span_batch's; SEQALIGN_E_TRACEBACK cannot occur.  The launches are recorded as
  * "score_rows" / "score_strips" (items: pairs).
- *   Not here: a search form, _cross_multi, _submit, the command-line tools, gap-open counts.  Sequences over 65 535 letters:
+ *   Not here: a search form, _cross_multi, _submit, the command-line tools.  Gap-open counts: seqalign_sw_gaps_batch below.
+ * Sequences over 65 535 letters:
  * seqalign_sw_counts_batch below returns score, end and the two counts at any length, seqalign_sw_span_batch start and length
  * (a four-word payload does not fit: DESIGN.md 3.22, 3.32).  The banded form is seqalign_sw_stats_banded below. */
 #define SEQALIGN_SW_STATS_MAX_LEN 65535u
@@ -696,12 +697,38 @@ int seqalign_sw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch
  * batches are chunked by these bytes (option chunk_bytes), 20 bytes per pair and the error word come back.  The launches are
  * recorded as "score_rows" / "score_strips" (items: pairs); the call adds no kernel kind.
  *   Not here: cross, search, _multi, _submit and command-line forms; one call that returns all seven integers at any length;
- * gap-open counts.  Banded: seqalign_sw_counts_banded and seqalign_sw_counts_banded_wide below. */
+ * gap-open counts (seqalign_sw_gaps_batch below).  Banded: seqalign_sw_counts_banded and seqalign_sw_counts_banded_wide below. */
 int seqalign_sw_counts_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
                              uint32_t *out_end_a, uint32_t *out_end_b, uint32_t *out_matches, uint32_t *out_mismatches);
 /* Kernel time of seqalign_sw_counts_batch (seq-align_amd/tools/sw_counts_bench.py), as seqalign_sw_stats_time_ms */
 int seqalign_sw_counts_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
                                float *ms_each);
+/* ---- SW gap-run counts at any length: score, end and the gap opens of the best local hit, no traceback ---- */
+/* The gapopen field of a BLAST-style tabular line without the strings.  For every pair, over the first hit of
+ * seqalign_sw_batch(min_score = 1, max_hits = 1):
+ *   out_score, out_end_a, out_end_b   byte for byte seqalign_sw_score_batch's three: the best match_scores cell in hit order,
+ *                      1-based; 0, 0, 0 when no cell is above 0;
+ *   out_gap_runs_a[p]  the number of maximal runs of '-' in that hit's string a;
+ *   out_gap_runs_b[p]  the same in its string b; both 0 where there is no hit.  BLAST's gapopen is their sum.  An insertion
+ *                      directly against a deletion is two runs, one in each string.  The number of gap COLUMNS follows from
+ *                      seqalign_sw_span_batch's lengths and seqalign_sw_counts_batch's counts
+ *                      (len_a + len_b - 2 (matches + mismatches)), so no word is spent on it.
+ * A run is counted at its first column, not at an "open" move of the scoring: with gap_extend > 0 a gap can extend out of a
+ * cell whose score is 0, where the hit begins, and that run counts as every other.  There is NO limit on the
+ * sequence lengths: both counts are full 32-bit words and a hit has fewer than len_a + len_b < 2^31 columns.  The recipe for a
+ * full tabular line (pident, length, mismatch, gapopen, qstart, qend, sstart, send, score): up to 65 535 letters
+ * seqalign_sw_stats_batch and this call; past that seqalign_sw_span_batch, seqalign_sw_counts_batch and this call.
+ *   Argument checks and their order, scoring admission (SEQALIGN_E_DOMAIN), SEQALIGN_E_UNKNOWN_PAIR, the chunk rules, the
+ * device bytes per pair and the 20 bytes per pair that come back are seqalign_sw_counts_batch's (the span call's) exactly;
+ * SEQALIGN_E_TRACEBACK cannot occur.  The launches are recorded as "score_rows" / "score_strips" (items: pairs); the call adds
+ * no kernel kind.
+ *   Not here: NW gap runs; cross, search, _multi, _submit and command-line forms; one call that returns a whole tabular line.
+ * Banded: seqalign_sw_gaps_banded and seqalign_sw_gaps_banded_wide below. */
+int seqalign_sw_gaps_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                           uint32_t *out_end_a, uint32_t *out_end_b, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b);
+/* Kernel time of seqalign_sw_gaps_batch (seq-align_amd/tools/sw_gaps_bench.py), as seqalign_sw_counts_time_ms */
+int seqalign_sw_gaps_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                             float *ms_each);
 /* ---- banded SW hit spans: start and end of the best local hit inside a band, no traceback ---- */
 /* seqalign_sw_span_batch over the banded SW matrices: the five integers a mapper reports per read at the cost of a banded
  * sweep, nothing stored per cell and no walk.
@@ -763,7 +790,7 @@ int seqalign_sw_span_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *b
  * one per width class of a chunk.
  * Widths over 512: seqalign_sw_stats_banded_wide ("wide banded calls" below).
  * Not in this call (banded NW statistics: seqalign_nw_stats_banded and seqalign_nw_stats_banded_wide below): cross, search,
- * _multi, _submit, the command-line tools, gap-open counts. */
+ * _multi, _submit, the command-line tools; gap-open counts are seqalign_sw_gaps_banded's. */
 int seqalign_sw_stats_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                              const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
                              uint32_t *out_pos_a, uint32_t *out_pos_b, uint32_t *out_len_a, uint32_t *out_len_b,
@@ -791,13 +818,34 @@ int seqalign_sw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *
  * only; SEQALIGN_E_NOMEM with the bytes named.  Device bytes per pair: len_a + len_b + 88 (the span call's); 20 bytes per
  * pair and the error word come home.  One wave per pair, 1 .. 6 or 8 band diagonals per lane.  The launches are counted
  * under band_score, one per width class of a chunk.  Widths over 512: seqalign_sw_counts_banded_wide below.
- * Not here: cross, search, _multi, _submit, the command-line tools, gap-open counts. */
+ * Not here: cross, search, _multi, _submit, the command-line tools; gap-open counts are seqalign_sw_gaps_banded's. */
 int seqalign_sw_counts_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                               const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
                               uint32_t *out_end_b, uint32_t *out_matches, uint32_t *out_mismatches);
 /* Timing hook (tools/sw_counts_bench.py), as seqalign_sw_stats_band_time_ms for seqalign_sw_counts_banded */
 int seqalign_sw_counts_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                     const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
+/* ---- banded SW gap-run counts at any length: score, end and the gap opens of the best hit inside a band ---- */
+/* seqalign_sw_gaps_batch over the banded SW matrices: the gapopen field of a long read against its window at the cost of a
+ * banded sweep, nothing stored per cell and no walk.
+ *   Band and matrices are seqalign_sw_score_banded's ("banded SW" below), word for word.
+ *   out_score, out_end_a, out_end_b   byte for byte seqalign_sw_score_banded's three;
+ *   out_gap_runs_a, out_gap_runs_b    the numbers of maximal runs of '-' in strings a and b of the hit
+ *                      seqalign_sw_align_banded(min_score = 1) delivers.  A cell outside the band ends the hit as a cell of
+ *                      score 0 does: a gap that extends out of it begins its run inside the band.
+ *   All five are 0 when no band cell is above 0, or when the band is empty after clipping.
+ * NO limit on the sequence lengths (two full words).
+ * Band geometry, clipping, argument checks, their order, every error, the device bytes per pair (len_a + len_b + 88) and the
+ * 20 bytes per pair that come home are seqalign_sw_counts_banded's (the span call's) exactly, the cap of
+ * SEQALIGN_SPAN_BAND_MAX_WIDTH = 512 clipped diagonals included.  One wave per pair, 1 .. 6 or 8 band diagonals per lane.  The
+ * launches are counted under band_score, one per width class of a chunk.  Widths over 512: seqalign_sw_gaps_banded_wide below.
+ * Not here: NW gap runs, cross, search, _multi, _submit, the command-line tools. */
+int seqalign_sw_gaps_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                            const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                            uint32_t *out_end_b, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b);
+/* Timing hook (tools/sw_gaps_bench.py), as seqalign_sw_counts_band_time_ms for seqalign_sw_gaps_banded */
+int seqalign_sw_gaps_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each);
 /* ---- banded NW statistics: identity counts of the global alignment inside a band, no traceback ---- */
 /* seqalign_nw_stats_batch over the banded NW matrices: score, matches and mismatches of long similar pairs at the cost of a
  * banded sweep, nothing stored per cell and no walk.
@@ -1051,6 +1099,20 @@ int seqalign_sw_span_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *ba
 int seqalign_sw_counts_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
                                    const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
                                    uint32_t *out_end_b, uint32_t *out_matches, uint32_t *out_mismatches);
+/* The wide form of seqalign_sw_gaps_banded: its argument list and contract word for word -- score and end byte for byte
+ * seqalign_sw_score_banded_wide's, the two run counts those of seqalign_sw_align_banded_wide(min_score = 1)'s strings, five
+ * zeros where no band cell is above 0 and for an empty band -- under the wide calls' width rule above: any clipped width is
+ * legal, and for every batch the narrow call accepts the same bytes, the same status and the same pair named.  There is NO
+ * limit on the lengths.  Checks, their order, every error, hand-off and best entries (32 bytes each, the two run counts where
+ * the span is) and the device bytes per pair are seqalign_sw_counts_banded_wide's (the span call's) exactly:
+ *     len_a + len_b + 88 + strips (32 width + 36) + 20,      strips = max(1, ceil(len_a / S)).
+ * The option band_strip_cols steers S as above; launches are counted under band_score, one per chunk, items = the busy (pair,
+ * strip) waves.  Kernel: sa_band_frame.hpp by sa_band_gaps.hip.  With seqalign_sw_span_banded_wide and
+ * seqalign_sw_counts_banded_wide on the same arguments this completes the tabular line of a 200 kb read in its band: three
+ * sweeps, nothing stored per cell.  No cross, search, _multi, _submit, timing-hook or command-line form. */
+int seqalign_sw_gaps_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                 const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                                 uint32_t *out_end_b, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b);
 /* ---- score matrices: every query against every target, score only ---------------- */
 /* A set of sequences: one byte arena, per-sequence offset and length (raw chars, as seqalign_batch_t). */
 typedef struct {

@@ -1,8 +1,8 @@
-// sa_batch_band.hip -- the banded calls over HOST batches: the twenty-one seqalign_*_banded, *_banded_wide and *_band_time_ms entry
-// points (the contracts: include/seqalign_hip.h; the kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip, sa_band_counts.hip,
+// sa_batch_band.hip -- the banded calls over HOST batches: the twenty-four seqalign_*_banded, *_banded_wide and *_band_time_ms entry
+// points (the contracts: include/seqalign_hip.h; the kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip, sa_band_counts.hip, sa_band_gaps.hip,
 // sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip).  DESIGN.md 3.23b.
 //
-// One driver, eight modes.  A mode is a traits struct (below): NW or SW, score family or align, its result words and fixed
+// One driver, nine modes.  A mode is a traits struct (below): NW or SW, score family or align, its result words and fixed
 // bytes per pair, its cap on the width, its kernels' parameter block and launches.  The driver is the same for all of them:
 //   checks   everything that can be refused from lengths and bands alone is refused before any device work
 //            (check_band_batch): the band of every pair is clipped to its matrix -- NW: w diagonals around the corner cells'
@@ -158,6 +158,24 @@ struct SwCountsBand {   // seqalign_sw_counts_banded(_wide), seqalign_sw_counts_
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_counts(p, max_width, st); }
   static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
     return sa_launch_band_sw_counts_strips({p, l}, cols, items, st);
+  }
+};
+
+struct SwGapsBand {   // seqalign_sw_gaps_banded(_wide), seqalign_sw_gaps_band_time_ms (sa_band_gaps.hip)
+  using Params = SaBandSwGapsParams;
+  static constexpr bool kSw = true, kAlign = false;
+  static constexpr int kFields = 5;             // score, end_a, end_b, gap_runs_a, gap_runs_b
+  static constexpr int kMarkField = 0;
+  // the span mode's bytes and its width rule; no length check: the two payload words are full-word run counts
+  static constexpr uint64_t kPairBytes = 88, kMaxWidth = SEQALIGN_SPAN_BAND_MAX_WIDTH;
+  static constexpr uint64_t kHandoffBytes = SA_BAND_STATS_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
+  static SaBandParams &base(Params &p) { return p.b; }
+  static void set_results(Params &p, uint32_t *res, uint64_t n) {   // the span block's arrays by their new names (sa_kernels.h)
+    p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
+  }
+  static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_sw_gaps(p, max_width, st); }
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    return sa_launch_band_sw_gaps_strips({p, l}, cols, items, st);
   }
 };
 
@@ -788,6 +806,42 @@ extern "C" int seqalign_sw_counts_band_time_ms(seqalign_ctx_t *ctx, const seqali
   int rc = check_band_batch<SwCountsBand>(batch, SwBands{diag_lo, diag_hi}, geom);
   if (rc) return rc;
   return band_time<SwCountsBand>(ctx, batch, scoring, geom, repeats, ms_each, "seqalign_sw_counts_band_time_ms");
+}
+
+// banded SW gap-run counts at any length: seqalign_sw_span_banded's checks in its order and nothing else; the wide form:
+// without the width check (kernels: sa_band_frame.hpp's two shells, by sa_band_gaps.hip)
+static int sw_gaps_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const int32_t *diag_lo,
+                            const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a, uint32_t *out_end_b,
+                            uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b, bool wide) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || !out_score || !out_end_a || !out_end_b || !out_gap_runs_a || !out_gap_runs_b) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch<SwGapsBand>(batch, SwBands{diag_lo, diag_hi}, geom, wide);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  uint32_t *const out[4] = {out_end_a, out_end_b, out_gap_runs_a, out_gap_runs_b};
+  return band_call<SwGapsBand>(ctx, batch, scoring, geom, wide, [&](auto &run) { return run.finish_words(out_score, out); });
+}
+
+extern "C" int seqalign_sw_gaps_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                         const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score, uint32_t *out_end_a,
+                                         uint32_t *out_end_b, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b) {
+  return sw_gaps_banded(ctx, batch, scoring, diag_lo, diag_hi, out_score, out_end_a, out_end_b, out_gap_runs_a, out_gap_runs_b, false);
+}
+
+extern "C" int seqalign_sw_gaps_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                              const int32_t *diag_lo, const int32_t *diag_hi, int32_t *out_score,
+                                              uint32_t *out_end_a, uint32_t *out_end_b, uint32_t *out_gap_runs_a,
+                                              uint32_t *out_gap_runs_b) {
+  return sw_gaps_banded(ctx, batch, scoring, diag_lo, diag_hi, out_score, out_end_a, out_end_b, out_gap_runs_a, out_gap_runs_b, true);
+}
+
+extern "C" int seqalign_sw_gaps_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                               const int32_t *diag_lo, const int32_t *diag_hi, int repeats, float *ms_each) {
+  if (!ctx || !batch || !scoring || !diag_lo || !diag_hi || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch<SwGapsBand>(batch, SwBands{diag_lo, diag_hi}, geom);
+  if (rc) return rc;
+  return band_time<SwGapsBand>(ctx, batch, scoring, geom, repeats, ms_each, "seqalign_sw_gaps_band_time_ms");
 }
 
 // banded NW statistics: seqalign_nw_score_banded's checks in its order, with the span cap on the width; the wide form: without

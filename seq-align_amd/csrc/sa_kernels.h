@@ -539,6 +539,16 @@ typedef SaSpanParams SaSwCountsParams;
 /* recorded as "score_rows" / "score_strips"; the callers' duties are sa_launch_span_*'s */
 hipError_t sa_launch_sw_counts_rows(const SaSwCountsParams &p, uint32_t max_len_a, hipStream_t stream);
 hipError_t sa_launch_sw_counts_strips(const SaSwCountsParams &p, hipStream_t stream);
+/* ---- SW gap-run counts (seqalign_sw_gaps_batch, sa_sw_gaps.hip): the SW counts sweep with the runs of '-' in the hit's two
+ * strings as the two full payload words, any length.  The span block reused, its four arrays behind the score
+ * read as
+ *   pos_a = end_a, pos_b = end_b (the best cell, 1-based, as SaScoreParams reports it), len_a = gap_runs_a, len_b = gap_runs_b;
+ * all five are 0 when no cell is above 0.  Everything else -- row classes, strips, hand-off, progress and strip_best layout --
+ * is SaSpanParams'; a strip_best entry is {score, end_a, end_b, 0} {gap_runs_a, gap_runs_b, 0, 0}.  No cross form. */
+typedef SaSpanParams SaSwGapsParams;
+/* recorded as "score_rows" / "score_strips"; the callers' duties are sa_launch_span_*'s */
+hipError_t sa_launch_sw_gaps_rows(const SaSwGapsParams &p, uint32_t max_len_a, hipStream_t stream);
+hipError_t sa_launch_sw_gaps_strips(const SaSwGapsParams &p, hipStream_t stream);
 /* top-k score search (seqalign_*_score_search, sa_score_select.hip): one workgroup per query row of a tile, after its
  * score_cross launches.  Keeps the k smallest keys (~(score ^ 0x80000000)) << 32 | (t_base + t) of the row's entries with
  * score >= min_score together with the query's running list, and writes them back sorted.  The running list's targets
@@ -659,6 +669,12 @@ hipError_t sa_launch_band_sw_stats(const SaBandSwStatsParams &p, uint32_t max_wi
 typedef SaBandSpanParams SaBandSwCountsParams;
 /* recorded as "band_score"; max_width as sa_launch_band_span */
 hipError_t sa_launch_band_sw_counts(const SaBandSwCountsParams &p, uint32_t max_width, hipStream_t stream);
+/* ---- banded SW gap-run counts (seqalign_sw_gaps_banded, sa_band_gaps.hip): the banded span sweep with SaSwGapsParams' payload,
+ * gap_runs_a and gap_runs_b as two full words, any length.  The banded span block reused as SaSwGapsParams reuses the span
+ * block: pos_a = end_a, pos_b = end_b, len_a = gap_runs_a, len_b = gap_runs_b (all 0 when no band cell is above 0). */
+typedef SaBandSpanParams SaBandSwGapsParams;
+/* recorded as "band_score"; max_width as sa_launch_band_span */
+hipError_t sa_launch_band_sw_gaps(const SaBandSwGapsParams &p, uint32_t max_width, hipStream_t stream);
 /* ---- banded NW statistics (seqalign_nw_stats_banded, sa_band_nw_stats.hip): SaStatsParams' payload through the NW band frame.
  * Pair k of a launch has the band of sa_launch_band_score (d_lo <= 0 <= d_hi, 1 <= width <= SA_SPAN_BAND_MAX_WIDTH) and any
  * length; b.score[k] is sa_launch_band_score's value, matches[k] / mismatches[k] the counts of the alignment inside the band
@@ -700,9 +716,11 @@ hipError_t sa_launch_band_strips(const SaBandWideParams<SaBandSwParams> &p, uint
  * NW statistics (sa_band_nw_stats_strips.hip): the words are matches and mismatches; there is no best cell, strip_best is unused.
  * SW statistics (sa_band_stats.hip): word 0 the stop cell x | y << 16, word 1 matches | mismatches << 16; both sequences of every
  * pair have at most SA_SW_STATS_MAX_LEN letters.  SW hit spans (sa_band_span.hip): the stop cell's x and y, any length.  SW
- * identity counts (sa_band_counts.hip): matches and mismatches, any length. */
+ * identity counts (sa_band_counts.hip): matches and mismatches, any length.  SW gap-run counts (sa_band_gaps.hip): gap_runs_a
+ * and gap_runs_b, any length. */
 #define SA_BAND_STATS_HANDOFF_BYTES 32u
 hipError_t sa_launch_band_sw_counts_strips(const SaBandWideParams<SaBandSwCountsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
+hipError_t sa_launch_band_sw_gaps_strips(const SaBandWideParams<SaBandSwGapsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 hipError_t sa_launch_band_nw_stats_strips(const SaBandWideParams<SaBandNwStatsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 hipError_t sa_launch_band_sw_stats_strips(const SaBandWideParams<SaBandSwStatsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 hipError_t sa_launch_band_span_strips(const SaBandWideParams<SaBandSpanParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);

@@ -108,8 +108,28 @@ struct SwCountsTraits {   // sa_sw_counts.hip: the span kernels' classes, strips
   // no cross form: nothing for the cross driver to instantiate
 };
 
+struct SwGapsTraits {   // sa_sw_gaps.hip: SwCountsTraits with the gap-run kernels -- the span kernels' classes, strips and bytes
+  using Params = SaSwGapsParams;
+  static constexpr int kRowClasses = SA_SPAN_ROW_CLASSES;
+  static constexpr uint32_t kRowMax = SA_SPAN_ROW_MAX;
+  static constexpr uint64_t kPairBytes = 72;   // descriptors (32), results (20), status (8), slack
+  static constexpr uint64_t kHandoffBytes = SA_SPAN_HANDOFF_BYTES, kBestBytes = SA_SPAN_BEST_BYTES;
+  static constexpr const char *kLaunch = "sw gaps kernel launch";
+  static constexpr int kMarkField = 0;
+  static int fields(bool) { return 5; }   // score, end_a, end_b, gap_runs_a, gap_runs_b
+  static int row_class(uint32_t la) { return sa_span_row_class(la); }
+  static uint32_t strips_per_pair(uint32_t la) { return sa_span_strips_per_pair(la); }
+  static void set_results(Params &p, uint32_t *res, uint64_t n) {   // the span block's arrays by their new names (sa_kernels.h)
+    p.pos_a = res + n; p.pos_b = res + 2 * n; p.len_a = res + 3 * n; p.len_b = res + 4 * n;
+  }
+  static void set_strip_best(Params &p, uint32_t *best) { p.strip_best = best; }
+  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_sw_gaps_rows(p, max_a, st); }
+  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_sw_gaps_strips(p, st); }
+  // no cross form: nothing for the cross driver to instantiate
+};
+
 // A family's batch call behind its entry checks: every chunk prepared, launched, brought home (sa_batch_score.hip, which
-// instantiates it for the five families).  out: the arrays behind the score, T::fields(is_sw) - 1 of them; fail_pair
+// instantiates it for the six families).  out: the arrays behind the score, T::fields(is_sw) - 1 of them; fail_pair
 // (optional): the failing pair it names, for SEQALIGN_E_TRACEBACK too.
 template <class T>
 int row_batch_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw, int32_t *out_score,

@@ -551,6 +551,31 @@ class Context:
                "seqalign_sw_counts_time_ms")
         return ms
 
+    # ---- SW gap-run counts at any length (seqalign_sw_gaps_batch) ------------------------------
+    def sw_gaps(self, batch, scoring: Scoring):
+        """seqalign_sw_gaps_batch: (score int32[n], end_a, end_b, gap_runs_a, gap_runs_b uint32[n]) -- sw_score's three and the
+        numbers of maximal '-' runs in strings a and b of the same hit (BLAST's gapopen is their sum), with no limit on the
+        sequence lengths.  All 0 when no cell scores above 0."""
+        _score_args(batch, scoring)
+        n = batch.n_pairs
+        score = np.zeros(n, np.int32)
+        words = tuple(np.zeros(n, np.uint32) for _ in range(4))
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_gaps_batch(self._h, C.byref(d), C.byref(scoring), _ptr(score), *(_ptr(w) for w in words)),
+               "seqalign_sw_gaps_batch")
+        return (score,) + words
+
+    def sw_gaps_time_ms(self, batch, scoring: Scoring, repeats: int = 10) -> np.ndarray:
+        """seqalign_sw_gaps_time_ms: sw_gaps' kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
+        _score_args(batch, scoring)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "sw_gaps_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_gaps_time_ms(self._h, C.byref(d), C.byref(scoring), C.c_int(repeats), _ptr(ms)),
+               "seqalign_sw_gaps_time_ms")
+        return ms
+
     def sw_stats_cross(self, queries, targets, scoring: Scoring):
         """seqalign_sw_stats_cross: (score int32, pos_a, pos_b, len_a, len_b, matches, mismatches uint32), each [n_queries,
         n_targets] -- sw_stats on workloads.cross_batch(queries, targets) without building that batch; pos_a / len_a are in
@@ -864,6 +889,29 @@ class Context:
         d = batch_desc(batch)
         _check(lib().seqalign_sw_counts_band_time_ms(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), C.c_int(repeats),
                                                      _ptr(ms)), "seqalign_sw_counts_band_time_ms")
+        return ms
+
+    # ---- banded SW gap-run counts at any length (seqalign_sw_gaps_banded) -------------------------------
+    def sw_gaps_banded(self, batch, scoring: Scoring, diag_lo, diag_hi):
+        """seqalign_sw_gaps_banded: what sw_gaps returns -- (score int32[n], end_a, end_b, gap_runs_a, gap_runs_b uint32[n])
+        -- over the banded matrices of sw_score_banded: its three and the '-' runs of sw_align_banded's strings, sequences of
+        any length.  Each bound an int or one per pair; clipped widths up to SEQALIGN_SPAN_BAND_MAX_WIDTH (512)."""
+        return self._sw_span_banded("seqalign_sw_gaps_banded", batch, scoring, diag_lo, diag_hi)
+
+    def sw_gaps_banded_wide(self, batch, scoring: Scoring, diag_lo, diag_hi):
+        """seqalign_sw_gaps_banded_wide: sw_gaps_banded without the cap on the band's width; sequences of any length."""
+        return self._sw_span_banded("seqalign_sw_gaps_banded_wide", batch, scoring, diag_lo, diag_hi)
+
+    def sw_gaps_band_time_ms(self, batch, scoring: Scoring, diag_lo, diag_hi, repeats: int = 10) -> np.ndarray:
+        """seqalign_sw_gaps_band_time_ms: kernel time (HIP events) of sw_gaps_banded's launches, float32[repeats]."""
+        _score_args(batch, scoring)
+        lo, hi = _diag_args(batch, diag_lo, diag_hi)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "sw_gaps_band_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_sw_gaps_band_time_ms(self._h, C.byref(d), C.byref(scoring), _ptr(lo), _ptr(hi), C.c_int(repeats),
+                                                   _ptr(ms)), "seqalign_sw_gaps_band_time_ms")
         return ms
 
     # ---- banded NW statistics (seqalign_nw_stats_banded) -------------------------------
@@ -1383,6 +1431,8 @@ EXPORTED_SYMBOLS = [
     "seqalign_nw_stats_banded_wide", "seqalign_sw_stats_banded_wide", "seqalign_sw_span_banded_wide",
     "seqalign_sw_counts_batch", "seqalign_sw_counts_time_ms", "seqalign_sw_counts_banded", "seqalign_sw_counts_band_time_ms",
     "seqalign_sw_counts_banded_wide",
+    "seqalign_sw_gaps_batch", "seqalign_sw_gaps_time_ms", "seqalign_sw_gaps_banded", "seqalign_sw_gaps_band_time_ms",
+    "seqalign_sw_gaps_banded_wide",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",

@@ -7,7 +7,8 @@ seqalign_nw_stats_banded (the counted strings of the oracle's walk over the band
 band named), seqalign_sw_span_banded, seqalign_sw_stats_banded (the oracle's
 banded hit and its counted strings) and (on from the command line, --no-wide leaves them out) the four wide banded score and align calls,
 seqalign_sw_span_banded_wide, seqalign_nw_stats_banded_wide and seqalign_sw_stats_banded_wide (each with its narrow call's bytes on the small pairs),
-and seqalign_sw_counts_batch / _banded / _banded_wide (each against the sw_stats and the sw_score call of the same geometry on the same batch), under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+and seqalign_sw_counts_batch / _banded / _banded_wide (each against the sw_stats and the sw_score call of the same geometry on the same batch),
+and seqalign_sw_gaps_batch / _banded / _banded_wide (the '-' runs of the oracle's strings on the same batches; no random draw of their own), under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -79,6 +80,18 @@ def counts_view(seven):
     return [seven[0], seven[1] + seven[3], seven[2] + seven[4], seven[5], seven[6]]
 
 
+def gaps_want(h):
+    """(score, end_a, end_b, gap_runs_a, gap_runs_b) of an oracle hit dict or None: what the sw_gaps call of that geometry returns."""
+    if not h:
+        return (0, 0, 0, 0, 0)
+    runs = tuple(sum(1 for k, ch in enumerate(t) if ch == "-" and (k == 0 or t[k - 1] != "-")) for t in (h["a"], h["b"]))
+    return (h["score"], h["pos_a"] + h["len_a"], h["pos_b"] + h["len_b"]) + runs
+
+
+def gaps_got(res):
+    return [tuple(int(x[k]) for x in res) for k in range(len(res[0]))]
+
+
 def scaled_spec(spec, f):
     """Every number of the scoring times f: match, mismatch, the gap penalties, wildcard and mutation scores."""
     out = dict(spec, init=[x * f for x in spec["init"][:4]] + list(spec["init"][4:]),
@@ -119,7 +132,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
     t_end = time.time() + seconds
     n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span_banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0, "sw_stats_banded": 0,
          "stats_banded": 0, "stats_banded_none": 0, "stats_banded_wide": 0, "sw_stats_banded_wide": 0,
-         "sw_counts": 0, "sw_counts_banded": 0, "sw_counts_banded_wide": 0}
+         "sw_counts": 0, "sw_counts_banded": 0, "sw_counts_banded_wide": 0,
+         "sw_gaps": 0, "sw_gaps_banded": 0, "sw_gaps_banded_wide": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -248,12 +262,14 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         # ---- SW hit spans: the oracle's first hit without its strings; SW statistics: that hit and its strings' counted columns
         got = ctx.sw_span(batch, sc)
         got7 = ctx.sw_stats(batch, sc)
+        want_runs = []
         for p, (a, b) in enumerate(pairs):
             rc, hits = O.oracle_sw_hits(osc, a, b, *fills[1, p], 1, 1)
             h = hits[0] if hits else None
             want = (h["score"], h["pos_a"], h["pos_b"], h["len_a"], h["len_b"]) if h else (0, 0, 0, 0, 0)
             if rc != 0 or tuple(int(x[p]) for x in got) != want:
                 fail("SW SPAN", spec, p, pairs[p], tuple(int(x[p]) for x in got), want)
+            want_runs.append(gaps_want(h))
             want7 = want + (ST.count_columns(osc, h["a"].encode(), h["b"].encode()) if h else (0, 0))
             if tuple(int(x[p]) for x in got7) != want7:
                 fail("SW STATS", spec, p, pairs[p], tuple(int(x[p]) for x in got7), want7)
@@ -264,6 +280,11 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         if any(x.tobytes() != y.tobytes() for x, y in zip(got5, counts_view(got7))) or any(x.tobytes() != y.tobytes() for x, y in zip(got5[:3], (s, ea, eb))):
             fail("SW COUNTS", spec, pairs, [tuple(int(x[p]) for x in got5) for p in range(len(pairs))])
         n["sw_counts"] += len(pairs)
+        # ---- SW gap runs on the same batch: sw_score's three byte for byte, the '-' runs of the oracle's strings
+        gaps5 = ctx.sw_gaps(batch, sc)
+        if gaps_got(gaps5) != want_runs or any(x.tobytes() != y.tobytes() for x, y in zip(gaps5[:3], (s, ea, eb))):
+            fail("SW GAPS", spec, pairs, gaps_got(gaps5), want_runs)
+        n["sw_gaps"] += len(pairs)
 
         # ---- NW statistics: the columns of the oracle's strings, counted on the host
         if nw_ok:
@@ -411,6 +432,11 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                     any(x.tobytes() != y.tobytes() for x, y in zip(res5[:3], ctx.sw_score_banded(W.from_pairs(sub), sc, lo, hi))):
                 fail("SW COUNTS BANDED", spec, sub, lo, hi, [tuple(int(x[k]) for x in res5) for k in range(len(sub))], want)
             n["sw_counts_banded"] += len(sub)
+            # ---- banded SW gap runs on the same pairs and bounds: sw_counts_banded's three, the '-' runs of the oracle's banded hit
+            gaps5 = ctx.sw_gaps_banded(W.from_pairs(sub), sc, lo, hi)
+            if gaps_got(gaps5) != [gaps_want(h) for h in hits] or any(x.tobytes() != y.tobytes() for x, y in zip(gaps5[:3], res5[:3])):
+                fail("SW GAPS BANDED", spec, sub, lo, hi, gaps_got(gaps5), [gaps_want(h) for h in hits])
+            n["sw_gaps_banded"] += len(sub)
 
         # ---- the wide banded calls: two small pairs (the narrow calls must agree) and one of 1 025 .. 1 624 columns whose band is
         # 700 .. 1 500 diagonals wide, under a random strip width
@@ -490,6 +516,16 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                     if any(x[:len(small)].tobytes() != y.tobytes() for x, y in zip(res5, narrow)):
                         fail("WIDE / NARROW BAND SW COUNTS", spec, "cols", cols, sub, lo, hi)
                 n["sw_counts_banded_wide"] += len(sub)
+                # ---- wide banded SW gap runs on the same pairs and bounds: sw_counts_banded_wide's three, the '-' runs of the
+                # oracle's banded hit at min_score = 1, and the narrow call's bytes on the small pairs
+                gaps5 = ctx.sw_gaps_banded_wide(wb, sc, lo, hi)
+                if gaps_got(gaps5) != [gaps_want(h) for h in hits1] or any(x.tobytes() != y.tobytes() for x, y in zip(gaps5[:3], res5[:3])):
+                    fail("WIDE BAND SW GAPS", spec, "cols", cols, sub, lo, hi, gaps_got(gaps5), [gaps_want(h) for h in hits1])
+                if small:
+                    narrow = ctx.sw_gaps_banded(W.from_pairs(sub[:len(small)]), sc, lo[:len(small)], hi[:len(small)])
+                    if any(x[:len(small)].tobytes() != y.tobytes() for x, y in zip(gaps5, narrow)):
+                        fail("WIDE / NARROW BAND SW GAPS", spec, "cols", cols, sub, lo, hi)
+                n["sw_gaps_banded_wide"] += len(sub)
         n["trials"] += 1
 
     if srng is not None:
@@ -499,7 +535,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
           f"{n['score']} scores, {n['span']} hit spans, {n['span_banded']} banded hit spans, {n['sw_stats_banded']} banded SW statistics, {n['cross']} cross cells, {n['search']} searches, {n['span_cross']} span cross cells, {n['span_search']} span searches, {n['stats']} NW and {n['sw_stats']} SW statistics, {n['stats_cross']} NW and {n['sw_stats_cross']} SW statistics cross cells, {n['long']} long alignments, {n['banded']} banded "
           f"alignments (+ {n['banded_none']} with none in their band), {n['stats_banded']} banded NW statistics (+ {n['stats_banded_none']} with none), {n['banded_wide']} wide banded results, {n['span_banded_wide']} wide banded hit spans, "
           f"{n['stats_banded_wide']} wide banded NW and {n['sw_stats_banded_wide']} wide banded SW statistics identical to the oracle; "
-          f"{n['sw_counts']} SW identity counts, {n['sw_counts_banded']} banded and {n['sw_counts_banded_wide']} wide banded identical to sw_stats* and sw_score* "
+          f"{n['sw_counts']} SW identity counts, {n['sw_counts_banded']} banded and {n['sw_counts_banded_wide']} wide banded identical to sw_stats* and sw_score*; "
+          f"{n['sw_gaps']} SW gap runs, {n['sw_gaps_banded']} banded and {n['sw_gaps_banded_wide']} wide banded identical to the oracle's strings "
           f"(seed {seed})", flush=True)
     return n
 
