@@ -1193,6 +1193,46 @@ int seqalign_sw_span_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries
  * There is no _cross_multi form. */
 int seqalign_nw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
                             const scoring_t *scoring, int32_t *out_score, uint32_t *out_matches, uint32_t *out_mismatches);
+/* ---- NW gap-run counts: score and the gap opens of the global alignment, no traceback ---- */
+/* For every pair, over the alignment seqalign_nw_batch returns for it -- the walk of alignment_reverse_move from the end
+ * pick, tie order GAP_A, GAP_B, MATCH, not merely some optimal alignment:
+ *   out_score[p]        byte for byte seqalign_nw_score_batch's;
+ *   out_gap_runs_a[p]   the number of maximal runs of '-' in string a of that alignment;
+ *   out_gap_runs_b[p]   the same count in string b.
+ * BLAST's gapopen is their sum; an insertion directly against a deletion is two runs.  With seqalign_nw_stats_batch on the
+ * same arguments this gives the tabular line of a global alignment -- pident, length, mismatch, gapopen, score -- in two
+ * sweeps, nothing stored per cell.  A leading or trailing gap is a run like any other, free (no_start_gap_penalty,
+ * no_end_gap_penalty) or not.  len_a = 0 < len_b gives (edge score, 1, 0), len_b = 0 < len_a (edge score, 0, 1), both empty
+ * (0, 0, 0).  There is no limit on the lengths: a string has fewer than 2^31 columns, so the counts are full words beside the
+ * sweep's "no walk" mark.
+ *   Argument checks and their order, every error (SEQALIGN_E_DOMAIN, SEQALIGN_E_UNKNOWN_PAIR before SEQALIGN_E_TRACEBACK on
+ * one pair), device bytes per pair, the 12 bytes home, chunking and launch kinds are seqalign_nw_stats_batch's.  Kernel:
+ * sa_nw_gaps.hip.  Not here: _multi, _cross_multi, search, _submit, the command-line tools. */
+int seqalign_nw_gaps_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int32_t *out_score,
+                           uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b);
+/* Kernel time of seqalign_nw_gaps_batch (seq-align_amd/tools/nw_gaps_bench.py), as seqalign_nw_stats_time_ms */
+int seqalign_nw_gaps_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                             float *ms_each);
+/* Gap-run matrices: seqalign_nw_gaps_batch's three outputs for every query against every target, [n_queries][n_targets] each;
+ * tiles, strips for long queries, checks, empty sets and errors are seqalign_nw_stats_cross's. */
+int seqalign_nw_gaps_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                           const scoring_t *scoring, int32_t *out_score, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b);
+/* seqalign_nw_gaps_batch over the banded NW matrices: out_score is seqalign_nw_score_banded's byte for byte, the two counts are
+ * the '-' runs of seqalign_nw_align_banded's strings; where the unbanded alignment stays inside the band all three are
+ * seqalign_nw_gaps_batch's.  The band, at most 512 diagonals, every check and its order, SEQALIGN_E_TRACEBACK for a pair with
+ * no alignment inside the band, device bytes per pair, bytes home and launch records are seqalign_nw_stats_banded's.  Kernel:
+ * sa_band_nw_frame.hpp by sa_band_nw_gaps.hip. */
+int seqalign_nw_gaps_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                            const uint32_t *band, int32_t *out_score, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b);
+/* Timing hook (tools/nw_gaps_bench.py), as seqalign_nw_stats_band_time_ms for seqalign_nw_gaps_banded */
+int seqalign_nw_gaps_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                  const uint32_t *band, int repeats, float *ms_each);
+/* The wide form of seqalign_nw_gaps_banded: its argument list and contract word for word at any band width, score byte for
+ * byte seqalign_nw_score_banded_wide's, the counts those of seqalign_nw_align_banded_wide's strings; strips, the option
+ * band_strip_cols, device bytes and records are seqalign_nw_stats_banded_wide's.  A 200 kb pair in a band of 4 097 diagonals
+ * gets its gapopen without any matrix.  No timing-hook, _multi, _submit or command-line form. */
+int seqalign_nw_gaps_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                 const uint32_t *band, int32_t *out_score, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b);
 /* SW statistics matrices: seqalign_sw_stats_batch's seven outputs for every query against every target, [n_queries][n_targets]
  * each, the result of that call on the batch whose pair q * n_targets + t is (query q, target t) -- which is never built; pos_a
  * and len_a are in the query.  It runs on seqalign_sw_span_cross's tiles with 28 result bytes per pair: queries of up to 512

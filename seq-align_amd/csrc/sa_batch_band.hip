@@ -1,8 +1,8 @@
-// sa_batch_band.hip -- the banded calls over HOST batches: the twenty-four seqalign_*_banded, *_banded_wide and *_band_time_ms entry
+// sa_batch_band.hip -- the banded calls over HOST batches: the twenty-eight seqalign_*_banded, *_banded_wide and *_band_time_ms entry
 // points (the contracts: include/seqalign_hip.h; the kernels: sa_band.hip, sa_band_span.hip, sa_band_stats.hip, sa_band_counts.hip, sa_band_gaps.hip,
-// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip).  DESIGN.md 3.23b.
+// sa_band_nw_stats.hip, sa_band_strips.hip, sa_band_nw_stats_strips.hip, sa_band_nw_gaps.hip).  DESIGN.md 3.23b.
 //
-// One driver, nine modes.  A mode is a traits struct (below): NW or SW, score family or align, its result words and fixed
+// One driver, ten modes.  A mode is a traits struct (below): NW or SW, score family or align, its result words and fixed
 // bytes per pair, its cap on the width, its kernels' parameter block and launches.  The driver is the same for all of them:
 //   checks   everything that can be refused from lengths and bands alone is refused before any device work
 //            (check_band_batch): the band of every pair is clipped to its matrix -- NW: w diagonals around the corner cells'
@@ -194,6 +194,14 @@ struct NwStatsBand {   // seqalign_nw_stats_banded(_wide), seqalign_nw_stats_ban
   static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_nw_stats(p, max_width, st); }
   static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
     return sa_launch_band_nw_stats_strips({p, l}, cols, items, st);
+  }
+};
+
+struct NwGapsBand : NwStatsBand {   // seqalign_nw_gaps_banded(_wide), seqalign_nw_gaps_band_time_ms (sa_band_nw_gaps.hip)
+  // NwStatsBand with the gap-run kernels: score, gap_runs_a, gap_runs_b; the mark is in the gap_runs_b word (kMarkField = 2)
+  static hipError_t launch(const Params &p, uint32_t max_width, hipStream_t st) { return sa_launch_band_nw_gaps(p, max_width, st); }
+  static hipError_t launch_strips(const Params &p, const SaBandStripsLayout &l, uint32_t cols, uint64_t items, hipStream_t st) {
+    return sa_launch_band_nw_gaps_strips({p, l}, cols, items, st);
   }
 };
 
@@ -875,4 +883,36 @@ extern "C" int seqalign_nw_stats_band_time_ms(seqalign_ctx_t *ctx, const seqalig
   int rc = check_band_batch<NwStatsBand>(batch, NwBands{band}, geom);
   if (rc) return rc;
   return band_time<NwStatsBand>(ctx, batch, scoring, geom, repeats, ms_each, "seqalign_nw_stats_band_time_ms");
+}
+
+// banded NW gap-run counts: seqalign_nw_stats_banded[_wide]'s checks in their order (kernels: sa_band_nw_gaps.hip)
+static int nw_gaps_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, const uint32_t *band,
+                          int32_t *out_score, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b, bool wide) {
+  if (!ctx || !batch || !scoring || !band || !out_score || !out_gap_runs_a || !out_gap_runs_b) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch<NwGapsBand>(batch, NwBands{band}, geom, wide);
+  if (rc) return rc;
+  CallScope scope(ctx);
+  uint32_t *const out[2] = {out_gap_runs_a, out_gap_runs_b};
+  return band_call<NwGapsBand>(ctx, batch, scoring, geom, wide, [&](auto &run) { return run.finish_words(out_score, out); });
+}
+
+extern "C" int seqalign_nw_gaps_banded(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                       const uint32_t *band, int32_t *out_score, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b) {
+  return nw_gaps_banded(ctx, batch, scoring, band, out_score, out_gap_runs_a, out_gap_runs_b, false);
+}
+
+extern "C" int seqalign_nw_gaps_banded_wide(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                            const uint32_t *band, int32_t *out_score, uint32_t *out_gap_runs_a,
+                                            uint32_t *out_gap_runs_b) {
+  return nw_gaps_banded(ctx, batch, scoring, band, out_score, out_gap_runs_a, out_gap_runs_b, true);
+}
+
+extern "C" int seqalign_nw_gaps_band_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                             const uint32_t *band, int repeats, float *ms_each) {
+  if (!ctx || !batch || !scoring || !band || repeats <= 0 || !ms_each) return SEQALIGN_E_ARG;
+  std::vector<Band> geom;
+  int rc = check_band_batch<NwGapsBand>(batch, NwBands{band}, geom);
+  if (rc) return rc;
+  return band_time<NwGapsBand>(ctx, batch, scoring, geom, repeats, ms_each, "seqalign_nw_gaps_band_time_ms");
 }

@@ -2,11 +2,12 @@
 // hook seqalign_score_time_ms), SW hit spans: seqalign_sw_span_batch (and seqalign_sw_span_time_ms), and NW alignment statistics:
 // seqalign_nw_stats_batch (and seqalign_nw_stats_time_ms), and SW alignment statistics: seqalign_sw_stats_batch (and
 // seqalign_sw_stats_time_ms), and SW identity counts at any length: seqalign_sw_counts_batch (and seqalign_sw_counts_time_ms), and SW
-// gap-run counts at any length: seqalign_sw_gaps_batch (and seqalign_sw_gaps_time_ms).  No matrices, no traceback: per chunk the sequences go up, the score kernels (sa_score.hip), the span
-// kernels (sa_span.hip) or the stats kernels (sa_nw_stats.hip, sa_sw_stats.hip, sa_sw_counts.hip, sa_sw_gaps.hip) run, and 4 or 12 bytes per pair come back, 20 for
+// gap-run counts at any length: seqalign_sw_gaps_batch (and seqalign_sw_gaps_time_ms), and NW gap-run counts: seqalign_nw_gaps_batch (and
+// seqalign_nw_gaps_time_ms).  No matrices, no traceback: per chunk the sequences go up, the score kernels (sa_score.hip), the span
+// kernels (sa_span.hip) or the stats kernels (sa_nw_stats.hip, sa_sw_stats.hip, sa_sw_counts.hip, sa_sw_gaps.hip, sa_nw_gaps.hip) run, and 4 or 12 bytes per pair come back, 20 for
 // a span (score, pos_a, pos_b, len_a, len_b), 12 for NW statistics (score, matches, mismatches), 28 for SW statistics (the span's
 // five, matches, mismatches), 20 for SW counts (score, end_a, end_b, matches, mismatches), 20 for SW gap runs (score, end_a, end_b, gap_runs_a,
-// gap_runs_b), plus the error word.
+// gap_runs_b), 12 for NW gap runs (score, gap_runs_a, gap_runs_b), plus the error word.
 //
 // A chunk's pairs are put in classes by row width -- the columns per lane of the one-wave kernel (score: 1 .. 16, span: 1 .. 6
 // and 8), or the strips kernel for rows over 1 024 (span: 512) columns -- and the descriptors are laid out class by class, so
@@ -180,6 +181,7 @@ template int sa_host::row_batch_call<StatsTraits>(seqalign_ctx_t *, const seqali
 template int sa_host::row_batch_call<SwStatsTraits>(seqalign_ctx_t *, const seqalign_batch_t *, const scoring_t *, bool, int32_t *, uint32_t *const *, uint64_t *);
 template int sa_host::row_batch_call<SwCountsTraits>(seqalign_ctx_t *, const seqalign_batch_t *, const scoring_t *, bool, int32_t *, uint32_t *const *, uint64_t *);
 template int sa_host::row_batch_call<SwGapsTraits>(seqalign_ctx_t *, const seqalign_batch_t *, const scoring_t *, bool, int32_t *, uint32_t *const *, uint64_t *);
+template int sa_host::row_batch_call<NwGapsTraits>(seqalign_ctx_t *, const seqalign_batch_t *, const scoring_t *, bool, int32_t *, uint32_t *const *, uint64_t *);
 
 namespace {
 
@@ -278,6 +280,22 @@ extern "C" int seqalign_nw_stats_time_ms(seqalign_ctx_t *ctx, const seqalign_bat
   if (!ctx || !scoring || repeats <= 0 || !ms_each || !batch_readable(batch) || batch->n_pairs == 0) return SEQALIGN_E_ARG;
   CallScope scope(ctx);
   return row_time_call<StatsTraits>(ctx, batch, scoring, false, repeats, ms_each, "seqalign_nw_stats_time_ms");
+}
+
+// NW gap-run counts: seqalign_nw_stats_batch's checks in its order
+extern "C" int seqalign_nw_gaps_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,
+                                      int32_t *out_score, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b) {
+  if (!ctx || !scoring || !out_score || !out_gap_runs_a || !out_gap_runs_b || !batch_readable(batch)) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);   // (every argument checked before the context is touched)
+  uint32_t *const out[2] = {out_gap_runs_a, out_gap_runs_b};
+  return row_batch_call<NwGapsTraits>(ctx, batch, scoring, false, out_score, out);
+}
+
+extern "C" int seqalign_nw_gaps_time_ms(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, int repeats,
+                                        float *ms_each) {
+  if (!ctx || !scoring || repeats <= 0 || !ms_each || !batch_readable(batch) || batch->n_pairs == 0) return SEQALIGN_E_ARG;
+  CallScope scope(ctx);
+  return row_time_call<NwGapsTraits>(ctx, batch, scoring, false, repeats, ms_each, "seqalign_nw_gaps_time_ms");
 }
 
 extern "C" int seqalign_sw_stats_batch(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring,

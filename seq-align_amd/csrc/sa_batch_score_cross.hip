@@ -429,6 +429,7 @@ template int sa_host::cross_call<ScoreTraits>(const CrossArgs &);
 template int sa_host::cross_call<SpanTraits>(const CrossArgs &);
 template int sa_host::cross_call<StatsTraits>(const CrossArgs &);
 template int sa_host::cross_call<SwStatsTraits>(const CrossArgs &);
+template int sa_host::cross_call<NwGapsTraits>(const CrossArgs &);
 
 int sa_host::score_search_check(const seqalign_seqset_t *queries, const seqalign_seqset_t *targets, uint32_t k) {
   if (k == 0 || k > SEQALIGN_SEARCH_MAX_K) {
@@ -603,6 +604,17 @@ extern "C" int seqalign_nw_stats_cross(seqalign_ctx_t *ctx, const seqalign_seqse
   uint32_t *const out_w[2] = {out_matches, out_mismatches};
   return cross_call<StatsTraits>({.ctx = ctx, .queries = queries, .targets = targets, .scoring = scoring,
                                   .is_sw = false, .out_score = out_score, .out_w = out_w, .q_base = 0});
+}
+
+// NW gap-run matrices: seqalign_nw_stats_cross with the gap-run kernels
+extern "C" int seqalign_nw_gaps_cross(seqalign_ctx_t *ctx, const seqalign_seqset_t *queries, const seqalign_seqset_t *targets,
+                                      const scoring_t *scoring, int32_t *out_score, uint32_t *out_gap_runs_a, uint32_t *out_gap_runs_b) {
+  if (!ctx || !scoring || !out_score || !out_gap_runs_a || !out_gap_runs_b) return SEQALIGN_E_ARG;
+  int rc = score_cross_check(queries, targets);
+  if (rc) return rc;
+  uint32_t *const out_w[2] = {out_gap_runs_a, out_gap_runs_b};
+  return cross_call<NwGapsTraits>({.ctx = ctx, .queries = queries, .targets = targets, .scoring = scoring,
+                                   .is_sw = false, .out_score = out_score, .out_w = out_w, .q_base = 0});
 }
 
 // seqalign_sw_stats_*'s length limit over a set (sa_host::sw_stats_check_batch): the lowest sequence over it is named

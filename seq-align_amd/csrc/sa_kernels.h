@@ -549,6 +549,17 @@ typedef SaSpanParams SaSwGapsParams;
 /* recorded as "score_rows" / "score_strips"; the callers' duties are sa_launch_span_*'s */
 hipError_t sa_launch_sw_gaps_rows(const SaSwGapsParams &p, uint32_t max_len_a, hipStream_t stream);
 hipError_t sa_launch_sw_gaps_strips(const SaSwGapsParams &p, hipStream_t stream);
+/* ---- NW gap-run counts (seqalign_nw_gaps_batch / _cross, sa_nw_gaps.hip): the NW statistics sweep with the runs of '-' in the
+ * alignment's two strings as the two payload words, any length.  The statistics block reused, its two arrays
+ * behind the score read as
+ *   matches = gap_runs_a, mismatches = gap_runs_b; bit 31 of mismatches[k] (SA_STATS_NO_WALK) = the end pick's state has no walk.
+ * Everything else -- row classes, strips, hand-off and progress layout -- is SaStatsParams'. */
+typedef SaStatsParams SaNwGapsParams;
+typedef SaStatsCrossParams SaNwGapsCrossParams;
+/* recorded as "score_rows" / "score_strips" / "score_cross"; the callers' duties are sa_launch_stats_*'s */
+hipError_t sa_launch_nw_gaps_rows(const SaNwGapsParams &p, uint32_t max_len_a, hipStream_t stream);
+hipError_t sa_launch_nw_gaps_strips(const SaNwGapsParams &p, hipStream_t stream);
+hipError_t sa_launch_nw_gaps_cross(const SaNwGapsCrossParams &p, uint32_t max_len_a, hipStream_t stream);
 /* top-k score search (seqalign_*_score_search, sa_score_select.hip): one workgroup per query row of a tile, after its
  * score_cross launches.  Keeps the k smallest keys (~(score ^ 0x80000000)) << 32 | (t_base + t) of the row's entries with
  * score >= min_score together with the query's running list, and writes them back sorted.  The running list's targets
@@ -686,6 +697,11 @@ struct SaBandNwStatsParams {
 };
 /* every pair of the launch has width <= max_width <= SA_SPAN_BAND_MAX_WIDTH; max_width picks the columns per lane */
 hipError_t sa_launch_band_nw_stats(const SaBandNwStatsParams &p, uint32_t max_width, hipStream_t stream);
+/* ---- banded NW gap-run counts (seqalign_nw_gaps_banded, sa_band_nw_gaps.hip): SaNwGapsParams' payload through the same frame.
+ * The banded statistics block reused: matches = gap_runs_a, mismatches = gap_runs_b of the alignment inside the band, the mark
+ * where it was. */
+typedef SaBandNwStatsParams SaBandNwGapsParams;
+hipError_t sa_launch_band_nw_gaps(const SaBandNwGapsParams &p, uint32_t max_width, hipStream_t stream);
 /* ---- the wide banded calls (seqalign_*_banded_wide): the same bands, matrices, results and layouts at any width, one wave
  * per (pair, strip of strip_cols columns) in the strips pipeline (sa_band_pipe.hpp).  A launch's block is the narrow launch's
  * record s and the pipeline's words w, the same for every family.  s.b.f.status (NW score and align: s.b alone is used) must hold
@@ -717,11 +733,12 @@ hipError_t sa_launch_band_strips(const SaBandWideParams<SaBandSwParams> &p, uint
  * SW statistics (sa_band_stats.hip): word 0 the stop cell x | y << 16, word 1 matches | mismatches << 16; both sequences of every
  * pair have at most SA_SW_STATS_MAX_LEN letters.  SW hit spans (sa_band_span.hip): the stop cell's x and y, any length.  SW
  * identity counts (sa_band_counts.hip): matches and mismatches, any length.  SW gap-run counts (sa_band_gaps.hip): gap_runs_a
- * and gap_runs_b, any length. */
+ * and gap_runs_b, any length.  NW gap-run counts (sa_band_nw_gaps.hip): gap_runs_a and gap_runs_b with the NW mark, no best cell. */
 #define SA_BAND_STATS_HANDOFF_BYTES 32u
 hipError_t sa_launch_band_sw_counts_strips(const SaBandWideParams<SaBandSwCountsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 hipError_t sa_launch_band_sw_gaps_strips(const SaBandWideParams<SaBandSwGapsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 hipError_t sa_launch_band_nw_stats_strips(const SaBandWideParams<SaBandNwStatsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
+hipError_t sa_launch_band_nw_gaps_strips(const SaBandWideParams<SaBandNwGapsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 hipError_t sa_launch_band_sw_stats_strips(const SaBandWideParams<SaBandSwStatsParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 hipError_t sa_launch_band_span_strips(const SaBandWideParams<SaBandSpanParams> &p, uint32_t strip_cols, uint64_t items, hipStream_t stream);
 /* the second launch record (seqalign_ctx_last_call_info_ext: SEQALIGN_KX_*) */

@@ -128,14 +128,22 @@ struct SwGapsTraits {   // sa_sw_gaps.hip: SwCountsTraits with the gap-run kerne
   // no cross form: nothing for the cross driver to instantiate
 };
 
+struct NwGapsTraits : StatsTraits {   // sa_nw_gaps.hip: StatsTraits with the gap-run kernels -- its classes, strips, bytes and cross
+  // params; the result words are score, gap_runs_a, gap_runs_b, and kMarkField = 2 is SA_STATS_NO_WALK in the gap_runs_b word
+  static constexpr const char *kLaunch = "nw gaps kernel launch", *kLaunchCross = "nw gaps cross kernel launch";
+  static hipError_t launch_rows(const Params &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_nw_gaps_rows(p, max_a, st); }
+  static hipError_t launch_strips(const Params &p, bool, hipStream_t st) { return sa_launch_nw_gaps_strips(p, st); }
+  static hipError_t launch_cross(const CrossParams &p, uint32_t max_a, bool, hipStream_t st) { return sa_launch_nw_gaps_cross(p, max_a, st); }
+};
+
 // A family's batch call behind its entry checks: every chunk prepared, launched, brought home (sa_batch_score.hip, which
-// instantiates it for the six families).  out: the arrays behind the score, T::fields(is_sw) - 1 of them; fail_pair
+// instantiates it for the seven families).  out: the arrays behind the score, T::fields(is_sw) - 1 of them; fail_pair
 // (optional): the failing pair it names, for SEQALIGN_E_TRACEBACK too.
 template <class T>
 int row_batch_call(seqalign_ctx_t *ctx, const seqalign_batch_t *batch, const scoring_t *scoring, bool is_sw, int32_t *out_score,
                    uint32_t *const *out, uint64_t *fail_pair = nullptr);
 
-// One context's cross call of a family (its own CallScope; sa_batch_score_cross.hip, which instantiates it for the four).  The
+// One context's cross call of a family (its own CallScope; sa_batch_score_cross.hip, which instantiates it for the five).  The
 // caller has checked the sets (score_cross_check).
 struct CrossArgs {
   seqalign_ctx_t *ctx;

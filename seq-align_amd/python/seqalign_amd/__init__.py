@@ -493,6 +493,41 @@ class Context:
                                              _ptr(mismatches)), "seqalign_nw_stats_cross")
         return score, matches, mismatches
 
+    # ---- NW gap-run counts (seqalign_nw_gaps_batch / seqalign_nw_gaps_cross) --------------------------------------
+    def nw_gaps(self, batch, scoring: Scoring):
+        """seqalign_nw_gaps_batch: (score int32[n], gap_runs_a uint32[n], gap_runs_b uint32[n]) -- nw_score's score and, over
+        the alignment nw_batch returns for the pair, the maximal runs of '-' in string a and in string b.  BLAST's gapopen is
+        their sum; an insertion directly against a deletion is two runs.  One forward pass, no strings, any length."""
+        _score_args(batch, scoring)
+        n = batch.n_pairs
+        score, runs_a, runs_b = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_gaps_batch(self._h, C.byref(d), C.byref(scoring), _ptr(score), _ptr(runs_a), _ptr(runs_b)),
+               "seqalign_nw_gaps_batch")
+        return score, runs_a, runs_b
+
+    def nw_gaps_time_ms(self, batch, scoring: Scoring, repeats: int = 10) -> np.ndarray:
+        """seqalign_nw_gaps_time_ms: nw_gaps' kernels of one chunk, `repeats` launches, each between HIP events (ms)."""
+        _score_args(batch, scoring)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "nw_gaps_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_gaps_time_ms(self._h, C.byref(d), C.byref(scoring), C.c_int(repeats), _ptr(ms)),
+               "seqalign_nw_gaps_time_ms")
+        return ms
+
+    def nw_gaps_cross(self, queries, targets, scoring: Scoring):
+        """seqalign_nw_gaps_cross: (score int32, gap_runs_a uint32, gap_runs_b uint32), each [n_queries, n_targets] -- nw_gaps
+        on workloads.cross_batch(queries, targets) without building that batch."""
+        _cross_args(queries, targets, scoring)
+        shape = (queries.n_seqs, targets.n_seqs)
+        score, runs_a, runs_b = np.zeros(shape, np.int32), np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        dq, dt = seqset_desc(queries), seqset_desc(targets)
+        _check(lib().seqalign_nw_gaps_cross(self._h, C.byref(dq), C.byref(dt), C.byref(scoring), _ptr(score), _ptr(runs_a),
+                                            _ptr(runs_b)), "seqalign_nw_gaps_cross")
+        return score, runs_a, runs_b
+
     # ---- SW alignment statistics (seqalign_sw_stats_batch / seqalign_sw_stats_cross) ------------------------------
     def sw_stats(self, batch, scoring: Scoring, peers=None):
         """seqalign_sw_stats_batch: (score int32[n], pos_a, pos_b, len_a, len_b, matches, mismatches uint32[n]) -- sw_span's
@@ -945,6 +980,30 @@ class Context:
         d = batch_desc(batch)
         _check(lib().seqalign_nw_stats_band_time_ms(self._h, C.byref(d), C.byref(scoring), _ptr(bw), C.c_int(repeats), _ptr(ms)),
                "seqalign_nw_stats_band_time_ms")
+        return ms
+
+    # ---- banded NW gap-run counts (seqalign_nw_gaps_banded) ----------------------------
+    def nw_gaps_banded(self, batch, scoring: Scoring, band):
+        """seqalign_nw_gaps_banded: what nw_gaps returns -- (score int32[n], gap_runs_a uint32[n], gap_runs_b uint32[n]) -- over
+        the banded matrices of nw_score_banded: its score and the '-' runs of nw_align_banded's strings.  band: an int or one
+        per pair; widths up to SEQALIGN_SPAN_BAND_MAX_WIDTH (512), sequences of any length.  A pair that has no alignment
+        inside its band raises SeqAlignError(E_TRACEBACK)."""
+        return self._nw_stats_banded("seqalign_nw_gaps_banded", batch, scoring, band)
+
+    def nw_gaps_banded_wide(self, batch, scoring: Scoring, band):
+        """seqalign_nw_gaps_banded_wide: nw_gaps_banded without the cap on the band's width."""
+        return self._nw_stats_banded("seqalign_nw_gaps_banded_wide", batch, scoring, band)
+
+    def nw_gaps_band_time_ms(self, batch, scoring: Scoring, band, repeats: int = 10) -> np.ndarray:
+        """seqalign_nw_gaps_band_time_ms: kernel time (HIP events) of nw_gaps_banded's launches, float32[repeats]."""
+        _score_args(batch, scoring)
+        bw = _band_arg(batch, band)
+        if repeats <= 0:
+            raise SeqAlignError(E_ARG, "nw_gaps_band_time_ms: repeats must be > 0")
+        ms = np.zeros(repeats, np.float32)
+        d = batch_desc(batch)
+        _check(lib().seqalign_nw_gaps_band_time_ms(self._h, C.byref(d), C.byref(scoring), _ptr(bw), C.c_int(repeats), _ptr(ms)),
+               "seqalign_nw_gaps_band_time_ms")
         return ms
 
     def sw_align_long(self, batch, scoring: Scoring, min_score):
@@ -1433,6 +1492,8 @@ EXPORTED_SYMBOLS = [
     "seqalign_sw_counts_banded_wide",
     "seqalign_sw_gaps_batch", "seqalign_sw_gaps_time_ms", "seqalign_sw_gaps_banded", "seqalign_sw_gaps_band_time_ms",
     "seqalign_sw_gaps_banded_wide",
+    "seqalign_nw_gaps_batch", "seqalign_nw_gaps_time_ms", "seqalign_nw_gaps_cross", "seqalign_nw_gaps_banded",
+    "seqalign_nw_gaps_band_time_ms", "seqalign_nw_gaps_banded_wide",
     # include/seqalign_io.h
     "seqalign_scoring_load_matrix", "seqalign_scoring_load_pairs", "seqalign_reader_open", "seqalign_reader_close",
     "seqalign_reader_next",

@@ -8,7 +8,8 @@ band named), seqalign_sw_span_banded, seqalign_sw_stats_banded (the oracle's
 banded hit and its counted strings) and (on from the command line, --no-wide leaves them out) the four wide banded score and align calls,
 seqalign_sw_span_banded_wide, seqalign_nw_stats_banded_wide and seqalign_sw_stats_banded_wide (each with its narrow call's bytes on the small pairs),
 and seqalign_sw_counts_batch / _banded / _banded_wide (each against the sw_stats and the sw_score call of the same geometry on the same batch),
-and seqalign_sw_gaps_batch / _banded / _banded_wide (the '-' runs of the oracle's strings on the same batches; no random draw of their own), under random scorings (penalties, the five flags, case sensitivity, a wildcard,
+and seqalign_sw_gaps_batch / _banded / _banded_wide (the '-' runs of the oracle's strings on the same batches; no random draw of their own),
+seqalign_nw_gaps_batch / _cross / _banded / _banded_wide (the '-' runs of the oracle's NW strings on the nw_stats calls' batches and bands; no random draw of their own), under random scorings (penalties, the five flags, case sensitivity, a wildcard,
 mutations that differ by direction) on random, related and tandem-repeat pairs, some wider than 1 024 columns.
 
     python seq-align_amd/tools/fuzz_calls.py --seconds 300
@@ -88,6 +89,11 @@ def gaps_want(h):
     return (h["score"], h["pos_a"] + h["len_a"], h["pos_b"] + h["len_b"]) + runs
 
 
+def dash_runs(s) -> int:
+    """Maximal runs of '-' in one string of an alignment (bytes)."""
+    return sum(1 for k in range(len(s)) if s[k] == 45 and (k == 0 or s[k - 1] != 45))
+
+
 def gaps_got(res):
     return [tuple(int(x[k]) for x in res) for k in range(len(res[0]))]
 
@@ -133,7 +139,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
     n = {"trials": 0, "redraws": 0, "redrawn_trials": 0, "nw_trials": 0, "score": 0, "cross": 0, "search": 0, "long": 0, "banded": 0, "banded_none": 0, "wide": 0, "banded_wide": 0, "span_banded_wide": 0, "span": 0, "span_banded": 0, "span_cross": 0, "span_search": 0, "stats": 0, "stats_cross": 0, "sw_stats": 0, "sw_stats_cross": 0, "sw_stats_banded": 0,
          "stats_banded": 0, "stats_banded_none": 0, "stats_banded_wide": 0, "sw_stats_banded_wide": 0,
          "sw_counts": 0, "sw_counts_banded": 0, "sw_counts_banded_wide": 0,
-         "sw_gaps": 0, "sw_gaps_banded": 0, "sw_gaps_banded_wide": 0}
+         "sw_gaps": 0, "sw_gaps_banded": 0, "sw_gaps_banded_wide": 0,
+         "nw_gaps": 0, "nw_gaps_cross": 0, "nw_gaps_banded": 0, "nw_gaps_banded_wide": 0}
 
     def rand(count, alpha=b"ACGT"):
         return bytes(alpha[i] for i in rng.below(len(alpha), count)) if count else b""
@@ -142,12 +149,15 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         print(f"{what} MISMATCH", spec, *details, flush=True)
         raise SystemExit(1)
 
-    def nw_stats_banded_check(what, call, narrow, spec, sub, bands, both, n_small):
+    def nw_stats_banded_check(what, call, narrow, spec, sub, bands, both, n_small, count=None):
         """seqalign_nw_stats_banded(_wide) on pairs whose banded (end value, walk) `both` holds: the end value and the counted
         columns of the walk's strings; the pairs the oracle does not walk inside their band (walked_along_the_floor
         included) make the call fail with the lowest of them named, and the rest runs without them.  narrow: the call whose
-        bytes `call` must return on the first n_small pairs.  Returns (pairs equal to the oracle, pairs without an alignment)."""
-        want = [None if x[1] is None or walked_along_the_floor(osc, a, b, w, x[1][1], x[1][2]) else (x[0],) + ST.count_columns(osc, x[1][1], x[1][2])
+        bytes `call` must return on the first n_small pairs.  count: what the call counts over the walk's two strings (default:
+        the statistics' columns; the gap-run calls: dash_runs of each).  Returns (pairs equal to the oracle, pairs without an
+        alignment)."""
+        count = count or (lambda ra, rb: ST.count_columns(osc, ra, rb))
+        want = [None if x[1] is None or walked_along_the_floor(osc, a, b, w, x[1][1], x[1][2]) else (x[0],) + count(x[1][1], x[1][2])
                 for (a, b), w, x in zip(sub, bands, both)]
         none = [k for k, x in enumerate(want) if x is None]
         if none:
@@ -289,12 +299,17 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
         # ---- NW statistics: the columns of the oracle's strings, counted on the host
         if nw_ok:
             got = ST.got_stats(ctx.nw_stats(batch, sc))
+            runs = ST.got_stats(ctx.nw_gaps(batch, sc))       # NW gap runs on the same batch: the '-' runs of the same strings
             for p, (a, b) in enumerate(pairs):
                 rc, score, ra, rb = O.oracle_nw_traceback(osc, a, b, *fills[0, p])
                 want = (score,) + ST.count_columns(osc, ra, rb) if rc == 0 else None
                 if got[p] != want:
                     fail("NW STATS", spec, p, pairs[p], got[p], want)
+                want = (score, dash_runs(ra), dash_runs(rb)) if rc == 0 else None
+                if runs[p] != want:
+                    fail("NW GAPS", spec, p, pairs[p], runs[p], want)
             n["stats"] += len(pairs)
+            n["nw_gaps"] += len(pairs)
 
         # ---- score matrices and the search over them: 4 queries x 6 targets taken from the pairs
         qi = [0, 3, 6, wide if wide >= 0 else 9]
@@ -336,6 +351,12 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                 if not (all(np.array_equal(g, w) for g, w in zip(got, want)) and np.array_equal(got[0], dense[0])):
                     fail("NW STATS CROSS", spec, queries, targets, [g.tolist() for g in got], [w.tolist() for w in want])
                 n["stats_cross"] += 24
+                # ---- and their gap-run matrices: nw_gaps on the explicit batch (held to the oracle's strings above)
+                want = tuple(x.reshape(4, 6) for x in ctx.nw_gaps(W.cross_batch(q, t), sc))
+                got = ctx.nw_gaps_cross(q, t, sc)
+                if not (all(np.array_equal(g, w) for g, w in zip(got, want)) and np.array_equal(got[0], dense[0])):
+                    fail("NW GAPS CROSS", spec, queries, targets, [g.tolist() for g in got], [w.tolist() for w in want])
+                n["nw_gaps_cross"] += 24
                 continue
             # ---- the same sets' span matrices and search with spans: sw_span on the explicit batch, the oracle's best cells
             want = tuple(x.reshape(4, 6) for x in ctx.sw_span(W.cross_batch(q, t), sc))
@@ -389,6 +410,9 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                 kept, lost = nw_stats_banded_check("BAND NW STATS", ctx.nw_stats_banded, None, spec, sub, bands, both, 0)
                 n["stats_banded"] += kept
                 n["stats_banded_none"] += lost
+                # ---- banded NW gap runs on the same pairs and bands: the '-' runs of the same walks, the same pairs without one
+                n["nw_gaps_banded"] += nw_stats_banded_check("BAND NW GAPS", ctx.nw_gaps_banded, None, spec, sub, bands, both, 0,
+                                                             lambda ra, rb: (dash_runs(ra), dash_runs(rb)))[0]
                 none = [k for k, x in enumerate(both) if x[1] is None]
                 if none:            # no alignment inside the band: the call says so and names the lowest such pair
                     try:
@@ -467,6 +491,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
                     # ---- wide banded NW statistics on the same pairs and bands, and the narrow call's bytes on the small pairs
                     n["stats_banded_wide"] += nw_stats_banded_check("WIDE BAND NW STATS", ctx.nw_stats_banded_wide, ctx.nw_stats_banded, spec, sub, bands,
                                                                     both, len(small))[0]
+                    n["nw_gaps_banded_wide"] += nw_stats_banded_check("WIDE BAND NW GAPS", ctx.nw_gaps_banded_wide, ctx.nw_gaps_banded, spec, sub, bands,
+                                                                      both, len(small), lambda ra, rb: (dash_runs(ra), dash_runs(rb)))[0]
                 shift = int(v[14] % 300) - 150
                 lo = [int(v[5] % 80) - 60] * len(small) + [shift - half]
                 hi = [lo[k] + int(v[6] % 90) for k in range(len(small))] + [shift + half]
@@ -536,7 +562,8 @@ def run(seconds=120.0, seed=1, max_trials=1 << 60, ctx=None, wide_calls=False, s
           f"alignments (+ {n['banded_none']} with none in their band), {n['stats_banded']} banded NW statistics (+ {n['stats_banded_none']} with none), {n['banded_wide']} wide banded results, {n['span_banded_wide']} wide banded hit spans, "
           f"{n['stats_banded_wide']} wide banded NW and {n['sw_stats_banded_wide']} wide banded SW statistics identical to the oracle; "
           f"{n['sw_counts']} SW identity counts, {n['sw_counts_banded']} banded and {n['sw_counts_banded_wide']} wide banded identical to sw_stats* and sw_score*; "
-          f"{n['sw_gaps']} SW gap runs, {n['sw_gaps_banded']} banded and {n['sw_gaps_banded_wide']} wide banded identical to the oracle's strings "
+          f"{n['sw_gaps']} SW gap runs, {n['sw_gaps_banded']} banded and {n['sw_gaps_banded_wide']} wide banded identical to the oracle's strings; "
+          f"{n['nw_gaps']} NW gap runs, {n['nw_gaps_cross']} cross cells, {n['nw_gaps_banded']} banded and {n['nw_gaps_banded_wide']} wide banded identical to the oracle's strings "
           f"(seed {seed})", flush=True)
     return n
 
